@@ -61,7 +61,14 @@ def parse_args():
     ap.add_argument("--partitioned-index", action="store_true", help="multi-GPU passes keep the index hash-partitioned: lookups travel to the buckets' owners, "
                     "matching records back (slower than replicating the built slices wherever the index fits every GPU; DESIGN.md section 5)")
     ap.add_argument("--force-distributed", action="store_true", help="run the multi-GPU code path (RCCL communicator, every exchange) even with one rank")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also what the headline figure does not need: rooflines with measured HBM ceilings, the "
+                    "host-to-host pass, the CPU baseline and the stage wall (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (float64): its counts, and the "
+                    "canonical edges and contained rows of a fixed sample of the reads")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # phase of disco_phase_ms -> the kernel(s) behind it
@@ -339,6 +346,60 @@ def stage_wall(args, spec, e_pre):
         shutil.rmtree(d, ignore_errors=True)
 
 
+DUMP_SAMPLE_READS = 1 << 17  # reads whose edges and contained rows --dump-outputs writes (every read of a smaller run)
+DUMP_MAX_ROWS = 1 << 19  # per file: at most 512 Ki rows x 7 float64 = 28 MiB
+
+
+def sampled_reads(ids, n_reads, seed):
+    """mask: read id in a fixed pseudo-random set of about DUMP_SAMPLE_READS reads (splitmix64 of the id) — the same rows whatever
+    order a build emits them in"""
+    import numpy as np
+
+    if n_reads <= DUMP_SAMPLE_READS:
+        return np.ones(len(ids), dtype=bool)
+    with np.errstate(over="ignore"):
+        x = np.asarray(ids, dtype=np.uint64) + np.uint64((0x9E3779B97F4A7C15 * (seed + 1)) % (1 << 64))
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    return x < np.uint64(((1 << 64) * DUMP_SAMPLE_READS) // n_reads)
+
+
+def canonical_edge_rows(e):
+    """edges -> sorted unique rows (a, b, orient, overlap, len_a, offset, len_b), a < b: the form the oracle's parity check compares"""
+    import numpy as np
+
+    src, dst, orient, offset, l1, l2 = (e[k].astype(np.int64) for k in ("src", "dst", "orient", "offset", "len_src", "len_dst"))
+    swap = src > dst
+    o = np.where(swap, np.array([3, 1, 2, 0])[orient], orient)
+    off = np.where(swap, l2 + offset - l1, offset)
+    la = np.where(swap, l2, l1)
+    t = np.stack([np.where(swap, dst, src), np.where(swap, src, dst), o, la - off, la, off, np.where(swap, l1, l2)], axis=1)
+    return np.unique(t, axis=0) if len(t) else np.zeros((0, 7), np.int64)
+
+
+def dump_sample(g, n_reads, seed):
+    """this rank's sampled edges (by their lower read) and contained rows (by the contained read)"""
+    import numpy as np
+
+    e, c = g.fetch_edges(), g.fetch_contained()
+    e, c = e[sampled_reads(np.minimum(e["src"], e["dst"]), n_reads, seed)], c[sampled_reads(c["contained"], n_reads, seed)]
+    return canonical_edge_rows(e), np.stack([c[k].astype(np.int64) for k in ("contained", "super", "orient", "len2", "len1", "start")], axis=1)
+
+
+def dump_outputs(path, counts, parts):
+    """DIR/counts.npy (e_pre, e_out, n_contained, cap_bind_sites, asymmetric_pairs), DIR/edges.npy (a, b, orient, overlap, len_a, offset,
+    len_b), DIR/contained.npy (contained, super, orient, len_contained, len_super, start): float64, rows sorted"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("counts", np.array(counts, dtype=np.int64)), ("edges", np.concatenate([p[0] for p in parts])),
+                    ("contained", np.concatenate([p[1] for p in parts]))):
+        a = (np.unique(a, axis=0) if a.ndim == 2 and len(a) else a)[:DUMP_MAX_ROWS]
+        assert a.size == 0 or np.abs(a).max() < (1 << 53), name  # exact in float64
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves, as a CHILD torch.distributed.run (this
     process has not touched the GPU and never will — no exec of a GPU-initialised process), relay its output and exit code.
@@ -480,6 +541,15 @@ def main():
                        cap_bind_sites=info["cap_bind_sites"], asymmetric_pairs=info["asymmetric_pairs"])
     else:
         cnt_all = cnt
+    if args.dump_outputs:  # the results of the last timed pass, still in HBM: nothing has run since
+        parts = [dump_sample(g, args.reads, args.seed)]
+        if sharded:
+            every = [None] * world if rank == 0 else None
+            cp.dist.gather_object(parts[0], every, dst=0)
+            parts = every
+        if rank == 0:
+            dump_outputs(args.dump_outputs, [cnt_all[k] for k in ("e_pre", "e_out", "n_contained", "cap_bind_sites", "asymmetric_pairs")], parts)
+        kick()
     total_b, kern_b = algorithmic_bytes(cnt_all, args.reads, words_mean)
     avg_ms = {k: sum(v) / max(len(v), 1) for k, v in kern_ms.items()}
     dominant = max(avg_ms, key=lambda k: avg_ms[k])  # the longest kernel of the pass
@@ -498,12 +568,12 @@ def main():
         except Exception:
             tj = {}
 
-    try:  # attainable HBM bandwidth on this box (streaming copy kernel), reported beside the nominal peak
-        hbm_measured = g.measure_hbm(2 << 30, 5)
+    try:  # attainable HBM bandwidth on this box (streaming copy kernel), reported beside the nominal peak (--full: runs of its own)
+        hbm_measured = g.measure_hbm(2 << 30, 5) if args.full else None
     except Exception:
         hbm_measured = None
     try:  # ... and of the pattern the dominant kernels actually issue: random 64-byte rows out of the packed-read table
-        gather_measured = g.measure_gather(max(args.reads * 64, 1 << 20), 3)
+        gather_measured = g.measure_gather(max(args.reads * 64, 1 << 20), 3) if args.full else None
     except Exception:
         gather_measured = None
 
@@ -527,7 +597,7 @@ def main():
         "metric": "overlaps/sec (BuildGraph stage), 150 bp reads",
         "value": e_pre / (ms_per_step * 1e-3),
         "timer": "hbm_resident",  # reads resident in HBM when the timed region starts, results left in HBM; SURVEY.md 8(d)'s t_graph
-                                  # (host buffers in, host structs out) is value_host_to_host, its stage timer stage_drop_in
+                                  # (host buffers in, host structs out) is value_host_to_host, its stage timer stage_drop_in (--full)
         "unit": "overlaps/s",
         "n_gpus": world,
         "steps": args.steps,
@@ -554,15 +624,16 @@ def main():
             "algorithmic_bytes_per_step": total_b,
             "path_gbs": total_b / (ms_per_step * 1e-3) / 1e9,
         },
-        "roofline": roof(dominant),
-        "roofline_other": [roof(k) for k in sorted(avg_ms, key=lambda k: -avg_ms[k]) if k != dominant],
+    }
+    if args.full:
+        out["roofline"] = roof(dominant)
+        out["roofline_other"] = [roof(k) for k in sorted(avg_ms, key=lambda k: -avg_ms[k]) if k != dominant]
         # share of ms_per_step that the kernels with a roofline entry account for (the rest: the grouping's scan / scatter, small
         # bookkeeping kernels, launch gaps)
-        "roofline_coverage_of_step": sum(avg_ms.values()) / ms_per_step if ms_per_step > 0 else None,
-    }
-    # round 6: the pass against the VECTOR-ISSUE roof — the one that binds it
-    out["roofline_issue"] = issue_pass({ph: issue(ph) for ph in PHASE_KERNELS}, ms_per_step, args.reads, traffic_note)
-    if not sharded and not args.no_host_to_host:
+        out["roofline_coverage_of_step"] = sum(avg_ms.values()) / ms_per_step if ms_per_step > 0 else None
+        # round 6: the pass against the VECTOR-ISSUE roof — the one that binds it
+        out["roofline_issue"] = issue_pass({ph: issue(ph) for ph in PHASE_KERNELS}, ms_per_step, args.reads, traffic_note)
+    if args.full and not sharded and not args.no_host_to_host:
         # SURVEY.md §8(d) 'graph' wall: host buffers in, host structs out (the HBM-resident `value` never includes the copies)
         try:
             h2h = g.host_to_host_pass()
@@ -589,7 +660,7 @@ def main():
             out["config"]["exchanges_rank0"]["first_pass_ms_is"] = ("the untimed first (warm-up) pass waits behind every all-to-all on multi-rank RCCL: the exchanges "
                                                                     "themselves, link time included (DISCO_DIST_NO_FIRST_CONTACT=1 takes the waits away)")
     g.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             kick()
             out["cpu_baseline"] = cpu_baseline(args, spec)
@@ -599,7 +670,7 @@ def main():
             ref3 = reference_at_config3()
             if ref3:
                 out["cpu_baseline"]["reference_at_benched_config"] = ref3
-    if rank == 0 and world == 1 and not args.no_stage:
+    if args.full and rank == 0 and world == 1 and not args.no_stage:
         try:
             out["stage_drop_in"] = stage_wall(args, spec, e_pre)
         except Exception as e:

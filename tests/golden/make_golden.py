@@ -8,6 +8,8 @@ tests/golden/inputs/) + the canonical outputs of the reference at -t 1 (SURVEY.m
     <case>.contained.txt  canonical contained rows, sorted
 or, for the larger cases, only their SHA-256 in cases.json.
 tests/golden/reference_data/ holds the reference's own data files (two FASTAs + its one golden edge list).
+    make_golden.py --parsimplify   recorded.json: digests of the reference parsimplify's output on the partial-simplification inputs
+    make_golden.py --live-small    recorded.json: digests of the reference on the reads of tests/test_oracle_golden.py's small live check
 """
 from __future__ import annotations
 
@@ -105,8 +107,58 @@ def canon_to_files(name, edges, cont, full):
                 n_contained=int(len(cont)), full_text=bool(full))
 
 
+def _update_recorded(key, value):
+    path = os.path.join(HERE, "recorded.json")
+    rec = json.load(open(path)) if os.path.exists(path) else {}
+    rec[key] = value
+    with open(path, "w") as f:
+        f.write(json.dumps(rec, indent=1, sort_keys=True) + "\n")
+
+
+def record_parsimplify():
+    """make_golden.py --parsimplify: recorded.json["parsimplify"] — the reference parsimplify with its length defect repaired on the inputs
+    of tests/test_host.py::test_partial_simplification_equals_the_reference_parsimplify (make -C oracle ref_parsimplify first)"""
+    import subprocess
+    import tempfile
+
+    from tests import golden_util as gu
+
+    exe = os.path.join(os.path.dirname(refrun.REF_BIN), "parsimplify_ref_initlen")
+    d = tempfile.mkdtemp(prefix="golden_ps_")
+    out = {}
+    for name in gu.PS_CASES:
+        for split in (False, True):
+            edge_file, res = os.path.join(d, "in_parGraph.txt"), os.path.join(d, "out.txt")
+            gu.partial_edge_file(name, split, edge_file)
+            subprocess.run([exe, edge_file, res, "30", "2"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            lines = gu.par_lines(res)
+            out[f"{name}.{'split' if split else 'whole'}"] = dict(sha256=pyoracle.digest("".join(l + "\n" for l in lines)), n_lines=len(lines))
+    _update_recorded("parsimplify", out)
+
+
+# tests/test_oracle_golden.py::test_oracle_vs_live_reference_small: the reference at -t 1 on these reads, recorded.json["live_1500"]
+LIVE_SMALL = dict(seed=2024, n_reads=1500, read_len=90, cov=20.0, len_max=150)
+
+
+def record_live_small():
+    import tempfile
+
+    reads = readgen.generate_reads(readgen.GenSpec.coverage(**LIVE_SMALL))
+    d = tempfile.mkdtemp(prefix="golden_")
+    fa = os.path.join(d, "r.fasta")
+    readgen.write_fasta(fa, reads)
+    r = refrun.run_reference([fa], 40, threads=1, workdir=d)
+    et, ct = pyoracle.edges_text(r["edges"]), pyoracle.contained_text(r["contained"])
+    _update_recorded("live_1500", dict(edges_sha256=pyoracle.digest(et), contained_sha256=pyoracle.digest(ct), n_edges=len(r["edges"]),
+                                       n_contained=len(r["contained"])))
+
+
 def main():
     assert refrun.available(), "build the reference first: make -C oracle ref"
+    if sys.argv[1:] == ["--parsimplify"]:
+        return record_parsimplify()
+    if sys.argv[1:] == ["--live-small"]:
+        return record_live_small()
     cases = {}
     import tempfile
 

@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "300000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "20000", "--no-stage"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--reads", "300000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "20000",
+           "--no-stage"] + extra
     env = dict(os.environ, MASTER_PORT="29641")
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -59,7 +60,7 @@ def test_bench_line_has_the_contract_fields():
 
 
 def test_bench_stage_wall_through_the_drop_in_executable():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "200000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-host-to-host"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--reads", "200000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-host-to-host"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.strip().split("\n") if l.strip()][-1])
@@ -93,3 +94,35 @@ def test_bench_illumina_like_variant():
     assert "1000 substitutions per 10^6 bases" in d["config"]["workload"] and "cpu_baseline" not in d
     assert 0.5 * clean["config"]["e_pre"] < d["config"]["e_pre"] < clean["config"]["e_pre"]
     assert d["config"]["e_out"] > clean["config"]["e_out"]  # broken transitivity leaves more edges
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline figure and the pass's own counters only; --dump-outputs writes the results of the
+    last timed step (counts, canonical edges and contained rows of the sampled reads), the same for the same arguments"""
+    import numpy as np
+
+    def run(steps, warmup, out):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "300000", "--steps", str(steps), "--warmup", str(warmup),
+               "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        return json.loads([l for l in p.stdout.strip().split("\n") if l.strip()][-1])
+
+    d = run(3, 1, tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "timer", "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "overlaps/s" and d["dtype"] == "u64"
+    assert abs(d["value"] - d["config"]["e_pre"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "roofline_other", "roofline_issue", "cpu_baseline", "graph_host_to_host", "value_host_to_host", "stage_drop_in"):
+        assert k not in d, k
+    files = {f: np.load(tmp_path / "a" / f) for f in ("counts.npy", "edges.npy", "contained.npy")}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    assert all(a.dtype == np.float64 for a in files.values())
+    c = d["config"]
+    assert files["counts.npy"].tolist() == [c["e_pre"], c["e_out"], c["n_contained"], c["cap_bind_sites"], c["asymmetric_pairs"]]
+    e, r = files["edges.npy"], files["contained.npy"]
+    assert e.shape[1] == 7 and 0 < len(e) < c["e_out"] and r.shape[1] == 6 and 0 < len(r) < c["n_contained"]  # a sample: 300 k reads
+    assert (e[:, 0] <= e[:, 1]).all() and len(np.unique(e, axis=0)) == len(e)
+    run(1, 0, tmp_path / "b")
+    for f in files:
+        assert np.array_equal(files[f], np.load(tmp_path / "b" / f)), f

@@ -393,16 +393,7 @@ REF_PS = os.path.join(os.path.dirname(refrun.REF_BIN), "parsimplify_ref")
 REF_PS_INITLEN = REF_PS + "_initlen"  # the reference with EdgeSimple::copyEdge copying the two read lengths too (oracle/Makefile)
 
 
-def _par_lines(path, drop_length=False):
-    """sorted lines of a ParSimpleEdges file; drop_length: without the edge-length column (offset + length of the destination),
-    which the STOCK reference fills from uninitialised members on some composite edges (SG/EdgeSimple.cpp:50-71); fullsimplify never
-    reads that column (SG/OverlapGraph.cpp:2028-2094 takes fields 0, 1 and 5)"""
-    out = []
-    for line in open(path):
-        f = line.rstrip("\n").split("\t")
-        info = f[2].split(",")
-        out.append("\t".join(f[:2] + [",".join(info[:2] + info[3:]) if drop_length else f[2]] + f[3:]))
-    return sorted(out)
+_par_lines = gu.par_lines
 
 
 def _run_ps(exe, edge_file, out, min_ovl, threads):
@@ -410,37 +401,30 @@ def _run_ps(exe, edge_file, out, min_ovl, threads):
     assert p.returncode == 0, p.stdout[-2000:]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PS_INITLEN), reason="prebuilt reference parsimplify (make -C oracle ref_parsimplify) not present")
-@pytest.mark.parametrize("name", ["u150_5k", "mixed_4k", "k30_6k", "k64_3k", "long_2k", "multifile"])
+@pytest.mark.parametrize("name", gu.PS_CASES)
 @pytest.mark.parametrize("split", [False, True])
 def test_partial_simplification_equals_the_reference_parsimplify(tmp_path, name, split):
     """disco_amd/bin/parsimplify (= the code behind buildG --par-simple) against the REAL parsimplify on the same
     edge file: the same lines — every (composite) edge, inner read lists and lengths included. split: a file that owns only the
     lower half of the nodes, edges to the other half carrying flags 0 / 1 — nodes that are not marked must neither be absorbed
     nor removed. The comparator is the reference with its uninitialised-length defect repaired (deterministic); the stock binary
-    must agree too up to the lines that defect decides."""
+    must agree too up to the lines that defect decides. The first comparison also holds against the reference's recorded output
+    (tests/golden/recorded.json), so it runs where the reference binaries are not built."""
     build.build_host()
-    src = os.path.join(gu.GOLD, name + ".edges.txt")
-    lines = [l.rstrip("\n") for l in open(src) if l.strip()]
-    ids = sorted({int(x) for l in lines for x in l.split("\t")[:2]})
-    cut = ids[len(ids) // 2]
     edge_file = tmp_path / "in_parGraph.txt"
-    with open(edge_file, "w") as f:
-        for l in lines:
-            a, b = (int(x) for x in l.split("\t")[:2])
-            if not split:
-                f.write(l + ",2\n")
-            elif a < cut or b < cut:
-                f.write(l + ("," + ("2" if (a < cut and b < cut) else "0" if a < cut else "1")) + "\n")
+    n_lines = gu.partial_edge_file(name, split, edge_file)
     ours, ref, stock = str(tmp_path / "ours.txt"), str(tmp_path / "ref.txt"), str(tmp_path / "stock.txt")
     _run_ps(os.path.join(BIN, "parsimplify"), edge_file, ours, 30, 4)
-    _run_ps(REF_PS_INITLEN, edge_file, ref, 30, 2)
-    a, b = _par_lines(ours), _par_lines(ref)
-    assert a == b
-    assert len(a) < len(lines)  # something was contracted
-    _run_ps(REF_PS, edge_file, stock, 30, 1)
-    s1, a1 = _par_lines(stock, True), _par_lines(ours, True)
-    assert len(set(s1) ^ set(a1)) <= max(4, len(a1) // 50)
+    a = _par_lines(ours)
+    gu.check_recorded_par_lines(name, split, a)
+    assert len(a) < n_lines  # something was contracted
+    if os.path.exists(REF_PS_INITLEN):
+        _run_ps(REF_PS_INITLEN, edge_file, ref, 30, 2)
+        assert a == _par_lines(ref)
+    if os.path.exists(REF_PS):
+        _run_ps(REF_PS, edge_file, stock, 30, 1)
+        s1, a1 = _par_lines(stock, True), _par_lines(ours, True)
+        assert len(set(s1) ^ set(a1)) <= max(4, len(a1) // 50)
 
 
 @pytest.mark.gpu

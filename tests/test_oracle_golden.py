@@ -77,15 +77,19 @@ def test_parse_records_fasta_fastq():
         pyoracle.parse_records(b"ACGT\n")
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(not refrun.available(), reason="reference binary not built (make -C oracle ref)")
 def test_oracle_vs_live_reference_small(tmp_path):
-    """live check against the real reference where it is available (build container / GPU box with the prebuilt binary)"""
+    """the real reference on a small generated input: its recorded output (tests/golden/recorded.json, make_golden.py --live-small),
+    and a live run where the reference binary is built"""
     from disco_amd import readgen
 
     reads = readgen.generate_reads(readgen.GenSpec.coverage(seed=2024, n_reads=1500, read_len=90, cov=20.0, len_max=150))
-    fa = str(tmp_path / "r.fasta")
-    readgen.write_fasta(fa, reads)
-    ref = refrun.run_reference([fa], 40, threads=1, workdir=str(tmp_path))
     ce, cc, _ = pyoracle.oracle_canonical(reads, np.arange(1, len(reads) + 1), 40)
-    assert np.array_equal(ce, ref["edges"]) and np.array_equal(cc, ref["contained"])
+    r = gu.RECORDED["live_1500"]
+    assert (len(ce), len(cc)) == (r["n_edges"], r["n_contained"]) and len(ce) > 100 and len(cc) > 100
+    assert pyoracle.digest(pyoracle.edges_text(ce)) == r["edges_sha256"]
+    assert pyoracle.digest(pyoracle.contained_text(cc)) == r["contained_sha256"]
+    if refrun.available():
+        fa = str(tmp_path / "r.fasta")
+        readgen.write_fasta(fa, reads)
+        ref = refrun.run_reference([fa], 40, threads=1, workdir=str(tmp_path))
+        assert np.array_equal(ce, ref["edges"]) and np.array_equal(cc, ref["contained"])

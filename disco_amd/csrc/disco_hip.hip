@@ -155,6 +155,16 @@ struct DevArena {
     std::map<size_t, size_t> live; /* offset -> bytes of every block handed out */
 };
 
+/* A device buffer the context owns: the pointer and the elements it was allocated with, which is what release gives back to hbm_bytes.
+ * It reads as a plain pointer. Only ensure / ensure_keep / release / adopt / disown (below) change it: frees stay ordered with the
+ * streams and the arena, so there is no destructor. */
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    u64 cap = 0;
+    operator T *() const { return p; }
+};
+
 struct disco_ctx {
     int device = 0;
     disco_params prm{};
@@ -169,8 +179,10 @@ struct disco_ctx {
     /* reads */
     u64 n = 0;
     int S = 0;
-    u64 *d_reads = nullptr;
-    u16 *d_len = nullptr;
+    u64 *d_reads = nullptr; /* what the kernels read: reads_own, or the caller's table (disco_adopt_reads) */
+    u16 *d_len = nullptr;   /* ... len_own, or the caller's lengths */
+    DevBuf<u64> reads_own;
+    DevBuf<u16> len_own;
     bool reads_owned = false;
     std::vector<uint16_t> h_len; /* lazily mirrored for result decoding */
     bool h_len_ok = false;       /* h_len holds the lengths of the current reads */
@@ -185,26 +197,23 @@ struct disco_ctx {
     u32 job_short_max = 0;
     int S_ext = 0;
     u64 n_long = 0;
-    u64 reads_rows = 0; /* rows d_reads was allocated with (two classes: n + n_long) */
-    u64 *d_full = nullptr;
-    u32 *d_ovf = nullptr, *d_long_ids = nullptr;
+    DevBuf<u64> d_full;
+    DevBuf<u32> d_ovf, d_long_ids;
     u32 max_len_all = 0; /* longest read of the set (max_len: of the short class) */
     int tailb = 0;
-    u32 *d_lpos = nullptr, *d_n_list = nullptr; /* the long reads' candidate rows of the pass (class_take_rows_kernel) */
-    uint2 *d_linfo = nullptr;
-    ulonglong2 *d_lmeta = nullptr;
+    DevBuf<u32> d_lpos, d_n_list; /* the long reads' candidate rows of the pass (class_take_rows_kernel) */
+    DevBuf<uint2> d_linfo;
+    DevBuf<ulonglong2> d_lmeta;
 
     /* index */
     u64 T = 0;
     int bshift = 0;
-    u32 *d_bkt = nullptr;
-    u64 *d_ent = nullptr;
-    ulonglong2 *d_rec = nullptr; /* {key, record}[2n] scratch of the index build */
-    u64 rec_cap = 0;
+    DevBuf<u32> d_bkt;
+    DevBuf<u64> d_ent;
+    DevBuf<ulonglong2> d_rec; /* {key, record}[2n] scratch of the index build */
 
     /* scan temporaries */
-    u64 *d_tile = nullptr;
-    size_t tile_cap = 0;
+    DevBuf<u64> d_tile;
     u64 *d_total = nullptr;
 
     /* counters */
@@ -213,32 +222,28 @@ struct disco_ctx {
     u64 h_ctr[CTR_COUNT] = {0};
 
     /* probe */
-    u64 *d_best = nullptr;
-    u64 *d_hits = nullptr;
-    u64 hits_cap = 0;
+    DevBuf<u64> d_best;
+    DevBuf<u64> d_hits;
     u64 hits_used = 0; /* high-water mark of the hit buffer after the probe: what lies behind it is free */
     u64 *d_bump = nullptr;
-    u64 *d_row_start = nullptr;
-    u32 *d_row_cnt = nullptr;
-    u64 *d_big_list = nullptr;
-    u32 *d_big_cnt = nullptr;
+    DevBuf<u64> d_row_start;
+    DevBuf<u32> d_row_cnt;
+    DevBuf<u64> d_big_list; /* (list and counts grow together: grow_big_lists) */
+    DevBuf<u32> d_big_cnt;
     u32 *d_n_big = nullptr;
     /* minimizer runs of the reads [runs_lo, runs_lo + runs_n) (index_runs_kernel -> probe_runs_kernel): runs_lpr u32 words per read
      * (16: up to 32 runs, reads of up to 128 windows; 32: up to 64 runs, 256 windows), 0 = the index pass left none */
-    u32 *d_runs = nullptr;
-    u64 runs_cap = 0, runs_lo = 0, runs_n = 0;
+    DevBuf<u32> d_runs;
+    u64 runs_lo = 0, runs_n = 0;
     int runs_lpr = 0;
-    u64 *d_slow_list = nullptr; /* reads whose run list is unusable (ties, too many runs): probe_kernel<2> */
+    DevBuf<u64> d_slow_list; /* reads whose run list is unusable (ties, too many runs): probe_kernel<2> */
     u32 *d_n_slow = nullptr;
-    u32 slow_cap = 0;
-    u32 big_cap = 0;
     u64 big_rows = 0, slow_rows = 0;
-    const u64 *d_order = nullptr; /* a caller's processing order of the query range (plain read ids), or null */
-    const u64 *d_order_used = nullptr; /* what the last probe walked: packed entries (ORDER_MAKE) in d_order_own, or null = file order */
+    const u64 *d_order = nullptr; /* not owned: a caller's processing order of the query range (plain read ids), or null */
+    const u64 *d_order_used = nullptr; /* not owned: what the last probe walked — packed entries (ORDER_MAKE) in d_order_own, or null = file order */
     bool order_external = false;
-    u32 *d_ocnt = nullptr, *d_okey = nullptr, *d_oslot = nullptr;
-    u64 *d_order_own = nullptr;
-    u64 okey_cap = 0, oslot_cap = 0, order_cap = 0, ocnt_cap = 0;
+    DevBuf<u32> d_ocnt, d_okey, d_oslot;
+    DevBuf<u64> d_order_own;
     /* the grouping's counting pass ran inside the index pass, for the reads [lo, hi) with 2^bits buckets (d_ocnt holds the counts,
      * d_oslot the slots): the next disco_probe over exactly that range skips its own */
     bool order_counted = false;
@@ -250,37 +255,33 @@ struct disco_ctx {
     /* contained rows on their way to the host while the pass goes on (disco_mark_contained -> disco_fetch_contained) */
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_crows = nullptr;
-    u32 *d_cpos = nullptr, *d_crow_id = nullptr;
-    u64 *d_crow_key = nullptr;
-    u64 cpos_cap = 0, crow_cap = 0;
-    u64 *d_tile2 = nullptr, *d_total2 = nullptr; /* scan temporaries of the side stream */
-    size_t tile2_cap = 0;
-    void *h_crows = nullptr; /* pinned, per order (by id, then grouped): keys u64[crows_hcap], ids u32[crows_hcap], lengths u32[crows_hcap] */
-    u32 *d_crow_len = nullptr; /* [crow_cap] len2 | len1 << 16 of the rows about to leave */
+    DevBuf<u32> d_cpos, d_crow_id; /* (d_crow_id / _key / _len grow together) */
+    DevBuf<u64> d_crow_key;
+    DevBuf<u64> d_tile2; /* scan temporaries of the side stream */
+    u64 *d_total2 = nullptr;
+    /* pinned, per order (by id, then grouped): keys u64[crows_hcap], ids u32[crows_hcap], lengths u32[crows_hcap] — an allocation of its
+     * own, or (crows_in_ring) not owned: the input stage's ring h_ring */
+    void *h_crows = nullptr;
+    DevBuf<u32> d_crow_len; /* len2 | len1 << 16 of the rows about to leave */
     u64 crows_hcap = 0, crows_n = 0;
     bool crows_pending = false; /* the rows of the CURRENT flags are on their way / in h_crows */
     bool crows_in_ring = false; /* h_crows is the input stage's pinned ring (h_ring), not an allocation of its own */
-    u32 *d_cgrp_cur = nullptr, *d_cgrp_id = nullptr; /* the same rows grouped by containing read (disco_fetch_contained_grouped) */
-    u64 *d_cgrp_key = nullptr, *d_cgrp_big = nullptr;
-    u64 cgrp_cur_cap = 0, cgrp_cap = 0;
+    DevBuf<u32> d_cgrp_cur, d_cgrp_id; /* the same rows grouped by containing read (disco_fetch_contained_grouped) */
+    DevBuf<u64> d_cgrp_key, d_cgrp_big;
     u64 h_cgrp_big = 0;
     bool cgrp_pending = false;
     /* disco_fetch_edges: the compacted edges before they travel (kept across passes) */
-    u32 *d_fetch_src = nullptr;
-    u64 *d_fetch_ent = nullptr;
-    u64 fetch_cap = 0;
+    DevBuf<u32> d_fetch_src;
+    DevBuf<u64> d_fetch_ent;
     /* input stage on the GPU (disco_ingest_fasta): what disco_ingest_fetch hands to the host afterwards */
-    u32 *d_rec_of_read = nullptr;
-    u64 rec_of_read_cap = 0;
+    DevBuf<u32> d_rec_of_read;
     std::vector<u64> ingest_id_base, ingest_rec_base; /* per file: first read id, records before the file */
     u64 ingest_n = 0;
     void *h_ring = nullptr; /* pinned: two halves of the text staging ring */
     std::vector<u64> text_off; /* disco_format_edges: byte range of every file inside d_text */
-    u8 *d_ingest = nullptr; /* the input stage's own arena (text, record arrays) when the hit buffer is allocated NEXT to it ... */
-    u64 ingest_cap = 0;
+    DevBuf<u8> d_ingest; /* the input stage's own arena (text, record arrays) when the hit buffer is allocated NEXT to it ... */
     std::thread hits_prealloc; /* ... by this thread, while the files travel and the filter runs (settle_hits_prealloc) */
-    u64 *prealloc_ptr = nullptr;
-    u64 prealloc_cap = 0;
+    DevBuf<u64> prealloc; /* (hipMalloc of that thread: not in hbm_bytes until settle_hits_prealloc adopts it) */
     size_t ring_half = 0;
     hipEvent_t ev_ring[2] = {nullptr, nullptr};
     hipStream_t copy_stream = nullptr; /* disco_upload_reads: the chunks of the host buffer travel here */
@@ -288,70 +289,63 @@ struct disco_ctx {
     bool index_counted = false; /* disco_upload_reads ran the index's count pass behind its copies: disco_build_index starts at the scan */
     u64 order_counted_lo = 0, order_counted_hi = 0;
     int order_counted_bits = 0;
-    u32 *d_asked = nullptr; /* multi-GPU flow: one bit per node — its row has been asked for in this pass (tr_request_*_kernel) */
-    u64 asked_cap = 0;
+    DevBuf<u32> d_asked; /* multi-GPU flow: one bit per node — its row has been asked for in this pass (tr_request_*_kernel) */
     u64 order_q_lo = 0, order_q_hi = 0;
-    ulonglong2 *d_meta_ord = nullptr; /* per-read headers by position in the processing order (probe -> verify) */
-    u64 meta_cap = 0;
+    DevBuf<ulonglong2> d_meta_ord; /* per-read headers by position in the processing order (probe -> verify) */
     u64 dropped_local = 0;
     ProbeRare h_probe_rare;
-    ProbeRare *d_probe_rare = nullptr;
+    DevBuf<ProbeRare> d_probe_rare;
     u32 max_len = 0, min_len = 0; /* longest / shortest read (validate_reads) */
     bool two_pass_last = false;    /* the last probe verified in two passes */
     bool contained_done = false;   /* multi-GPU pass: the containment exchange already ran between the two verify passes */
 
     /* containment */
-    u8 *d_contained = nullptr;
-    u64 *d_cbits = nullptr; /* one bit per read */
-    u64 *d_dropbits = nullptr; /* one bit per read: its edge selection dropped a verified hit; valid for reads [drop_lo, drop_hi) */
-    u64 *d_drop_node = nullptr, *d_drop_key = nullptr; /* exact overlaps: the dropped hits themselves (EdgeSelArgs.drop_node), DROP_LIST_CAP items */
+    DevBuf<u8> d_contained;
+    DevBuf<u64> d_cbits; /* one bit per read */
+    DevBuf<u64> d_dropbits; /* one bit per read: its edge selection dropped a verified hit; valid for reads [drop_lo, drop_hi) */
+    DevBuf<u64> d_drop_node, d_drop_key; /* exact overlaps: the dropped hits themselves (EdgeSelArgs.drop_node), DROP_LIST_CAP items */
     u64 n_drop_items = 0;                              /* how many the last selection recorded (or would have: > DROP_LIST_CAP = list useless) */
     u64 drop_lo = 0, drop_hi = 0;
     u64 n_contained = 0;
 
     /* edges */
-    u64 *d_adj_ref = nullptr; /* [n] position | degree << 40 */
-    u64 *d_adj = nullptr;     /* entries: the hit buffer itself (single GPU) or d_adj_own (imported / merged, node-ordered) */
-    u64 *d_adj_own = nullptr; /* kept across passes: re-allocating GBs every pass costs more than the kernels */
-    u64 *d_adj_spare = nullptr; /* the rebuilding merge writes here and swaps: its 9 GB at 50 M reads are not allocated and freed per pass */
-    u64 adj_spare_cap = 0;
-    u64 *d_start_tmp = nullptr; /* [n+1] scan scratch of export / import */
+    DevBuf<u64> d_adj_ref; /* [n] position | degree << 40 */
+    u64 *d_adj = nullptr;     /* not owned: the entries — the hit buffer itself (single GPU) or d_adj_own (imported / merged, node-ordered) */
+    DevBuf<u64> d_adj_own; /* kept across passes: re-allocating GBs every pass costs more than the kernels */
+    DevBuf<u64> d_adj_spare; /* the rebuilding merge writes here and swaps: its 9 GB at 50 M reads are not allocated and freed per pass */
+    DevBuf<u64> d_start_tmp; /* [n+1] scan scratch of export / import */
     u64 adj_total = 0; /* directed edges the context currently addresses */
-    u64 adj_cap = 0, flag_cap = 0, out_cap = 0, valid_cap = 0, bkt_cap = 0, ent_cap = 0; /* buffers are kept across passes */
     bool flags_pending = false; /* sharded flow: gathered flag bytes wait to be OR-ed into the entries */
     bool adj_imported = false;
     u64 adj_span = 0;          /* size of the position space of d_adj in the sharded flow (compact: adj_total, padded: world*max) */
     bool half_complete = false; /* half/hcnt hold the survivor lists of ALL nodes */
-    u64 start_cap = 0;
-    u32 *d_extra_cnt = nullptr;
-    u64 *d_extra_node = nullptr, *d_extra_key = nullptr;
+    DevBuf<u32> d_extra_cnt;
+    DevBuf<u64> d_extra_node, d_extra_key; /* (grow together) */
     u32 *d_n_extra = nullptr;
-    u32 extra_cap = 0;
     u32 n_extra = 0;
     u64 asym_local = 0;
     u64 dropped = 0; /* hits edge selection dropped in the local query range (0 => the selected edges are symmetric) */
 
     /* reduction */
-    u8 *d_flag = nullptr;
-    u64 *d_half = nullptr; /* [n][HALF_CAP] */
-    u32 *d_hcnt = nullptr; /* [n] */
+    DevBuf<u64> d_half; /* [n][HALF_CAP] */
+    DevBuf<u32> d_hcnt; /* [n] */
     bool use_half = false;
-    u64 *d_wide = nullptr; /* nodes with more than HALF_CAP surviving edges */
-    u32 *d_n_wide = nullptr;
-    u32 wide_cap = 0, n_wide = 0;
-    u8 *d_out_valid = nullptr;
-    u64 *d_out_pos = nullptr;
+    DevBuf<u64> d_wide; /* nodes with more than HALF_CAP surviving edges */
+    DevBuf<u32> d_n_wide;
+    u32 n_wide = 0;
+    DevBuf<u8> d_out_valid; /* (with d_out_pos: sized together) */
+    DevBuf<u64> d_out_pos;
     u64 *h_stage = nullptr; /* pinned: two halves of {sources, entries} for the chunked copy-out of disco_fetch_edges */
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
     /* chain contraction (disco_contract_chains): composite edges, their links, absorbed flag per edge in fetch order */
-    ChainEdgeOut *d_ch_comp = nullptr;
-    ChainLinkOut *d_ch_links = nullptr;
-    u8 *d_ch_dead = nullptr;
-    u64 ch_comp_n = 0, ch_links_n = 0, ch_edges_n = 0, ch_comp_cap = 0, ch_links_cap = 0, ch_dead_cap = 0;
+    DevBuf<ChainEdgeOut> d_ch_comp;
+    DevBuf<ChainLinkOut> d_ch_links;
+    DevBuf<u8> d_ch_dead;
+    u64 ch_comp_n = 0, ch_links_n = 0, ch_edges_n = 0;
     bool ch_ready = false;
-    char *d_text = nullptr; /* disco_format_edges: the edge lines of all files, file after file */
-    u64 text_cap = 0, text_bytes = 0;
-    u64 *d_out_src = nullptr, *d_out_ent = nullptr;
+    DevBuf<char> d_text; /* disco_format_edges: the edge lines of all files, file after file */
+    u64 text_bytes = 0;
+    DevBuf<u64> d_out_src, d_out_ent; /* (grow together) */
     u64 out_used = 0; /* chunk slots written by the emission (survivors + ~0 tails) */
     u64 n_out = 0;
 
@@ -372,42 +366,34 @@ struct disco_ctx {
     u64 n_alloc = 0;    /* rows of the per-read tables (n on one GPU, world * per in the multi-GPU flow) */
     bool part_index = false;   /* the current multi-GPU pass keeps the index partitioned (DISCO_DIST_KEEP_INDEX_PARTITIONED) */
     u64 part_blo = 0, part_bhi = 0, part_nrec = 0; /* this rank's bucket range and records */
-    u64 *d_pq_start = nullptr; /* scan scratch of the lookup exchange */
-    u64 pq_start_cap = 0;
+    DevBuf<u64> d_pq_start; /* scan scratch of the lookup exchange */
     bool dist_reads = false;   /* the read table was set through disco_dist_*: rows [q_lo, q_hi) are this rank's */
     bool dist_active = false;  /* the current pass is a multi-GPU pass in the regular regime (emission judges local pairs only) */
-    u64 *d_route = nullptr;    /* [2 * DIST_MAX_WORLD] counters / cursors of the routing kernels */
-    ulonglong2 *d_x16a = nullptr, *d_x16b = nullptr; /* 16-byte items: send (partitioned) / receive */
-    u64 x16a_cap = 0, x16b_cap = 0;
-    u32 *d_req_flat = nullptr, *d_req_s = nullptr, *d_req_r = nullptr; /* row requests: flat list, partitioned, received */
-    u64 req_flat_cap = 0, req_s_cap = 0, req_r_cap = 0;
-    u32 *d_rdeg_s = nullptr, *d_rdeg_r = nullptr, *d_rdata_s = nullptr; /* responses: degrees out / back, entries out */
-    u64 rdeg_s_cap = 0, rdeg_r_cap = 0, rdata_s_cap = 0;
-    u64 *d_rpos = nullptr;
-    u64 rpos_cap = 0;
-    u32 *d_nadj32_own = nullptr; /* rows fetched from other ranks as they arrive (4-byte entries), before rows_place_kernel puts them behind the own rows */
-    u64 nadj_cap = 0, nadj_used = 0; /* nadj_used: entries of fetched rows behind the own rows so far */
-    u32 *d_deg_tmp = nullptr;
-    u64 deg_tmp_cap = 0;
-    u64 *d_list_n = nullptr; /* length of the flat list being built */
-    u64 *d_dense = nullptr; /* the job's reads at W words per row, for the all-gather (rows of the table are padded to 64 bytes) */
-    u64 dense_cap = 0;
-    ulonglong2 *d_push_r = nullptr; /* received half-edge pushes (alias of d_x16b while a pass is in flight) */
+    DevBuf<u64> d_route;    /* [2 * DIST_MAX_WORLD] counters / cursors of the routing kernels */
+    DevBuf<ulonglong2> d_x16a, d_x16b; /* 16-byte items: send (partitioned) / receive */
+    DevBuf<u32> d_req_flat, d_req_s, d_req_r; /* row requests: flat list, partitioned, received */
+    DevBuf<u32> d_rdeg_s, d_rdeg_r, d_rdata_s; /* responses: degrees out / back, entries out */
+    DevBuf<u64> d_rpos;
+    DevBuf<u32> d_nadj32_own; /* rows fetched from other ranks as they arrive (4-byte entries), before rows_place_kernel puts them behind the own rows */
+    u64 nadj_used = 0; /* entries of fetched rows behind the own rows so far */
+    DevBuf<u32> d_deg_tmp;
+    DevBuf<u64> d_list_n; /* length of the flat list being built */
+    DevBuf<u64> d_dense; /* the job's reads at W words per row, for the all-gather (rows of the table are padded to 64 bytes) */
+    ulonglong2 *d_push_r = nullptr; /* not owned: received half-edge pushes (d_x16b while a pass is in flight) */
     u64 n_push_r = 0;
     /* ranks own loci: the reads — graph nodes — of a pass are dealt to the ranks by their read-level minimizer;
      * [home_lo, home_hi) is the id range the rank's reads arrived in (and the range whose containment flags it fixes). While such a pass
      * runs, q_lo / q_hi are POSITIONS in the rank's own list: [0, n_own) of d_order_own. */
     bool loci = false;
     bool runs_by_pos = false; /* d_runs is indexed by position in the processing order, not by read id */
-    u8 *d_otab = nullptr;     /* [n_alloc] owner of every read */
-    u32 *d_own_ids = nullptr; /* scratch: the own reads before they are grouped */
-    u64 own_ids_cap = 0, n_own = 0;
+    DevBuf<u8> d_otab;     /* [n_alloc] owner of every read */
+    DevBuf<u32> d_own_ids; /* scratch: the own reads before they are grouped */
+    u64 n_own = 0;
     u64 home_lo = 0, home_hi = 0;
     u64 home_probes = 0; /* sum of len - k over the home range */
     /* the containment keys' reduce-scatter runs behind the pass on the second communicator (dist_mark_contained): whoever touches best[]
      * next waits for ev_keys */
-    u64 *d_cb_all = nullptr; /* the ranks' "has a key" bitmaps, rank after rank */
-    u64 cb_all_cap = 0;
+    DevBuf<u64> d_cb_all; /* the ranks' "has a key" bitmaps, rank after rank */
     hipEvent_t ev_keys = nullptr, ev_keys_go = nullptr;
     bool keys_pending = false;
     disco_dist_info dinfo{};
@@ -497,22 +483,79 @@ static void dev_free(disco_ctx *c, T **p, size_t count)
             tl_pass.dev_frees++;
             (void)hipFree(*p);
         }
-        size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-        c->hbm_bytes = c->hbm_bytes >= bytes ? c->hbm_bytes - bytes : 0;
+        c->hbm_bytes -= std::max<size_t>(count, 1) * sizeof(T);
         *p = nullptr;
     }
 }
 
-/* grow-only buffer: reallocate when the need exceeds the capacity (steady-state passes allocate nothing) */
 template <typename T>
-static int ensure_cap(disco_ctx *c, T **p, u64 *cap, u64 need)
+static void release(disco_ctx *c, DevBuf<T> &b)
 {
-    if (*p && need <= *cap) return DISCO_OK;
-    dev_free(c, p, *cap);
-    *cap = 0;
-    CHK(dev_alloc(c, p, need));
-    *cap = std::max<u64>(need, 1);
+    dev_free(c, &b.p, b.cap);
+    b.cap = 0;
+}
+
+/* grow-only: reallocate when the need exceeds the capacity (steady-state passes allocate nothing) */
+template <typename T>
+static int ensure(disco_ctx *c, DevBuf<T> &b, u64 need)
+{
+    if (b.p && need <= b.cap) return DISCO_OK;
+    release(c, b);
+    CHK(dev_alloc(c, &b.p, need));
+    b.cap = std::max<u64>(need, 1);
     return DISCO_OK;
+}
+
+/* buffers that grow together (the kernels take one capacity for all of them): when any holds fewer than `need` elements, all are freed
+ * and then allocated with `size` elements each, in order (the arena's first fit sees the frees before the allocations); a failure leaves
+ * none of them allocated, so the next call allocates them all again */
+template <typename... T>
+static int ensure_group(disco_ctx *c, u64 need, u64 size, DevBuf<T> &...b)
+{
+    if (((need <= b.cap) && ...)) return DISCO_OK;
+    (release(c, b), ...);
+    int rc = DISCO_OK;
+    ((rc = rc == DISCO_OK ? ensure(c, b, size) : rc), ...);
+    if (rc != DISCO_OK) (release(c, b), ...);
+    return rc;
+}
+
+/* b moves to a new allocation of ncap elements that starts with its first `used` ones */
+template <typename T>
+static int move_keep(disco_ctx *c, DevBuf<T> &b, u64 ncap, u64 used)
+{
+    DevBuf<T> q;
+    CHK(ensure(c, q, ncap));
+    if (b.p && used) HIPCHK(c, hipMemcpyAsync(q.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    release(c, b);
+    b = q;
+    return DISCO_OK;
+}
+
+/* grow-only buffer that keeps its first `used` elements */
+template <typename T>
+static int ensure_keep(disco_ctx *c, DevBuf<T> &b, u64 need, u64 used)
+{
+    if (b.p && need <= b.cap) return DISCO_OK;
+    return move_keep(c, b, need + need / 8, used);
+}
+
+/* hand-overs: b (empty) takes memory allocated outside dev_alloc, counted from now on; disown gives b's memory up without freeing it */
+template <typename T>
+static void adopt(disco_ctx *c, DevBuf<T> &b, DevBuf<T> from)
+{
+    b = from;
+    c->hbm_bytes += b.cap * sizeof(T);
+}
+
+template <typename T>
+static T *disown(disco_ctx *c, DevBuf<T> &b)
+{
+    T *p = b.p;
+    c->hbm_bytes -= b.cap * sizeof(T);
+    b = DevBuf<T>();
+    return p;
 }
 
 static DiscoView view(const disco_ctx *c)
@@ -619,18 +662,14 @@ static int zero_counter(disco_ctx *c, int idx)
 /* exclusive scan of in[0..n) into out[0..n) (+ out[n] = total when write_total); returns total through *total_host
  * when non-null (this synchronises the stream) */
 template <typename InT, typename OutT>
-static int scan_exclusive_on(disco_ctx *c, hipStream_t st, u64 **tile, size_t *tile_cap, u64 *total, const InT *in, u64 n, OutT *out, bool write_total, u64 *total_host)
+static int scan_exclusive_on(disco_ctx *c, hipStream_t st, DevBuf<u64> &tile, u64 *total, const InT *in, u64 n, OutT *out, bool write_total, u64 *total_host)
 {
     u64 nt = (n + SCAN_TILE - 1) / SCAN_TILE;
     if (nt == 0) nt = 1;
-    if (nt > *tile_cap) {
-        dev_free(c, tile, *tile_cap);
-        CHK(dev_alloc(c, tile, nt));
-        *tile_cap = nt;
-    }
-    hipLaunchKernelGGL((scan_tile_sums_kernel<InT>), dim3((unsigned)nt), dim3(SCAN_BLOCK), 0, st, in, n, *tile);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, st, *tile, nt, total);
-    hipLaunchKernelGGL((scan_apply_kernel<InT, OutT>), dim3((unsigned)nt), dim3(SCAN_BLOCK), 0, st, in, n, *tile, out);
+    CHK(ensure(c, tile, nt));
+    hipLaunchKernelGGL((scan_tile_sums_kernel<InT>), dim3((unsigned)nt), dim3(SCAN_BLOCK), 0, st, in, n, tile.p);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, st, tile.p, nt, total);
+    hipLaunchKernelGGL((scan_apply_kernel<InT, OutT>), dim3((unsigned)nt), dim3(SCAN_BLOCK), 0, st, in, n, tile.p, out);
     if (write_total) hipLaunchKernelGGL((scan_write_total_kernel<OutT>), dim3(1), dim3(1), 0, st, total, out + n);
     HIPCHK(c, hipGetLastError());
     if (total_host) {
@@ -643,7 +682,7 @@ static int scan_exclusive_on(disco_ctx *c, hipStream_t st, u64 **tile, size_t *t
 template <typename InT, typename OutT>
 static int scan_exclusive(disco_ctx *c, const InT *in, u64 n, OutT *out, bool write_total, u64 *total_host)
 {
-    return scan_exclusive_on<InT, OutT>(c, c->stream, &c->d_tile, &c->tile_cap, c->d_total, in, n, out, write_total, total_host);
+    return scan_exclusive_on<InT, OutT>(c, c->stream, c->d_tile, c->d_total, in, n, out, write_total, total_host);
 }
 
 static void free_graph_state(disco_ctx *c)
@@ -655,93 +694,78 @@ static void free_graph_state(disco_ctx *c)
         c->keys_pending = false;
         if (c->ev_keys) (void)hipEventSynchronize(c->ev_keys);
     }
-    dev_free(c, &c->d_bkt, c->bkt_cap);
-    dev_free(c, &c->d_ent, c->ent_cap);
-    dev_free(c, &c->d_rec, c->rec_cap);
-    c->bkt_cap = c->ent_cap = c->rec_cap = 0;
-    dev_free(c, &c->d_best, c->n_alloc);
-    dev_free(c, &c->d_hits, c->hits_cap);
-    c->hits_cap = 0;
-    dev_free(c, &c->d_row_start, c->n);
-    dev_free(c, &c->d_row_cnt, c->n);
-    dev_free(c, &c->d_big_list, c->big_cap);
-    dev_free(c, &c->d_big_cnt, c->big_cap);
-    c->big_cap = 0;
-    dev_free(c, &c->d_slow_list, c->slow_cap);
-    c->slow_cap = 0;
-    dev_free(c, &c->d_runs, c->runs_cap);
-    c->runs_cap = c->runs_n = 0;
+    release(c, c->d_bkt);
+    release(c, c->d_ent);
+    release(c, c->d_rec);
+    release(c, c->d_best);
+    release(c, c->d_hits);
+    release(c, c->d_row_start);
+    release(c, c->d_row_cnt);
+    release(c, c->d_big_list);
+    release(c, c->d_big_cnt);
+    release(c, c->d_slow_list);
+    release(c, c->d_runs);
+    c->runs_n = 0;
     c->runs_lpr = 0;
-    dev_free(c, &c->d_contained, c->n_alloc);
-    dev_free(c, &c->d_cbits, c->n_alloc / 64 + 1);
-    dev_free(c, &c->d_dropbits, c->n_alloc / 64 + 1);
-    dev_free(c, &c->d_drop_node, DROP_LIST_CAP);
-    dev_free(c, &c->d_drop_key, DROP_LIST_CAP);
-    dev_free(c, &c->d_adj_ref, c->n);
-    dev_free(c, &c->d_adj_own, c->adj_cap);
-    dev_free(c, &c->d_adj_spare, c->adj_spare_cap);
-    dev_free(c, &c->d_start_tmp, c->start_cap);
-    c->start_cap = 0;
-    dev_free(c, &c->d_ocnt, c->ocnt_cap);
-    dev_free(c, &c->d_okey, c->okey_cap);
-    dev_free(c, &c->d_meta_ord, c->meta_cap);
-    dev_free(c, &c->d_asked, c->asked_cap);
-    c->meta_cap = 0;
-    dev_free(c, &c->d_oslot, c->oslot_cap);
-    dev_free(c, &c->d_order_own, c->order_cap);
-    c->okey_cap = c->oslot_cap = c->order_cap = c->ocnt_cap = 0;
+    release(c, c->d_contained);
+    release(c, c->d_cbits);
+    release(c, c->d_dropbits);
+    release(c, c->d_drop_node);
+    release(c, c->d_drop_key);
+    release(c, c->d_adj_ref);
+    release(c, c->d_adj_own);
+    release(c, c->d_adj_spare);
+    release(c, c->d_start_tmp);
+    release(c, c->d_ocnt);
+    release(c, c->d_okey);
+    release(c, c->d_meta_ord);
+    release(c, c->d_asked);
+    release(c, c->d_oslot);
+    release(c, c->d_order_own);
     c->d_order_used = nullptr;
     c->d_adj = nullptr;
-    dev_free(c, &c->d_extra_cnt, c->n);
-    dev_free(c, &c->d_extra_node, c->extra_cap);
-    dev_free(c, &c->d_extra_key, c->extra_cap);
-    c->extra_cap = 0;
-    dev_free(c, &c->d_flag, c->flag_cap);
-    dev_free(c, &c->d_half, c->n * HALF_CAP);
-    dev_free(c, &c->d_hcnt, c->n);
-    dev_free(c, &c->d_wide, c->wide_cap);
-    dev_free(c, &c->d_n_wide, 1);
-    c->wide_cap = 0;
-    c->adj_total = c->adj_cap = c->adj_spare_cap = c->flag_cap = 0;
-    dev_free(c, &c->d_out_valid, c->valid_cap);
-    dev_free(c, &c->d_ch_comp, c->ch_comp_cap);
-    dev_free(c, &c->d_ch_links, c->ch_links_cap);
-    dev_free(c, &c->d_ch_dead, c->ch_dead_cap);
-    dev_free(c, &c->d_text, c->text_cap);
-    c->text_cap = c->text_bytes = 0;
-    c->ch_comp_cap = c->ch_links_cap = c->ch_dead_cap = 0;
+    release(c, c->d_extra_cnt);
+    release(c, c->d_extra_node);
+    release(c, c->d_extra_key);
+    release(c, c->d_half);
+    release(c, c->d_hcnt);
+    release(c, c->d_wide);
+    release(c, c->d_n_wide);
+    c->adj_total = 0;
+    release(c, c->d_out_valid);
+    release(c, c->d_ch_comp);
+    release(c, c->d_ch_links);
+    release(c, c->d_ch_dead);
+    release(c, c->d_text);
+    c->text_bytes = 0;
     c->ch_ready = false;
-    dev_free(c, &c->d_out_pos, c->valid_cap + 1);
-    dev_free(c, &c->d_out_src, c->out_cap);
-    dev_free(c, &c->d_out_ent, c->out_cap);
-    c->n_out = c->out_cap = c->valid_cap = c->out_used = 0;
+    release(c, c->d_out_pos);
+    release(c, c->d_out_src);
+    release(c, c->d_out_ent);
+    c->n_out = c->out_used = 0;
     c->flags_pending = false;
     c->adj_imported = false;
     c->T = 0;
-    dev_free(c, &c->d_x16a, c->x16a_cap);
-    dev_free(c, &c->d_x16b, c->x16b_cap);
-    dev_free(c, &c->d_req_flat, c->req_flat_cap);
-    dev_free(c, &c->d_req_s, c->req_s_cap);
-    dev_free(c, &c->d_req_r, c->req_r_cap);
-    dev_free(c, &c->d_rdeg_s, c->rdeg_s_cap);
-    dev_free(c, &c->d_rdeg_r, c->rdeg_r_cap);
-    dev_free(c, &c->d_rdata_s, c->rdata_s_cap);
-    dev_free(c, &c->d_rpos, c->rpos_cap);
-    dev_free(c, &c->d_nadj32_own, c->nadj_cap);
-    dev_free(c, &c->d_deg_tmp, c->deg_tmp_cap);
-    dev_free(c, &c->d_dense, c->dense_cap);
-    c->dense_cap = 0;
-    dev_free(c, &c->d_pq_start, c->pq_start_cap);
-    c->pq_start_cap = 0;
-    c->x16a_cap = c->x16b_cap = c->req_flat_cap = c->req_s_cap = c->req_r_cap = c->rdeg_s_cap = c->rdeg_r_cap = c->rdata_s_cap = 0;
-    c->rpos_cap = c->nadj_cap = c->nadj_used = c->deg_tmp_cap = 0;
+    release(c, c->d_x16a);
+    release(c, c->d_x16b);
+    release(c, c->d_req_flat);
+    release(c, c->d_req_s);
+    release(c, c->d_req_r);
+    release(c, c->d_rdeg_s);
+    release(c, c->d_rdeg_r);
+    release(c, c->d_rdata_s);
+    release(c, c->d_rpos);
+    release(c, c->d_nadj32_own);
+    release(c, c->d_deg_tmp);
+    release(c, c->d_dense);
+    release(c, c->d_pq_start);
+    c->nadj_used = 0;
     c->d_push_r = nullptr;
     c->n_push_r = 0;
-    dev_free(c, &c->d_cb_all, c->cb_all_cap);
-    c->cb_all_cap = 0;
-    dev_free(c, &c->d_otab, c->n_alloc);
-    dev_free(c, &c->d_own_ids, c->own_ids_cap);
-    c->own_ids_cap = c->n_own = 0;
+    release(c, c->d_cb_all);
+    release(c, c->d_otab);
+    release(c, c->d_own_ids);
+    c->n_own = 0;
     c->loci = c->runs_by_pos = false;
 }
 
@@ -749,25 +773,23 @@ static void free_graph_state(disco_ctx *c)
  * two_class still false, and the next table must not find a d_ovf sized for this one */
 static void free_long_class(disco_ctx *c)
 {
-    dev_free(c, &c->d_full, c->n_long * (u64)c->S_ext);
-    dev_free(c, &c->d_ovf, c->n_alloc);
-    dev_free(c, &c->d_long_ids, c->n_long);
-    dev_free(c, &c->d_lpos, c->n_long);
-    dev_free(c, &c->d_lmeta, c->n_long);
-    dev_free(c, &c->d_linfo, c->n_long);
-    dev_free(c, &c->d_n_list, 1);
+    release(c, c->d_full);
+    release(c, c->d_ovf);
+    release(c, c->d_long_ids);
+    release(c, c->d_lpos);
+    release(c, c->d_lmeta);
+    release(c, c->d_linfo);
+    release(c, c->d_n_list);
     c->two_class = false;
-    c->n_long = c->reads_rows = 0;
+    c->n_long = 0;
     c->S_ext = 0;
     c->tailb = 0;
 }
 
 static void free_reads(disco_ctx *c)
 {
-    if (c->reads_owned) {
-        dev_free(c, &c->d_reads, (c->reads_rows ? c->reads_rows : c->n_alloc) * (u64)c->S);
-        dev_free(c, &c->d_len, c->n_alloc);
-    }
+    release(c, c->reads_own);
+    release(c, c->len_own);
     free_long_class(c);
     c->d_reads = nullptr;
     c->d_len = nullptr;
@@ -775,6 +797,22 @@ static void free_reads(disco_ctx *c)
     c->h_len.clear();
     c->n = 0;
 }
+
+/* a read table of the context's own: rows of `words` words in all, n_len lengths */
+static int alloc_reads(disco_ctx *c, u64 words, u64 n_len)
+{
+    CHK(ensure(c, c->reads_own, words));
+    c->d_reads = c->reads_own;
+    CHK(ensure(c, c->len_own, n_len));
+    c->d_len = c->len_own;
+    return DISCO_OK;
+}
+
+/* the twin search's extras lists (node and key arrays grow together): the capacity both have, as the kernels take it */
+static u32 extra_cap(const disco_ctx *c) { return (u32)std::min<u64>(std::min(c->d_extra_node.cap, c->d_extra_key.cap), 0xFFFFFFFFull); }
+
+/* the big-item lists (rows / nodes beyond the LDS capacities; fewer than 2^32): list and counts grow together */
+static int grow_big_lists(disco_ctx *c, u64 need) { return ensure_group(c, need, need, c->d_big_list, c->d_big_cnt); }
 
 /* the count pass of the index build over the reads [lo, hi): with the minimizer runs for probe_runs_kernel where the shape of the job
  * allows them — a window of 17 m-mers (min-overlap 40, the default), 64-byte rows (reads up to 256 bases, so a read has at most 256
@@ -848,8 +886,8 @@ static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, In
     int obits = 0;
     if (lo == c->q_lo && hi == c->q_hi && own_order_wanted(c, nloc, &obits) && !getenv("DISCO_NO_ORDER_FUSE")) {
         const u64 order_buckets = 1ull << obits;
-        CHK(ensure_cap(c, &c->d_ocnt, &c->ocnt_cap, order_buckets + 1));
-        CHK(ensure_cap(c, &c->d_oslot, &c->oslot_cap, nloc));
+        CHK(ensure(c, c->d_ocnt, order_buckets + 1));
+        CHK(ensure(c, c->d_oslot, nloc));
         HIPCHK(c, hipMemsetAsync(c->d_ocnt, 0, (order_buckets + 1) * sizeof(u32), c->stream));
         pl->ocnt = c->d_ocnt;
         pl->oslot = c->d_oslot;
@@ -865,7 +903,7 @@ static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, In
     const int nf = v.k - v.m + 1;
     const int lpr = c->S == VERIFY_SW ? runs_lpr_for(c, nf, c->max_len, nloc) : 0;
     if (lpr && nloc) {
-        CHK(ensure_cap(c, &c->d_runs, &c->runs_cap, nloc * (u64)lpr));
+        CHK(ensure(c, c->d_runs, nloc * (u64)lpr));
         c->runs_lpr = lpr;
         c->runs_lo = lo;
         c->runs_n = nloc;
@@ -950,11 +988,11 @@ static int index_begin(disco_ctx *c)
     }
     c->T = T;
     c->bshift = 64 - logT;
-    CHK(ensure_cap(c, &c->d_bkt, &c->bkt_cap, T + 1));
-    CHK(ensure_cap(c, &c->d_ent, &c->ent_cap, 2 * c->n));
+    CHK(ensure(c, c->d_bkt, T + 1));
+    CHK(ensure(c, c->d_ent, 2 * c->n));
     /* {key, record} of both end k-mers of every read, computed once by the count pass and re-read by the fill pass */
-    CHK(ensure_cap(c, &c->d_rec, &c->rec_cap, 2 * c->n));
-    CHK(ensure_cap(c, &c->d_okey, &c->okey_cap, c->n)); /* grouping keys of all reads (disco_probe orders its query range by them) */
+    CHK(ensure(c, c->d_rec, 2 * c->n));
+    CHK(ensure(c, c->d_okey, c->n)); /* grouping keys of all reads (disco_probe orders its query range by them) */
     c->adj_imported = false;
     HIPCHK(c, hipMemsetAsync(c->d_bkt, 0, (T + 1) * sizeof(u32), c->stream));
     return DISCO_OK;
@@ -980,18 +1018,8 @@ static int start_contained_rows(disco_ctx *c, bool grouped)
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_crows, hipEventDisableTiming));
         HIPCHK(c, hipMalloc((void **)&c->d_total2, sizeof(u64)));
     }
-    CHK(ensure_cap(c, &c->d_cpos, &c->cpos_cap, c->n + 1));
-    if (nc > c->crow_cap) {
-        dev_free(c, &c->d_crow_id, c->crow_cap);
-        dev_free(c, &c->d_crow_key, c->crow_cap);
-        dev_free(c, &c->d_crow_len, c->crow_cap);
-        c->crow_cap = 0;
-        const u64 want = nc + nc / 4 + 1024;
-        CHK(dev_alloc(c, &c->d_crow_id, want));
-        CHK(dev_alloc(c, &c->d_crow_key, want));
-        CHK(dev_alloc(c, &c->d_crow_len, want));
-        c->crow_cap = want;
-    }
+    CHK(ensure(c, c->d_cpos, c->n + 1));
+    CHK(ensure_group(c, nc, nc + nc / 4 + 1024, c->d_crow_id, c->d_crow_key, c->d_crow_len));
     if (nc > c->crows_hcap && c->h_ring && !c->crows_in_ring && (u64)c->ring_half * 2 >= (nc + 1024) * 32) {
         /* the pinned ring of the input stage is idle between the input stage and the text output: the rows stage there (pinning
          * 140 MB for them took 0.05 s of the host thread that feeds the pass) */
@@ -1015,7 +1043,7 @@ static int start_contained_rows(disco_ctx *c, bool grouped)
     }
     if (!have_rows) {
     /* (the flags are complete: disco_mark_contained synchronised the context's stream) */
-    CHK((scan_exclusive_on<u8, u32>(c, c->aux_stream, &c->d_tile2, &c->tile2_cap, c->d_total2, c->d_contained, c->n, c->d_cpos, false, nullptr)));
+    CHK((scan_exclusive_on<u8, u32>(c, c->aux_stream, c->d_tile2, c->d_total2, c->d_contained, c->n, c->d_cpos, false, nullptr)));
     hipLaunchKernelGGL(contain_rows32_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->aux_stream, c->d_best, c->d_contained, c->d_cpos, c->n, c->d_crow_id, c->d_crow_key);
     HIPCHK(c, hipGetLastError());
     u64 *hkey = (u64 *)c->h_crows;
@@ -1031,21 +1059,13 @@ static int start_contained_rows(disco_ctx *c, bool grouped)
     }
     /* ... and, on request, once more in the order of the contained-read files (crow_* kernels), behind the first copy on the same stream */
     if (grouped && !c->cgrp_pending) {
-        CHK(ensure_cap(c, &c->d_cgrp_cur, &c->cgrp_cur_cap, c->n + 1));
-        if (nc > c->cgrp_cap) {
-            dev_free(c, &c->d_cgrp_id, c->cgrp_cap);
-            dev_free(c, &c->d_cgrp_key, c->cgrp_cap);
-            c->cgrp_cap = 0;
-            const u64 want = nc + nc / 4 + 1024;
-            CHK(dev_alloc(c, &c->d_cgrp_id, want));
-            CHK(dev_alloc(c, &c->d_cgrp_key, want));
-            c->cgrp_cap = want;
-        }
-        if (!c->d_cgrp_big) CHK(dev_alloc(c, &c->d_cgrp_big, 1));
+        CHK(ensure(c, c->d_cgrp_cur, c->n + 1));
+        CHK(ensure_group(c, nc, nc + nc / 4 + 1024, c->d_cgrp_id, c->d_cgrp_key));
+        CHK(ensure(c, c->d_cgrp_big, 1));
         HIPCHK(c, hipMemsetAsync(c->d_cpos, 0, (c->n + 1) * sizeof(u32), c->aux_stream)); /* (the flag scan has served the gather) */
         HIPCHK(c, hipMemsetAsync(c->d_cgrp_big, 0, sizeof(u64), c->aux_stream));
         hipLaunchKernelGGL(crow_count_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->aux_stream, (const u64 *)c->d_crow_key, nc, c->d_cpos);
-        CHK((scan_exclusive_on<u32, u32>(c, c->aux_stream, &c->d_tile2, &c->tile2_cap, c->d_total2, c->d_cpos, c->n + 1, c->d_cgrp_cur, false, nullptr)));
+        CHK((scan_exclusive_on<u32, u32>(c, c->aux_stream, c->d_tile2, c->d_total2, c->d_cpos, c->n + 1, c->d_cgrp_cur, false, nullptr)));
         hipLaunchKernelGGL(crow_place_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->aux_stream, (const u32 *)c->d_crow_id, (const u64 *)c->d_crow_key, nc, c->d_cgrp_cur, c->d_cgrp_id,
                            c->d_cgrp_key);
         hipLaunchKernelGGL(crow_sort_groups_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->aux_stream, c->d_cgrp_id, c->d_cgrp_key, nc, c->d_cgrp_big);
@@ -1091,16 +1111,13 @@ static void settle_hits_prealloc(disco_ctx *c)
 {
     if (!c->hits_prealloc.joinable()) return;
     c->hits_prealloc.join();
-    if (c->prealloc_ptr) {
-        if (c->prealloc_cap > c->hits_cap) {
-            dev_free(c, &c->d_hits, c->hits_cap);
-            c->d_hits = c->prealloc_ptr;
-            c->hits_cap = c->prealloc_cap;
-            c->hbm_bytes += c->prealloc_cap * 8;
+    if (c->prealloc) {
+        if (c->prealloc.cap > c->d_hits.cap) {
+            release(c, c->d_hits);
+            adopt(c, c->d_hits, c->prealloc);
         } else
-            (void)hipFree(c->prealloc_ptr);
-        c->prealloc_ptr = nullptr;
-        c->prealloc_cap = 0;
+            (void)hipFree(c->prealloc.p);
+        c->prealloc = DevBuf<u64>();
     }
 }
 
@@ -1167,7 +1184,7 @@ void disco_destroy(disco_ctx *c)
     (void)hipStreamSynchronize(c->stream);
     free_graph_state(c);
     free_reads(c);
-    dev_free(c, &c->d_tile, c->tile_cap);
+    release(c, c->d_tile);
     (void)hipFree(c->d_ctr);
     (void)hipFree(c->d_total);
     (void)hipFree(c->d_wq);
@@ -1178,9 +1195,9 @@ void disco_destroy(disco_ctx *c)
     (void)hipFree(c->d_n_big);
     (void)hipFree(c->d_n_slow);
     (void)hipFree(c->d_n_extra);
-    dev_free(c, &c->d_probe_rare, 1);
-    dev_free(c, &c->d_route, 2 * DIST_MAX_WORLD);
-    dev_free(c, &c->d_list_n, 1);
+    release(c, c->d_probe_rare);
+    release(c, c->d_route);
+    release(c, c->d_list_n);
     delete c->comm_bulk;
     delete c->comm;
     c->comm = c->comm_bulk = nullptr;
@@ -1192,24 +1209,24 @@ void disco_destroy(disco_ctx *c)
         (void)hipEventDestroy(c->ev_crows);
         (void)hipFree(c->d_total2);
     }
-    dev_free(c, &c->d_tile2, c->tile2_cap);
-    dev_free(c, &c->d_cpos, c->cpos_cap);
-    dev_free(c, &c->d_crow_id, c->crow_cap);
-    dev_free(c, &c->d_crow_key, c->crow_cap);
-    dev_free(c, &c->d_crow_len, c->crow_cap);
-    dev_free(c, &c->d_cgrp_cur, c->cgrp_cur_cap);
-    dev_free(c, &c->d_cgrp_id, c->cgrp_cap);
-    dev_free(c, &c->d_cgrp_key, c->cgrp_cap);
-    dev_free(c, &c->d_cgrp_big, 1);
-    dev_free(c, &c->d_fetch_src, c->fetch_cap);
-    dev_free(c, &c->d_fetch_ent, c->fetch_cap);
+    release(c, c->d_tile2);
+    release(c, c->d_cpos);
+    release(c, c->d_crow_id);
+    release(c, c->d_crow_key);
+    release(c, c->d_crow_len);
+    release(c, c->d_cgrp_cur);
+    release(c, c->d_cgrp_id);
+    release(c, c->d_cgrp_key);
+    release(c, c->d_cgrp_big);
+    release(c, c->d_fetch_src);
+    release(c, c->d_fetch_ent);
     if (c->h_crows && !c->crows_in_ring) (void)hipHostFree(c->h_crows);
     settle_hits_prealloc(c);
-    dev_free(c, &c->d_ingest, c->ingest_cap);
+    release(c, c->d_ingest);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     for (int i = 0; i < 2; i++)
         if (c->ev_ring[i]) (void)hipEventDestroy(c->ev_ring[i]);
-    dev_free(c, &c->d_rec_of_read, c->rec_of_read_cap);
+    release(c, c->d_rec_of_read);
     for (int i = 0; i < 3; i++) {
         if (c->ev_copied[i]) (void)hipEventDestroy(c->ev_copied[i]);
         if (c->ev_unpacked[i]) (void)hipEventDestroy(c->ev_unpacked[i]);
@@ -1412,13 +1429,10 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
     CHK(set_reads_common(c, n, classes ? (uint32_t)VERIFY_SW : dstride, classes ? nullptr : &kept));
     c->reads_owned = true; /* the old table is gone (or kept, and then it was the context's own): whatever is allocated from here on is released by free_reads */
     if (classes) {
-        CHK(dev_alloc(c, &c->d_reads, (n + n_long) * 8));
-        CHK(dev_alloc(c, &c->d_len, n));
+        CHK(alloc_reads(c, (n + n_long) * 8, n));
         CHK(two_class_alloc(c, n_long, (int)dstride, a_smax.load()));
-    } else if (!kept) {
-        CHK(dev_alloc(c, &c->d_reads, n * (u64)dstride));
-        CHK(dev_alloc(c, &c->d_len, n));
-    }
+    } else if (!kept)
+        CHK(alloc_reads(c, n * (u64)dstride, n));
     c->reads_owned = true;
     c->max_len = n ? (classes ? a_smax.load() : a_max.load()) : 0;
     c->max_len_all = n ? a_max.load() : 0;
@@ -1443,12 +1457,12 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
         u64 ring_words = 0; /* words of the largest chunk as it lies on the host */
         for (u64 k = 0; k < n_chunks; k++)
             ring_words = std::max<u64>(ring_words, ragged ? chunk_words[k + 1] - chunk_words[k] : (std::min<u64>(n, (k + 1) * CH) - k * CH) * (u64)stride_words);
-        if (!direct) CHK(ensure_cap(c, &c->d_dense, &c->dense_cap, 3 * ring_words));
-        u64 *woff = nullptr;
-        u32 *nw = nullptr;
+        if (!direct) CHK(ensure(c, c->d_dense, 3 * ring_words));
+        DevBuf<u64> woff;
+        DevBuf<u32> nw;
         if (ragged) { /* word offset of every read: scan of ceil(len / 32) */
-            CHK(dev_alloc(c, &woff, n));
-            CHK(dev_alloc(c, &nw, n));
+            CHK(ensure(c, woff, n));
+            CHK(ensure(c, nw, n));
             hipLaunchKernelGGL(words_per_read_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u16 *)c->d_len, n, nw);
             CHK((scan_exclusive<u32, u64>(c, nw, n, woff, false, nullptr)));
         }
@@ -1502,8 +1516,8 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
                     t_mirror, lapms(), classes ? "two classes of rows" : "one stride", eager ? ", index counted behind the copies" : "");
         if (woff) { /* (read by the unpack kernels on the context's stream) */
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            dev_free(c, &woff, n);
-            dev_free(c, &nw, n);
+            release(c, woff);
+            release(c, nw);
         }
         c->index_counted = eager;
     } else
@@ -1726,7 +1740,7 @@ extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_
             if (f.fd >= 0) close(f.fd);
         for (auto &o : owned) {
             (void)hipFree(o.p);
-            c->hbm_bytes = c->hbm_bytes >= o.bytes ? c->hbm_bytes - o.bytes : 0;
+            c->hbm_bytes -= o.bytes;
         }
         owned.clear();
     };
@@ -1773,45 +1787,34 @@ extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_
         }
         const u64 rest = (total_bytes / 150) * 200 + (4ull << 30); /* the read table and the index next to it */
         if (c->arena.base && !c->comm && c->arena.used == 0 && !c->d_ingest) { /* the last call's arena, idle again: this call's text goes there */
-            c->d_ingest = (u8 *)c->arena.base;
-            c->ingest_cap = c->arena.size;
+            /* (counted as one buffer again: the handover below took it out of the sum) */
+            adopt(c, c->d_ingest, DevBuf<u8>{(u8 *)c->arena.base, c->arena.size});
             c->arena = DevArena();
-            c->hbm_bytes += c->ingest_cap; /* (counted as one buffer again: the handover below took it out of the sum) */
             c->hbm_peak = std::max(c->hbm_peak, c->hbm_bytes);
         }
-        const bool split = !getenv("DISCO_INGEST_SHARED_ARENA") && !c->arena.base && (u64)fr + c->hits_cap * 8 + c->ingest_cap > std::max(want, c->hits_cap) * 8 + own_bytes + rest + (16ull << 30);
+        const bool split = !getenv("DISCO_INGEST_SHARED_ARENA") && !c->arena.base && (u64)fr + c->d_hits.cap * 8 + c->d_ingest.cap > std::max(want, c->d_hits.cap) * 8 + own_bytes + rest + (16ull << 30);
         if (split) {
-            if (own_bytes > c->ingest_cap) {
-                dev_free(c, &c->d_ingest, c->ingest_cap);
-                c->ingest_cap = 0;
-                if (dev_alloc(c, &c->d_ingest, own_bytes) == DISCO_OK) c->ingest_cap = own_bytes;
-                else c->err.clear();
-            }
-            if (want > c->hits_cap && c->ingest_cap) {
+            if (own_bytes > c->d_ingest.cap && ensure(c, c->d_ingest, own_bytes) != DISCO_OK) c->err.clear();
+            if (want > c->d_hits.cap && c->d_ingest.cap) {
                 const int dev = c->device;
                 disco_ctx *cc = c;
                 c->hits_prealloc = std::thread([cc, dev, want]() {
                     void *p = nullptr;
                     if (hipSetDevice(dev) == hipSuccess && hipMalloc(&p, want * 8) == hipSuccess) {
-                        cc->prealloc_ptr = (u64 *)p;
-                        cc->prealloc_cap = want;
+                        cc->prealloc = DevBuf<u64>{(u64 *)p, want};
                     } else
                         (void)hipGetLastError();
                 });
             }
         }
-        if (split && c->ingest_cap) {
+        if (split && c->d_ingest.cap) {
             arena.base = c->d_ingest;
-            arena.cap = c->ingest_cap;
+            arena.cap = c->d_ingest.cap;
         } else {
-            if (want > c->hits_cap && (u64)fr + c->hits_cap * 8 > want * 8 + rest) { /* room for it next to the table and the index */
-                dev_free(c, &c->d_hits, c->hits_cap);
-                c->hits_cap = 0;
-                if (dev_alloc(c, &c->d_hits, want) == DISCO_OK) c->hits_cap = want;
-                else c->err.clear();
-            }
-            arena.base = (u8 *)c->d_hits;
-            arena.cap = c->hits_cap * 8;
+            if (want > c->d_hits.cap && (u64)fr + c->d_hits.cap * 8 > want * 8 + rest && ensure(c, c->d_hits, want) != DISCO_OK) /* room for it next to the table and the index */
+                c->err.clear();
+            arena.base = (u8 *)c->d_hits.p;
+            arena.cap = c->d_hits.cap * 8;
         }
     }
     const float t_arena = ms_since(t_begin) * 1e-3f;
@@ -1920,29 +1923,23 @@ extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_
     /* ---- pass B: ids in file order, rows of the read table -------------------------------------------------------------------- */
     const uint32_t stride_words = std::max<u32>(1, (longest + 31) / 32), dstride = (stride_words + 7u) & ~7u;
     auto pass_b = [&]() -> int {
-        u64 *keep_hits = c->d_hits; /* set_reads_common may drop the graph state of a read set of another shape: the arena must survive it */
-        const u64 keep_cap = c->hits_cap;
-        c->d_hits = nullptr;
-        c->hits_cap = 0;
+        DevBuf<u64> keep_hits = c->d_hits; /* set_reads_common may drop the graph state of a read set of another shape: the arena must survive it */
+        c->d_hits = DevBuf<u64>();
         bool kept = false;
         /* a few long reads among short ones: the rows are packed per class straight from the text (two classes of rows, disco_kernels.h) —
          * the table of one stride, n rows as wide as the longest read, is never made */
         const bool classes = two_class_ok(c, (int)dstride, n_good, n_long_reads, short_max, true);
         const int src = set_reads_common(c, n_good, classes ? (uint32_t)VERIFY_SW : dstride, classes ? nullptr : &kept);
         c->d_hits = keep_hits;
-        c->hits_cap = keep_cap;
         CHK(src);
         c->reads_owned = true; /* (as in upload_reads_impl: only now) */
         if (classes) {
-            CHK(dev_alloc(c, &c->d_reads, (n_good + n_long_reads) * 8));
-            CHK(dev_alloc(c, &c->d_len, n_good));
+            CHK(alloc_reads(c, (n_good + n_long_reads) * 8, n_good));
             CHK(two_class_alloc(c, n_long_reads, (int)dstride, short_max));
-        } else if (!kept) {
-            CHK(dev_alloc(c, &c->d_reads, n_good * (u64)dstride));
-            CHK(dev_alloc(c, &c->d_len, n_good));
-        }
+        } else if (!kept)
+            CHK(alloc_reads(c, n_good * (u64)dstride, n_good));
         c->reads_owned = true;
-        CHK(ensure_cap(c, &c->d_rec_of_read, &c->rec_of_read_cap, n_good));
+        CHK(ensure(c, c->d_rec_of_read, n_good));
         c->ingest_id_base.assign((size_t)n_files + 1, 0);
         c->ingest_rec_base.assign((size_t)n_files + 1, 0);
         u64 max_rec = 0;
@@ -1999,14 +1996,11 @@ extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_
      * and result buffers: a dozen device allocations of 5-10 ms each that the first pass of a fresh context otherwise waits for) */
     if (c->d_ingest && arena.base == c->d_ingest && owned.empty() && !getenv("DISCO_NO_ARENA_HANDOVER")) {
         c->arena = DevArena();
-        c->arena.base = (char *)c->d_ingest;
-        c->arena.size = c->ingest_cap & ~(u64)255;
+        c->arena.size = c->d_ingest.cap & ~(u64)255;
         c->arena.free_at[0] = c->arena.size;
         /* what the allocator serves out of it is counted buffer by buffer (dev_alloc): the arena itself leaves the sum, or every byte of
          * it would count twice in hbm_bytes / hbm_peak */
-        c->hbm_bytes = c->hbm_bytes >= c->ingest_cap ? c->hbm_bytes - c->ingest_cap : 0;
-        c->d_ingest = nullptr;
-        c->ingest_cap = 0;
+        c->arena.base = (char *)disown(c, c->d_ingest);
     }
     c->ingest_n = n_good;
     if (c->two_class) {
@@ -2084,10 +2078,7 @@ int disco_generate_reads(disco_ctx *c, const disco_genspec_abi *s)
     uint32_t stride = (((longest + 31) / 32) + 7u) & ~7u; /* 64-B aligned rows */
     bool kept = false;
     CHK(set_reads_common(c, s->n_reads, stride, &kept));
-    if (!kept) {
-        CHK(dev_alloc(c, &c->d_reads, c->n * (u64)stride));
-        CHK(dev_alloc(c, &c->d_len, c->n));
-    }
+    if (!kept) CHK(alloc_reads(c, c->n * (u64)stride, c->n));
     c->reads_owned = true;
     disco_genspec g;
     memcpy(&g, s, sizeof g);
@@ -2117,9 +2108,9 @@ int disco_download_reads(disco_ctx *c, uint64_t *packed, uint16_t *len)
 {
     if (!c || c->phase < 1) return c ? fail(c, DISCO_E_STATE, "no reads") : DISCO_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    u64 *joined = nullptr;
+    DevBuf<u64> joined;
     if (packed && c->n && c->two_class) { /* the table as the caller knows it: one stride */
-        CHK(dev_alloc(c, &joined, c->n * (u64)c->S_ext));
+        CHK(ensure(c, joined, c->n * (u64)c->S_ext));
         hipLaunchKernelGGL(class_join_kernel, dim3(flat_grid(c, c->n * (u64)c->S_ext)), dim3(256), 0, c->stream, (const u64 *)c->d_reads, (const u64 *)c->d_full, c->S_ext,
                            (const u16 *)c->d_len, (const u32 *)c->d_ovf, c->n, joined);
         (void)hipMemcpyAsync(packed, joined, c->n * (u64)c->S_ext * 8, hipMemcpyDeviceToHost, c->stream);
@@ -2127,7 +2118,7 @@ int disco_download_reads(disco_ctx *c, uint64_t *packed, uint16_t *len)
         HIPCHK(c, hipMemcpyAsync(packed, c->d_reads, c->n * (u64)c->S * 8, hipMemcpyDeviceToHost, c->stream));
     if (len && c->n) (void)hipMemcpyAsync(len, c->d_len, c->n * 2, hipMemcpyDeviceToHost, c->stream);
     const hipError_t e = hipStreamSynchronize(c->stream);
-    if (joined) dev_free(c, &joined, c->n * (u64)c->S_ext);
+    release(c, joined);
     if (e != hipSuccess) return fail(c, DISCO_E_HIP, "disco_download_reads: %s", hipGetErrorString(e));
     return DISCO_OK;
 }
@@ -2158,18 +2149,17 @@ static int two_class_alloc(disco_ctx *c, u64 n_long, int Sx, u32 short_max)
     c->n_long = n_long;
     c->S_ext = Sx;
     int rc = DISCO_OK;
-    if (!c->d_ovf) rc = dev_alloc(c, &c->d_ovf, c->n_alloc);
-    if (rc == DISCO_OK) rc = dev_alloc(c, &c->d_full, n_long * (u64)Sx);
-    if (rc == DISCO_OK) rc = dev_alloc(c, &c->d_long_ids, n_long);
-    if (rc == DISCO_OK) rc = dev_alloc(c, &c->d_lpos, n_long);
-    if (rc == DISCO_OK) rc = dev_alloc(c, &c->d_lmeta, n_long);
-    if (rc == DISCO_OK) rc = dev_alloc(c, &c->d_linfo, n_long);
-    if (rc == DISCO_OK) rc = dev_alloc(c, &c->d_n_list, 1);
+    rc = ensure(c, c->d_ovf, c->n_alloc);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_full, n_long * (u64)Sx);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_long_ids, n_long);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_lpos, n_long);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_lmeta, n_long);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_linfo, n_long);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_n_list, 1);
     if (rc != DISCO_OK) {
         free_long_class(c);
         return rc;
     }
-    c->reads_rows = c->n + n_long;
     c->S = VERIFY_SW;
     c->tailb = short_max <= 160 ? 160 : 256; /* what the staged compare of the short class moves per row (verify_flat_kernel<5 / 8>) */
     c->two_class = true;
@@ -2183,33 +2173,34 @@ static int two_class_convert(disco_ctx *c)
 {
     if (c->two_class || !c->n || c->max_len <= (u32)DISCO_SHORT_MAX || !two_class_ok(c, c->S, c->n, 1, (u32)c->k + 1)) return DISCO_OK; /* (cheap part first) */
     const int Sx = c->S;
-    u32 *ovf = nullptr;
-    CHK(dev_alloc(c, &ovf, c->n_alloc));
+    DevBuf<u32> ovf;
+    CHK(ensure(c, ovf, c->n_alloc));
     CHK(zero_counter(c, CTR_SHORT_MAX));
-    hipLaunchKernelGGL(class_flag_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_len, c->n, ovf, c->d_ctr);
+    hipLaunchKernelGGL(class_flag_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_len, c->n, ovf.p, c->d_ctr);
     u64 n_long = 0;
     CHK((scan_exclusive<u32, u32>(c, ovf, c->n, ovf, false, &n_long)));
     CHK(read_counters(c));
     const u32 short_max = (u32)c->h_ctr[CTR_SHORT_MAX];
     if (!two_class_ok(c, Sx, c->n, n_long, short_max)) {
-        dev_free(c, &ovf, c->n_alloc);
+        release(c, ovf);
         return DISCO_OK;
     }
-    u64 *rows8 = nullptr, *old = c->d_reads;
+    DevBuf<u64> rows8;
     c->d_ovf = ovf; /* (the context's from here on: released with the long class, also when something below fails) */
-    int rca = dev_alloc(c, &rows8, (c->n + n_long) * 8);
+    int rca = ensure(c, rows8, (c->n + n_long) * 8);
     if (rca == DISCO_OK) rca = two_class_alloc(c, n_long, Sx, short_max);
     if (rca != DISCO_OK) { /* the table keeps its one stride */
-        dev_free(c, &rows8, (c->n + n_long) * 8);
+        release(c, rows8);
         free_long_class(c);
         return rca;
     }
-    hipLaunchKernelGGL(class_split_kernel, dim3(flat_grid(c, c->n * 8)), dim3(256), 0, c->stream, (const u64 *)old, Sx, (const u16 *)c->d_len, (const u32 *)ovf, c->n, c->tailb, rows8,
-                       c->d_full, c->d_long_ids);
+    hipLaunchKernelGGL(class_split_kernel, dim3(flat_grid(c, c->n * 8)), dim3(256), 0, c->stream, (const u64 *)c->reads_own, Sx, (const u16 *)c->d_len, (const u32 *)ovf, c->n, c->tailb,
+                       rows8.p, c->d_full, c->d_long_ids);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream)); /* (the old table goes back: nothing of it may still be in flight) */
-    dev_free(c, &old, c->n_alloc * (u64)Sx);
-    c->d_reads = rows8;
+    release(c, c->reads_own);
+    c->reads_own = rows8;
+    c->d_reads = c->reads_own;
     c->max_len_all = c->max_len;
     c->max_len = short_max;
     return DISCO_OK;
@@ -2244,7 +2235,7 @@ int disco_build_index(disco_ctx *c)
     c->order_ready = false;
     if (c->order_counted && c->order_counted_lo == 0 && c->order_counted_hi == c->n && !c->two_class && !getenv("DISCO_NO_ORDERED_FILL")) {
         const u64 order_buckets = 1ull << c->order_counted_bits;
-        CHK(ensure_cap(c, &c->d_order_own, &c->order_cap, c->n));
+        CHK(ensure(c, c->d_order_own, c->n));
         ph_end(c, DISCO_PH_INDEX);
         ph_begin(c, DISCO_PH_ORDER);
         CHK((scan_exclusive<u32, u32>(c, c->d_ocnt, order_buckets + 1, c->d_ocnt, false, nullptr)));
@@ -2276,11 +2267,9 @@ int disco_probe(disco_ctx *c)
     CHK(settle_keys(c));           /* ... and so does a key exchange that runs behind a multi-GPU pass */
     settle_hits_prealloc(c);
     const u64 nq = c->q_hi - c->q_lo;
-    if (!c->d_best) {
-        CHK(dev_alloc(c, &c->d_best, c->n_alloc));
-        CHK(dev_alloc(c, &c->d_row_start, c->n));
-        CHK(dev_alloc(c, &c->d_row_cnt, c->n));
-    }
+    CHK(ensure(c, c->d_best, c->n_alloc));
+    CHK(ensure(c, c->d_row_start, c->n));
+    CHK(ensure(c, c->d_row_cnt, c->n));
     if (c->n_alloc) hipLaunchKernelGGL(fill_u64_kernel, dim3(flat_grid(c, c->n_alloc)), dim3(256), 0, c->stream, c->d_best, c->n_alloc, DISCO_NOKEY);
     HIPCHK(c, hipMemsetAsync(c->d_row_cnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
     const bool ldsrow = c->S <= PROBE_ACAP; /* (two classes of rows: c->S = 8; the lists' kernels take the long class's stride into account: launch_probe) */
@@ -2332,9 +2321,8 @@ int disco_probe(disco_ctx *c)
     u32 want_slow = use_runs ? (u32)std::min<u64>(nq, nq / 64 + 1024 + (c->two_class ? c->n_long : 0)) : 1u;
     u32 want_big = (u32)std::min<u64>(nq, nq / 64 + 1024);
     for (int attempt = 0; attempt < 8; attempt++) {
-        if (want_hits > c->hits_cap) {
-            dev_free(c, &c->d_hits, c->hits_cap);
-            c->hits_cap = 0;
+        if (want_hits > c->d_hits.cap) {
+            release(c, c->d_hits);
             size_t fr = 0, tot = 0;
             HIPCHK(c, hipMemGetInfo(&fr, &tot));
             if (want_hits * 8 > fr) {
@@ -2342,23 +2330,10 @@ int disco_probe(disco_ctx *c)
                 if (can < (u64)grid * chunk_slots * 2) return fail(c, DISCO_E_NOMEM, "disco_probe: not enough HBM for the hit buffer (%llu entries wanted)", (unsigned long long)want_hits);
                 want_hits = can;
             }
-            CHK(dev_alloc(c, &c->d_hits, want_hits));
-            c->hits_cap = want_hits;
+            CHK(ensure(c, c->d_hits, want_hits));
         }
-        if (want_slow > c->slow_cap) {
-            dev_free(c, &c->d_slow_list, c->slow_cap);
-            c->slow_cap = 0;
-            CHK(dev_alloc(c, &c->d_slow_list, want_slow));
-            c->slow_cap = want_slow;
-        }
-        if (want_big > c->big_cap) {
-            dev_free(c, &c->d_big_list, c->big_cap);
-            dev_free(c, &c->d_big_cnt, c->big_cap);
-            c->big_cap = 0;
-            CHK(dev_alloc(c, &c->d_big_list, want_big));
-            CHK(dev_alloc(c, &c->d_big_cnt, want_big));
-            c->big_cap = want_big;
-        }
+        if (want_slow > c->d_slow_list.cap) CHK(ensure(c, c->d_slow_list, want_slow));
+        CHK(grow_big_lists(c, want_big));
         HIPCHK(c, hipMemsetAsync(c->d_bump, 0, sizeof(u64), c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_n_big, 0, sizeof(u32), c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_n_slow, 0, sizeof(u32), c->stream));
@@ -2373,19 +2348,19 @@ int disco_probe(disco_ctx *c)
         a.row_start = c->d_row_start;
         a.row_cnt = c->d_row_cnt;
         c->h_probe_rare.bump = c->d_bump;
-        c->h_probe_rare.hits_cap = c->hits_cap;
+        c->h_probe_rare.hits_cap = c->d_hits.cap;
         c->h_probe_rare.big_list = c->d_big_list;
         c->h_probe_rare.big_cnt = c->d_big_cnt;
         c->h_probe_rare.n_big = c->d_n_big;
-        c->h_probe_rare.big_cap = c->big_cap;
-        c->h_probe_rare.slow_cap = c->slow_cap;
+        c->h_probe_rare.big_cap = c->d_big_list.cap;
+        c->h_probe_rare.slow_cap = c->d_slow_list.cap;
         c->h_probe_rare.slow_list = c->d_slow_list;
         c->h_probe_rare.n_slow = c->d_n_slow;
         c->h_probe_rare.ctr = c->d_ctr;
-        if (!c->d_probe_rare) CHK(dev_alloc(c, &c->d_probe_rare, 1));
+        CHK(ensure(c, c->d_probe_rare, 1));
         HIPCHK(c, hipMemcpyAsync(c->d_probe_rare, &c->h_probe_rare, sizeof(ProbeRare), hipMemcpyHostToDevice, c->stream));
         a.rare = c->d_probe_rare;
-        CHK(ensure_cap(c, &c->d_meta_ord, &c->meta_cap, std::max<u64>(nq, 1)));
+        CHK(ensure(c, c->d_meta_ord, std::max<u64>(nq, 1)));
         a.meta_ord = c->d_meta_ord;
         /* grouping of the query range by read-level minimizer for the probe and verify passes (DISCO_NO_ORDER=1: file order) */
         int order_bits = 16;
@@ -2400,9 +2375,9 @@ int disco_probe(disco_ctx *c)
         } else if (own_order && c->order_ready && counted) { /* disco_build_index finished the grouping (its fill walks the order) */
             c->d_order_used = c->d_order_own; /* (DISCO_PH_ORDER was timed there) */
         } else if (own_order) {
-            CHK(ensure_cap(c, &c->d_ocnt, &c->ocnt_cap, order_buckets + 1));
-            CHK(ensure_cap(c, &c->d_oslot, &c->oslot_cap, nq));
-            CHK(ensure_cap(c, &c->d_order_own, &c->order_cap, nq));
+            CHK(ensure(c, c->d_ocnt, order_buckets + 1));
+            CHK(ensure(c, c->d_oslot, nq));
+            CHK(ensure(c, c->d_order_own, nq));
             /* keys -> counts (+ slots) -> starts -> order */
             const u32 oshift = 32u - (u32)order_bits;
             ph_begin(c, DISCO_PH_ORDER);
@@ -2416,7 +2391,7 @@ int disco_probe(disco_ctx *c)
             HIPCHK(c, hipGetLastError());
             c->d_order_used = c->d_order_own;
         } else if (c->order_external && nq) {
-            CHK(ensure_cap(c, &c->d_order_own, &c->order_cap, nq));
+            CHK(ensure(c, c->d_order_own, nq));
             hipLaunchKernelGGL(order_pack_kernel, dim3(flat_grid(c, nq)), dim3(256), 0, c->stream, c->d_order, nq, c->d_len, c->d_order_own);
             HIPCHK(c, hipGetLastError());
             c->d_order_used = c->d_order_own;
@@ -2490,8 +2465,8 @@ int disco_probe(disco_ctx *c)
                                    (const u64 *)c->d_order_used, c->q_lo, nq, (const u32 *)c->d_ovf, c->d_lpos, c->d_lmeta, c->d_linfo, c->d_n_list, (u32)c->n_long);
             }
             if (two_pass) {
-                if (!c->d_contained) CHK(dev_alloc(c, &c->d_contained, c->n_alloc));
-                if (!c->d_cbits) CHK(dev_alloc(c, &c->d_cbits, c->n_alloc / 64 + 1));
+                CHK(ensure(c, c->d_contained, c->n_alloc));
+                CHK(ensure(c, c->d_cbits, c->n_alloc / 64 + 1));
                 va.cbits = c->d_cbits;
                 const bool short_rows = c->max_len <= 160;
                 if (nq && flat) {
@@ -2559,12 +2534,12 @@ int disco_probe(disco_ctx *c)
         }
         if (getenv("DISCO_VERBOSE"))
             fprintf(stderr, "[disco] probe attempt %d overflowed: hits_cap=%llu needed=%llu n_big=%u big_cap=%u overflow=%llu\n", attempt,
-                    (unsigned long long)c->hits_cap, (unsigned long long)c->h_ctr[CTR_HITS_NEEDED], n_big, c->big_cap, (unsigned long long)c->h_ctr[CTR_OVERFLOW]);
+                    (unsigned long long)c->d_hits.cap, (unsigned long long)c->h_ctr[CTR_HITS_NEEDED], n_big, (unsigned)c->d_big_list.cap, (unsigned long long)c->h_ctr[CTR_OVERFLOW]);
         /* something was too small: grow and redo the pass (atomicMin on best is idempotent) */
-        if (n_big > c->big_cap) want_big = (u32)std::min<u64>(nq, (u64)n_big + n_big / 4 + 1024);
-        if (n_slow > c->slow_cap) want_slow = (u32)std::min<u64>(nq, (u64)n_slow + n_slow / 4 + 1024);
+        if (n_big > c->d_big_list.cap) want_big = (u32)std::min<u64>(nq, (u64)n_big + n_big / 4 + 1024);
+        if (n_slow > c->d_slow_list.cap) want_slow = (u32)std::min<u64>(nq, (u64)n_slow + n_slow / 4 + 1024);
         u64 needed = c->h_ctr[CTR_HITS_NEEDED];
-        want_hits = std::max<u64>(c->hits_cap * 2, needed + needed / 4 + (u64)grid * chunk_slots);
+        want_hits = std::max<u64>(c->d_hits.cap * 2, needed + needed / 4 + (u64)grid * chunk_slots);
     }
     return fail(c, DISCO_E_CAPACITY, "disco_probe: hit buffer could not be sized");
 }
@@ -2576,8 +2551,8 @@ int disco_mark_contained(disco_ctx *c, uint64_t *n_contained)
     if (!c) return DISCO_E_ARG;
     if (c->phase < 3) return fail(c, DISCO_E_STATE, "disco_mark_contained: run disco_probe first");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_contained) CHK(dev_alloc(c, &c->d_contained, c->n_alloc));
-    if (!c->d_cbits) CHK(dev_alloc(c, &c->d_cbits, c->n_alloc / 64 + 1));
+    CHK(ensure(c, c->d_contained, c->n_alloc));
+    CHK(ensure(c, c->d_cbits, c->n_alloc / 64 + 1));
     CHK(zero_counter(c, CTR_N_CONTAINED));
     ph_begin(c, DISCO_PH_CONTAIN);
     if (c->n) hipLaunchKernelGGL(contain_flags_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_best, c->n, c->d_contained, c->d_cbits, c->d_ctr);
@@ -2603,23 +2578,15 @@ static int ensure_big_cap(disco_ctx *c, const u32 *cnt, const u64 *ref, u32 thr)
     HIPCHK(c, hipGetLastError());
     CHK(read_counters(c));
     const u64 need = c->h_ctr[CTR_ES_BIG] + 1024;
-    if (need > c->big_cap) {
-        if (need > 0xFFFFFFFFull) return fail(c, DISCO_E_CAPACITY, "more than 2^32 big rows");
-        dev_free(c, &c->d_big_list, c->big_cap);
-        dev_free(c, &c->d_big_cnt, c->big_cap);
-        c->big_cap = 0;
-        CHK(dev_alloc(c, &c->d_big_list, need));
-        CHK(dev_alloc(c, &c->d_big_cnt, need));
-        c->big_cap = (u32)need;
-    }
-    return DISCO_OK;
+    if (need > 0xFFFFFFFFull) return fail(c, DISCO_E_CAPACITY, "more than 2^32 big rows");
+    return grow_big_lists(c, need);
 }
 
 static int select_edges(disco_ctx *c)
 {
     DISCO_TRACE("select_edges");
     const u64 nq = c->q_hi - c->q_lo;
-    if (!c->d_adj_ref) CHK(dev_alloc(c, &c->d_adj_ref, c->n));
+    CHK(ensure(c, c->d_adj_ref, c->n));
     HIPCHK(c, hipMemsetAsync(c->d_adj_ref, 0, std::max<u64>(c->n, 1) * sizeof(u64), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_n_big, 0, sizeof(u32), c->stream));
     CHK(zero_counter(c, CTR_CAP_SITES));
@@ -2637,21 +2604,14 @@ static int select_edges(disco_ctx *c)
     const bool select_small = rows_counted && env_int("DISCO_SELECT_SMALL", c->h_ctr[CTR_ES_MID] * 100 <= nq ? 1 : 0) != 0;
     if (rows_counted) {
         const u64 need = c->h_ctr[select_small ? CTR_ES_MID : CTR_ES_BIG] + 1024;
-        if (need > c->big_cap) {
-            if (need > 0xFFFFFFFFull) return fail(c, DISCO_E_CAPACITY, "more than 2^32 big rows");
-            dev_free(c, &c->d_big_list, c->big_cap);
-            dev_free(c, &c->d_big_cnt, c->big_cap);
-            c->big_cap = 0;
-            CHK(dev_alloc(c, &c->d_big_list, need));
-            CHK(dev_alloc(c, &c->d_big_cnt, need));
-            c->big_cap = (u32)need;
-        }
+        if (need > 0xFFFFFFFFull) return fail(c, DISCO_E_CAPACITY, "more than 2^32 big rows");
+        CHK(grow_big_lists(c, need));
     } else
         CHK(ensure_big_cap(c, c->d_row_cnt, nullptr, ES_CAP));
     c->es_big_counted = false;
     EdgeSelArgs a;
     a.v = view(c);
-    if (!c->d_dropbits) CHK(dev_alloc(c, &c->d_dropbits, c->n_alloc / 64 + 1));
+    CHK(ensure(c, c->d_dropbits, c->n_alloc / 64 + 1));
     HIPCHK(c, hipMemsetAsync(c->d_dropbits, 0, (c->n_alloc / 64 + 1) * sizeof(u64), c->stream));
     c->drop_lo = c->loci ? 0 : c->q_lo;
     c->drop_hi = c->loci ? 0 : c->q_hi; /* (ranks own loci: the bitmap is complete once the lists have been exchanged: dist_complete_twins) */
@@ -2661,8 +2621,8 @@ static int select_edges(disco_ctx *c)
     a.drop_cap = 0;
     CHK(zero_counter(c, CTR_DROP_ITEMS));
     if (c->prm.max_substitutions == 0 && !getenv("DISCO_NO_DROP_LIST")) {
-        if (!c->d_drop_node) CHK(dev_alloc(c, &c->d_drop_node, DROP_LIST_CAP));
-        if (!c->d_drop_key) CHK(dev_alloc(c, &c->d_drop_key, DROP_LIST_CAP));
+        CHK(ensure(c, c->d_drop_node, DROP_LIST_CAP));
+        CHK(ensure(c, c->d_drop_key, DROP_LIST_CAP));
         a.drop_node = c->d_drop_node;
         a.drop_key = c->d_drop_key;
         a.drop_cap = (u32)std::min<u64>(DROP_LIST_CAP, (u64)env_int("DISCO_DROP_LIST_CAP", (int)DROP_LIST_CAP)); /* (tests: a list that overflows) */
@@ -2675,7 +2635,7 @@ static int select_edges(disco_ctx *c)
     a.max_per_kmer = c->prm.max_edges_per_kmer;
     a.big_list = c->d_big_list;
     a.n_big = c->d_n_big;
-    a.big_cap = c->big_cap;
+    a.big_cap = c->d_big_list.cap;
     a.scratch = nullptr;
     a.scratch_cap = 0;
     a.order = c->d_order_used; /* the headers in meta_ord are by position in THIS order */
@@ -2717,15 +2677,15 @@ static int select_edges(disco_ctx *c)
     if (n_big && c->h_ctr[CTR_MAX_ROW] > ES_MID) {
         int g2 = (int)std::min<u64>(n_big, (u64)c->n_cu * 8); /* work queue, one big row per grab */
         u64 cap = c->h_ctr[CTR_MAX_ROW] + 64;
-        u64 *scratch = nullptr;
-        CHK(dev_alloc(c, &scratch, (u64)g2 * 2 * cap));
+        DevBuf<u64> scratch;
+        CHK(ensure(c, scratch, (u64)g2 * 2 * cap));
         a.scratch = scratch;
         a.scratch_cap = cap;
         HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
         hipLaunchKernelGGL(edge_select_kernel<true>, dim3(g2), dim3(64), 0, c->stream, a);
         hipError_t e = hipGetLastError();
         int rc = read_counters(c);
-        dev_free(c, &scratch, (u64)g2 * 2 * cap);
+        release(c, scratch);
         if (e != hipSuccess) return fail(c, DISCO_E_HIP, "edge_select_kernel<true>: %s", hipGetErrorString(e));
         CHK(rc);
     }
@@ -2771,7 +2731,7 @@ static int twin_check(disco_ctx *c, u64 lo, u64 hi)
 static int twin_check_search(disco_ctx *c, u64 lo, u64 hi)
 {
     DISCO_TRACE("twin_check");
-    if (!c->d_extra_cnt) CHK(dev_alloc(c, &c->d_extra_cnt, c->n));
+    CHK(ensure(c, c->d_extra_cnt, c->n));
     /* After the contained filter the verified-hit relation is symmetric: a hit A->B at window j >= 1 of overlap length
      * ovl >= k+1 shows up from B's side at window ovl-k >= 1 against A's other end record, and verifies over the same
      * region. A find can therefore miss its twin only if the twin's owner DROPPED a verified hit (second hit to the same
@@ -2833,23 +2793,17 @@ static int twin_check_search(disco_ctx *c, u64 lo, u64 hi)
             return DISCO_OK;
         }
     }
-    u32 want = std::max<u32>(4096, c->extra_cap); /* the lists kept from the last pass are the best guess */
+    u32 want = std::max<u32>(4096, extra_cap(c)); /* the lists kept from the last pass are the best guess */
     if (by_list) want = std::max<u32>(want, (u32)c->n_drop_items); /* (an item yields at most one extra) */
     for (int attempt = 0; attempt < 6; attempt++) {
-        if (want > c->extra_cap) {
-            dev_free(c, &c->d_extra_node, c->extra_cap);
-            dev_free(c, &c->d_extra_key, c->extra_cap);
-            CHK(dev_alloc(c, &c->d_extra_node, want));
-            CHK(dev_alloc(c, &c->d_extra_key, want));
-            c->extra_cap = want;
-        }
+        CHK(ensure_group(c, want, want, c->d_extra_node, c->d_extra_key));
         HIPCHK(c, hipMemsetAsync(c->d_extra_cnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_n_extra, 0, sizeof(u32), c->stream));
         CHK(zero_counter(c, CTR_ASYM));
         CHK(zero_counter(c, CTR_OVERFLOW));
         a.extra_node = c->d_extra_node;
         a.extra_key = c->d_extra_key;
-        a.extra_cap = c->extra_cap;
+        a.extra_cap = extra_cap(c);
         a.up_only = 0;
         ph_begin(c, DISCO_PH_TWIN);
         if (by_list) {
@@ -2893,7 +2847,7 @@ static int merge_extras(disco_ctx *c)
         u64 need = 0;
         HIPCHK(c, hipMemcpyAsync(&need, c->d_bump, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->hits_used + need <= c->hits_cap) {
+        if (c->hits_used + need <= c->d_hits.cap) {
             HIPCHK(c, hipMemsetAsync(c->d_bump, 0, sizeof(u64), c->stream));
             hipLaunchKernelGGL(merge_sparse_kernel, dim3((unsigned)std::min<u64>(c->n_extra, (u64)c->n_cu * 16)), dim3(64), 0, c->stream, c->d_extra_node, c->d_extra_key,
                                c->n_extra, c->d_extra_cnt, c->d_adj_ref, c->d_adj, c->hits_used, c->d_bump);
@@ -2905,23 +2859,19 @@ static int merge_extras(disco_ctx *c)
             return DISCO_OK;
         }
     }
-    u32 *new_deg = nullptr;
-    u64 *new_start = nullptr, *new_adj = nullptr, *scratch = nullptr;
-    u64 total = 0, scratch_n = 0, new_cap = 0;
+    DevBuf<u32> new_deg;
+    DevBuf<u64> new_start, new_adj, scratch;
+    u64 total = 0;
     auto body = [&]() -> int {
-        CHK(dev_alloc(c, &new_deg, c->n));
-        CHK(dev_alloc(c, &new_start, c->n + 1));
+        CHK(ensure(c, new_deg, c->n));
+        CHK(ensure(c, new_start, c->n + 1));
         hipLaunchKernelGGL(merge_deg_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_adj_ref, c->d_extra_cnt, c->n, new_deg);
         CHK((scan_exclusive<u32, u64>(c, new_deg, c->n, new_start, true, &total)));
-        if (c->adj_spare_cap >= total && c->d_adj_spare) { /* the buffer the previous pass's merge left behind */
+        if (c->d_adj_spare.cap >= total && c->d_adj_spare) { /* the buffer the previous pass's merge left behind */
             new_adj = c->d_adj_spare;
-            new_cap = c->adj_spare_cap;
-            c->d_adj_spare = nullptr;
-            c->adj_spare_cap = 0;
-        } else {
-            CHK(dev_alloc(c, &new_adj, total + total / 16));
-            new_cap = total + total / 16;
-        }
+            c->d_adj_spare = DevBuf<u64>();
+        } else
+            CHK(ensure(c, new_adj, total + total / 16));
         hipLaunchKernelGGL(merge_scatter_kernel, dim3(flat_grid(c, c->n_extra)), dim3(256), 0, c->stream, c->d_extra_node, c->d_extra_key, c->n_extra, c->d_adj_ref, new_start, new_adj);
         /* row scratch: the longest merged row (reduced on the device) */
         CHK(zero_counter(c, CTR_MAX_DEG));
@@ -2930,8 +2880,7 @@ static int merge_extras(disco_ctx *c)
         CHK(read_counters(c));
         const u64 maxdeg = c->h_ctr[CTR_MAX_DEG];
         const int g = (int)std::min<u64>(c->n, (u64)c->n_cu * 32); /* one wavefront per row at a time */
-        scratch_n = (u64)g * (maxdeg + 1);
-        CHK(dev_alloc(c, &scratch, scratch_n));
+        CHK(ensure(c, scratch, (u64)g * (maxdeg + 1)));
         hipLaunchKernelGGL(merge_rows_kernel, dim3(g), dim3(64), 0, c->stream, c->d_adj_ref, c->d_adj, c->d_extra_cnt, new_start, new_adj, c->n, scratch, maxdeg + 1);
         hipLaunchKernelGGL(ref_from_start_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, new_start, new_deg, c->n, c->d_adj_ref);
         HIPCHK(c, hipGetLastError());
@@ -2939,20 +2888,18 @@ static int merge_extras(disco_ctx *c)
         return DISCO_OK;
     };
     const int rc = body();
-    dev_free(c, &scratch, scratch_n);
-    dev_free(c, &new_deg, c->n);
-    dev_free(c, &new_start, c->n + 1);
+    release(c, scratch);
+    release(c, new_deg);
+    release(c, new_start);
     if (rc != DISCO_OK) {
-        dev_free(c, &new_adj, new_cap);
+        release(c, new_adj);
         return rc;
     }
     /* the rows move to new_adj; what held the imported / merged rows so far waits for the next pass's merge */
-    dev_free(c, &c->d_adj_spare, c->adj_spare_cap);
+    release(c, c->d_adj_spare);
     c->d_adj_spare = c->d_adj_own;
-    c->adj_spare_cap = c->d_adj_own ? c->adj_cap : 0;
     c->d_adj_own = new_adj;
-    c->d_adj = new_adj;
-    c->adj_cap = new_cap;
+    c->d_adj = c->d_adj_own;
     c->adj_total = total;
     c->adj_span = total; /* compact, node ordered */
     c->n_extra = 0;
@@ -3015,7 +2962,7 @@ int disco_export_adjacency(disco_ctx *c, void *d_deg_u32, void *d_entries_u64)
     if (nq) hipLaunchKernelGGL(deg_from_ref_kernel, dim3(flat_grid(c, nq)), dim3(256), 0, c->stream, c->d_adj_ref, c->q_lo, c->q_hi, (u32 *)d_deg_u32);
     HIPCHK(c, hipGetLastError());
     if (nq && c->adj_total && d_entries_u64) { /* compact the local rows into node order */
-        CHK(ensure_cap(c, &c->d_start_tmp, &c->start_cap, c->n + 1));
+        CHK(ensure(c, c->d_start_tmp, c->n + 1));
         u64 *start = c->d_start_tmp;
         u64 total = 0;
         int rc = scan_exclusive<u32, u64>(c, (const u32 *)d_deg_u32, nq, start, true, &total);
@@ -3041,13 +2988,13 @@ int disco_import_adjacency(disco_ctx *c, const void *d_deg_u32_all, const void *
     if (!c || !d_deg_u32_all) return DISCO_E_ARG;
     if (c->phase < 5) return fail(c, DISCO_E_STATE, "disco_import_adjacency: select edges first");
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(ensure_cap(c, &c->d_start_tmp, &c->start_cap, c->n + 1));
+    CHK(ensure(c, c->d_start_tmp, c->n + 1));
     u64 *start = c->d_start_tmp;
     u64 total = 0;
     CHK((scan_exclusive<u32, u64>(c, (const u32 *)d_deg_u32_all, c->n, start, true, &total)));
     if (total != n_entries_all)
         return fail(c, DISCO_E_ARG, "disco_import_adjacency: degrees sum to %llu but %llu entries were passed", (unsigned long long)total, (unsigned long long)n_entries_all);
-    CHK(ensure_cap(c, &c->d_adj_own, &c->adj_cap, total));
+    CHK(ensure(c, c->d_adj_own, total));
     c->d_adj = c->d_adj_own;
     c->adj_total = total;
     if (total) HIPCHK(c, hipMemcpyAsync(c->d_adj, d_entries_u64_all, total * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -3081,15 +3028,8 @@ int disco_transitive_mark(disco_ctx *c)
     const bool tr_small = env_int("DISCO_TR_SMALL", counted_nodes && c->h_ctr[CTR_TR_MID] * 100 <= nq ? 1 : 0) != 0 && counted_nodes;
     if (counted_nodes) { /* edge selection counted the nodes beyond TR_CAP (and beyond TR_CAP_SMALL) */
         const u64 need = c->h_ctr[tr_small ? CTR_TR_MID : CTR_TR_BIG] + 1024;
-        if (need > c->big_cap) {
-            if (need > 0xFFFFFFFFull) return fail(c, DISCO_E_CAPACITY, "more than 2^32 big nodes");
-            dev_free(c, &c->d_big_list, c->big_cap);
-            dev_free(c, &c->d_big_cnt, c->big_cap);
-            c->big_cap = 0;
-            CHK(dev_alloc(c, &c->d_big_list, need));
-            CHK(dev_alloc(c, &c->d_big_cnt, need));
-            c->big_cap = (u32)need;
-        }
+        if (need > 0xFFFFFFFFull) return fail(c, DISCO_E_CAPACITY, "more than 2^32 big nodes");
+        CHK(grow_big_lists(c, need));
     } else
         CHK(ensure_big_cap(c, nullptr, c->d_adj_ref, TR_CAP));
     TrArgs a;
@@ -3098,28 +3038,25 @@ int disco_transitive_mark(disco_ctx *c)
     a.adj = c->d_adj;
     a.big_list = c->d_big_list;
     a.n_big = c->d_n_big;
-    a.big_cap = c->big_cap;
+    a.big_cap = c->d_big_list.cap;
     a.scratch = nullptr;
     a.hcap = 0;
     a.half = nullptr;
     a.hcnt = nullptr;
     c->use_half = !getenv("DISCO_NO_HALF");
     if (c->use_half) {
-        if (!c->d_half) CHK(dev_alloc(c, &c->d_half, c->n * HALF_CAP));
-        if (!c->d_hcnt) CHK(dev_alloc(c, &c->d_hcnt, c->n));
+        CHK(ensure(c, c->d_half, c->n * HALF_CAP));
+        CHK(ensure(c, c->d_hcnt, c->n));
         HIPCHK(c, hipMemsetAsync(c->d_hcnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
-        if (!c->d_wide) {
-            c->wide_cap = (u32)std::min<u64>(c->n, c->n / 32 + 4096);
-            CHK(dev_alloc(c, &c->d_wide, c->wide_cap));
-            CHK(dev_alloc(c, &c->d_n_wide, 1));
-        }
+        CHK(ensure(c, c->d_wide, std::min<u64>(c->n, c->n / 32 + 4096)));
+        CHK(ensure(c, c->d_n_wide, 1));
         HIPCHK(c, hipMemsetAsync(c->d_n_wide, 0, sizeof(u32), c->stream));
         a.half = c->d_half;
         a.hcnt = c->d_hcnt;
     }
     a.wide_list = c->d_wide;
     a.n_wide = c->d_n_wide;
-    a.wide_cap = c->wide_cap;
+    a.wide_cap = c->d_wide.cap;
     a.order = (c->d_order_used && c->order_q_lo == c->q_lo && c->order_q_hi == c->q_hi && !c->adj_imported && !getenv("DISCO_TR_NO_ORDER")) ? c->d_order_used : nullptr;
     /* every row needs its flags when the emission cannot rely on the survivor lists alone */
     a.all_flags = (c->adj_imported || !c->use_half || c->q_lo != 0 || c->q_hi != c->n) ? 1u : 0u;
@@ -3152,15 +3089,15 @@ int disco_transitive_mark(disco_ctx *c)
         while (hcap < 2 * maxd) hcap <<= 1;
         int g2 = (int)std::min<u64>(n_big, (u64)c->n_cu * 8);
         u64 per = hcap * 8 + hcap * 4 + hcap;
-        u8 *scratch = nullptr;
-        CHK(dev_alloc(c, &scratch, (u64)g2 * per));
-        a.scratch = (u64 *)scratch;
+        DevBuf<u8> scratch;
+        CHK(ensure(c, scratch, (u64)g2 * per));
+        a.scratch = (u64 *)scratch.p;
         a.hcap = hcap;
         HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
         hipLaunchKernelGGL((transitive_mark_kernel<true, false>), dim3(g2), dim3(64), 0, c->stream, a);
         hipError_t e = hipGetLastError();
         const int rc2 = read_counters(c); /* synchronises; the big pass may have raised CTR_OVERFLOW */
-        dev_free(c, &scratch, (u64)g2 * per);
+        release(c, scratch);
         if (e != hipSuccess) return fail(c, DISCO_E_HIP, "transitive_mark_kernel (big nodes): %s", hipGetErrorString(e));
         CHK(rc2);
         if (c->h_ctr[CTR_OVERFLOW]) return fail(c, DISCO_E_CAPACITY, "transitive marking (big nodes): list overflow");
@@ -3186,14 +3123,7 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
     const u64 nwaves = (u64)grid * 2 + (n_push ? (u64)grid_push : 0); /* emit_half_kernel + emit_kernel (+ emit_push_recv_kernel) */
     u64 want = std::max<u64>(2 * nq, 1024) + n_push + nwaves * EMIT_CHUNK;
     for (int attempt = 0; attempt < 6; attempt++) {
-        if (!c->d_out_src || want > c->out_cap) {
-            dev_free(c, &c->d_out_src, c->out_cap);
-            dev_free(c, &c->d_out_ent, c->out_cap);
-            c->out_cap = 0;
-            CHK(dev_alloc(c, &c->d_out_src, want));
-            CHK(dev_alloc(c, &c->d_out_ent, want));
-            c->out_cap = want;
-        }
+        CHK(ensure_group(c, want, want, c->d_out_src, c->d_out_ent));
         HIPCHK(c, hipMemsetAsync(c->d_bump, 0, sizeof(u64), c->stream));
         const bool half_emit = c->use_half && c->half_complete; /* else: rows + flags of every node (sharded fallback) */
         if (half_emit && nq) {
@@ -3205,7 +3135,7 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
             h.hcnt = c->d_hcnt;
             h.out_src = c->d_out_src;
             h.out_ent = c->d_out_ent;
-            h.out_cap = c->out_cap;
+            h.out_cap = c->d_out_src.cap;
             h.bump = c->d_bump;
             h.local_only = c->dist_active ? 1u : 0u;
             h.own = own_set(c);
@@ -3219,12 +3149,12 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
         a.adj = c->d_adj;
         a.hcnt = half_emit ? c->d_hcnt : nullptr;
         a.half = half_emit ? c->d_half : nullptr;
-        const bool listed = half_emit && c->n_wide <= c->wide_cap; /* else the list overflowed: scan the whole range */
+        const bool listed = half_emit && c->n_wide <= c->d_wide.cap; /* else the list overflowed: scan the whole range */
         a.list = listed ? c->d_wide : nullptr;
         a.n_list = listed ? c->n_wide : 0;
         a.out_src = c->d_out_src;
         a.out_ent = c->d_out_ent;
-        a.out_cap = c->out_cap;
+        a.out_cap = c->d_out_src.cap;
         a.bump = c->d_bump;
         a.local_only = c->dist_active ? 1u : 0u;
         a.own = own_set(c);
@@ -3240,7 +3170,7 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
             pr.hcnt = c->d_hcnt;
             pr.out_src = c->d_out_src;
             pr.out_ent = c->d_out_ent;
-            pr.out_cap = c->out_cap;
+            pr.out_cap = c->d_out_src.cap;
             pr.bump = c->d_bump;
             pr.wq = c->d_wq;
             HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
@@ -3250,7 +3180,7 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
         u64 used = 0;
         HIPCHK(c, hipMemcpyAsync(&used, c->d_bump, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (used <= c->out_cap) {
+        if (used <= c->d_out_src.cap) {
             c->out_used = used;
             break;
         }
@@ -3260,12 +3190,15 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
     /* survivors = chunk slots that are not the ~0 tail marker: count them (the compaction happens at fetch time) */
     u64 total = 0;
     if (c->out_used) {
-        if (!c->d_out_valid || c->out_used > c->valid_cap) {
-            dev_free(c, &c->d_out_valid, c->valid_cap);
-            dev_free(c, &c->d_out_pos, c->valid_cap + 1);
-            CHK(dev_alloc(c, &c->d_out_valid, c->out_cap));
-            CHK(dev_alloc(c, &c->d_out_pos, c->out_cap + 1));
-            c->valid_cap = c->out_cap;
+        if (c->out_used > c->d_out_valid.cap || c->out_used + 1 > c->d_out_pos.cap) { /* (grown together; sized by the output buffer) */
+            release(c, c->d_out_valid);
+            release(c, c->d_out_pos);
+            int rc = ensure(c, c->d_out_valid, c->d_out_src.cap);
+            if (rc == DISCO_OK) rc = ensure(c, c->d_out_pos, c->d_out_src.cap + 1);
+            if (rc != DISCO_OK) {
+                release(c, c->d_out_valid);
+                return rc;
+            }
         }
         hipLaunchKernelGGL(emit_valid_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->out_used, c->d_out_valid);
         CHK((scan_exclusive<u8, u64>(c, c->d_out_valid, c->out_used, c->d_out_pos, true, nullptr)));
@@ -3298,8 +3231,8 @@ int disco_run_graph(disco_ctx *c)
     CHK(disco_probe(c));
     auto t2 = now();
     { /* disco_mark_contained without its wait: the count of the flags comes back with edge selection's counters */
-        if (!c->d_contained) CHK(dev_alloc(c, &c->d_contained, c->n_alloc));
-        if (!c->d_cbits) CHK(dev_alloc(c, &c->d_cbits, c->n_alloc / 64 + 1));
+        CHK(ensure(c, c->d_contained, c->n_alloc));
+        CHK(ensure(c, c->d_cbits, c->n_alloc / 64 + 1));
         CHK(zero_counter(c, CTR_N_CONTAINED));
         ph_begin(c, DISCO_PH_CONTAIN);
         if (c->n) hipLaunchKernelGGL(contain_flags_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_best, c->n, c->d_contained, c->d_cbits, c->d_ctr);
@@ -3371,12 +3304,12 @@ int64_t disco_fetch_contained(disco_ctx *c, disco_contained_row *out, uint64_t c
     }
     CHK(ensure_host_len(c));
     CHK(settle_keys(c));
-    u64 *pos = nullptr, *ids = nullptr, *keys = nullptr;
+    DevBuf<u64> pos, ids, keys;
     std::vector<u64> hid(nc), hkey(nc);
     auto gather = [&]() -> int {
-        CHK(dev_alloc(c, &pos, c->n + 1));
-        CHK(dev_alloc(c, &ids, nc));
-        CHK(dev_alloc(c, &keys, nc));
+        CHK(ensure(c, pos, c->n + 1));
+        CHK(ensure(c, ids, nc));
+        CHK(ensure(c, keys, nc));
         CHK((scan_exclusive<u8, u64>(c, c->d_contained, c->n, pos, false, nullptr)));
         hipLaunchKernelGGL(contain_rows_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_best, c->d_contained, pos, c->n, ids, keys);
         HIPCHK(c, hipMemcpyAsync(hid.data(), ids, nc * 8, hipMemcpyDeviceToHost, c->stream));
@@ -3385,9 +3318,9 @@ int64_t disco_fetch_contained(disco_ctx *c, disco_contained_row *out, uint64_t c
         return DISCO_OK;
     };
     const int grc = gather();
-    dev_free(c, &pos, c->n + 1);
-    dev_free(c, &ids, nc);
-    dev_free(c, &keys, nc);
+    release(c, pos);
+    release(c, ids);
+    release(c, keys);
     CHK(grc);
     for (u64 i = 0; i < nc; i++) /* (a key that names no read must not index the length table: fail loudly) */
         if (CKEY_SUPER(hkey[i]) >= c->n || hid[i] >= c->n)
@@ -3449,15 +3382,7 @@ int64_t disco_fetch_edges(disco_ctx *c, disco_edge *out, uint64_t cap)
     /* drop the unused chunk tails of the emission (into buffers the context keeps: two allocations of 0.4 GB per call cost more than the
      * copy), then copy out 12 bytes per edge — source as 32 bits, packed entry — chunk k into pinned staging memory (kept by the context)
      * while the host threads turn chunk k - 1 into disco_edge records; a copy into pageable memory ran at a third of the link's rate */
-    if (ne > c->fetch_cap) {
-        dev_free(c, &c->d_fetch_src, c->fetch_cap);
-        dev_free(c, &c->d_fetch_ent, c->fetch_cap);
-        c->fetch_cap = 0;
-        const u64 want = ne + ne / 8 + 1024;
-        CHK(dev_alloc(c, &c->d_fetch_src, want));
-        CHK(dev_alloc(c, &c->d_fetch_ent, want));
-        c->fetch_cap = want;
-    }
+    CHK(ensure_group(c, ne, ne + ne / 8 + 1024, c->d_fetch_src, c->d_fetch_ent));
     u32 *csrc = c->d_fetch_src;
     u64 *cent = c->d_fetch_ent;
     hipLaunchKernelGGL(emit_compact32_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos, c->out_used, csrc, cent);
@@ -3526,13 +3451,13 @@ int64_t disco_fetch_edge_substitutions(disco_ctx *c, uint16_t *out, uint64_t cap
         memset(out, 0, ne * sizeof(uint16_t));
         return (int64_t)ne;
     }
-    u16 *subs = nullptr;
-    CHK(dev_alloc(c, &subs, ne));
+    DevBuf<u16> subs;
+    CHK(ensure(c, subs, ne));
     hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos,
                        c->out_used, c->d_reads, c->d_len, c->S, subs);
     hipError_t e1 = hipMemcpyAsync(out, subs, ne * sizeof(u16), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);
-    dev_free(c, &subs, ne);
+    release(c, subs);
     if (e1 != hipSuccess || e2 != hipSuccess) return fail(c, DISCO_E_HIP, "disco_fetch_edge_substitutions: copy failed");
     return (int64_t)ne;
 }
@@ -3543,18 +3468,18 @@ static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent,
                                uint32_t n_files, uint16_t *out)
 {
     DISCO_TRACE("partition_edges");
-    u32 *parent = nullptr, *cnt = nullptr, *d_nlist = nullptr;
-    u16 *cfile = nullptr, *efile = nullptr;
-    u64 *list = nullptr;
+    DevBuf<u32> parent, cnt, d_nlist;
+    DevBuf<u16> cfile, efile;
+    DevBuf<u64> list;
     const u32 list_cap = n_files * 64 + 64;
     int rc = DISCO_OK;
     auto cleanup = [&]() {
-        dev_free(c, &parent, n);
-        dev_free(c, &cnt, n);
-        dev_free(c, &cfile, n);
-        dev_free(c, &efile, ne);
-        dev_free(c, &list, list_cap);
-        dev_free(c, &d_nlist, 1);
+        release(c, parent);
+        release(c, cnt);
+        release(c, cfile);
+        release(c, efile);
+        release(c, list);
+        release(c, d_nlist);
     };
 #define PART_CHK(x)            \
     do {                       \
@@ -3564,12 +3489,12 @@ static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent,
             return rc;         \
         }                      \
     } while (0)
-    PART_CHK(dev_alloc(c, &parent, n));
-    PART_CHK(dev_alloc(c, &cnt, n));
-    PART_CHK(dev_alloc(c, &cfile, n));
-    PART_CHK(dev_alloc(c, &efile, ne));
-    PART_CHK(dev_alloc(c, &list, list_cap));
-    PART_CHK(dev_alloc(c, &d_nlist, 1));
+    PART_CHK(ensure(c, parent, n));
+    PART_CHK(ensure(c, cnt, n));
+    PART_CHK(ensure(c, cfile, n));
+    PART_CHK(ensure(c, efile, ne));
+    PART_CHK(ensure(c, list, list_cap));
+    PART_CHK(ensure(c, d_nlist, 1));
     hipLaunchKernelGGL(uf_init_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, parent, n);
     hipLaunchKernelGGL(uf_hook_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, d_src, d_ent, d_valid, n_slots, parent);
     hipLaunchKernelGGL(uf_compress_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, parent, n);
@@ -3636,8 +3561,8 @@ int64_t disco_partition_edges(disco_ctx *c, const disco_edge *edges, uint64_t n_
     if (n_nodes >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_partition_edges: more than 2^31 nodes");
     HIPCHK(c, hipSetDevice(c->device));
     if (n_edges == 0) return 0;
-    u64 *d_src = nullptr, *d_ent = nullptr, *d_pos = nullptr;
-    u8 *d_valid = nullptr;
+    DevBuf<u64> d_src, d_ent, d_pos;
+    DevBuf<u8> d_valid;
     std::unique_ptr<u64[]> hs(new u64[n_edges]), he(new u64[n_edges]);
     parallel_for(n_edges, [&](u64 b, u64 e_) {
         for (u64 i = b; i < e_; i++) {
@@ -3648,10 +3573,10 @@ int64_t disco_partition_edges(disco_ctx *c, const disco_edge *edges, uint64_t n_
     int rc = DISCO_OK;
     int64_t res = 0;
     do {
-        if ((rc = dev_alloc(c, &d_src, n_edges)) != DISCO_OK) break;
-        if ((rc = dev_alloc(c, &d_ent, n_edges)) != DISCO_OK) break;
-        if ((rc = dev_alloc(c, &d_pos, n_edges)) != DISCO_OK) break;
-        if ((rc = dev_alloc(c, &d_valid, n_edges)) != DISCO_OK) break;
+        if ((rc = ensure(c, d_src, n_edges)) != DISCO_OK) break;
+        if ((rc = ensure(c, d_ent, n_edges)) != DISCO_OK) break;
+        if ((rc = ensure(c, d_pos, n_edges)) != DISCO_OK) break;
+        if ((rc = ensure(c, d_valid, n_edges)) != DISCO_OK) break;
         if (hipMemcpyAsync(d_src, hs.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
             hipMemcpyAsync(d_ent, he.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
             hipMemsetAsync(d_valid, 1, n_edges, c->stream) != hipSuccess) {
@@ -3661,10 +3586,10 @@ int64_t disco_partition_edges(disco_ctx *c, const disco_edge *edges, uint64_t n_
         hipLaunchKernelGGL(iota_u64_kernel, dim3(flat_grid(c, n_edges)), dim3(256), 0, c->stream, d_pos, n_edges);
         res = partition_edges(c, d_src, d_ent, d_valid, d_pos, n_edges, n_edges, n_nodes, n_files, out);
     } while (0);
-    dev_free(c, &d_src, n_edges);
-    dev_free(c, &d_ent, n_edges);
-    dev_free(c, &d_pos, n_edges);
-    dev_free(c, &d_valid, n_edges);
+    release(c, d_src);
+    release(c, d_ent);
+    release(c, d_pos);
+    release(c, d_valid);
     return rc != DISCO_OK ? rc : res;
 }
 
@@ -3689,20 +3614,20 @@ int64_t disco_format_edges(disco_ctx *c, uint32_t n_files, const uint16_t *edge_
     g.pos = c->d_out_pos;
     g.len = c->d_len;
     g.n_slots = c->out_used;
-    u64 *d_findex = nullptr, *within = nullptr, *place = nullptr;
-    u8 *bytes = nullptr, *sel = nullptr;
-    u16 *efile = nullptr;
+    DevBuf<u64> d_findex, within, place;
+    DevBuf<u8> bytes, sel;
+    DevBuf<u16> efile;
     auto body = [&]() -> int {
         if (file_index) {
-            CHK(dev_alloc(c, &d_findex, c->n));
+            CHK(ensure(c, d_findex, c->n));
             HIPCHK(c, hipMemcpyAsync(d_findex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
         }
         g.file_index = d_findex;
-        CHK(dev_alloc(c, &bytes, ne));
-        CHK(dev_alloc(c, &sel, ne));
-        CHK(dev_alloc(c, &efile, ne));
-        CHK(dev_alloc(c, &within, ne + 1));
-        CHK(dev_alloc(c, &place, ne));
+        CHK(ensure(c, bytes, ne));
+        CHK(ensure(c, sel, ne));
+        CHK(ensure(c, efile, ne));
+        CHK(ensure(c, within, ne + 1));
+        CHK(ensure(c, place, ne));
         if (edge_file) HIPCHK(c, hipMemcpyAsync(efile, edge_file, ne * sizeof(u16), hipMemcpyHostToDevice, c->stream));
         else HIPCHK(c, hipMemsetAsync(efile, 0, ne * sizeof(u16), c->stream));
         hipLaunchKernelGGL(text_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, bytes);
@@ -3717,7 +3642,7 @@ int64_t disco_format_edges(disco_ctx *c, uint32_t n_files, const uint16_t *edge_
         }
         file_offsets[n_files] = base;
         c->text_off.assign(file_offsets, file_offsets + n_files + 1);
-        CHK(ensure_cap(c, &c->d_text, &c->text_cap, std::max<u64>(base, 1)));
+        CHK(ensure(c, c->d_text, std::max<u64>(base, 1)));
         hipLaunchKernelGGL(text_write_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, place, c->d_text);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3725,12 +3650,12 @@ int64_t disco_format_edges(disco_ctx *c, uint32_t n_files, const uint16_t *edge_
         return DISCO_OK;
     };
     const int rc = body();
-    dev_free(c, &d_findex, c->n);
-    dev_free(c, &bytes, ne);
-    dev_free(c, &sel, ne);
-    dev_free(c, &efile, ne);
-    dev_free(c, &within, ne + 1);
-    dev_free(c, &place, ne);
+    release(c, d_findex);
+    release(c, bytes);
+    release(c, sel);
+    release(c, efile);
+    release(c, within);
+    release(c, place);
     return rc != DISCO_OK ? rc : (int64_t)c->text_bytes;
 }
 
@@ -3848,19 +3773,19 @@ static int contract_chains(disco_ctx *c, const u64 *d_src, const u64 *d_ent, con
     g.len = c->d_len;
     g.n_slots = n_slots;
     g.min_ovl = min_ovl;
-    u32 *deg = nullptr, *he = nullptr, *links_of = nullptr, *live = nullptr;
-    u8 *internal = nullptr, *is_head = nullptr;
-    ChRank *ra = nullptr, *rb = nullptr;
-    u64 *comp_id = nullptr, *link_start = nullptr;
+    DevBuf<u32> deg, he, links_of, live;
+    DevBuf<u8> internal, is_head;
+    DevBuf<ChRank> ra, rb;
+    DevBuf<u64> comp_id, link_start;
     const u64 n_half = 2 * n_slots;
     int rc = DISCO_OK;
     auto body = [&]() -> int {
-        CHK(dev_alloc(c, &deg, n));
-        CHK(dev_alloc(c, &he, 2 * n));
-        CHK(dev_alloc(c, &internal, n));
-        CHK(dev_alloc(c, &ra, n_half));
-        CHK(dev_alloc(c, &rb, n_half));
-        CHK(dev_alloc(c, &live, 1));
+        CHK(ensure(c, deg, n));
+        CHK(ensure(c, he, 2 * n));
+        CHK(ensure(c, internal, n));
+        CHK(ensure(c, ra, n_half));
+        CHK(ensure(c, rb, n_half));
+        CHK(ensure(c, live, 1));
         HIPCHK(c, hipMemsetAsync(deg, 0, n * sizeof(u32), c->stream));
         hipLaunchKernelGGL(ch_degree_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, deg, he);
         hipLaunchKernelGGL(ch_internal_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, g, deg, he, n, internal);
@@ -3880,20 +3805,20 @@ static int contract_chains(disco_ctx *c, const u64 *d_src, const u64 *d_ent, con
             std::swap(ra, rb);
             if (!h_live) break;
         }
-        dev_free(c, &rb, n_half);
-        dev_free(c, &deg, n);
-        CHK(dev_alloc(c, &is_head, n_slots));
-        CHK(dev_alloc(c, &links_of, n_slots));
-        CHK(ensure_cap(c, &c->d_ch_dead, &c->ch_dead_cap, std::max<u64>(ne, 1)));
+        release(c, rb);
+        release(c, deg);
+        CHK(ensure(c, is_head, n_slots));
+        CHK(ensure(c, links_of, n_slots));
+        CHK(ensure(c, c->d_ch_dead, std::max<u64>(ne, 1)));
         HIPCHK(c, hipMemsetAsync(c->d_ch_dead, 0, std::max<u64>(ne, 1), c->stream));
         hipLaunchKernelGGL(ch_heads_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, ra, is_head, links_of, c->d_ch_dead);
-        CHK(dev_alloc(c, &comp_id, n_slots + 1));
-        CHK(dev_alloc(c, &link_start, n_slots + 1));
+        CHK(ensure(c, comp_id, n_slots + 1));
+        CHK(ensure(c, link_start, n_slots + 1));
         u64 n_comp = 0, n_links = 0;
         CHK((scan_exclusive<u8, u64>(c, is_head, n_slots, comp_id, false, &n_comp)));
         CHK((scan_exclusive<u32, u64>(c, links_of, n_slots, link_start, false, &n_links)));
-        CHK(ensure_cap(c, &c->d_ch_comp, &c->ch_comp_cap, std::max<u64>(n_comp, 1)));
-        CHK(ensure_cap(c, &c->d_ch_links, &c->ch_links_cap, std::max<u64>(n_links, 1)));
+        CHK(ensure(c, c->d_ch_comp, std::max<u64>(n_comp, 1)));
+        CHK(ensure(c, c->d_ch_links, std::max<u64>(n_links, 1)));
         hipLaunchKernelGGL(ch_emit_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, ra, comp_id, link_start, c->d_ch_comp, c->d_ch_links);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3904,16 +3829,16 @@ static int contract_chains(disco_ctx *c, const u64 *d_src, const u64 *d_ent, con
         return DISCO_OK;
     };
     rc = body();
-    dev_free(c, &deg, n);
-    dev_free(c, &he, 2 * n);
-    dev_free(c, &internal, n);
-    dev_free(c, &ra, n_half);
-    dev_free(c, &rb, n_half);
-    dev_free(c, &live, 1);
-    dev_free(c, &is_head, n_slots);
-    dev_free(c, &links_of, n_slots);
-    dev_free(c, &comp_id, n_slots + 1);
-    dev_free(c, &link_start, n_slots + 1);
+    release(c, deg);
+    release(c, he);
+    release(c, internal);
+    release(c, ra);
+    release(c, rb);
+    release(c, live);
+    release(c, is_head);
+    release(c, links_of);
+    release(c, comp_id);
+    release(c, link_start);
     return rc;
 }
 
@@ -3942,8 +3867,8 @@ int disco_contract_chains_of(disco_ctx *c, const disco_edge *edges, uint64_t n_e
         c->ch_comp_n = c->ch_links_n = c->ch_edges_n = 0;
         c->ch_ready = true;
     } else {
-        u64 *d_src = nullptr, *d_ent = nullptr, *d_pos = nullptr;
-        u8 *d_valid = nullptr;
+        DevBuf<u64> d_src, d_ent, d_pos;
+        DevBuf<u8> d_valid;
         std::unique_ptr<u64[]> hs(new u64[n_edges]), he(new u64[n_edges]);
         std::atomic<bool> bad{false};
         parallel_for(n_edges, [&](u64 b, u64 e_) {
@@ -3956,10 +3881,10 @@ int disco_contract_chains_of(disco_ctx *c, const disco_edge *edges, uint64_t n_e
         if (bad) return fail(c, DISCO_E_ARG, "disco_contract_chains_of: an edge names a read the context does not hold");
         int rc = DISCO_OK;
         do {
-            if ((rc = dev_alloc(c, &d_src, n_edges)) != DISCO_OK) break;
-            if ((rc = dev_alloc(c, &d_ent, n_edges)) != DISCO_OK) break;
-            if ((rc = dev_alloc(c, &d_pos, n_edges)) != DISCO_OK) break;
-            if ((rc = dev_alloc(c, &d_valid, n_edges)) != DISCO_OK) break;
+            if ((rc = ensure(c, d_src, n_edges)) != DISCO_OK) break;
+            if ((rc = ensure(c, d_ent, n_edges)) != DISCO_OK) break;
+            if ((rc = ensure(c, d_pos, n_edges)) != DISCO_OK) break;
+            if ((rc = ensure(c, d_valid, n_edges)) != DISCO_OK) break;
             if (hipMemcpyAsync(d_src, hs.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                 hipMemcpyAsync(d_ent, he.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                 hipMemsetAsync(d_valid, 1, n_edges, c->stream) != hipSuccess) {
@@ -3969,10 +3894,10 @@ int disco_contract_chains_of(disco_ctx *c, const disco_edge *edges, uint64_t n_e
             hipLaunchKernelGGL(iota_u64_kernel, dim3(flat_grid(c, n_edges)), dim3(256), 0, c->stream, d_pos, n_edges);
             rc = contract_chains(c, d_src, d_ent, d_valid, d_pos, n_edges, n_edges, c->n, min_overlap_simplify);
         } while (0);
-        dev_free(c, &d_src, n_edges);
-        dev_free(c, &d_ent, n_edges);
-        dev_free(c, &d_pos, n_edges);
-        dev_free(c, &d_valid, n_edges);
+        release(c, d_src);
+        release(c, d_ent);
+        release(c, d_pos);
+        release(c, d_valid);
         if (rc != DISCO_OK) return rc;
     }
     if (n_composite) *n_composite = c->ch_comp_n;
@@ -4144,22 +4069,6 @@ int disco_get_counters(disco_ctx *c, disco_counters *o)
         if (rc_ != DISCO_OK) return fail((c), rc_, "%s: %s", #expr, (c)->comm->err.c_str());    \
     } while (0)
 
-/* grow-only buffer that keeps its first `used` elements */
-template <typename T>
-static int ensure_cap_keep(disco_ctx *c, T **p, u64 *cap, u64 need, u64 used)
-{
-    if (*p && need <= *cap) return DISCO_OK;
-    T *q = nullptr;
-    const u64 ncap = std::max<u64>(need + need / 8, 1);
-    CHK(dev_alloc(c, &q, ncap));
-    if (*p && used) HIPCHK(c, hipMemcpyAsync(q, *p, used * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    dev_free(c, p, *cap);
-    *p = q;
-    *cap = ncap;
-    return DISCO_OK;
-}
-
 static void dist_range(const disco_ctx *c, u64 n, u64 *per, u64 *lo, u64 *hi)
 {
     const u64 G = c->comm ? (u64)c->comm->world : 1, r = c->comm ? (u64)c->comm->rank : 0;
@@ -4177,7 +4086,7 @@ static int route_items(disco_ctx *c, const T *items, u64 n, F owner, T *out, std
 {
     const u32 G = (u32)c->comm->world;
     cnt.assign(G, 0);
-    if (!c->d_route) CHK(dev_alloc(c, &c->d_route, 2 * DIST_MAX_WORLD));
+    CHK(ensure(c, c->d_route, 2 * DIST_MAX_WORLD));
     HIPCHK(c, hipMemsetAsync(c->d_route, 0, 2 * DIST_MAX_WORLD * sizeof(u64), c->stream));
     if (n) hipLaunchKernelGGL((route_count_kernel<T, F>), dim3(flat_grid(c, n)), dim3(256), 0, c->stream, items, n, owner, G, c->d_route);
     HIPCHK(c, hipGetLastError());
@@ -4255,8 +4164,8 @@ static int dist_deal_rows(disco_ctx *c)
     typedef ReadItem<W> Item;
     const u64 nhome = c->home_hi - c->home_lo;
     const u64 per16 = (sizeof(Item) + 15) / 16; /* (d_x16a / d_x16b are arrays of 16-byte items) */
-    CHK(ensure_cap(c, &c->d_x16a, &c->x16a_cap, std::max<u64>(2 * nhome * per16, 1)));
-    Item *items = (Item *)c->d_x16a, *sorted = (Item *)(c->d_x16a + nhome * per16);
+    CHK(ensure(c, c->d_x16a, std::max<u64>(2 * nhome * per16, 1)));
+    Item *items = (Item *)c->d_x16a.p, *sorted = (Item *)(c->d_x16a + nhome * per16);
     if (nhome) hipLaunchKernelGGL(read_items_kernel<W>, dim3(flat_grid(c, nhome * (W + 1))), dim3(256), 0, c->stream, (const u64 *)c->d_reads, (const u16 *)c->d_len, c->S, c->home_lo, c->home_hi, items);
     HIPCHK(c, hipGetLastError());
     std::vector<u64> scnt, rcnt;
@@ -4265,9 +4174,9 @@ static int dist_deal_rows(disco_ctx *c)
     CHK(exchange_counts(c, scnt, rcnt));
     const u64 nr = vsum(rcnt);
     if (nr != c->n_own) return fail(c, DISCO_E_STATE, "dealt reads: %llu rows arrive for %llu own reads", (unsigned long long)nr, (unsigned long long)c->n_own);
-    CHK(ensure_cap(c, &c->d_x16b, &c->x16b_cap, std::max<u64>(nr * per16, 1)));
+    CHK(ensure(c, c->d_x16b, std::max<u64>(nr * per16, 1)));
     CHK(a2a_items(c, DISCO_X_READS_DEALT, sorted, scnt, c->d_x16b, rcnt, sizeof(Item)));
-    if (nr) hipLaunchKernelGGL(read_items_place_kernel<W>, dim3(flat_grid(c, nr * (W + 1))), dim3(256), 0, c->stream, (const Item *)c->d_x16b, nr, c->S, c->d_reads, c->d_len);
+    if (nr) hipLaunchKernelGGL(read_items_place_kernel<W>, dim3(flat_grid(c, nr * (W + 1))), dim3(256), 0, c->stream, (const Item *)c->d_x16b.p, nr, c->S, c->d_reads, c->d_len);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
 }
@@ -4285,8 +4194,8 @@ static int dist_deal_reads(disco_ctx *c)
     DISCO_TRACE("dist_deal_reads");
     const u32 G = (u32)c->comm->world, r = (u32)c->comm->rank;
     const u64 hlo = c->home_lo, hhi = c->home_hi;
-    CHK(ensure_cap(c, &c->d_okey, &c->okey_cap, c->n_alloc));
-    if (!c->d_otab) CHK(dev_alloc(c, &c->d_otab, c->n_alloc));
+    CHK(ensure(c, c->d_okey, c->n_alloc));
+    CHK(ensure(c, c->d_otab, c->n_alloc));
     DiscoView v = view(c);
     if (hhi > hlo) {
         if (v.m == RUNS_M) hipLaunchKernelGGL(read_keys_kernel<true>, dim3((unsigned)((hhi - hlo + 255) / 256)), dim3(256), 0, c->stream, v, hlo, hhi, c->d_okey);
@@ -4300,8 +4209,8 @@ static int dist_deal_reads(disco_ctx *c)
         c->dinfo.ms[DISCO_X_KEYS] += ms_since(t0);
     }
     /* owners and the own reads (about n / G of them: sized for the whole job once — 4 bytes per read) */
-    CHK(ensure_cap(c, &c->d_own_ids, &c->own_ids_cap, std::max<u64>(c->n, 1)));
-    if (!c->d_list_n) CHK(dev_alloc(c, &c->d_list_n, 1));
+    CHK(ensure(c, c->d_own_ids, std::max<u64>(c->n, 1)));
+    CHK(ensure(c, c->d_list_n, 1));
     HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
     /* the grouping of the own reads (the rank's processing order) counts its buckets in the same pass: how many buckets follows from
      * the number of own reads, which this pass produces — it is taken from the job's share n / G instead (the keys spread the reads to
@@ -4310,8 +4219,8 @@ static int dist_deal_reads(disco_ctx *c)
     const bool order_own = own_order_wanted(c, std::max<u64>(c->n / G, 1), &obits) && !getenv("DISCO_DIST_ORDER_TWO_PASSES");
     const u32 oshift = 32u - (u32)obits;
     if (order_own) {
-        CHK(ensure_cap(c, &c->d_ocnt, &c->ocnt_cap, (1ull << obits) + 1));
-        CHK(ensure_cap(c, &c->d_oslot, &c->oslot_cap, std::max<u64>(c->n, 1))); /* (about n / G are used: sized like the list of own ids) */
+        CHK(ensure(c, c->d_ocnt, (1ull << obits) + 1));
+        CHK(ensure(c, c->d_oslot, std::max<u64>(c->n, 1))); /* (about n / G are used: sized like the list of own ids) */
         HIPCHK(c, hipMemsetAsync(c->d_ocnt, 0, ((1ull << obits) + 1) * sizeof(u32), c->stream));
     }
     if (c->n) hipLaunchKernelGGL(own_select_kernel, dim3((unsigned)std::min<u64>((c->n + OWN_TILE - 1) / OWN_TILE, (u64)c->n_cu * 16)), dim3(256), 0, c->stream, (const u32 *)c->d_okey, c->n, G, r,
@@ -4337,7 +4246,7 @@ static int dist_deal_reads(disco_ctx *c)
         }
     }
     /* the processing order: the own reads grouped by key (disco_probe's grouping, over the list) */
-    CHK(ensure_cap(c, &c->d_order_own, &c->order_cap, std::max<u64>(n_own, 1)));
+    CHK(ensure(c, c->d_order_own, std::max<u64>(n_own, 1)));
     ph_begin(c, DISCO_PH_ORDER);
     int obits2 = 16;
     const bool order_two = !order_own && own_order_wanted(c, n_own, &obits2); /* (DISCO_DIST_ORDER_TWO_PASSES: the counting pass of rounds 5 as a pass of its own) */
@@ -4346,8 +4255,8 @@ static int dist_deal_reads(disco_ctx *c)
         const u64 order_buckets = 1ull << ob;
         const u32 oshift = 32u - (u32)ob;
         if (order_two) {
-            CHK(ensure_cap(c, &c->d_ocnt, &c->ocnt_cap, order_buckets + 1));
-            CHK(ensure_cap(c, &c->d_oslot, &c->oslot_cap, n_own));
+            CHK(ensure(c, c->d_ocnt, order_buckets + 1));
+            CHK(ensure(c, c->d_oslot, n_own));
             HIPCHK(c, hipMemsetAsync(c->d_ocnt, 0, (order_buckets + 1) * sizeof(u32), c->stream));
             hipLaunchKernelGGL(order_count_list_kernel, dim3(flat_grid(c, n_own)), dim3(256), 0, c->stream, (const u32 *)c->d_okey, (const u32 *)c->d_own_ids, n_own, G, r, oshift, c->d_ocnt, c->d_oslot);
         }
@@ -4377,7 +4286,7 @@ static int index_count_own_list(disco_ctx *c, const DiscoView &v, ulonglong2 *re
     const dim3 grid((unsigned)((n_own + 255) / 256));
     const u64 *list = c->d_order_own;
     if (lpr) {
-        CHK(ensure_cap(c, &c->d_runs, &c->runs_cap, n_own * (u64)lpr));
+        CHK(ensure(c, c->d_runs, n_own * (u64)lpr));
         c->runs_lpr = lpr;
         c->runs_lo = 0;
         c->runs_n = n_own;
@@ -4442,11 +4351,11 @@ static int dist_build_index(disco_ctx *c)
     const u64 blo = blo_of(r), bhi = blo_of(r + 1);
     const bool part = c->part_index;
     if (!part) { /* (partitioned: the slices are sized below, once the records have arrived) */
-        CHK(ensure_cap(c, &c->d_bkt, &c->bkt_cap, T + 1));
-        CHK(ensure_cap(c, &c->d_ent, &c->ent_cap, 2 * c->n));
+        CHK(ensure(c, c->d_bkt, T + 1));
+        CHK(ensure(c, c->d_ent, 2 * c->n));
     }
-    CHK(ensure_cap(c, &c->d_okey, &c->okey_cap, c->loci ? c->n_alloc : c->n));
-    CHK(ensure_cap(c, &c->d_rec, &c->rec_cap, std::max<u64>(2 * nloc, 1)));
+    CHK(ensure(c, c->d_okey, c->loci ? c->n_alloc : c->n));
+    CHK(ensure(c, c->d_rec, std::max<u64>(2 * nloc, 1)));
     c->adj_imported = false;
     ph_begin(c, DISCO_PH_INDEX);
     DiscoView v = view(c);
@@ -4473,13 +4382,13 @@ static int dist_build_index(disco_ctx *c)
         }
     }
     /* records -> owner of their bucket range */
-    CHK(ensure_cap(c, &c->d_x16a, &c->x16a_cap, std::max<u64>(2 * nloc, 1)));
+    CHK(ensure(c, c->d_x16a, std::max<u64>(2 * nloc, 1)));
     std::vector<u64> scnt, rcnt, matrix;
     RouteByBucket f{logT, G};
-    CHK(route_items(c, c->d_rec, 2 * nloc, f, c->d_x16a, scnt));
+    CHK(route_items(c, c->d_rec.p, 2 * nloc, f, c->d_x16a.p, scnt));
     CHK(exchange_counts(c, scnt, rcnt, &matrix));
     const u64 nrec = vsum(rcnt);
-    CHK(ensure_cap(c, &c->d_x16b, &c->x16b_cap, std::max<u64>(nrec, 1)));
+    CHK(ensure(c, c->d_x16b, std::max<u64>(nrec, 1)));
     CHK(a2a_items(c, DISCO_X_INDEX_RECORDS, c->d_x16a, scnt, c->d_x16b, rcnt, sizeof(ulonglong2)));
     /* my bucket range and the position of my records in the global record array (shards in rank order) */
     std::vector<u64> shard((size_t)G, 0);
@@ -4492,8 +4401,8 @@ static int dist_build_index(disco_ctx *c)
     if (part) {
         /* the index STAYS partitioned: this rank's slice of the bucket table (bhi - blo + 1 entries, bucket b at [b - blo]) and its
          * records (positions inside the slice) are all it ever holds; the lookups come to it (dist_partitioned_probe) */
-        CHK(ensure_cap(c, &c->d_bkt, &c->bkt_cap, bhi - blo + 1));
-        CHK(ensure_cap(c, &c->d_ent, &c->ent_cap, std::max<u64>(nrec, 1)));
+        CHK(ensure(c, c->d_bkt, bhi - blo + 1));
+        CHK(ensure(c, c->d_ent, std::max<u64>(nrec, 1)));
         u32 *bkt0 = c->d_bkt - blo; /* indexed by global bucket number */
         HIPCHK(c, hipMemsetAsync(c->d_bkt, 0, (bhi - blo + 1) * sizeof(u32), c->stream));
         if (nrec) hipLaunchKernelGGL(shard_count_kernel, dim3(flat_grid(c, nrec)), dim3(256), 0, c->stream, c->d_x16b, nrec, bkt0);
@@ -4559,12 +4468,12 @@ static int dist_partitioned_probe(disco_ctx *c)
     while ((1ull << logT) < c->T) ++logT;
     /* 1. queries. With the minimizer runs of the index pass: one per run (count, then fill), reads with an unusable run list the long
      *    way; without them (windows other than 17 m-mers, reads beyond 256 bases) every read the long way */
-    if (!c->d_list_n) CHK(dev_alloc(c, &c->d_list_n, 1));
+    CHK(ensure(c, c->d_list_n, 1));
     u32 *d_nslow = c->d_n_slow;
     auto make = [&](ulonglong2 *out, bool collect_slow) {
         const int grid = flat_grid(c, nloc * (u64)c->runs_lpr);
-        u32 *slow = collect_slow ? (u32 *)c->d_slow_list : nullptr;
-        const u32 cap = c->slow_cap * 2; /* (the list's u64 slots hold two read indices each) */
+        u32 *slow = collect_slow ? (u32 *)c->d_slow_list.p : nullptr;
+        const u32 cap = c->d_slow_list.cap * 2; /* (the list's u64 slots hold two read indices each) */
         if (c->runs_lpr == 16) hipLaunchKernelGGL(pq_make_kernel<16>, dim3(grid), dim3(256), 0, c->stream, v, (const u32 *)c->d_runs, lo, c->q_hi, r, out, c->d_list_n, slow, cap, d_nslow);
         else hipLaunchKernelGGL(pq_make_kernel<32>, dim3(grid), dim3(256), 0, c->stream, v, (const u32 *)c->d_runs, lo, c->q_hi, r, out, c->d_list_n, slow, cap, d_nslow);
     };
@@ -4574,12 +4483,7 @@ static int dist_partitioned_probe(disco_ctx *c)
         u32 ns = 0;
         for (int attempt = 0;; attempt++) { /* the list of reads without a usable run list: sized by a first try */
             const u32 want = attempt ? ns / 2 + 1024 : (u32)std::min<u64>(nloc, nloc / 128 + 1024);
-            if (want > c->slow_cap) {
-                dev_free(c, &c->d_slow_list, c->slow_cap);
-                c->slow_cap = 0;
-                CHK(dev_alloc(c, &c->d_slow_list, want));
-                c->slow_cap = want;
-            }
+            if (want > c->d_slow_list.cap) CHK(ensure(c, c->d_slow_list, want));
             HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
             HIPCHK(c, hipMemsetAsync(d_nslow, 0, sizeof(u32), c->stream));
             if (nloc) make(nullptr, true);
@@ -4587,22 +4491,22 @@ static int dist_partitioned_probe(disco_ctx *c)
             HIPCHK(c, hipMemcpyAsync(&nq_fast, c->d_list_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(&ns, d_nslow, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (ns <= c->slow_cap * 2 || attempt) break;
+            if (ns <= c->d_slow_list.cap * 2 || attempt) break;
         }
-        if (ns > c->slow_cap * 2) return fail(c, DISCO_E_CAPACITY, "dist_partitioned_probe: slow list could not be sized");
+        if (ns > c->d_slow_list.cap * 2) return fail(c, DISCO_E_CAPACITY, "dist_partitioned_probe: slow list could not be sized");
         n_slow = ns;
-        slow = (const u32 *)c->d_slow_list;
+        slow = (const u32 *)c->d_slow_list.p;
     } else
         n_slow = nloc;
     /* the long way: queries per read, scan, fill behind the fast ones */
-    u32 *slow_cnt = nullptr;
-    u64 *slow_start = nullptr;
+    DevBuf<u32> slow_cnt;
+    DevBuf<u64> slow_start;
     u64 nq_slow = 0;
     int rc = DISCO_OK;
     auto slow_count = [&]() -> int {
         if (!n_slow) return DISCO_OK;
-        CHK(dev_alloc(c, &slow_cnt, n_slow));
-        CHK(dev_alloc(c, &slow_start, n_slow + 1));
+        CHK(ensure(c, slow_cnt, n_slow));
+        CHK(ensure(c, slow_start, n_slow + 1));
         if (c->k > 64) hipLaunchKernelGGL(pq_slow_kernel<true>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)nullptr, (ulonglong2 *)nullptr);
         else hipLaunchKernelGGL(pq_slow_kernel<false>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)nullptr, (ulonglong2 *)nullptr);
         CHK((scan_exclusive<u32, u64>(c, slow_cnt, n_slow, slow_start, false, &nq_slow)));
@@ -4610,7 +4514,7 @@ static int dist_partitioned_probe(disco_ctx *c)
     };
     rc = slow_count();
     const u64 nqs = nq_fast + nq_slow;
-    if (rc == DISCO_OK) rc = ensure_cap(c, &c->d_x16a, &c->x16a_cap, std::max<u64>(2 * nqs, 1)); /* flat list | partitioned by owner */
+    if (rc == DISCO_OK) rc = ensure(c, c->d_x16a, std::max<u64>(2 * nqs, 1)); /* flat list | partitioned by owner */
     if (rc == DISCO_OK) {
         HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
         if (have_runs && nloc) make(c->d_x16a, false);
@@ -4620,50 +4524,44 @@ static int dist_partitioned_probe(disco_ctx *c)
         }
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, DISCO_E_HIP, "dist_partitioned_probe: query kernels failed");
     }
-    dev_free(c, &slow_cnt, n_slow);
-    dev_free(c, &slow_start, n_slow + 1);
+    release(c, slow_cnt);
+    release(c, slow_start);
     CHK(rc);
     c->slow_rows = have_runs ? n_slow : 0;
     /* 2. queries -> owners of their buckets */
     std::vector<u64> scnt, rcnt;
     RouteByBucket fb{logT, G};
     ulonglong2 *q_sorted = c->d_x16a + nqs;
-    CHK(route_items(c, c->d_x16a, nqs, fb, q_sorted, scnt));
+    CHK(route_items(c, c->d_x16a.p, nqs, fb, q_sorted, scnt));
     CHK(exchange_counts(c, scnt, rcnt));
     const u64 nq_in = vsum(rcnt);
-    CHK(ensure_cap(c, &c->d_x16b, &c->x16b_cap, std::max<u64>(nq_in, 1)));
+    CHK(ensure(c, c->d_x16b, std::max<u64>(nq_in, 1)));
     CHK(a2a_items(c, DISCO_X_QUERIES, q_sorted, scnt, c->d_x16b, rcnt, sizeof(ulonglong2)));
     /* 3. the owner answers: hits per query, scan, fill */
-    CHK(ensure_cap(c, &c->d_deg_tmp, &c->deg_tmp_cap, std::max<u64>(nq_in, 1)));
-    CHK(ensure_cap(c, &c->d_pq_start, &c->pq_start_cap, nq_in + 1));
+    CHK(ensure(c, c->d_deg_tmp, std::max<u64>(nq_in, 1)));
+    CHK(ensure(c, c->d_pq_start, nq_in + 1));
     const u32 *bkt = c->d_bkt;
     u64 n_hits_out = 0;
     if (nq_in) hipLaunchKernelGGL(pq_answer_kernel<false>, dim3(flat_grid(c, nq_in)), dim3(256), 0, c->stream, (const ulonglong2 *)c->d_x16b, nq_in, bkt, (const u64 *)c->d_ent, c->part_blo, c->per,
                                   nf, c->d_deg_tmp, (const u64 *)nullptr, (ulonglong2 *)nullptr);
     CHK((scan_exclusive<u32, u64>(c, c->d_deg_tmp, nq_in, c->d_pq_start, false, &n_hits_out)));
     /* hits: flat list | partitioned by requester — in the send buffer (the queries it held have been answered into counts) */
-    CHK(ensure_cap_keep(c, &c->d_x16a, &c->x16a_cap, std::max<u64>(2 * n_hits_out, 1), 0));
+    CHK(ensure_keep(c, c->d_x16a, std::max<u64>(2 * n_hits_out, 1), 0));
     if (nq_in) hipLaunchKernelGGL(pq_answer_kernel<true>, dim3(flat_grid(c, nq_in)), dim3(256), 0, c->stream, (const ulonglong2 *)c->d_x16b, nq_in, bkt, (const u64 *)c->d_ent, c->part_blo, c->per,
                                   nf, c->d_deg_tmp, (const u64 *)c->d_pq_start, c->d_x16a);
     HIPCHK(c, hipGetLastError());
     /* 4. hits -> the reads' owners */
     ulonglong2 *h_sorted = c->d_x16a + n_hits_out;
     RouteByHitRank fh;
-    CHK(route_items(c, c->d_x16a, n_hits_out, fh, h_sorted, scnt));
+    CHK(route_items(c, c->d_x16a.p, n_hits_out, fh, h_sorted, scnt));
     CHK(exchange_counts(c, scnt, rcnt));
     const u64 n_hits = vsum(rcnt);
-    CHK(ensure_cap(c, &c->d_x16b, &c->x16b_cap, std::max<u64>(n_hits, 1)));
+    CHK(ensure(c, c->d_x16b, std::max<u64>(n_hits, 1)));
     CHK(a2a_items(c, DISCO_X_HITS, h_sorted, scnt, c->d_x16b, rcnt, sizeof(ulonglong2)));
     /* 5. rows of the hit buffer (exactly sized), headers by read and by position in the processing order */
-    if (n_hits + 65536 > c->hits_cap) {
-        dev_free(c, &c->d_hits, c->hits_cap);
-        c->hits_cap = 0;
-        const u64 want = n_hits + n_hits / 8 + 65536;
-        CHK(dev_alloc(c, &c->d_hits, want));
-        c->hits_cap = want;
-    }
-    CHK(ensure_cap(c, &c->d_deg_tmp, &c->deg_tmp_cap, std::max<u64>(2 * nloc, 1))); /* counts | cursors of the own reads */
-    CHK(ensure_cap(c, &c->d_pq_start, &c->pq_start_cap, nloc + 1));
+    if (n_hits + 65536 > c->d_hits.cap) CHK(ensure(c, c->d_hits, n_hits + n_hits / 8 + 65536));
+    CHK(ensure(c, c->d_deg_tmp, std::max<u64>(2 * nloc, 1))); /* counts | cursors of the own reads */
+    CHK(ensure(c, c->d_pq_start, nloc + 1));
     HIPCHK(c, hipMemsetAsync(c->d_deg_tmp, 0, std::max<u64>(2 * nloc, 1) * sizeof(u32), c->stream));
     if (n_hits) hipLaunchKernelGGL(pq_rows_count_kernel, dim3(flat_grid(c, n_hits)), dim3(256), 0, c->stream, (const ulonglong2 *)c->d_x16b, n_hits, c->d_deg_tmp);
     u64 placed = 0;
@@ -4690,8 +4588,8 @@ static int dist_mark_contained(disco_ctx *c)
     const u32 G = (u32)c->comm->world;
     /* (the flags of an id range are fixed by the rank whose reads arrived in it, whoever processes them: best[] is a table by read id) */
     const u64 lo = c->home_lo, nloc = c->home_hi - c->home_lo, per = c->per;
-    if (!c->d_contained) CHK(dev_alloc(c, &c->d_contained, c->n_alloc));
-    if (!c->d_cbits) CHK(dev_alloc(c, &c->d_cbits, c->n_alloc / 64 + 1));
+    CHK(ensure(c, c->d_contained, c->n_alloc));
+    CHK(ensure(c, c->d_cbits, c->n_alloc / 64 + 1));
     const auto t0 = HClock::now();
     const u64 r = (u64)c->comm->rank;
     /* Who is contained decides everything that follows in the pass (edge selection, the second verify pass); by WHOM — the smallest key
@@ -4700,7 +4598,7 @@ static int dist_mark_contained(disco_ctx *c)
      * link time at G = 8 / 50 M reads that nothing used to hide. DISCO_DIST_KEYS_ON_PATH=1 (every rank alike), one communicator: as before */
     if (c->comm_bulk && !getenv("DISCO_DIST_ONE_COMM") && !getenv("DISCO_DIST_KEYS_ON_PATH")) {
         const u64 words = c->n_alloc / 64;
-        CHK(ensure_cap(c, &c->d_cb_all, &c->cb_all_cap, std::max<u64>(words * G, 1)));
+        CHK(ensure(c, c->d_cb_all, std::max<u64>(words * G, 1)));
         if (!c->ev_keys) {
             HIPCHK(c, hipEventCreateWithFlags(&c->ev_keys, hipEventDisableTiming));
             HIPCHK(c, hipEventCreateWithFlags(&c->ev_keys_go, hipEventDisableTiming));
@@ -4758,25 +4656,15 @@ static int adj_tail_reserve(disco_ctx *c, u64 need, u64 *base)
     const u64 used = (in_hits ? c->hits_used : c->adj_total) + c->nadj_used;
     /* test hook: the array counts as full — every call with something to place moves it (the path a probe that sizes the buffer exactly takes) */
     const bool tight = getenv("DISCO_TEST_TIGHT_TAIL") != nullptr && need != 0;
-    auto move_to_larger = [&](u64 **p, u64 *cap) -> int { /* (ensure_cap_keep's steps, for an array that is large enough on paper) */
-        u64 *q = nullptr;
-        const u64 ncap = used + need + (used + need) / 8;
-        CHK(dev_alloc(c, &q, ncap));
-        if (used) HIPCHK(c, hipMemcpyAsync(q, *p, used * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        dev_free(c, p, *cap);
-        *p = q;
-        *cap = ncap;
-        return DISCO_OK;
-    };
+    const u64 tight_cap = used + need + (used + need) / 8; /* (ensure_keep's size, for an array that is large enough on paper) */
     if (in_hits) {
-        if (tight) CHK(move_to_larger(&c->d_hits, &c->hits_cap));
-        else if (used + need > c->hits_cap) CHK(ensure_cap_keep(c, &c->d_hits, &c->hits_cap, used + need, used));
+        if (tight) CHK(move_keep(c, c->d_hits, tight_cap, used));
+        else if (used + need > c->d_hits.cap) CHK(ensure_keep(c, c->d_hits, used + need, used));
         c->d_adj = c->d_hits;
     } else {
         if (c->d_adj != c->d_adj_own) return fail(c, DISCO_E_STATE, "neighbour rows: the adjacency is in neither of the buffers that can grow");
-        if (tight) CHK(move_to_larger(&c->d_adj_own, &c->adj_cap));
-        else if (used + need > c->adj_cap) CHK(ensure_cap_keep(c, &c->d_adj_own, &c->adj_cap, used + need, used));
+        if (tight) CHK(move_keep(c, c->d_adj_own, tight_cap, used));
+        else if (used + need > c->d_adj_own.cap) CHK(ensure_keep(c, c->d_adj_own, used + need, used));
         c->d_adj = c->d_adj_own;
     }
     *base = used;
@@ -4790,16 +4678,16 @@ static int dist_fetch_rows(disco_ctx *c, u64 n_flat)
     DISCO_TRACE("dist_fetch_rows");
     const u32 G = (u32)c->comm->world;
     std::vector<u64> scnt, rcnt;
-    CHK(ensure_cap(c, &c->d_req_s, &c->req_s_cap, std::max<u64>(n_flat, 1)));
+    CHK(ensure(c, c->d_req_s, std::max<u64>(n_flat, 1)));
     RouteByRowRequest f{c->per, c->loci ? c->d_otab : nullptr};
-    CHK(route_items(c, c->d_req_flat, n_flat, f, c->d_req_s, scnt));
+    CHK(route_items(c, c->d_req_flat.p, n_flat, f, c->d_req_s.p, scnt));
     CHK(exchange_counts(c, scnt, rcnt));
     const u64 nrq = vsum(rcnt);
-    CHK(ensure_cap(c, &c->d_req_r, &c->req_r_cap, std::max<u64>(nrq, 1)));
+    CHK(ensure(c, c->d_req_r, std::max<u64>(nrq, 1)));
     CHK(a2a_items(c, DISCO_X_ROW_REQUESTS, c->d_req_s, scnt, c->d_req_r, rcnt, sizeof(u32)));
     /* the owner's side: degree of every requested row, positions, entries */
-    CHK(ensure_cap(c, &c->d_rdeg_s, &c->rdeg_s_cap, std::max<u64>(nrq, 1)));
-    CHK(ensure_cap(c, &c->d_rpos, &c->rpos_cap, std::max<u64>(std::max(nrq, n_flat), 1) + 1));
+    CHK(ensure(c, c->d_rdeg_s, std::max<u64>(nrq, 1)));
+    CHK(ensure(c, c->d_rpos, std::max<u64>(std::max(nrq, n_flat), 1) + 1));
     const int rgrid = (int)std::max<u64>(std::min<u64>((nrq + 3) / 4, (u64)c->n_cu * 32), 1);
     if (nrq) hipLaunchKernelGGL(tr_respond_deg_kernel, dim3(flat_grid(c, nrq)), dim3(256), 0, c->stream, c->d_req_r, nrq, c->d_adj_ref, c->d_rdeg_s);
     HIPCHK(c, hipGetLastError());
@@ -4817,12 +4705,12 @@ static int dist_fetch_rows(disco_ctx *c, u64 n_flat)
         bpos[G] = total_s;
         for (u32 p = 0; p < G; p++) ecnt_s[p] = bpos[p + 1] - bpos[p];
     }
-    CHK(ensure_cap(c, &c->d_rdata_s, &c->rdata_s_cap, std::max<u64>(total_s, 1)));
+    CHK(ensure(c, c->d_rdata_s, std::max<u64>(total_s, 1)));
     if (nrq) hipLaunchKernelGGL(tr_respond_kernel, dim3(rgrid), dim3(64), 0, c->stream, c->d_req_r, nrq, c->d_adj_ref, c->d_adj, c->d_rpos, c->d_rdata_s);
     HIPCHK(c, hipGetLastError());
     /* degrees back (same segmentation as the requests, reversed), then the entries. How many entries every owner sends follows from
      * the degrees themselves: the requester sums them per segment (positions at the segment boundaries) — no exchange of counts */
-    CHK(ensure_cap(c, &c->d_rdeg_r, &c->rdeg_r_cap, std::max<u64>(n_flat, 1)));
+    CHK(ensure(c, c->d_rdeg_r, std::max<u64>(n_flat, 1)));
     CHK(a2a_items(c, DISCO_X_ROW_REQUESTS, c->d_rdeg_s, rcnt, c->d_rdeg_r, scnt, sizeof(u32)));
     u64 total_r = 0;
     CHK((scan_exclusive<u32, u64>(c, c->d_rdeg_r, n_flat, c->d_rpos, true, &total_r))); /* (d_rpos: the owner's positions were consumed by tr_respond_kernel above) */
@@ -4839,7 +4727,7 @@ static int dist_fetch_rows(disco_ctx *c, u64 n_flat)
         for (u32 p = 0; p < G; p++) ecnt_r[p] = bpos[p + 1] - bpos[p];
     }
     /* the rows that arrive (4-byte entries) ... */
-    CHK(ensure_cap(c, &c->d_nadj32_own, &c->nadj_cap, std::max<u64>(total_r, 1)));
+    CHK(ensure(c, c->d_nadj32_own, std::max<u64>(total_r, 1)));
     CHK(a2a_items(c, DISCO_X_ROW_DATA, c->d_rdata_s, ecnt_s, c->d_nadj32_own, ecnt_r, sizeof(u32)));
     /* ... go behind the own rows, as 8-byte entries under the nodes' reference words */
     u64 base = 0;
@@ -4858,16 +4746,16 @@ static int dist_transitive_mark(disco_ctx *c)
     const OwnSet own = own_set(c);
     /* the reference words of other ranks' nodes are 0 = "not fetched" (edge selection cleared the table and wrote the own nodes' words; a
      * merge rebuilt it from degrees: 0 for every node of another rank); one bit per node: somebody on this rank has asked for its row */
-    CHK(ensure_cap(c, &c->d_asked, &c->asked_cap, c->n / 32 + 2));
+    CHK(ensure(c, c->d_asked, c->n / 32 + 2));
     HIPCHK(c, hipMemsetAsync(c->d_asked, 0, (c->n / 32 + 2) * sizeof(u32), c->stream));
     c->nadj_used = 0; /* fetched rows: behind the own rows (adj_tail_reserve) */
     /* round 1: slot 0 and the first slot on the other side of every register-resident node */
-    if (!c->d_list_n) CHK(dev_alloc(c, &c->d_list_n, 1));
-    CHK(ensure_cap(c, &c->d_req_flat, &c->req_flat_cap, 2 * nloc + 64));
+    CHK(ensure(c, c->d_list_n, 1));
+    CHK(ensure(c, c->d_req_flat, 2 * nloc + 64));
     HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
     CHK(zero_counter(c, CTR_OVERFLOW));
     ph_begin(c, DISCO_PH_CSR);
-    if (nloc) hipLaunchKernelGGL(tr_request_first_kernel, dim3((int)std::max<u64>(std::min<u64>((nloc + 63) / 64, (u64)c->n_cu * 32), 1)), dim3(64), 0, c->stream, (const u64 *)c->d_adj, own, (const u64 *)c->d_adj_ref, c->d_asked, c->d_req_flat, c->d_list_n, c->req_flat_cap, c->d_ctr);
+    if (nloc) hipLaunchKernelGGL(tr_request_first_kernel, dim3((int)std::max<u64>(std::min<u64>((nloc + 63) / 64, (u64)c->n_cu * 32), 1)), dim3(64), 0, c->stream, (const u64 *)c->d_adj, own, (const u64 *)c->d_adj_ref, c->d_asked, c->d_req_flat, c->d_list_n, c->d_req_flat.cap, c->d_ctr);
     ph_end(c, DISCO_PH_CSR);
     HIPCHK(c, hipGetLastError());
     u64 n_flat = 0;
@@ -4879,14 +4767,7 @@ static int dist_transitive_mark(disco_ctx *c)
 
     /* marking of the own nodes; nodes beyond the register path or short of a row land in big_list */
     const u64 need_big = nloc + 1024;
-    if (need_big > c->big_cap) {
-        dev_free(c, &c->d_big_list, c->big_cap);
-        dev_free(c, &c->d_big_cnt, c->big_cap);
-        c->big_cap = 0;
-        CHK(dev_alloc(c, &c->d_big_list, need_big));
-        CHK(dev_alloc(c, &c->d_big_cnt, need_big));
-        c->big_cap = (u32)need_big;
-    }
+    CHK(grow_big_lists(c, need_big));
     HIPCHK(c, hipMemsetAsync(c->d_n_big, 0, sizeof(u32), c->stream));
     TrArgs a;
     a.v = view(c);
@@ -4895,24 +4776,21 @@ static int dist_transitive_mark(disco_ctx *c)
     a.adj = c->d_adj;
     a.big_list = c->d_big_list;
     a.n_big = c->d_n_big;
-    a.big_cap = c->big_cap;
+    a.big_cap = c->d_big_list.cap;
     a.scratch = nullptr;
     a.hcap = 0;
     c->use_half = true;
-    if (!c->d_half) CHK(dev_alloc(c, &c->d_half, c->n * HALF_CAP));
-    if (!c->d_hcnt) CHK(dev_alloc(c, &c->d_hcnt, c->n));
+    CHK(ensure(c, c->d_half, c->n * HALF_CAP));
+    CHK(ensure(c, c->d_hcnt, c->n));
     HIPCHK(c, hipMemsetAsync(c->d_hcnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
-    if (!c->d_wide) {
-        c->wide_cap = (u32)std::min<u64>(c->n, c->n / 32 + 4096);
-        CHK(dev_alloc(c, &c->d_wide, c->wide_cap));
-        CHK(dev_alloc(c, &c->d_n_wide, 1));
-    }
+    CHK(ensure(c, c->d_wide, std::min<u64>(c->n, c->n / 32 + 4096)));
+    CHK(ensure(c, c->d_n_wide, 1));
     HIPCHK(c, hipMemsetAsync(c->d_n_wide, 0, sizeof(u32), c->stream));
     a.half = c->d_half;
     a.hcnt = c->d_hcnt;
     a.wide_list = c->d_wide;
     a.n_wide = c->d_n_wide;
-    a.wide_cap = c->wide_cap;
+    a.wide_cap = c->d_wide.cap;
     /* the transitive flags go into the rows of nodes with more than HALF_CAP survivors only, as on one GPU: everybody who judges an edge
      * — the local emission, the survivor push and its receiver — reads a narrow node's survivor LIST and a wide node's row, never a narrow
      * node's row (rounds 1-4 wrote every flag here: a quarter of this kernel's memory requests, left over from the flag exchange the
@@ -4939,9 +4817,9 @@ static int dist_transitive_mark(disco_ctx *c)
         if (n_big) hipLaunchKernelGGL(list_degree_sum_kernel, dim3(flat_grid(c, n_big)), dim3(256), 0, c->stream, c->d_big_list, (u64)n_big, c->d_adj_ref, c->d_list_n);
         HIPCHK(c, hipMemcpyAsync(&bound, c->d_list_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        CHK(ensure_cap(c, &c->d_req_flat, &c->req_flat_cap, bound + 64));
+        CHK(ensure(c, c->d_req_flat, bound + 64));
         HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
-        if (n_big) hipLaunchKernelGGL(tr_request_all_kernel, dim3((int)std::min<u64>(n_big, (u64)c->n_cu * 32)), dim3(64), 0, c->stream, c->d_big_list, (u64)n_big, (const u64 *)c->d_adj, own, (const u64 *)c->d_adj_ref, c->d_asked, c->d_req_flat, c->d_list_n, c->req_flat_cap, c->d_ctr);
+        if (n_big) hipLaunchKernelGGL(tr_request_all_kernel, dim3((int)std::min<u64>(n_big, (u64)c->n_cu * 32)), dim3(64), 0, c->stream, c->d_big_list, (u64)n_big, (const u64 *)c->d_adj, own, (const u64 *)c->d_adj_ref, c->d_asked, c->d_req_flat, c->d_list_n, c->d_req_flat.cap, c->d_ctr);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(&n_flat, c->d_list_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         CHK(read_counters(c));
@@ -4956,16 +4834,16 @@ static int dist_transitive_mark(disco_ctx *c)
             while (hcap < 2 * maxd) hcap <<= 1;
             const int g2 = (int)std::min<u64>(n_big, (u64)c->n_cu * 8);
             const u64 perb = hcap * 8 + hcap * 4 + hcap;
-            u8 *scratch = nullptr;
-            CHK(dev_alloc(c, &scratch, (u64)g2 * perb));
-            a.scratch = (u64 *)scratch;
+            DevBuf<u8> scratch;
+            CHK(ensure(c, scratch, (u64)g2 * perb));
+            a.scratch = (u64 *)scratch.p;
             a.hcap = hcap;
             a.adj = c->d_adj; /* the array may have moved (adj_tail_reserve) */
             HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
             hipLaunchKernelGGL((transitive_mark_kernel<true, true>), dim3(g2), dim3(64), 0, c->stream, a);
             hipError_t e = hipGetLastError();
             int rc = read_counters(c);
-            dev_free(c, &scratch, (u64)g2 * perb);
+            release(c, scratch);
             if (e != hipSuccess) return fail(c, DISCO_E_HIP, "transitive_mark_kernel (second round): %s", hipGetErrorString(e));
             CHK(rc);
             if (c->h_ctr[CTR_OVERFLOW]) return fail(c, DISCO_E_STATE, "transitive marking: a row was still missing after the request-all round");
@@ -4989,9 +4867,9 @@ static int dist_push_survivors(disco_ctx *c)
      * the room the exchange buffer has anyway (the index records went through it: two per own read) — rounds 1-5 counted them first, a
      * second walk over every own node's survivors and a host round trip. A list that does not fit (the counter of lost items says so)
      * is counted and written again, as before */
-    CHK(ensure_cap(c, &c->d_x16b, &c->x16b_cap, std::max<u64>(nloc / 4, 1u << 16)));
+    CHK(ensure(c, c->d_x16b, std::max<u64>(nloc / 4, 1u << 16)));
     for (int attempt = 0; attempt < 2; attempt++) {
-        u64 cap = attempt ? n_items : c->x16b_cap;
+        u64 cap = attempt ? n_items : c->d_x16b.cap;
         if (!attempt && getenv("DISCO_TEST_TIGHT_PUSH")) cap = std::min<u64>(cap, 1); /* test hook: the first pass loses items, the second one runs */
         HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
         CHK(zero_counter(c, CTR_OVERFLOW));
@@ -5001,15 +4879,15 @@ static int dist_push_survivors(disco_ctx *c)
         CHK(read_counters(c)); /* (synchronises: n_items is there) */
         if (!c->h_ctr[CTR_OVERFLOW]) break;
         if (attempt) return fail(c, DISCO_E_STATE, "survivor push: the second pass produced more items than the first counted");
-        CHK(ensure_cap(c, &c->d_x16b, &c->x16b_cap, std::max<u64>(n_items, 1))); /* (the counter counted every item, lost or not) */
+        CHK(ensure(c, c->d_x16b, std::max<u64>(n_items, 1))); /* (the counter counted every item, lost or not) */
     }
-    CHK(ensure_cap(c, &c->d_x16a, &c->x16a_cap, std::max<u64>(n_items, 1)));
+    CHK(ensure(c, c->d_x16a, std::max<u64>(n_items, 1)));
     std::vector<u64> scnt, rcnt;
     RouteByNode f{c->per, c->loci ? c->d_otab : nullptr};
-    CHK(route_items(c, c->d_x16b, n_items, f, c->d_x16a, scnt));
+    CHK(route_items(c, c->d_x16b.p, n_items, f, c->d_x16a.p, scnt));
     CHK(exchange_counts(c, scnt, rcnt));
     const u64 nr = vsum(rcnt);
-    CHK(ensure_cap(c, &c->d_x16b, &c->x16b_cap, std::max<u64>(nr, 1)));
+    CHK(ensure(c, c->d_x16b, std::max<u64>(nr, 1)));
     CHK(a2a_items(c, DISCO_X_PUSH, c->d_x16a, scnt, c->d_x16b, rcnt, sizeof(ulonglong2)));
     c->d_push_r = c->d_x16b;
     c->n_push_r = nr;
@@ -5044,7 +4922,7 @@ static int dist_complete_twins(disco_ctx *c, bool *done, u64 *asym_total)
             cnt[p2] = (size_t)cnts[p2] * sizeof(u32);
             tot += (size_t)cnts[p2];
         }
-        CHK(ensure_cap(c, &c->d_req_flat, &c->req_flat_cap, std::max<u64>(tot, 1) + 64));
+        CHK(ensure(c, c->d_req_flat, std::max<u64>(tot, 1) + 64));
         u32 *my_list = c->d_req_flat + off[r] / sizeof(u32);
         HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
         CHK(zero_counter(c, CTR_OVERFLOW));
@@ -5071,8 +4949,8 @@ static int dist_complete_twins(disco_ctx *c, bool *done, u64 *asym_total)
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(&n_items, c->d_list_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    CHK(ensure_cap(c, &c->d_x16b, &c->x16b_cap, std::max<u64>(n_items, 1)));
-    CHK(ensure_cap(c, &c->d_x16a, &c->x16a_cap, std::max<u64>(n_items, 1)));
+    CHK(ensure(c, c->d_x16b, std::max<u64>(n_items, 1)));
+    CHK(ensure(c, c->d_x16a, std::max<u64>(n_items, 1)));
     HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
     CHK(zero_counter(c, CTR_OVERFLOW));
     if (nloc) hipLaunchKernelGGL(twin_push_kernel<true>, dim3(flat_grid(c, nloc * 64)), dim3(256), 0, c->stream, c->d_adj_ref, c->d_adj, c->d_len, own, c->d_dropbits,
@@ -5082,25 +4960,22 @@ static int dist_complete_twins(disco_ctx *c, bool *done, u64 *asym_total)
     if (c->h_ctr[CTR_OVERFLOW]) return fail(c, DISCO_E_STATE, "twin push: the fill pass produced more items than the count pass");
     std::vector<u64> scnt, rcnt;
     RouteByNode f{per, c->loci ? c->d_otab : nullptr};
-    CHK(route_items(c, c->d_x16b, n_items, f, c->d_x16a, scnt));
+    CHK(route_items(c, c->d_x16b.p, n_items, f, c->d_x16a.p, scnt));
     CHK(exchange_counts(c, scnt, rcnt));
     const u64 nr = vsum(rcnt);
-    CHK(ensure_cap(c, &c->d_x16b, &c->x16b_cap, std::max<u64>(nr, 1)));
+    CHK(ensure(c, c->d_x16b, std::max<u64>(nr, 1)));
     CHK(a2a_items(c, DISCO_X_TWINS, c->d_x16a, scnt, c->d_x16b, rcnt, sizeof(ulonglong2)));
     /* room for every received item to turn out missing, behind the extras of the local check */
     const u64 want = (u64)c->n_extra + nr + 1;
     if (want > 0xFFFFFFFFull) return fail(c, DISCO_E_CAPACITY, "twin completion: more than 2^32 extras on one rank");
-    if (want > c->extra_cap) {
-        u64 cap_n = c->extra_cap, cap_k = c->extra_cap;
-        CHK(ensure_cap_keep(c, &c->d_extra_node, &cap_n, want, c->n_extra));
-        CHK(ensure_cap_keep(c, &c->d_extra_key, &cap_k, want, c->n_extra));
-        if (cap_n != cap_k) return fail(c, DISCO_E_STATE, "twin completion: extras arrays out of step");
-        c->extra_cap = (u32)std::min<u64>(cap_n, 0xFFFFFFFFull);
+    if (want > extra_cap(c)) { /* (each keeps its items; a retry after a failure grows the one that is still short) */
+        CHK(ensure_keep(c, c->d_extra_node, want, c->n_extra));
+        CHK(ensure_keep(c, c->d_extra_key, want, c->n_extra));
     }
     CHK(zero_counter(c, CTR_ASYM));
     CHK(zero_counter(c, CTR_OVERFLOW));
     if (nr) hipLaunchKernelGGL(twin_recv_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const ulonglong2 *)c->d_x16b, nr, c->d_adj_ref, c->d_adj, c->d_extra_node,
-                               c->d_extra_key, c->d_extra_cnt, c->d_n_extra, c->extra_cap, c->d_ctr);
+                               c->d_extra_key, c->d_extra_cnt, c->d_n_extra, extra_cap(c), c->d_ctr);
     HIPCHK(c, hipGetLastError());
     u32 ne = 0;
     HIPCHK(c, hipMemcpyAsync(&ne, c->d_n_extra, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
@@ -5116,7 +4991,7 @@ static int dist_complete_twins(disco_ctx *c, bool *done, u64 *asym_total)
         HIPCHK(c, hipMemcpyAsync(&need, c->d_bump, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    const bool fits = c->d_adj == c->d_hits && ne <= 16384 && c->hits_used + need <= c->hits_cap && !getenv("DISCO_MERGE_REBUILD");
+    const bool fits = c->d_adj == c->d_hits && ne <= 16384 && c->hits_used + need <= c->d_hits.cap && !getenv("DISCO_MERGE_REBUILD");
     u64 v[2] = {fits ? 0ull : 1ull, asym};
     CHK(host_reduce(c, v, 2));
     c->dinfo.ms[DISCO_X_TWINS] += ms_since(t0);
@@ -5136,11 +5011,11 @@ static int dist_irregular(disco_ctx *c, const std::vector<u64> &adj_totals)
     DISCO_TRACE("dist_irregular");
     const u32 G = (u32)c->comm->world, r = (u32)c->comm->rank;
     const u64 lo = c->q_lo, hi = c->q_hi, nloc = hi - lo, per = c->per;
-    u32 *deg_all = nullptr;
-    u64 *rows_all = nullptr;
+    DevBuf<u32> deg_all;
+    DevBuf<u64> rows_all;
     const u64 total = vsum(adj_totals);
-    CHK(dev_alloc(c, &deg_all, (u64)G * per));
-    CHK(dev_alloc(c, &rows_all, std::max<u64>(total, 1)));
+    CHK(ensure(c, deg_all, (u64)G * per));
+    CHK(ensure(c, rows_all, std::max<u64>(total, 1)));
     u64 base = 0;
     for (u32 p = 0; p < r; p++) base += adj_totals[p];
     int rc = DISCO_OK;
@@ -5171,8 +5046,8 @@ static int dist_irregular(disco_ctx *c, const std::vector<u64> &adj_totals)
         c->drop_lo = 0;
         c->drop_hi = c->n;
     } while (0);
-    dev_free(c, &deg_all, (u64)G * per);
-    dev_free(c, &rows_all, std::max<u64>(total, 1));
+    release(c, deg_all);
+    release(c, rows_all);
     if (rc != DISCO_OK) return c->err.empty() ? fail(c, rc, "adjacency exchange: %s", c->comm->err.c_str()) : rc;
     CHK(disco_symmetrize(c, 1, nullptr));
     CHK(merge_extras(c));
@@ -5322,8 +5197,7 @@ static int dist_set_reads(disco_ctx *c, u64 n_total, uint32_t dstride)
     c->n_alloc = per * (u64)c->comm->world;
     c->q_lo = c->home_lo = lo;
     c->q_hi = c->home_hi = hi;
-    CHK(dev_alloc(c, &c->d_reads, c->n_alloc * (u64)dstride));
-    CHK(dev_alloc(c, &c->d_len, c->n_alloc));
+    CHK(alloc_reads(c, c->n_alloc * (u64)dstride, c->n_alloc));
     /* unused words of a row are zero (disco_device.h): the other ranks' rows arrive at their used words only */
     HIPCHK(c, hipMemsetAsync(c->d_reads, 0, c->n_alloc * (u64)dstride * 8, c->stream));
     c->reads_owned = true;
@@ -5348,7 +5222,7 @@ static int dist_validate(disco_ctx *c)
     c->max_len = (u32)ext[0];
     c->min_len = 0xFFFFu - (u32)ext[1];
     /* the k-mer probes of the home range (disco_dist_info.probes): a property of the reads, summed once here instead of in every pass */
-    if (!c->d_list_n) CHK(dev_alloc(c, &c->d_list_n, 1));
+    CHK(ensure(c, c->d_list_n, 1));
     HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
     if (nloc) hipLaunchKernelGGL(probes_sum_kernel, dim3(flat_grid(c, nloc)), dim3(256), 0, c->stream, c->d_len, c->q_lo, c->q_hi, (u32)c->k, c->d_list_n);
     HIPCHK(c, hipMemcpyAsync(&c->home_probes, c->d_list_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
@@ -5357,13 +5231,14 @@ static int dist_validate(disco_ctx *c)
     c->job_n_long = 0;
     c->job_short_max = c->max_len;
     if (c->max_len > (u32)DISCO_SHORT_MAX) {
-        u64 *d_ls = nullptr, hls[2] = {0, 0};
-        CHK(dev_alloc(c, &d_ls, 2));
+        DevBuf<u64> d_ls;
+        u64 hls[2] = {0, 0};
+        CHK(ensure(c, d_ls, 2));
         HIPCHK(c, hipMemsetAsync(d_ls, 0, 2 * sizeof(u64), c->stream));
         if (nloc) hipLaunchKernelGGL(long_stats_kernel, dim3(flat_grid(c, nloc)), dim3(256), 0, c->stream, (const u16 *)c->d_len, c->q_lo, c->q_hi, d_ls);
         HIPCHK(c, hipMemcpyAsync(hls, d_ls, sizeof hls, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        dev_free(c, &d_ls, 2);
+        release(c, d_ls);
         CHK(host_reduce(c, &hls[0], 1));
         CHK(host_reduce(c, &hls[1], 1, true));
         c->job_n_long = hls[0];
@@ -5555,7 +5430,7 @@ static int dist_run_graph_pass(disco_ctx *c, uint32_t flags, bool allow_loci, bo
             /* a rank's block = its rows and, behind them, its lengths (per is a multiple of 64: 2 per bytes are whole words): ONE operation */
             const u64 total_rows = c->per * (u64)G;
             const u64 rows_words = c->per * (u64)W, block_words = rows_words + c->per / 4;
-            CHK(ensure_cap(c, &c->d_dense, &c->dense_cap, block_words * (u64)G));
+            CHK(ensure(c, c->d_dense, block_words * (u64)G));
             u64 *mine = c->d_dense + (u64)r * block_words;
             hipLaunchKernelGGL(pack_rows_kernel, dim3(flat_grid(c, c->per * W)), dim3(256), 0, bstream, c->d_reads, c->S, W, (u64)r * c->per, c->per, mine);
             HIPCHK(c, hipMemcpyAsync(mine + rows_words, c->d_len + (u64)r * c->per, c->per * 2, hipMemcpyDeviceToDevice, bstream));
@@ -5591,7 +5466,7 @@ static int dist_run_graph_pass(disco_ctx *c, uint32_t flags, bool allow_loci, bo
     CHK(select_edges(c));
     /* whole-job figures and the regime decision */
     const u64 probes = c->home_probes; /* (dist_validate) */
-    if (!c->d_list_n) CHK(dev_alloc(c, &c->d_list_n, 1));
+    CHK(ensure(c, c->d_list_n, 1));
     u64 g[8] = {c->adj_total, c->dropped_local, c->n_contained, c->h_ctr[CTR_CAP_SITES], c->h_ctr[CTR_KMER_HITS], probes, 0, 0};
     {
         constexpr int NV = 6;

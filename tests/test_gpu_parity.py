@@ -356,6 +356,28 @@ def test_read_sets_of_the_same_shape_reuse_the_buffers():
                 assert cnt[k] == wcnt[k], (i, k)
 
 
+def test_hbm_bytes_do_not_drift_across_read_sets():
+    """every device buffer is given back with the size it was allocated with: a context that ran A, B, A ends where one that ran B, A
+    ends — the same edges and contained rows, and the same hbm_bytes (the buffers kept across read sets have seen the same sizes in both,
+    so a free that accounts other bytes than its allocation shows as the difference of one extra cycle)"""
+    a = readgen.GenSpec.coverage(71, 6000, 150, 30.0)
+    b = readgen.GenSpec.coverage(72, 9000, 150, 30.0, long_len=600, long_share=1300)  # a tail of long reads: two classes of rows
+
+    def run(specs):
+        with buildgraph.BuildGraph(min_overlap=40) as g:
+            for spec in specs:
+                g.upload_ascii(readgen.generate_reads(spec))
+                assert (g.long_rows > 0) == (spec is b), "B must take the two-class path (its long class is accounted too), A one stride"
+                g.run_graph()
+                res = canon_hip(g.fetch_edges(), g.fetch_contained())
+            return res, g.counters()["hbm_bytes"]
+
+    (e1, c1), hbm1 = run([a, b, a])
+    (e2, c2), hbm2 = run([b, a])
+    assert np.array_equal(e1, e2) and np.array_equal(c1, c2)
+    assert hbm1 == hbm2 > 0, (hbm1, hbm2)
+
+
 def test_cap_binds_in_short_rows():
     """rows of a handful of hits in which ONE window collects eight acceptable hits: read A ends 42 bases into a 45-base unit U,
     eight reads B_i start with U and continue into flanks of their own — A's suffix overlaps every B_i's prefix at the same window, the

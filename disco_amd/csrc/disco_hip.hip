@@ -211,6 +211,11 @@ struct disco_ctx {
     DevBuf<u32> d_bkt;
     DevBuf<u64> d_ent;
     DevBuf<ulonglong2> d_rec; /* {key, record}[2n] scratch of the index build */
+    /* binned build (binned_build_index): decided once per index by index_begin — the count pass then leaves out its bucket atomics, and
+     * the bucket table is neither cleared nor scanned */
+    bool binned_index = false;
+    DevBuf<ulonglong2> d_rec2; /* the other side of the partition levels' ping-pong */
+    DevBuf<u32> d_binx;        /* segment starts and tile bases of two levels, the tile x bin counts of one */
 
     /* scan temporaries */
     DevBuf<u64> d_tile;
@@ -697,6 +702,8 @@ static void free_graph_state(disco_ctx *c)
     release(c, c->d_bkt);
     release(c, c->d_ent);
     release(c, c->d_rec);
+    release(c, c->d_rec2);
+    release(c, c->d_binx);
     release(c, c->d_best);
     release(c, c->d_hits);
     release(c, c->d_row_start);
@@ -972,6 +979,22 @@ static int launch_index_count(disco_ctx *c, const DiscoView &v, ulonglong2 *rec,
     return index_count_chunk<COUNT>(c, v, pl, rec, lo, hi);
 }
 
+/* does the binned build make this index (single GPU: the only callers of index_begin)? DISCO_NO_BINNED_INDEX=1: the counting atomics,
+ * the scan of the bucket table and the ordered fill, as before. The scratch side of the ping-pong is allocated here, so that a table
+ * it does not fit next to takes the old path. No size policy: the index phase with the builder against the old path, same box, ms at
+ * 1 / 3 / 10 / 20 / 50 M reads: 0.26 / 0.70 / 2.17 / 4.34 / 11.09 against 0.26 / 0.70 / 2.40 / 5.20 / 14.24 — no crossover, level at
+ * the small sizes (profiles/binned_index_ab.txt) */
+static bool binned_index_wanted(disco_ctx *c, int logT)
+{
+    if (getenv("DISCO_NO_BINNED_INDEX") || 2 * c->n >= 0xFFFF0000ull) return false;
+    if (logT > BINX_SPAN_BITS && ensure(c, c->d_rec2, 2 * c->n) != DISCO_OK) {
+        (void)hipGetLastError();
+        c->err.clear();
+        return false;
+    }
+    return true;
+}
+
 /* sizes of the index for the context's reads and the cleared bucket table (the start of disco_build_index, or of an upload that
  * counts while it copies) */
 static int index_begin(disco_ctx *c)
@@ -994,7 +1017,69 @@ static int index_begin(disco_ctx *c)
     CHK(ensure(c, c->d_rec, 2 * c->n));
     CHK(ensure(c, c->d_okey, c->n)); /* grouping keys of all reads (disco_probe orders its query range by them) */
     c->adj_imported = false;
-    HIPCHK(c, hipMemsetAsync(c->d_bkt, 0, (T + 1) * sizeof(u32), c->stream));
+    c->binned_index = binned_index_wanted(c, logT);
+    if (!c->binned_index) HIPCHK(c, hipMemsetAsync(c->d_bkt, 0, (T + 1) * sizeof(u32), c->stream));
+    return DISCO_OK;
+}
+
+/* the levels of the binned build for a table of 2^logT buckets: partitions of 2^span buckets, their prefix of logT - span bits cut into
+ * `levels` digits of at most BINX_MAX_BITS bits, the first ones a bit wider where it does not divide (27: 7 + 6 over 14; 29: 8 + 7;
+ * 32: 6 + 6 + 6; up to 14: no level, one partition) */
+struct BinxPlan {
+    int span = 0, levels = 0, bits[3] = {0, 0, 0};
+};
+static BinxPlan binx_plan(int logT)
+{
+    BinxPlan b;
+    b.span = std::min(logT, BINX_SPAN_BITS);
+    const int prefix = logT - b.span;
+    b.levels = (prefix + BINX_MAX_BITS - 1) / BINX_MAX_BITS;
+    for (int l = 0; l < b.levels; l++) b.bits[l] = prefix / b.levels + (l < prefix % b.levels ? 1 : 0);
+    return b;
+}
+
+/* records rec[0 .. 2n) = {bucket << 32, payload} of the count pass (COUNT = false) -> bkt[0 .. T], ent[0 .. 2n): see "binned index build"
+ * in disco_kernels.h */
+static int binned_build_index(disco_ctx *c)
+{
+    const int logT = 64 - c->bshift;
+    const BinxPlan bp = binx_plan(logT);
+    const u32 total = (u32)(2 * c->n);
+    const u32 n_part = 1u << (logT - bp.span);
+    const u32 tiles = (total + BINX_TILE - 1u) / BINX_TILE;
+    /* d_binx: seg / tb of the level at work and of the one before (n_part + 1 words each at the most), then the counts */
+    u64 hist_len = 1;
+    for (int l = 0, done = 0; l < bp.levels; done += bp.bits[l], l++) hist_len = std::max<u64>(hist_len, ((u64)tiles + (1ull << done)) * (1ull << bp.bits[l]) + 1);
+    const u64 tab = ((u64)n_part + 1 + 63) & ~63ull;
+    CHK(ensure(c, c->d_binx, 4 * tab + hist_len));
+    u32 *seg[2] = {c->d_binx.p, c->d_binx.p + tab}, *tb[2] = {c->d_binx.p + 2 * tab, c->d_binx.p + 3 * tab}, *hist = c->d_binx.p + 4 * tab;
+    if (getenv("DISCO_VERBOSE"))
+        fprintf(stderr, "[disco] binned index build: 2^%d buckets, %u partitions of 2^%d, %d level(s) of %d / %d / %d bits\n", logT, n_part, bp.span, bp.levels, bp.bits[0], bp.bits[1], bp.bits[2]);
+    ulonglong2 *src = c->d_rec, *dst = c->d_rec2;
+    u32 pseg = 1, pnb = 1;
+    int cur = 0, done = 0;
+    for (int l = 0; l < bp.levels; l++) {
+        const u32 nseg = 1u << done, nb = 1u << bp.bits[l], shift = (u32)(logT - done - bp.bits[l]);
+        const u32 grid = tiles + nseg;
+        const u64 hlen = (u64)grid * nb + 1;
+        hipLaunchKernelGGL(binx_segs_kernel, dim3(1), dim3(1024), 0, c->stream, l ? (const u32 *)hist : (const u32 *)nullptr, (const u32 *)tb[cur ^ 1], pseg, pnb, total, seg[cur], tb[cur]);
+        HIPCHK(c, hipMemsetAsync(hist, 0, hlen * sizeof(u32), c->stream));
+        hipLaunchKernelGGL(binx_hist_kernel, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const ulonglong2 *)src, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb, hist);
+        CHK((scan_exclusive<u32, u32>(c, hist, hlen, hist, false, nullptr)));
+        hipLaunchKernelGGL(binx_scatter_kernel, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const ulonglong2 *)src, dst, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb,
+                           (const u32 *)hist);
+        HIPCHK(c, hipGetLastError());
+        std::swap(src, dst);
+        pseg = nseg;
+        pnb = nb;
+        done += bp.bits[l];
+        cur ^= 1;
+    }
+    /* the partitions' starts: the segments the last level made (no level: the one partition) */
+    hipLaunchKernelGGL(binx_segs_kernel, dim3(1), dim3(1024), 0, c->stream, bp.levels ? (const u32 *)hist : (const u32 *)nullptr, (const u32 *)tb[cur ^ 1], pseg, pnb, total, seg[cur],
+                       (u32 *)nullptr);
+    hipLaunchKernelGGL(binx_build_kernel, dim3(n_part), dim3(BINX_BUILD_BLOCK), 0, c->stream, (const ulonglong2 *)src, (const u32 *)seg[cur], (u32)bp.span, total, c->T, c->d_bkt.p, c->d_ent.p);
+    HIPCHK(c, hipGetLastError());
     return DISCO_OK;
 }
 
@@ -1500,7 +1585,7 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
                 HIPCHK(c, hipEventRecord(c->ev_copied[b], c->copy_stream));
                 HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied[b], 0));
             }
-            if (eager) CHK((index_count_chunk<true>(c, v, pl, c->d_rec, lo, hi)));
+            if (eager) CHK(c->binned_index ? (index_count_chunk<false>(c, v, pl, c->d_rec, lo, hi)) : (index_count_chunk<true>(c, v, pl, c->d_rec, lo, hi)));
         }
         HIPCHK(c, hipGetLastError());
         t_issued = lapms();
@@ -2221,15 +2306,24 @@ int disco_build_index(disco_ctx *c)
         const DiscoView v = view(c);
         IndexCountPlan pl;
         CHK(index_count_plan(c, v, 0, c->n, &pl));
-        CHK(index_count_chunk<true>(c, v, pl, c->d_rec, 0, c->n));
+        CHK(c->binned_index ? index_count_chunk<false>(c, v, pl, c->d_rec, 0, c->n) : index_count_chunk<true>(c, v, pl, c->d_rec, 0, c->n));
         if (c->two_class) { /* the long reads' records, keys and slots, from their full rows */
             const dim3 g((unsigned)((c->n_long + 255) / 256));
-            if (c->k > 64) hipLaunchKernelGGL((index_count_kernel<true, true, true>), g, dim3(256), 0, c->stream, v, c->d_bkt, c->d_rec, c->d_okey, (u64)0, c->n_long, pl.ocnt, pl.oslot, pl.oshift);
-            else hipLaunchKernelGGL((index_count_kernel<true, false, true>), g, dim3(256), 0, c->stream, v, c->d_bkt, c->d_rec, c->d_okey, (u64)0, c->n_long, pl.ocnt, pl.oslot, pl.oshift);
+#define DISCO_LONG_LAUNCH(COUNT_, LONGK_) \
+    hipLaunchKernelGGL((index_count_kernel<COUNT_, LONGK_, true>), g, dim3(256), 0, c->stream, v, c->d_bkt, c->d_rec, c->d_okey, (u64)0, c->n_long, pl.ocnt, pl.oslot, pl.oshift)
+            if (c->binned_index) {
+                if (c->k > 64) DISCO_LONG_LAUNCH(false, true);
+                else DISCO_LONG_LAUNCH(false, false);
+            } else {
+                if (c->k > 64) DISCO_LONG_LAUNCH(true, true);
+                else DISCO_LONG_LAUNCH(true, false);
+            }
+#undef DISCO_LONG_LAUNCH
             HIPCHK(c, hipGetLastError());
         }
     }
-    CHK((scan_exclusive<u32, u32>(c, c->d_bkt, c->T + 1, c->d_bkt, false, nullptr)));
+    const bool binned = c->binned_index; /* (index_begin's decision, whoever counted) */
+    if (!binned) CHK((scan_exclusive<u32, u32>(c, c->d_bkt, c->T + 1, c->d_bkt, false, nullptr)));
     /* the grouping of the reads (the processing order of probe / verify / selection / marking) was counted inside the index pass: it is
      * finished here, so that the fill can walk it (index_fill_ordered_kernel); disco_probe finds it ready */
     c->order_ready = false;
@@ -2242,14 +2336,16 @@ int disco_build_index(disco_ctx *c)
         hipLaunchKernelGGL(order_scatter_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_okey, c->d_oslot, c->d_ocnt, 32u - (u32)c->order_counted_bits, (u64)0, c->n, c->d_len, c->d_order_own);
         ph_end(c, DISCO_PH_ORDER);
         ph_begin(c, DISCO_PH_INDEX2);
-        hipLaunchKernelGGL(index_fill_ordered_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->n, (const u64 *)c->d_order_own, (const ulonglong2 *)c->d_rec, (const u32 *)c->d_bkt, c->d_ent);
+        if (binned) CHK(binned_build_index(c)); /* (streams the records: no use for the order) */
+        else hipLaunchKernelGGL(index_fill_ordered_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->n, (const u64 *)c->d_order_own, (const ulonglong2 *)c->d_rec, (const u32 *)c->d_bkt, c->d_ent);
         ph_end(c, DISCO_PH_INDEX2);
         HIPCHK(c, hipGetLastError());
         c->order_ready = true;
         c->phase = 2;
         return DISCO_OK;
     }
-    if (c->n) hipLaunchKernelGGL(index_fill_kernel, dim3(flat_grid(c, 2 * c->n)), dim3(256), 0, c->stream, 2 * c->n, c->d_rec, c->d_bkt, c->d_ent);
+    if (binned) CHK(binned_build_index(c));
+    else if (c->n) hipLaunchKernelGGL(index_fill_kernel, dim3(flat_grid(c, 2 * c->n)), dim3(256), 0, c->stream, 2 * c->n, c->d_rec, c->d_bkt, c->d_ent);
     HIPCHK(c, hipGetLastError());
     ph_end(c, DISCO_PH_INDEX);
     c->phase = 2;

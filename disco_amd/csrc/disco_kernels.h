@@ -577,9 +577,7 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
             }
         }
         if (okey) okey[i] = best;
-#if !defined(INDEX_EXP_NOATOMIC)
         if (ocnt) oslot[i - lo] = atomicAdd(&ocnt[ORDER_BUCKET(best, oshift)], 1u); /* the grouping's counting pass (order_count_kernel), fused */
-#endif
         if ((tie & ~1u) != 0 || cnt > (u32)CAP) my[0] = 0xFFFEu; /* (bit 0 of m1 ^ m2: the two strands of a tie may differ) */
         /* the two end k-mers' records: window_minimizer's rule on the minima of windows 0 and npos */
         auto resolve = [&](u32 k1, u32 k2, int wbase, int j0, u32 &t, u32 &rev) {
@@ -598,12 +596,8 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
         const u64 kp = resolve(P1, P2, 0, 0, tp, rp);
         const u64 ks = resolve(sx[0], sx[256], (int)sx[512], npos, ts, rs);
         const u64 bp = kp >> v.bshift, bs = ks >> v.bshift;
-#if defined(INDEX_EXP_NOATOMIC) /* timing experiment (results are wrong): the pass without its three counting atomics */
-        const u32 sp = 0u, ss = 0u;
-#else
         const u32 sp = COUNT ? atomicAdd(&bkt[bp], 1u) : 0u;
         const u32 ss = COUNT ? atomicAdd(&bkt[bs], 1u) : 0u;
-#endif
         rec[2 * (i - lo)] = make_ulonglong2((bp << 32) | sp, PAY_MAKE(kp, rid, tp, rp, 0, L));
         rec[2 * (i - lo) + 1] = make_ulonglong2((bs << 32) | ss, PAY_MAKE(ks, rid, ts, rs, 1, L));
     }
@@ -641,6 +635,203 @@ __global__ void index_fill_ordered_kernel(u64 nq, const u64 *__restrict__ order,
         const ulonglong2 r0 = rec[2 * id], r1 = rec[2 * id + 1];
         ent[(u64)bkt[r0.x >> 32] + (u32)r0.x] = r0.y;
         ent[(u64)bkt[r1.x >> 32] + (u32)r1.x] = r1.y;
+    }
+}
+
+/* ================================================================================================================
+ * binned index build (single GPU) — the index as what it is: a counting sort of the 2n records {bucket << 32, payload} by bucket.
+ * The count pass runs without its two bucket atomics per read (COUNT = false) and everything behind it streams: the records are
+ * partitioned by the HIGH bits of the bucket, most significant digit first, in levels of at most BINX_MAX_BITS bits (per level:
+ * histogram per tile in LDS -> exclusive scan of the tile x bin counts -> scatter with the tile staged in LDS, so that a bin leaves as
+ * one contiguous run), down to partitions of at most 2^BINX_SPAN_BITS buckets; then one workgroup per partition counts its buckets in
+ * LDS, scans them and places the payloads (binx_build_kernel). No global atomics, no memset or scan of the bucket table, no random
+ * access outside a partition's window of ent[]. Kernel boundaries are the only global synchronisation.
+ *
+ * A level works on SEGMENTS (the bins of the levels before; one segment, the whole array, at the first level): segment s is
+ * [seg[s], seg[s + 1]) and is cut into tiles of BINX_TILE records that start at the segment's start, tiles [tb[s], tb[s + 1]) of the
+ * level. Tile t of segment s counts into hist[nb tb[s] + d nt(s) + (t - tb[s])] for digit d — segment-major, then digit, then tile —
+ * so ONE exclusive scan of hist gives every (segment, digit, tile) its place in the output, and hist[nb tb[s] + d nt(s)] is where
+ * segment s nb + d of the next level starts. The grid is the host's bound on the tiles, ceil(2n / BINX_TILE) + segments; what lies
+ * behind the last tile does nothing (hist is cleared up to that bound).
+ * ============================================================================================================== */
+#define BINX_SPAN_BITS 14 /* buckets per partition of the build kernel: 2^14 32-bit counters = 64 KB of LDS, two workgroups per CU */
+#define BINX_MAX_BITS 8   /* bits per partition level */
+#define BINX_TILE 2048u   /* records per tile of a partition level: 32 KB staged; 128 bins leave in runs of 16 records = 256 bytes on average */
+#define BINX_BLOCK 256u
+#define BINX_BUILD_BLOCK 1024u /* the build kernel's tile: records per step of its two sweeps */
+
+/* exclusive scan over the 1024 threads of a block (s_w: 16 words), returns the exclusive value; *total = the block's sum */
+__device__ __forceinline__ u32 binx_block_scan1024(u32 x, u32 *s_w, u32 *total)
+{
+    u32 incl = x;
+    for (int o = 1; o < 64; o <<= 1) {
+        const u32 y = __shfl_up(incl, o);
+        if ((int)(threadIdx.x & 63) >= o) incl += y;
+    }
+    __syncthreads(); /* (s_w of the call before has been read) */
+    if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    u32 off = 0, sum = 0;
+    for (u32 w = 0; w < 16u; w++) {
+        const u32 t = s_w[w];
+        off += w < (threadIdx.x >> 6) ? t : 0u;
+        sum += t;
+    }
+    *total = sum;
+    return off + incl - x;
+}
+
+/* single block: the segments of a level and their tiles. prev_scan == nullptr: one segment [0, total). Otherwise the nseg = pseg x pnb
+ * segments the level before made: segment s pnb + d starts at prev_scan[pnb ptb[s] + d nt(s)]. tb == nullptr (behind the last level:
+ * the partitions of the build kernel): starts only. */
+__global__ void __launch_bounds__(1024) binx_segs_kernel(const u32 *__restrict__ prev_scan, const u32 *__restrict__ ptb, u32 pseg, u32 pnb, u32 total, u32 *__restrict__ seg,
+                                                         u32 *__restrict__ tb)
+{
+    __shared__ u32 s_w[16];
+    const u32 nseg = prev_scan ? pseg * pnb : 1u;
+    for (u32 x = threadIdx.x; x < nseg; x += 1024u) {
+        u32 st = 0;
+        if (prev_scan) {
+            const u32 s = x / pnb, d = x % pnb;
+            const u32 t0 = ptb[s], nt = ptb[s + 1] - t0;
+            st = prev_scan[(u64)pnb * t0 + (u64)d * nt];
+        }
+        seg[x] = st;
+    }
+    if (threadIdx.x == 0) seg[nseg] = total;
+    if (!tb) return;
+    __syncthreads();
+    u32 carry = 0;
+    for (u32 base = 0; base < nseg; base += 1024u) {
+        const u32 x = base + threadIdx.x;
+        const u32 nt = x < nseg ? (seg[x + 1] - seg[x] + BINX_TILE - 1u) / BINX_TILE : 0u;
+        u32 sum;
+        const u32 ex = binx_block_scan1024(nt, s_w, &sum);
+        if (x < nseg) tb[x] = carry + ex;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) tb[nseg] = carry;
+}
+
+/* the tile of this workgroup: its segment (the last s with tb[s] <= t: segments without tiles are stepped over), its place among the
+ * segment's tiles and its records [lo, hi); false: behind the last tile */
+__device__ __forceinline__ bool binx_tile(const u32 *__restrict__ seg, const u32 *__restrict__ tb, u32 nseg, u32 &t0, u32 &nt, u32 &ti, u32 &lo, u32 &hi)
+{
+    const u32 t = blockIdx.x;
+    if (t >= tb[nseg]) return false;
+    u32 a = 0, b = nseg; /* tb[a] <= t < tb[b] */
+    while (b - a > 1u) {
+        const u32 mid = (a + b) >> 1;
+        if (tb[mid] <= t) a = mid;
+        else b = mid;
+    }
+    t0 = tb[a];
+    nt = tb[a + 1] - t0;
+    ti = t - t0;
+    const u32 end = seg[a + 1];
+    lo = seg[a] + ti * BINX_TILE;
+    hi = end - lo > BINX_TILE ? lo + BINX_TILE : end;
+    return true;
+}
+
+/* the digit of a level: bits [shift, shift + log2 nb) of the bucket */
+#define BINX_DIGIT(recx, shift, nb) ((u32)((recx) >> (32u + (shift))) & ((nb)-1u))
+
+__global__ void __launch_bounds__(BINX_BLOCK) binx_hist_kernel(const ulonglong2 *__restrict__ rec, const u32 *__restrict__ seg, const u32 *__restrict__ tb, u32 nseg, u32 shift, u32 nb,
+                                                               u32 *__restrict__ hist)
+{
+    __shared__ u32 s_h[1u << BINX_MAX_BITS];
+    u32 t0, nt, ti, lo, hi;
+    if (!binx_tile(seg, tb, nseg, t0, nt, ti, lo, hi)) return;
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    for (u32 i = lo + threadIdx.x; i < hi; i += BINX_BLOCK) atomicAdd(&s_h[BINX_DIGIT(rec[i].x, shift, nb)], 1u);
+    __syncthreads();
+    if (threadIdx.x < nb) hist[(u64)nb * t0 + (u64)threadIdx.x * nt + ti] = s_h[threadIdx.x];
+}
+
+/* a tile's records to their bins' places in dst: staged in LDS in bin order, written out as one run per bin */
+__global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const ulonglong2 *__restrict__ src, ulonglong2 *__restrict__ dst, const u32 *__restrict__ seg, const u32 *__restrict__ tb,
+                                                                  u32 nseg, u32 shift, u32 nb, const u32 *__restrict__ scan)
+{
+    static_assert(BINX_BLOCK == (1u << BINX_MAX_BITS) && BINX_TILE % BINX_BLOCK == 0, "a thread per bin; whole rounds per tile");
+    constexpr u32 PER = BINX_TILE / BINX_BLOCK;
+    __shared__ ulonglong2 s_rec[BINX_TILE];
+    __shared__ u32 s_cnt[BINX_BLOCK], s_base[BINX_BLOCK], s_w[BINX_BLOCK / 64u];
+    const u32 tid = threadIdx.x;
+    u32 t0, nt, ti, lo, hi;
+    if (!binx_tile(seg, tb, nseg, t0, nt, ti, lo, hi)) return;
+    s_cnt[tid] = 0;
+    __syncthreads();
+    ulonglong2 r[PER];
+    u32 rank[PER];
+#pragma unroll
+    for (u32 j = 0; j < PER; j++) {
+        const u32 i = lo + j * BINX_BLOCK + tid;
+        if (i < hi) {
+            r[j] = src[i];
+            rank[j] = atomicAdd(&s_cnt[BINX_DIGIT(r[j].x, shift, nb)], 1u);
+        }
+    }
+    __syncthreads();
+    /* where a bin starts inside the tile; s_base[d] = what a record's place in the staged tile is short of its place in dst */
+    const u32 cnt = s_cnt[tid];
+    u32 incl = cnt;
+    for (int o = 1; o < 64; o <<= 1) {
+        const u32 y = __shfl_up(incl, o);
+        if ((int)(tid & 63u) >= o) incl += y;
+    }
+    if ((tid & 63u) == 63u) s_w[tid >> 6] = incl;
+    __syncthreads();
+    u32 start = incl - cnt;
+    for (u32 w = 0; w < (tid >> 6); w++) start += s_w[w];
+    __syncthreads(); /* (every thread has read its count) */
+    s_cnt[tid] = start;
+    if (tid < nb) s_base[tid] = scan[(u64)nb * t0 + (u64)tid * nt + ti] - start;
+    __syncthreads();
+#pragma unroll
+    for (u32 j = 0; j < PER; j++) {
+        const u32 i = lo + j * BINX_BLOCK + tid;
+        if (i < hi) s_rec[s_cnt[BINX_DIGIT(r[j].x, shift, nb)] + rank[j]] = r[j];
+    }
+    __syncthreads();
+    for (u32 j = tid; j < hi - lo; j += BINX_BLOCK) {
+        const ulonglong2 x = s_rec[j];
+        dst[s_base[BINX_DIGIT(x.x, shift, nb)] + j] = x;
+    }
+}
+
+/* one workgroup per partition p = the buckets [p nbk, (p + 1) nbk), nbk = 2^span (1024 .. 2^BINX_SPAN_BITS), whose records are
+ * rec[part[p], part[p + 1]): sweep 1 counts the buckets in LDS, a block-wide scan turns the counts into starts (the partition's slice of
+ * bkt[], written coalesced; an empty partition writes its starts all the same), sweep 2 hands every record its slot from the bucket's
+ * cursor and places the payload: the writes of a workgroup fall into the partition's window of ent[] (about 100 KB). A partition holds
+ * any number of records (copies of one read: all in one bucket); the sweeps step through it BINX_BUILD_BLOCK at a time. */
+__global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const ulonglong2 *__restrict__ rec, const u32 *__restrict__ part, u32 span, u32 total, u64 T, u32 *__restrict__ bkt,
+                                                                      u64 *__restrict__ ent)
+{
+    __shared__ u32 s_c[1u << BINX_SPAN_BITS];
+    __shared__ u32 s_w[16];
+    const u32 tid = threadIdx.x, p = blockIdx.x;
+    const u32 nbk = 1u << span, mask = nbk - 1u;
+    const u32 beg = part[p], end = part[p + 1];
+    for (u32 x = tid; x < nbk; x += BINX_BUILD_BLOCK) s_c[x] = 0;
+    __syncthreads();
+    for (u32 i = beg + tid; i < end; i += BINX_BUILD_BLOCK) atomicAdd(&s_c[(u32)(rec[i].x >> 32) & mask], 1u);
+    __syncthreads();
+    u32 carry = beg;
+    for (u32 base = 0; base < nbk; base += BINX_BUILD_BLOCK) { /* (nbk is a multiple of the block) */
+        const u32 x = s_c[base + tid];
+        u32 sum;
+        const u32 ex = binx_block_scan1024(x, s_w, &sum);
+        s_c[base + tid] = carry + ex;
+        bkt[(u64)p * nbk + base + tid] = carry + ex;
+        carry += sum;
+    }
+    if ((u64)(p + 1u) * nbk == T && tid == 0) bkt[T] = total;
+    __syncthreads();
+    for (u32 i = beg + tid; i < end; i += BINX_BUILD_BLOCK) {
+        const ulonglong2 x = rec[i];
+        ent[atomicAdd(&s_c[(u32)(x.x >> 32) & mask], 1u)] = x.y;
     }
 }
 
@@ -4863,8 +5054,8 @@ __global__ void uf_edge_file_kernel(const u64 *__restrict__ out_src, const u8 *_
         }
 }
 
-/* the query range grouped by read-level minimizer: count per hash value (the atomic hands every read its slot; the 32 MB of
- * counters stay in the L2 / Infinity Cache), exclusive scan, then order[start[hash] + slot] = read */
+/* the query range grouped by read-level minimizer: count per hash value (the atomic hands every read its slot; one counter per
+ * bucket of the grouping, about one per read: 2^26 x 4 bytes = 0.27 GB at 50 M reads, more than the Infinity Cache holds), exclusive scan, then order[start[hash] + slot] = read */
 /* ================================================================================================================
  * processing order of the probe and verify passes. Reads are grouped by their READ-LEVEL MINIMIZER: the smallest order
  * hash among all m-mers of the read. Two reads with the same key contain the same genome m-mer (up to hash collisions), so

@@ -103,6 +103,14 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+    # the device input stage's BGZF decode core on the host: the same header, a serial byte sink
+    chk = os.path.join(HERE, "bin", "inflate_check")
+    csrc = [os.path.join(HERE, "host", "inflate_check.cpp"), os.path.join(HERE, "csrc", "disco_inflate.h")]
+    if force or _stale(chk, csrc):
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", chk, csrc[0]]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
     return BUILDG
 
 

@@ -110,6 +110,7 @@ ABI = [
     ("disco_dist_get_info", C.c_int, [_P, _P]),
     ("disco_ingest_fasta", C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, C.c_uint32, _P, _P]),
     ("disco_ingest_fetch", C.c_int, [_P, _P, _P]),
+    ("disco_inflate_bgzf", C.c_int64, [_P, _P, C.c_uint64, _P, C.c_uint64]),
 ]
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
@@ -529,6 +530,22 @@ class BuildGraph:
             return None
         self._chk(rc)
         return ({n: getattr(info, n) for n, _ in IngestInfo._fields_}, [{n: getattr(f, n) for n, _ in IngestFile._fields_} for f in files])
+
+    def inflate_bgzf(self, data: bytes):
+        """the text of a BGZF buffer, decoded on the device (disco_inflate_bgzf: one wavefront per member, CRC32 checked), or None when
+        the buffer is not BGZF or a member is corrupt — last_error() then names the member and the reason"""
+        data = bytes(data)
+        n = self.L.disco_inflate_bgzf(self._h, data, len(data), None, 0)
+        if n == -6:  # DISCO_E_UNSUPPORTED
+            return None
+        out = C.create_string_buffer(max(self._chk(n), 1))
+        n = self.L.disco_inflate_bgzf(self._h, data, len(data), out, n)
+        if n == -6:
+            return None
+        return out.raw[:self._chk(n)]
+
+    def last_error(self) -> str:
+        return self.L.disco_last_error(self._h).decode()
 
     def ingest_fetch(self):
         """(lengths, 1-based file indices) of the reads the last ingest_fasta kept"""

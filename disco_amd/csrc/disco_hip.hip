@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fcntl.h>
+#include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <string>
@@ -42,6 +43,7 @@
 #include "disco_chains.h"
 #include "disco_text.h"
 #include "disco_ingest.h"
+#include "disco_bgzf.h"
 #include "read_filter_tables.h"
 #include "disco_comm.h"
 
@@ -1640,6 +1642,11 @@ struct IngestFile {
     u32 *d_wrap = nullptr;
     u16 *d_glen = nullptr;
     u64 n_start = 0, n_rec = 0, good = 0;
+    /* a BGZF file: n and d_text are its TEXT (known once the member chain is walked); the file itself is comp_n bytes at d_comp */
+    bool gz = false;
+    const u8 *map = nullptr;
+    u64 comp_n = 0;
+    u8 *d_comp = nullptr;
 };
 /* the transient buffers of the input stage are carved out of ONE arena — the context's hit buffer, sized here as the probe will want it
  * (64 candidate slots per read: about three times the text): freeing 10 GB right before the pass made its first allocations take
@@ -1806,6 +1813,77 @@ static int ingest_read_file(disco_ctx *c, int fd, u64 n, u8 *d_text, unsigned th
     return DISCO_OK;
 }
 
+/* ---- BGZF: the members of a compressed file decoded on the device (kernel: disco_bgzf.h, decoder: disco_inflate.h) ------------------- */
+/* one wavefront per member on the context's stream, waited for. d_blk: room for the member table, d_status: a word per member and one
+ * more. *why = INFL_OK, or the error of member *bad, the first one the kernel did not accept (its text is then not written) */
+static int bgzf_inflate_run(disco_ctx *c, const u8 *d_comp, const std::vector<infl::BgzfBlock> &blocks, infl::BgzfBlock *d_blk, u32 *d_status, u8 *d_text, uint64_t *bad, int *why)
+{
+    const u64 nb = blocks.size();
+    *why = infl::INFL_OK;
+    *bad = 0;
+    if (nb == 0 || nb >= (1ull << 31)) return fail(c, DISCO_E_ARG, "BGZF: %llu members out of range", (unsigned long long)nb);
+    HIPCHK(c, hipMemcpyAsync(d_blk, blocks.data(), nb * sizeof(infl::BgzfBlock), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_status, 0, (nb + 1) * sizeof(u32), c->stream));
+    BgzfArgs a;
+    a.comp = d_comp;
+    a.blk = d_blk;
+    a.n_blk = (u32)nb;
+    a.text = d_text;
+    a.status = d_status;
+    hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)nb), dim3(64), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    u32 n_err = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_err, d_status + nb, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_err) {
+        std::vector<u32> st(nb);
+        HIPCHK(c, hipMemcpy(st.data(), d_status, nb * sizeof(u32), hipMemcpyDeviceToHost));
+        for (u64 k = 0; k < nb; k++)
+            if (st[k]) {
+                *bad = k;
+                *why = (int)st[k];
+                break;
+            }
+        if (*why == infl::INFL_OK) return fail(c, DISCO_E_STATE, "BGZF: %u members in error, none marked", n_err);
+    }
+    return DISCO_OK;
+}
+
+extern "C" int64_t disco_inflate_bgzf(disco_ctx *c, const void *bgzf, uint64_t n_bytes, void *out, uint64_t cap)
+{
+    DISCO_TRACE("disco_inflate_bgzf");
+    if (!c || !bgzf) return c ? fail(c, DISCO_E_ARG, "disco_inflate_bgzf: null argument") : DISCO_E_ARG;
+    std::vector<infl::BgzfBlock> blocks;
+    uint64_t total = 0, bad = 0;
+    if (const char *why = infl::bgzf_walk((const u8 *)bgzf, n_bytes, blocks, &total, &bad))
+        return fail(c, DISCO_E_UNSUPPORTED, "disco_inflate_bgzf: member %llu: %s", (unsigned long long)bad, why);
+    if (!out) return (int64_t)total;
+    if (cap < total) return fail(c, DISCO_E_CAPACITY, "disco_inflate_bgzf: %llu bytes of text, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<u8> d_comp, d_text;
+    DevBuf<infl::BgzfBlock> d_blk;
+    DevBuf<u32> d_status;
+    int e = infl::INFL_OK;
+    auto body = [&]() -> int {
+        CHK(ensure(c, d_comp, n_bytes));
+        CHK(ensure(c, d_text, total));
+        CHK(ensure(c, d_blk, blocks.size()));
+        CHK(ensure(c, d_status, blocks.size() + 1));
+        HIPCHK(c, hipMemcpyAsync(d_comp.p, bgzf, n_bytes, hipMemcpyHostToDevice, c->stream));
+        CHK(bgzf_inflate_run(c, d_comp, blocks, d_blk, d_status, d_text, &bad, &e));
+        if (e == infl::INFL_OK && total) HIPCHK(c, hipMemcpy(out, d_text.p, total, hipMemcpyDeviceToHost));
+        return DISCO_OK;
+    };
+    const int rc = body();
+    release(c, d_comp);
+    release(c, d_text);
+    release(c, d_blk);
+    release(c, d_status);
+    CHK(rc);
+    if (e != infl::INFL_OK) return fail(c, DISCO_E_UNSUPPORTED, "disco_inflate_bgzf: member %llu: %s", (unsigned long long)bad, infl::reason(e));
+    return (int64_t)total;
+}
+
 extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_files, uint32_t host_threads, disco_ingest_info *info, disco_ingest_file *files)
 {
     DISCO_TRACE("disco_ingest_fasta");
@@ -1821,8 +1899,12 @@ extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_
     std::vector<Owned> owned;
     IngestArena arena;
     auto cleanup = [&]() {
-        for (auto &f : F)
+        for (auto &f : F) {
+            if (f.map) munmap((void *)f.map, (size_t)f.comp_n);
+            f.map = nullptr;
             if (f.fd >= 0) close(f.fd);
+            f.fd = -1;
+        }
         for (auto &o : owned) {
             (void)hipFree(o.p);
             c->hbm_bytes -= o.bytes;
@@ -1833,12 +1915,27 @@ extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_
         cleanup();
         return fail(c, DISCO_E_UNSUPPORTED, "disco_ingest_fasta: %s (%s): the host input stage takes this job", why, path.c_str());
     };
-    /* ---- the files: regular, not gzip, first byte '>' --------------------------------------------------------------------------- */
+    /* ---- the files: regular, first byte '>' or '@'; under a .gz name BGZF only (plain gzip is one serial stream: the host stage's) ----- */
     u64 total_bytes = 0;
     for (int fi = 0; fi < n_files; fi++) {
         IngestFile &f = F[(size_t)fi];
         f.path = paths[fi] ? paths[fi] : "";
-        if (f.path.size() >= 3 && f.path.compare(f.path.size() - 3, 3, ".gz") == 0) return unsupported("gzip input", f.path);
+        if (f.path.size() >= 3 && f.path.compare(f.path.size() - 3, 3, ".gz") == 0) {
+            struct stat gst;
+            u32 hdr = 0, bsize = 0;
+            f.fd = open(f.path.c_str(), O_RDONLY);
+            if (f.fd < 0 || fstat(f.fd, &gst) != 0 || !S_ISREG(gst.st_mode) || gst.st_size < 1) return unsupported("gzip input", f.path);
+            void *m = mmap(nullptr, (size_t)gst.st_size, PROT_READ, MAP_PRIVATE, f.fd, 0); /* for the header walk only: the readers pread */
+            if (m == MAP_FAILED) return unsupported("gzip input", f.path);
+            f.map = (const u8 *)m;
+            f.comp_n = (u64)gst.st_size;
+            if (infl::bgzf_header(f.map, f.comp_n, 0, &hdr, &bsize)) return unsupported("gzip input", f.path);
+            f.gz = true;
+            /* the text's size is known when the chain is walked, behind the transfer: the arena is sized for five times the file (FASTA
+             * at level 6: four); a text that does not fit gets a piece of its own */
+            total_bytes += ((f.comp_n + 255) & ~255ull) + (f.comp_n * 5 + FX_TILE + 63) / FX_TILE * FX_TILE + 64;
+            continue;
+        }
         f.fd = open(f.path.c_str(), O_RDONLY);
         if (f.fd < 0) return unsupported("unreadable file", f.path);
         struct stat st;
@@ -1932,9 +2029,66 @@ extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_
     for (int fi = 0; fi < n_files; fi++) {
         IngestFile &f = F[(size_t)fi];
         const auto t_read = HClock::now();
-        if ((rc = get(&f.d_text, f.text_cap)) == DISCO_OK && hipMemsetAsync(f.d_text + f.n, 0, f.text_cap - f.n, c->stream) != hipSuccess) rc = DISCO_E_HIP;
-        if (rc == DISCO_OK) rc = ingest_read_file(c, f.fd, f.n, f.d_text, host_threads ? host_threads : 16u);
-        read_s += ms_since(t_read) * 1e-3f;
+        std::string gz_why;
+        /* a BGZF file: the file into HBM while a host thread walks its member chain; then one wavefront per member writes the text */
+        auto gz_stage = [&]() -> int {
+            CHK(get(&f.d_comp, f.comp_n));
+            std::vector<infl::BgzfBlock> blocks;
+            uint64_t total = 0, bad = 0;
+            const char *why = nullptr;
+            float walk_ms = 0;
+            std::thread walker([&]() {
+                const auto t0 = HClock::now();
+                why = infl::bgzf_walk(f.map, f.comp_n, blocks, &total, &bad);
+                walk_ms = ms_since(t0);
+            });
+            const int rrc = ingest_read_file(c, f.fd, f.comp_n, f.d_comp, host_threads ? host_threads : 16u);
+            walker.join();
+            read_s += ms_since(t_read) * 1e-3f;
+            CHK(rrc);
+            char msg[160];
+            if (why || total == 0) {
+                snprintf(msg, sizeof msg, "gzip input, member %llu: %s", (unsigned long long)bad, why ? why : "no text");
+                gz_why = msg;
+                return DISCO_E_UNSUPPORTED;
+            }
+            const auto t_inf = HClock::now();
+            f.n = total;
+            f.text_cap = (f.n + FX_TILE + 63) / FX_TILE * FX_TILE + 64;
+            infl::BgzfBlock *d_blk = nullptr;
+            u32 *d_status = nullptr;
+            CHK(get(&f.d_text, f.text_cap));
+            CHK(get(&d_blk, blocks.size()));
+            CHK(get(&d_status, blocks.size() + 1));
+            HIPCHK(c, hipMemsetAsync(f.d_text + f.n, 0, f.text_cap - f.n, c->stream));
+            int e = infl::INFL_OK;
+            CHK(bgzf_inflate_run(c, f.d_comp, blocks, d_blk, d_status, f.d_text, &bad, &e));
+            if (e != infl::INFL_OK) {
+                snprintf(msg, sizeof msg, "BGZF member %llu: %s", (unsigned long long)bad, infl::reason(e));
+                gz_why = msg;
+                return DISCO_E_UNSUPPORTED;
+            }
+            char first = 0;
+            HIPCHK(c, hipMemcpy(&first, f.d_text, 1, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(&f.last, f.d_text + f.n - 1, 1, hipMemcpyDeviceToHost));
+            if (getenv("DISCO_VERBOSE"))
+                fprintf(stderr, "[disco] BGZF %s: %.1f MB in %llu members -> %.1f MB of text; header walk %.1f ms (behind the transfer), inflate %.1f ms\n", f.path.c_str(), f.comp_n / 1e6,
+                        (unsigned long long)blocks.size(), f.n / 1e6, walk_ms, ms_since(t_inf));
+            if (first != '>' && first != '@') {
+                gz_why = "neither FASTA nor FASTQ";
+                return DISCO_E_UNSUPPORTED;
+            }
+            f.fastq = first == '@';
+            return DISCO_OK;
+        };
+        if (f.gz) {
+            rc = gz_stage();
+            if (rc == DISCO_E_UNSUPPORTED && !gz_why.empty()) return unsupported(gz_why.c_str(), f.path);
+        } else {
+            if ((rc = get(&f.d_text, f.text_cap)) == DISCO_OK && hipMemsetAsync(f.d_text + f.n, 0, f.text_cap - f.n, c->stream) != hipSuccess) rc = DISCO_E_HIP;
+            if (rc == DISCO_OK) rc = ingest_read_file(c, f.fd, f.n, f.d_text, host_threads ? host_threads : 16u);
+            read_s += ms_since(t_read) * 1e-3f;
+        }
         const u64 tiles = (f.n + FX_TILE - 1) / FX_TILE;
         u64 *d_tile_base = nullptr;
         u32 *d_tile_cnt = nullptr;

@@ -282,9 +282,13 @@ int disco_dist_get_info(disco_ctx *ctx, disco_dist_info *out);
  * files in the order given (pass the -pe files, then the -se files). The graph results of a previous pass on the context are discarded
  * by the call, whatever it returns. Returns DISCO_E_UNSUPPORTED — the context's reads are unchanged — when a file is not
  * of a form the device stage accepts (FASTA: it must start with '>' and every '>' must begin a line; sequences may be wrapped — at one
- * width per record, or irregularly up to 4096 bases; FASTQ: it starts with '@', records of four lines; not accepted: .gz, empty or
+ * width per record, or irregularly up to 4096 bases; FASTQ: it starts with '@', records of four lines; not accepted: plain gzip, empty or
  * unreadable files): the caller then runs its host stage (disco_amd/host/fastx.cpp follows the reference's
- * getline calls literally and produces its error messages) and disco_upload_reads. */
+ * getline calls literally and produces its error messages) and disco_upload_reads.
+ * A file named .gz is accepted when it is BGZF (what bgzip / htslib write: gzip members of at most 64 KB of text that carry their own
+ * sizes; any gzip reader reads them): the file travels to HBM as it is and the device decodes it, a wavefront per member, CRC32 checked,
+ * in front of the kernels above. Plain and BGZF files may be mixed in one call. A .gz file that is one ordinary gzip stream, a member
+ * chain that does not end with the file, or a member the decoder or its CRC32 refuses (the message names the member) declines the call. */
 typedef struct disco_ingest_file {
     uint64_t first_index, last_index; /* 1-based file indices of the file's first / last record (every record counts, BG/Dataset.cpp:294) */
     uint64_t good, bad;
@@ -296,6 +300,10 @@ typedef struct disco_ingest_info {
     float read_s, device_s;                    /* host wall: files into HBM / everything after                                        */
 } disco_ingest_info;
 int disco_ingest_fasta(disco_ctx *ctx, const char *const *paths, int n_files, uint32_t host_threads, disco_ingest_info *info, disco_ingest_file *files);
+/* decode a BGZF buffer held by the host on the device: returns the number of text bytes (out == NULL: the size only, nothing decoded),
+ * DISCO_E_UNSUPPORTED when the buffer is not BGZF or a member is corrupt (disco_last_error names the member and the reason),
+ * DISCO_E_CAPACITY when cap is too small */
+int64_t disco_inflate_bgzf(disco_ctx *ctx, const void *bgzf, uint64_t n_bytes, void *out, uint64_t cap);
 /* lengths and 1-based file indices (for <prefix>_ReadIDMap.txt and the id columns of every output line) of the reads the last
  * disco_ingest_fasta kept: len[n_reads], file_index[n_reads]. The ONE call that may run on a host thread of its own while another
  * thread drives a pass on the same context (it works on the copy stream and shares only the mirrored lengths, under a lock); its

@@ -1,9 +1,13 @@
 """differential fuzzing of the input stage (disco_amd/bin/fastx_dump = the parser / filter / id assignment of the drop-in buildG)
 against the oracle's restatement of Dataset::readDataset + testRead, on randomly malformed FASTA / FASTQ text.
    python tools/fuzz_fastx.py [ITERATIONS=200] [SEED=1] [gpu]      (CPU only; with "gpu": the input stage on the GPU, disco_ingest_fasta, on
-   the same files as well — whatever it ACCEPTS must come out exactly as the oracle's parser has it; declining is always allowed)"""
-import gzip, os, subprocess, sys, tempfile
+   the same files as well — whatever it ACCEPTS must come out exactly as the oracle's parser has it; declining is always allowed)
+   --bgzf (anywhere): every file is written as BGZF under a .gz name (tests/bgzf_util.py: random level, strategy, member size, an empty
+   stored block inside, with or without the end-of-file member) — zlib reads it in the host stage, the device stage decodes it itself"""
+import gzip, os, subprocess, sys, tempfile, zlib
 sys.path.insert(0, '.')
+BGZF = "--bgzf" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--bgzf"]
 import numpy as np
 from oracle import pyoracle
 from disco_amd import build
@@ -103,7 +107,15 @@ with tempfile.TemporaryDirectory() as d:
             p = os.path.join(d, "f%d_%d.%s" % (it, f, "fa"))
             open(p, "w", newline="").write(text)
             plain.append(p)
-            if rng.random() < 0.2:  # the drop-in reads the gzip, the oracle the same bytes uncompressed
+            if BGZF:
+                from tests import bgzf_util as bz
+
+                kw = dict(level=int(rng.choice([0, 1, 6, 9])), strategy=int(rng.choice([zlib.Z_DEFAULT_STRATEGY, zlib.Z_FIXED, zlib.Z_HUFFMAN_ONLY, zlib.Z_RLE])))
+                if rng.random() < 0.3:
+                    kw["flush_at"] = int(rng.integers(1, 200))
+                open(p + ".gz", "wb").write(bz.bgzf_bytes(text.encode(), int(rng.choice([1, 100, 4096, 65280])), eof=bool(rng.random() < 0.7), **kw))
+                p += ".gz"
+            elif rng.random() < 0.2:  # the drop-in reads the gzip, the oracle the same bytes uncompressed
                 with gzip.open(p + ".gz", "wb") as fh:
                     fh.write(text.encode())
                 p += ".gz"

@@ -646,6 +646,16 @@ static int wq_grid(disco_ctx *c, K kernel, u64 items, const char *env, int cap =
     return (int)std::max<u64>(g, 1);
 }
 
+/* a work-queue kernel sized and launched from ONE pointer (these kernels are tuned by resident blocks per CU: a grid sized from one
+ * instantiation and launched with another is a silent slowdown). Where the grid is needed first (disco_probe sizes its hit buffer from
+ * it): wq_grid with the pointer, and the same pointer to the launch */
+template <typename K, typename... A>
+static void wq_launch(disco_ctx *c, K kernel, u64 items, const char *env, int cap, A... args)
+{
+    const int g = wq_grid(c, kernel, items, env, cap);
+    hipLaunchKernelGGL(kernel, dim3(g), dim3(64), 0, c->stream, args...);
+}
+
 static int flat_grid(const disco_ctx *c, u64 items, int block = 256)
 {
     u64 g = (items + block - 1) / block;
@@ -846,18 +856,21 @@ struct IndexCountPlan {
     int lpr = 0, nf = 0;
     u32 *ocnt = nullptr, *oslot = nullptr;
     u32 oshift = 0;
+    const u64 *list = nullptr; /* ranks own loci: position x of [lo, hi) stands for read ORDER_ID(list[x]) (records, runs, slots by position) */
 };
+
+/* the window lengths index_runs_kernel has an instantiation of their own for (a block of NF order words in registers): the reference's
+ * default min-overlap 30 (NF 7), 35, BASELINE's 40 (NF 17), 45, 50 */
+static bool runs_nf_built(int nf, int m) { return (nf == 7 || nf == 12 || nf == 17 || nf == 22 || nf == 27) && m == RUNS_M; }
 
 /* 32-bit words of minimizer runs per read for a table of 64-byte rows whose longest read has max_len bases, or 0: no runs */
 static int runs_lpr_for(const disco_ctx *c, int nf, u32 max_len, u64 nloc)
 {
     int lpr = 0;
-    /* (index_runs_kernel keeps a block of NF order words in registers: one instantiation per window length — the reference's default
-     * min-overlap 30 (NF 7), 35, BASELINE's 40 (NF 17), 45, 50) */
     /* round 6: every other window of 2 .. 64 m-mers — any min-overlap up to 95, k above 64 and minimizers of up to 31 bases included —
      * takes the instantiation with a run-time window length (DISCO_NO_GENERIC_RUNS=1: round 2's probe for those, as before) */
     const int m = view(c).m;
-    const bool nf_built = (nf == 7 || nf == 12 || nf == 17 || nf == 22 || nf == 27) && m == RUNS_M;
+    const bool nf_built = runs_nf_built(nf, m);
     const bool nf_generic = nf >= 2 && nf <= 64 && m > 16 && m <= 31 && !getenv("DISCO_NO_GENERIC_RUNS");
     if ((nf_built || nf_generic) && max_len > (u32)c->k && !getenv("DISCO_NO_RUNS")) {
         const u32 maxwin = max_len - (u32)c->k;
@@ -884,16 +897,18 @@ static bool two_class_ok(const disco_ctx *c, int S, u64 n, u64 n_long, u32 short
 
 static int two_class_alloc(disco_ctx *c, u64 n_long, int Sx, u32 short_max);
 
-static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, IndexCountPlan *pl)
+/* (list: the own list of a rank that owns loci, [lo, hi) = its positions — it IS the processing order: no grouping to count) */
+static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, IndexCountPlan *pl, const u64 *list = nullptr)
 {
     const u64 nloc = hi - lo;
     *pl = IndexCountPlan();
     pl->lo = lo;
     pl->hi = hi;
+    pl->list = list;
     /* the counting pass of the grouping rides along when the indexed range is the query range (always, unless a caller narrows it) */
-    c->order_counted = c->order_ready = false;
+    if (!list) c->order_counted = c->order_ready = false;
     int obits = 0;
-    if (lo == c->q_lo && hi == c->q_hi && own_order_wanted(c, nloc, &obits) && !getenv("DISCO_NO_ORDER_FUSE")) {
+    if (!list && lo == c->q_lo && hi == c->q_hi && own_order_wanted(c, nloc, &obits) && !getenv("DISCO_NO_ORDER_FUSE")) {
         const u64 order_buckets = 1ull << obits;
         CHK(ensure(c, c->d_ocnt, order_buckets + 1));
         CHK(ensure(c, c->d_oslot, nloc));
@@ -916,69 +931,87 @@ static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, In
         c->runs_lpr = lpr;
         c->runs_lo = lo;
         c->runs_n = nloc;
+        c->runs_by_pos = list != nullptr;
         pl->lpr = lpr;
         pl->nf = nf;
     }
     return DISCO_OK;
 }
 
-/* reads [a, b) of the planned range; rec_base = the records of read pl.lo */
+/* which instantiation counts this shape — the ONLY place that names the template arguments of index_runs_kernel / index_count_kernel.
+ * lpr != 0: with the minimizer runs (16 / 32 words per read: NL 1 / 2), a window of nf m-mers; long_class: the long reads of two row
+ * classes, from their full rows (never with runs) */
+typedef void (*IndexRunsFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u32 *, u32, const u64 *);
+typedef void (*IndexCountFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u32, const u64 *);
+struct IndexCountKernel {
+    IndexRunsFn runs = nullptr; /* one of the two */
+    IndexCountFn plain = nullptr;
+};
+template <bool COUNT, int NF, int NFMAX, bool LONGK>
+static IndexCountKernel index_runs_pick(int lpr)
+{
+    IndexCountKernel k;
+    k.runs = lpr == 16 ? index_runs_kernel<COUNT, NF, 1, NFMAX, LONGK> : index_runs_kernel<COUNT, NF, 2, NFMAX, LONGK>;
+    return k;
+}
 template <bool COUNT>
-static int index_count_chunk(disco_ctx *c, const DiscoView &v, const IndexCountPlan &pl, ulonglong2 *rec_base, u64 a, u64 b)
+static IndexCountKernel index_count_pick(int nf, int m, int lpr, bool longk, bool long_class)
+{
+    if (long_class || !lpr) {
+        IndexCountKernel k;
+        if (long_class) k.plain = longk ? index_count_kernel<COUNT, true, true> : index_count_kernel<COUNT, false, true>;
+        else k.plain = longk ? index_count_kernel<COUNT, true> : index_count_kernel<COUNT>;
+        return k;
+    }
+    if (runs_nf_built(nf, m)) switch (nf) {
+        case 7: return index_runs_pick<COUNT, 7, 7, false>(lpr);
+        case 12: return index_runs_pick<COUNT, 12, 12, false>(lpr);
+        case 17: return index_runs_pick<COUNT, 17, 17, false>(lpr);
+        case 22: return index_runs_pick<COUNT, 22, 22, false>(lpr);
+        default: return index_runs_pick<COUNT, 27, 27, false>(lpr);
+        }
+    /* the window length as a run-time value: arrays for 32 or 64 m-mers */
+    /* (the arrays are registers: an instantiation per size class keeps the waves per SIMD near the specialised kernels' — windows of 10
+     * in arrays for 32 ran 9.8 ms at 20 M reads, in arrays for 12: 6.7) */
+    if (longk) return nf <= 48 ? index_runs_pick<COUNT, 0, 48, true>(lpr) : index_runs_pick<COUNT, 0, 64, true>(lpr);
+    if (nf <= 8) return index_runs_pick<COUNT, 0, 8, false>(lpr);
+    if (nf <= 12) return index_runs_pick<COUNT, 0, 12, false>(lpr);
+    if (nf <= 16) return index_runs_pick<COUNT, 0, 16, false>(lpr);
+    if (nf <= 24) return index_runs_pick<COUNT, 0, 24, false>(lpr);
+    if (nf <= 32) return index_runs_pick<COUNT, 0, 32, false>(lpr);
+    if (nf <= 48) return index_runs_pick<COUNT, 0, 48, false>(lpr);
+    return index_runs_pick<COUNT, 0, 64, false>(lpr);
+}
+/* count: the counting atomics on the bucket table ride along (the binned build counts for itself) */
+static IndexCountKernel index_count_pick(bool count, int nf, int m, int lpr, bool longk, bool long_class)
+{
+    return count ? index_count_pick<true>(nf, m, lpr, longk, long_class) : index_count_pick<false>(nf, m, lpr, longk, long_class);
+}
+
+/* reads [a, b) of the planned range; rec_base = the records of read pl.lo */
+static int index_count_chunk(disco_ctx *c, const DiscoView &v, const IndexCountPlan &pl, bool count, ulonglong2 *rec_base, u64 a, u64 b)
 {
     if (b <= a) return DISCO_OK;
     const dim3 grid((unsigned)((b - a + 255) / 256));
     ulonglong2 *rec = rec_base + 2 * (a - pl.lo);
     u32 *oslot = pl.oslot ? pl.oslot + (a - pl.lo) : nullptr;
-    if (pl.lpr) {
-        u32 *runs = c->d_runs + (a - pl.lo) * (u64)pl.lpr;
-#define DISCO_RUNS_LAUNCH(NF_)                                                                                                                              \
-    do {                                                                                                                                                  \
-        if (pl.lpr == 16) hipLaunchKernelGGL((index_runs_kernel<COUNT, NF_, 1>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, a, b, runs, pl.ocnt, oslot, pl.oshift); \
-        else hipLaunchKernelGGL((index_runs_kernel<COUNT, NF_, 2>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, a, b, runs, pl.ocnt, oslot, pl.oshift);             \
-    } while (0)
-#define DISCO_RUNS_LAUNCH_RT(NFMAX_, LONGK_)                                                                                                                 \
-    do {                                                                                                                                                  \
-        if (pl.lpr == 16) hipLaunchKernelGGL((index_runs_kernel<COUNT, 0, 1, NFMAX_, LONGK_>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, a, b, runs, pl.ocnt, oslot, pl.oshift); \
-        else hipLaunchKernelGGL((index_runs_kernel<COUNT, 0, 2, NFMAX_, LONGK_>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, a, b, runs, pl.ocnt, oslot, pl.oshift);             \
-    } while (0)
-        const bool built = v.m == RUNS_M && (pl.nf == 7 || pl.nf == 12 || pl.nf == 17 || pl.nf == 22 || pl.nf == 27);
-        if (!built) { /* the window length as a run-time value: arrays for 32 or 64 m-mers */
-            /* (the arrays are registers: an instantiation per size class keeps the waves per SIMD near the specialised kernels' — windows of 10
-             * in arrays for 32 ran 9.8 ms at 20 M reads, in arrays for 12: 6.7) */
-            if (c->k > 64) {
-                if (pl.nf <= 48) DISCO_RUNS_LAUNCH_RT(48, true);
-                else DISCO_RUNS_LAUNCH_RT(64, true);
-            } else if (pl.nf <= 8) DISCO_RUNS_LAUNCH_RT(8, false);
-            else if (pl.nf <= 12) DISCO_RUNS_LAUNCH_RT(12, false);
-            else if (pl.nf <= 16) DISCO_RUNS_LAUNCH_RT(16, false);
-            else if (pl.nf <= 24) DISCO_RUNS_LAUNCH_RT(24, false);
-            else if (pl.nf <= 32) DISCO_RUNS_LAUNCH_RT(32, false);
-            else if (pl.nf <= 48) DISCO_RUNS_LAUNCH_RT(48, false);
-            else DISCO_RUNS_LAUNCH_RT(64, false);
-        } else
-            switch (pl.nf) {
-            case 7: DISCO_RUNS_LAUNCH(7); break;
-            case 12: DISCO_RUNS_LAUNCH(12); break;
-            case 17: DISCO_RUNS_LAUNCH(17); break;
-            case 22: DISCO_RUNS_LAUNCH(22); break;
-            default: DISCO_RUNS_LAUNCH(27); break;
-            }
-#undef DISCO_RUNS_LAUNCH
-#undef DISCO_RUNS_LAUNCH_RT
-    } else
-        if (c->k > 64) hipLaunchKernelGGL((index_count_kernel<COUNT, true>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, a, b, pl.ocnt, oslot, pl.oshift);
-        else hipLaunchKernelGGL(index_count_kernel<COUNT>, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, a, b, pl.ocnt, oslot, pl.oshift);
+    u32 *okey = pl.list ? nullptr : c->d_okey.p; /* (a list: the keys were made when the reads were dealt, by read id) */
+    const IndexCountKernel k = index_count_pick(count, pl.nf, v.m, pl.lpr, c->k > 64, false);
+    if (k.runs) hipLaunchKernelGGL(k.runs, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, c->d_runs + (a - pl.lo) * (u64)pl.lpr, pl.ocnt, oslot, pl.oshift, pl.list);
+    else hipLaunchKernelGGL(k.plain, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, pl.ocnt, oslot, pl.oshift, pl.list);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
 }
 
-template <bool COUNT>
-static int launch_index_count(disco_ctx *c, const DiscoView &v, ulonglong2 *rec, u64 lo, u64 hi)
+/* the long reads [x_lo, x_hi) of two row classes (positions in long_ids): their records, keys and slots, from their full rows; rec and
+ * oslot by read id */
+static int index_count_long(disco_ctx *c, const DiscoView &v, const IndexCountPlan &pl, bool count, ulonglong2 *rec, u32 *oslot, u64 x_lo, u64 x_hi)
 {
-    IndexCountPlan pl;
-    CHK(index_count_plan(c, v, lo, hi, &pl));
-    return index_count_chunk<COUNT>(c, v, pl, rec, lo, hi);
+    const dim3 g((unsigned)((x_hi - x_lo + 255) / 256));
+    hipLaunchKernelGGL(index_count_pick(count, 0, v.m, 0, c->k > 64, true).plain, g, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, x_lo, x_hi, pl.ocnt, oslot, pl.oshift,
+                       (const u64 *)nullptr);
+    HIPCHK(c, hipGetLastError());
+    return DISCO_OK;
 }
 
 /* does the binned build make this index (single GPU: the only callers of index_begin)? DISCO_NO_BINNED_INDEX=1: the counting atomics,
@@ -997,9 +1030,8 @@ static bool binned_index_wanted(disco_ctx *c, int logT)
     return true;
 }
 
-/* sizes of the index for the context's reads and the cleared bucket table (the start of disco_build_index, or of an upload that
- * counts while it copies) */
-static int index_begin(disco_ctx *c)
+/* the bucket table of an index over the context's n reads: c->T = 2^logT buckets, c->bshift; returns logT */
+static int size_bucket_table(disco_ctx *c)
 {
     u64 T = 1024;
     int logT = 10;
@@ -1013,6 +1045,15 @@ static int index_begin(disco_ctx *c)
     }
     c->T = T;
     c->bshift = 64 - logT;
+    return logT;
+}
+
+/* sizes of the index for the context's reads and the cleared bucket table (the start of disco_build_index, or of an upload that
+ * counts while it copies) */
+static int index_begin(disco_ctx *c)
+{
+    const int logT = size_bucket_table(c);
+    const u64 T = c->T;
     CHK(ensure(c, c->d_bkt, T + 1));
     CHK(ensure(c, c->d_ent, 2 * c->n));
     /* {key, record} of both end k-mers of every read, computed once by the count pass and re-read by the fill pass */
@@ -1206,6 +1247,182 @@ static void settle_hits_prealloc(disco_ctx *c)
             (void)hipFree(c->prealloc.p);
         c->prealloc = DevBuf<u64>();
     }
+}
+
+/* ---- which instantiation serves a shape ---------------------------------------------------------------------------------------
+ * One selector per family of templated kernels (the index count pass has its own next to index_count_chunk, above): a plain function
+ * from the shape and the knobs to the kernel pointer, and the only place that names the family's template arguments. The work-queue
+ * kernels are sized and launched from that one pointer (wq_launch). */
+
+/* which instantiation probes this shape — the ONLY place that names the template arguments of probe_kernel / probe_runs_kernel.
+ * mode 0: the query range (use_runs: from the minimizer runs the index pass left), 1: big_list (rows of known size), 2: slow_list */
+typedef void (*ProbeFn)(ProbeArgs);
+typedef void (*ProbeRunsFn)(ProbeArgs, const u32 *, u64);
+struct ProbeKernel {
+    ProbeRunsFn runs = nullptr; /* one of the two */
+    ProbeFn plain = nullptr;
+};
+template <int PMODE>
+static ProbeFn probe_mode_pick(bool ldsrow, bool row17, bool longk, bool long_class)
+{
+    if constexpr (PMODE != 0) { /* the long class does not fit the LDS row: the lists' reads from global memory */
+        if (long_class) return longk ? probe_kernel<PMODE, false, false, true, true> : row17 ? probe_kernel<PMODE, false, true, false, true> : probe_kernel<PMODE, false, false, false, true>;
+    }
+    if constexpr (PMODE != 2) { /* (slow_list only exists next to probe_runs_kernel: 64-byte rows) */
+        if (!ldsrow) return longk ? probe_kernel<PMODE, false, false, true> : row17 ? probe_kernel<PMODE, false, true> : probe_kernel<PMODE, false, false>;
+    }
+    return longk ? probe_kernel<PMODE, true, false, true> : row17 ? probe_kernel<PMODE, true, true> : probe_kernel<PMODE, true, false>;
+}
+static ProbeKernel probe_pick(const disco_ctx *c, int mode, bool use_runs)
+{
+    const bool ldsrow = c->S <= PROBE_ACAP; /* (two classes of rows: c->S = 8; the lists' kernels take the long class's stride into account) */
+    const bool row17 = c->k - view(c).m == 16 && !getenv("DISCO_NO_ROW17"); /* window = 17 m-mers: DPP row-scan variant */
+    const bool longk = c->k > 64;                                            /* three-word k-mers: variants of their own (kmer_is_rev) */
+    const bool long_class = c->two_class && c->S_ext > PROBE_ACAP;
+    ProbeKernel k;
+    if (mode == 0 && use_runs) k.runs = c->runs_lpr == 16 ? probe_runs_kernel<16> : probe_runs_kernel<32>;
+    else if (mode == 0) k.plain = probe_mode_pick<0>(ldsrow, row17, longk, long_class);
+    else if (mode == 1) k.plain = probe_mode_pick<1>(ldsrow, row17, longk, long_class);
+    else k.plain = probe_mode_pick<2>(ldsrow, row17, longk, long_class);
+    return k;
+}
+
+/* which instantiation verifies this shape, and the cap on its blocks per CU — the ONLY place that names the template arguments of
+ * verify_kernel / verify_flat_kernel. mode 0: the single pass; 1 / 2: the containment-type candidates, then the overlap-type ones of
+ * the non-contained reads (64-byte rows only); flat: verify_flat_kernel (64-byte rows, exact overlaps) */
+typedef void (*VerifyFn)(VerifyArgs);
+template <bool INEXACT>
+static VerifyFn verify_rows_pick(int S, bool short_rows) /* the wave-per-read kernel by row stride */
+{
+    if (S == VERIFY_SW) return short_rows ? verify_kernel<5, 0, INEXACT> : verify_kernel<8, 0, INEXACT>;
+    return S == 16 ? verify_kernel<16, 0, INEXACT> : S == 24 ? verify_kernel<24, 0, INEXACT> : S == 32 ? verify_kernel<32, 0, INEXACT> : verify_kernel<0, 0, INEXACT>;
+}
+template <int MODE>
+static VerifyFn verify_pass_pick(bool flat, bool short_rows) /* a pass of the two */
+{
+    if (flat) return short_rows ? verify_flat_kernel<5, MODE> : verify_flat_kernel<8, MODE>;
+    return short_rows ? verify_kernel<5, MODE> : verify_kernel<8, MODE>;
+}
+static VerifyFn verify_pick(const disco_ctx *c, int mode, bool flat, bool inexact, int *cap)
+{
+    const bool short_rows = c->max_len <= 160; /* rows of 5 words */
+    *cap = 32;
+    if (mode == 1) return verify_pass_pick<1>(flat, short_rows);
+    if (mode == 2) return verify_pass_pick<2>(flat, short_rows);
+    if (inexact) return verify_rows_pick<true>(c->S, short_rows);
+    if (!flat) return verify_rows_pick<false>(c->S, short_rows);
+    /* pairs of batches share their row fetches (verify_flat_kernel<·, 0, true>): 21.5 against 22.6 ms and 18 GB less traffic at config 3
+     * (reads of up to 160 bases); 32.3 against 33.0–35.1 ms on 50 M reads of 100–250 bases, 72.9 against 76.3 with config 5's
+     * abundances (256-base rows, 15 KB of LDS per wavefront). DISCO_VERIFY_CACHE=0 forbids it */
+    const char *vce = getenv("DISCO_VERIFY_CACHE");
+    const bool vcache = vce ? atoi(vce) != 0 : true;
+    if (!vcache) return short_rows ? verify_flat_kernel<5> : verify_flat_kernel<8>;
+    /* (round 5: 128 registers and 10 KB of LDS hold sixteen blocks per CU; 12 / 14 / 16 resident: 22.8 / 21.5 / 22.0 ms — the rows of
+     * sixteen blocks' pairs no longer shared the L2 as well. Round 6: with the work queue split by XCD (wq_grab_split: an XCD's waves
+     * work through one contiguous eighth of the processing order) 12 / 14 / 16: 22.7 / 20.8 / 19.8 ms — all sixteen) */
+    if (short_rows) *cap = 16;
+    return short_rows ? verify_flat_kernel<5, 0, true> : verify_flat_kernel<8, 0, true>;
+}
+static void verify_launch(disco_ctx *c, const VerifyArgs &va, u64 nq, int mode, bool flat, bool inexact)
+{
+    int cap = 0;
+    const VerifyFn k = verify_pick(c, mode, flat, inexact, &cap);
+    wq_launch(c, k, nq, "DISCO_VERIFY_WAVES", cap, va);
+}
+
+/* which instantiation selects the edges — the ONLY place that names the template arguments of edge_select_flat_kernel /
+ * edge_select_kernel. big: the rows of the big-row list, one per grab; flat: the hits of several reads as one flat list; small: its
+ * variant with five waves per SIMD */
+typedef void (*EdgeSelFn)(EdgeSelArgs);
+/* sub-chunks of up to 4 rows / 4 batches: 9.7 KB of LDS, 16 waves per CU. Larger ones fill their last batch better and repeat the
+ * per-sub-chunk work less often (8 rows: 140 instead of 175 vector instructions per read) but hold 11 waves per CU, and the kernel's
+ * time follows the resident waves (LDS round trips between its phases): 8 x 4: 25.4 ms, 4 x 4: 19.2 ms at 50 M reads */
+/* (round 6: sub-chunks of 4 rows x 3 batches — 16.35 against 17.1 ms with 3 x 2; in round 5 that shape spilled three registers with the
+ * sequential path compiled in, the branch-free load pipeline made room; 4 x 4, 5 x 3 and 5 x 4 still spill 12 / 3 / 17) */
+#ifndef SEL_SMALL_ROWS
+#define SEL_SMALL_ROWS 4
+#define SEL_SMALL_NB 3
+#endif
+static EdgeSelFn edge_select_pick(bool big, bool flat, bool small)
+{
+    if (big) return edge_select_kernel<true>;
+    if (flat) return small ? edge_select_flat_kernel<SEL_SMALL_ROWS, SEL_SMALL_NB, true> : edge_select_flat_kernel<4, 4>;
+    return edge_select_kernel<false>;
+}
+
+/* which instantiation marks the transitive edges — the ONLY place that names the template arguments of transitive_mark_kernel.
+ * big: the nodes of the big-node list (hash tables in global scratch); defer: the multi-rank kernel (a node short of a row waits for the
+ * request-all round; its first pass always with the small arrays); small: LDS arrays for TR_CAP_SMALL neighbours (eight waves per
+ * SIMD); lists: the survivor lists are the result */
+typedef void (*TrFn)(TrArgs);
+static TrFn tr_pick(bool big, bool defer, bool small, bool lists)
+{
+    if (big) return defer ? transitive_mark_kernel<true, true> : transitive_mark_kernel<true, false>;
+    if (defer) return lists ? transitive_mark_kernel<false, true, TR_CAP_SMALL, true> : transitive_mark_kernel<false, true, TR_CAP_SMALL>;
+#if defined(TR_EXP_DEFER_SINGLE) /* timing experiment: the multi-rank variant of the kernel on one GPU's nodes */
+    if (small) return transitive_mark_kernel<false, true, TR_CAP_SMALL>;
+#else
+    if (small) return lists ? transitive_mark_kernel<false, false, TR_CAP_SMALL, true> : transitive_mark_kernel<false, false, TR_CAP_SMALL>;
+#endif
+    return transitive_mark_kernel<false, false>;
+}
+
+/* the fields of TrArgs both marking drivers fill alike, after the big-node list has its size; c->use_half: the survivor lists and the
+ * list of wide nodes, cleared (order and all_flags are the caller's) */
+static int tr_args_begin(disco_ctx *c, TrArgs *a)
+{
+    a->v = view(c);
+    a->ref = c->d_adj_ref;
+    a->adj = c->d_adj;
+    a->big_list = c->d_big_list;
+    a->n_big = c->d_n_big;
+    a->big_cap = c->d_big_list.cap;
+    a->scratch = nullptr;
+    a->hcap = 0;
+    a->half = nullptr;
+    a->hcnt = nullptr;
+    if (c->use_half) {
+        CHK(ensure(c, c->d_half, c->n * HALF_CAP));
+        CHK(ensure(c, c->d_hcnt, c->n));
+        HIPCHK(c, hipMemsetAsync(c->d_hcnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
+        CHK(ensure(c, c->d_wide, std::min<u64>(c->n, c->n / 32 + 4096)));
+        CHK(ensure(c, c->d_n_wide, 1));
+        HIPCHK(c, hipMemsetAsync(c->d_n_wide, 0, sizeof(u32), c->stream));
+        a->half = c->d_half;
+        a->hcnt = c->d_hcnt;
+    }
+    a->wide_list = c->d_wide;
+    a->n_wide = c->d_n_wide;
+    a->wide_cap = c->d_wide.cap;
+    return DISCO_OK;
+}
+
+/* the big-node pass of the marking: the n_big nodes of big_list through hash tables in global scratch. It may raise CTR_OVERFLOW (read
+ * back here: the caller says what that means) */
+static int tr_big_nodes(disco_ctx *c, TrArgs *a, u32 n_big, bool defer, const char *what)
+{
+    /* longest list among the big nodes bounds the hash size: one reduction on the device, one read-back */
+    CHK(zero_counter(c, CTR_MAX_DEG));
+    hipLaunchKernelGGL(list_max_degree_kernel, dim3(flat_grid(c, n_big)), dim3(256), 0, c->stream, c->d_big_list, (u64)n_big, c->d_adj_ref, c->d_ctr + CTR_MAX_DEG);
+    HIPCHK(c, hipGetLastError());
+    CHK(read_counters(c));
+    const u64 maxd = c->h_ctr[CTR_MAX_DEG];
+    u64 hcap = 64;
+    while (hcap < 2 * maxd) hcap <<= 1;
+    const int g2 = (int)std::min<u64>(n_big, (u64)c->n_cu * 8);
+    const u64 per = hcap * 8 + hcap * 4 + hcap;
+    DevBuf<u8> scratch;
+    CHK(ensure(c, scratch, (u64)g2 * per));
+    a->scratch = (u64 *)scratch.p;
+    a->hcap = hcap;
+    a->adj = c->d_adj; /* (multi-rank: the array may have moved — adj_tail_reserve) */
+    HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
+    hipLaunchKernelGGL(tr_pick(true, defer, false, false), dim3(g2), dim3(64), 0, c->stream, *a);
+    const hipError_t e = hipGetLastError();
+    const int rc = read_counters(c); /* synchronises; the scratch goes back before anything is reported */
+    release(c, scratch);
+    if (e != hipSuccess) return fail(c, DISCO_E_HIP, "transitive_mark_kernel (%s): %s", what, hipGetErrorString(e));
+    return rc;
 }
 
 static int dist_mark_contained(disco_ctx *c); /* multi-GPU flow, below */
@@ -1587,7 +1804,7 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
                 HIPCHK(c, hipEventRecord(c->ev_copied[b], c->copy_stream));
                 HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied[b], 0));
             }
-            if (eager) CHK(c->binned_index ? (index_count_chunk<false>(c, v, pl, c->d_rec, lo, hi)) : (index_count_chunk<true>(c, v, pl, c->d_rec, lo, hi)));
+            if (eager) CHK(index_count_chunk(c, v, pl, !c->binned_index, c->d_rec, lo, hi));
         }
         HIPCHK(c, hipGetLastError());
         t_issued = lapms();
@@ -2460,21 +2677,8 @@ int disco_build_index(disco_ctx *c)
         const DiscoView v = view(c);
         IndexCountPlan pl;
         CHK(index_count_plan(c, v, 0, c->n, &pl));
-        CHK(c->binned_index ? index_count_chunk<false>(c, v, pl, c->d_rec, 0, c->n) : index_count_chunk<true>(c, v, pl, c->d_rec, 0, c->n));
-        if (c->two_class) { /* the long reads' records, keys and slots, from their full rows */
-            const dim3 g((unsigned)((c->n_long + 255) / 256));
-#define DISCO_LONG_LAUNCH(COUNT_, LONGK_) \
-    hipLaunchKernelGGL((index_count_kernel<COUNT_, LONGK_, true>), g, dim3(256), 0, c->stream, v, c->d_bkt, c->d_rec, c->d_okey, (u64)0, c->n_long, pl.ocnt, pl.oslot, pl.oshift)
-            if (c->binned_index) {
-                if (c->k > 64) DISCO_LONG_LAUNCH(false, true);
-                else DISCO_LONG_LAUNCH(false, false);
-            } else {
-                if (c->k > 64) DISCO_LONG_LAUNCH(true, true);
-                else DISCO_LONG_LAUNCH(true, false);
-            }
-#undef DISCO_LONG_LAUNCH
-            HIPCHK(c, hipGetLastError());
-        }
+        CHK(index_count_chunk(c, v, pl, !c->binned_index, c->d_rec, 0, c->n));
+        if (c->two_class) CHK(index_count_long(c, v, pl, !c->binned_index, c->d_rec, pl.oslot, 0, c->n_long));
     }
     const bool binned = c->binned_index; /* (index_begin's decision, whoever counted) */
     if (!binned) CHK((scan_exclusive<u32, u32>(c, c->d_bkt, c->T + 1, c->d_bkt, false, nullptr)));
@@ -2522,49 +2726,14 @@ int disco_probe(disco_ctx *c)
     CHK(ensure(c, c->d_row_cnt, c->n));
     if (c->n_alloc) hipLaunchKernelGGL(fill_u64_kernel, dim3(flat_grid(c, c->n_alloc)), dim3(256), 0, c->stream, c->d_best, c->n_alloc, DISCO_NOKEY);
     HIPCHK(c, hipMemsetAsync(c->d_row_cnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
-    const bool ldsrow = c->S <= PROBE_ACAP; /* (two classes of rows: c->S = 8; the lists' kernels take the long class's stride into account: launch_probe) */
-    const bool row17 = c->k - view(c).m == 16 && !getenv("DISCO_NO_ROW17"); /* window = 17 m-mers: DPP row-scan variant */
-    const bool longk = c->k > 64;                                            /* three-word k-mers: variants of their own (kmer_is_rev) */
     /* the index pass left the minimizer runs of the whole query range: probe_runs_kernel (several reads per wavefront, starts at the
      * bucket lookups); probe_kernel then only does the reads it is handed (unusable run lists, rows that outgrew their chunk) */
     const bool use_runs = c->runs_lpr != 0 && c->d_runs && c->q_lo >= c->runs_lo && c->q_hi <= c->runs_lo + c->runs_n;
-    const int grid = use_runs ? (c->runs_lpr == 16 ? wq_grid(c, probe_runs_kernel<16>, nq, "DISCO_PROBE_WAVES") : wq_grid(c, probe_runs_kernel<32>, nq, "DISCO_PROBE_WAVES"))
-                     : longk  ? (ldsrow ? wq_grid(c, probe_kernel<0, true, false, true>, nq, "DISCO_PROBE_WAVES") : wq_grid(c, probe_kernel<0, false, false, true>, nq, "DISCO_PROBE_WAVES"))
-                     : row17  ? (ldsrow ? wq_grid(c, probe_kernel<0, true, true>, nq, "DISCO_PROBE_WAVES") : wq_grid(c, probe_kernel<0, false, true>, nq, "DISCO_PROBE_WAVES"))
-                              : (ldsrow ? wq_grid(c, probe_kernel<0, true, false>, nq, "DISCO_PROBE_WAVES") : wq_grid(c, probe_kernel<0, false, false>, nq, "DISCO_PROBE_WAVES"));
-    /* mode 0: the query range, 1: big_list (rows of known size), 2: slow_list */
-    auto launch_probe = [&](const ProbeArgs &a, int mode, int g) {
-#define DISCO_PROBE_LAUNCH(B, L, R) hipLaunchKernelGGL((probe_kernel<B, L, R>), dim3(g), dim3(64), 0, c->stream, a)
-#define DISCO_PROBE_LAUNCH_LONG(B, L) hipLaunchKernelGGL((probe_kernel<B, L, false, true>), dim3(g), dim3(64), 0, c->stream, a)
-#define DISCO_PROBE_MODE(B)                                                                      \
-    do {                                                                                         \
-        if (longk) { if (ldsrow) DISCO_PROBE_LAUNCH_LONG(B, true); else DISCO_PROBE_LAUNCH_LONG(B, false); }     \
-        else if (ldsrow) { if (row17) DISCO_PROBE_LAUNCH(B, true, true); else DISCO_PROBE_LAUNCH(B, true, false); }   \
-        else { if (row17) DISCO_PROBE_LAUNCH(B, false, true); else DISCO_PROBE_LAUNCH(B, false, false); }        \
-    } while (0)
-        if (mode != 0 && c->two_class && c->S_ext > PROBE_ACAP) { /* the long class does not fit the LDS row: the lists' reads from global memory */
-#define DISCO_PROBE_LAUNCH_CLASS(B)                                                                                                            \
-    do {                                                                                                                                        \
-        if (longk) hipLaunchKernelGGL((probe_kernel<B, false, false, true, true>), dim3(g), dim3(64), 0, c->stream, a);                        \
-        else if (row17) hipLaunchKernelGGL((probe_kernel<B, false, true, false, true>), dim3(g), dim3(64), 0, c->stream, a);                   \
-        else hipLaunchKernelGGL((probe_kernel<B, false, false, false, true>), dim3(g), dim3(64), 0, c->stream, a);                             \
-    } while (0)
-            if (mode == 1) DISCO_PROBE_LAUNCH_CLASS(1);
-            else DISCO_PROBE_LAUNCH_CLASS(2);
-#undef DISCO_PROBE_LAUNCH_CLASS
-        } else if (mode == 0 && use_runs) {
-            if (c->runs_lpr == 16) hipLaunchKernelGGL(probe_runs_kernel<16>, dim3(g), dim3(64), 0, c->stream, a, (const u32 *)c->d_runs, c->runs_by_pos ? ~0ull : c->runs_lo);
-            else hipLaunchKernelGGL(probe_runs_kernel<32>, dim3(g), dim3(64), 0, c->stream, a, (const u32 *)c->d_runs, c->runs_by_pos ? ~0ull : c->runs_lo);
-        } else if (mode == 0) DISCO_PROBE_MODE(0);
-        else if (mode == 1) DISCO_PROBE_MODE(1);
-        else { /* slow_list only exists next to probe_runs_kernel: 64-byte rows */
-            if (longk) DISCO_PROBE_LAUNCH_LONG(2, true);
-            else if (row17) DISCO_PROBE_LAUNCH(2, true, true);
-            else DISCO_PROBE_LAUNCH(2, true, false);
-        }
-#undef DISCO_PROBE_LAUNCH_LONG
-#undef DISCO_PROBE_MODE
-#undef DISCO_PROBE_LAUNCH
+    const ProbeKernel range_kernel = probe_pick(c, 0, use_runs);
+    const int grid = range_kernel.runs ? wq_grid(c, range_kernel.runs, nq, "DISCO_PROBE_WAVES") : wq_grid(c, range_kernel.plain, nq, "DISCO_PROBE_WAVES");
+    auto launch_probe = [&](const ProbeArgs &a, const ProbeKernel &k, int g) {
+        if (k.runs) hipLaunchKernelGGL(k.runs, dim3(g), dim3(64), 0, c->stream, a, (const u32 *)c->d_runs, c->runs_by_pos ? ~0ull : c->runs_lo);
+        else hipLaunchKernelGGL(k.plain, dim3(g), dim3(64), 0, c->stream, a);
     };
     const u64 chunk_slots = use_runs ? PR_CHUNK : PROBE_CHUNK;
     u64 want_hits = nq * 64 + (u64)grid * chunk_slots + (1u << 16);
@@ -2655,7 +2824,7 @@ int disco_probe(disco_ctx *c)
         const bool partitioned = c->dist_active && c->part_index; /* the lookups travel to the buckets' owners (collective) */
         if (partitioned) CHK(dist_partitioned_probe(c));
         else if (nq) {
-            launch_probe(a, 0, grid);
+            launch_probe(a, range_kernel, grid);
         }
         ph_end(c, DISCO_PH_PROBE_KERNEL);
         HIPCHK(c, hipGetLastError());
@@ -2669,7 +2838,7 @@ int disco_probe(disco_ctx *c)
         if (!c->h_ctr[CTR_OVERFLOW] && n_slow) { /* reads without a usable run list, the long way (they may add big rows) */
             int g2 = wave_grid(c, (n_slow + WQ_CHUNK - 1) / WQ_CHUNK, 24);
             HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
-            launch_probe(a, 2, g2);
+            launch_probe(a, probe_pick(c, 2, false), g2);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(&n_big, c->d_n_big, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
             CHK(read_counters(c));
@@ -2678,7 +2847,7 @@ int disco_probe(disco_ctx *c)
         if (!c->h_ctr[CTR_OVERFLOW] && n_big) {
             int g2 = wave_grid(c, (n_big + WQ_CHUNK - 1) / WQ_CHUNK, 8);
             HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
-            launch_probe(a, 1, g2);
+            launch_probe(a, probe_pick(c, 1, false), g2);
             HIPCHK(c, hipGetLastError());
             CHK(read_counters(c));
         }
@@ -2718,14 +2887,7 @@ int disco_probe(disco_ctx *c)
                 CHK(ensure(c, c->d_contained, c->n_alloc));
                 CHK(ensure(c, c->d_cbits, c->n_alloc / 64 + 1));
                 va.cbits = c->d_cbits;
-                const bool short_rows = c->max_len <= 160;
-                if (nq && flat) {
-                    if (short_rows) hipLaunchKernelGGL((verify_flat_kernel<5, 1>), dim3(wq_grid(c, verify_flat_kernel<5, 1>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                    else hipLaunchKernelGGL((verify_flat_kernel<8, 1>), dim3(wq_grid(c, verify_flat_kernel<8, 1>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                } else if (nq) {
-                    if (short_rows) hipLaunchKernelGGL((verify_kernel<5, 1>), dim3(wq_grid(c, verify_kernel<5, 1>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                    else hipLaunchKernelGGL((verify_kernel<8, 1>), dim3(wq_grid(c, verify_kernel<8, 1>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                }
+                if (nq) verify_launch(c, va, nq, 1, flat, inexact);
                 if (c->dist_active) { /* the keys of other ranks' containing reads count too: exchange, then the flags (collective) */
                     CHK(dist_mark_contained(c));
                     c->contained_done = true;
@@ -2733,47 +2895,13 @@ int disco_probe(disco_ctx *c)
                     CHK(zero_counter(c, CTR_N_CONTAINED));
                     hipLaunchKernelGGL(contain_flags_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_best, c->n, c->d_contained, c->d_cbits, c->d_ctr);
                 }
-                if (nq && flat) {
-                    if (short_rows) hipLaunchKernelGGL((verify_flat_kernel<5, 2>), dim3(wq_grid(c, verify_flat_kernel<5, 2>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                    else hipLaunchKernelGGL((verify_flat_kernel<8, 2>), dim3(wq_grid(c, verify_flat_kernel<8, 2>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                } else if (nq) {
-                    if (short_rows) hipLaunchKernelGGL((verify_kernel<5, 2>), dim3(wq_grid(c, verify_kernel<5, 2>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                    else hipLaunchKernelGGL((verify_kernel<8, 2>), dim3(wq_grid(c, verify_kernel<8, 2>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                }
-            } else if (nq && inexact) {
-                va.cbits = nullptr;
-#define VERIFY_INEXACT(NW) hipLaunchKernelGGL((verify_kernel<NW, 0, true>), dim3(wq_grid(c, verify_kernel<NW, 0, true>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va)
-                if (c->S == VERIFY_SW && c->max_len <= 160) VERIFY_INEXACT(5);
-                else if (c->S == VERIFY_SW) VERIFY_INEXACT(8);
-                else if (c->S == 16) VERIFY_INEXACT(16);
-                else if (c->S == 24) VERIFY_INEXACT(24);
-                else if (c->S == 32) VERIFY_INEXACT(32);
-                else VERIFY_INEXACT(0);
-#undef VERIFY_INEXACT
+                if (nq) verify_launch(c, va, nq, 2, flat, inexact);
             } else if (nq) {
                 va.cbits = nullptr;
-                /* pairs of batches share their row fetches (verify_flat_kernel<·, 0, true>): 21.5 against 22.6 ms and 18 GB less traffic at config 3
-                 * (reads of up to 160 bases); 32.3 against 33.0–35.1 ms on 50 M reads of 100–250 bases, 72.9 against 76.3 with config 5's
-                 * abundances (256-base rows, 15 KB of LDS per wavefront). DISCO_VERIFY_CACHE=0 forbids it */
-                const char *vce = getenv("DISCO_VERIFY_CACHE");
-                const bool vcache = vce ? atoi(vce) != 0 : true;
-                /* (round 5: 128 registers and 10 KB of LDS hold sixteen blocks per CU; 12 / 14 / 16 resident: 22.8 / 21.5 / 22.0 ms — the rows of
-                 * sixteen blocks' pairs no longer shared the L2 as well. Round 6: with the work queue split by XCD (wq_grab_split: an XCD's waves
-                 * work through one contiguous eighth of the processing order) 12 / 14 / 16: 22.7 / 20.8 / 19.8 ms — all sixteen) */
-                if (flat && vcache && c->max_len <= 160) hipLaunchKernelGGL((verify_flat_kernel<5, 0, true>), dim3(wq_grid(c, verify_flat_kernel<5, 0, true>, nq, "DISCO_VERIFY_WAVES", 16)), dim3(64), 0, c->stream, va);
-                else if (flat && vcache) hipLaunchKernelGGL((verify_flat_kernel<8, 0, true>), dim3(wq_grid(c, verify_flat_kernel<8, 0, true>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                else if (flat && c->max_len <= 160) hipLaunchKernelGGL(verify_flat_kernel<5>, dim3(wq_grid(c, verify_flat_kernel<5>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                else if (flat) hipLaunchKernelGGL(verify_flat_kernel<8>, dim3(wq_grid(c, verify_flat_kernel<8>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                else if (c->S == VERIFY_SW && c->max_len <= 160) hipLaunchKernelGGL(verify_kernel<5>, dim3(wq_grid(c, verify_kernel<5>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                else if (c->S == VERIFY_SW) hipLaunchKernelGGL(verify_kernel<8>, dim3(wq_grid(c, verify_kernel<8>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                else if (c->S == 16) hipLaunchKernelGGL(verify_kernel<16>, dim3(wq_grid(c, verify_kernel<16>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                else if (c->S == 24) hipLaunchKernelGGL(verify_kernel<24>, dim3(wq_grid(c, verify_kernel<24>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                else if (c->S == 32) hipLaunchKernelGGL(verify_kernel<32>, dim3(wq_grid(c, verify_kernel<32>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
-                else hipLaunchKernelGGL(verify_kernel<0>, dim3(wq_grid(c, verify_kernel<0>, nq, "DISCO_VERIFY_WAVES")), dim3(64), 0, c->stream, va);
+                verify_launch(c, va, nq, 0, flat, inexact);
             }
             if (c->two_class && nq)
-                hipLaunchKernelGGL(verify_long_kernel, dim3(wq_grid(c, verify_long_kernel, c->n_long * 16, "DISCO_VL_WAVES")), dim3(64), 0, c->stream, va, (const u32 *)c->d_lpos, (const ulonglong2 *)c->d_lmeta,
-                                   (const uint2 *)c->d_linfo, (const u32 *)c->d_n_list);
+                wq_launch(c, verify_long_kernel, c->n_long * 16, "DISCO_VL_WAVES", 32, va, (const u32 *)c->d_lpos, (const ulonglong2 *)c->d_lmeta, (const uint2 *)c->d_linfo, (const u32 *)c->d_n_list);
             ph_end(c, DISCO_PH_VERIFY);
             HIPCHK(c, hipGetLastError());
             CHK(read_counters(c));
@@ -2893,18 +3021,7 @@ static int select_edges(disco_ctx *c)
     ph_begin(c, DISCO_PH_SELECT);
     /* reads of up to 256 bases, exact overlaps: the hits of several reads as one flat list, full wavefronts (edge_select_flat_kernel) */
     const bool flat_select = c->S == VERIFY_SW && c->max_len <= 256 && !a.hidden_flags && a.max_per_kmer < 255u && !getenv("DISCO_NO_FLAT_SELECT");
-    /* sub-chunks of up to 4 rows / 4 batches: 9.7 KB of LDS, 16 waves per CU. Larger ones fill their last batch better and repeat the
-     * per-sub-chunk work less often (8 rows: 140 instead of 175 vector instructions per read) but hold 11 waves per CU, and the kernel's
-     * time follows the resident waves (LDS round trips between its phases): 8 x 4: 25.4 ms, 4 x 4: 19.2 ms at 50 M reads */
-    /* (round 6: sub-chunks of 4 rows x 3 batches — 16.35 against 17.1 ms with 3 x 2; in round 5 that shape spilled three registers with the
-     * sequential path compiled in, the branch-free load pipeline made room; 4 x 4, 5 x 3 and 5 x 4 still spill 12 / 3 / 17) */
-#ifndef SEL_SMALL_ROWS
-#define SEL_SMALL_ROWS 4
-#define SEL_SMALL_NB 3
-#endif
-    if (nq && flat_select && select_small) hipLaunchKernelGGL((edge_select_flat_kernel<SEL_SMALL_ROWS, SEL_SMALL_NB, true>), dim3(wq_grid(c, edge_select_flat_kernel<SEL_SMALL_ROWS, SEL_SMALL_NB, true>, nq, "DISCO_SELECT_WAVES")), dim3(64), 0, c->stream, a);
-    else if (nq && flat_select) hipLaunchKernelGGL((edge_select_flat_kernel<4, 4>), dim3(wq_grid(c, edge_select_flat_kernel<4, 4>, nq, "DISCO_SELECT_WAVES")), dim3(64), 0, c->stream, a);
-    else if (nq) hipLaunchKernelGGL(edge_select_kernel<false>, dim3(wq_grid(c, edge_select_kernel<false>, nq, "DISCO_SELECT_WAVES")), dim3(64), 0, c->stream, a);
+    if (nq) wq_launch(c, edge_select_pick(false, flat_select, select_small), nq, "DISCO_SELECT_WAVES", 32, a);
     ph_end(c, DISCO_PH_SELECT);
     HIPCHK(c, hipGetLastError());
     u32 n_big = 0;
@@ -2932,11 +3049,11 @@ static int select_edges(disco_ctx *c)
         a.scratch = scratch;
         a.scratch_cap = cap;
         HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
-        hipLaunchKernelGGL(edge_select_kernel<true>, dim3(g2), dim3(64), 0, c->stream, a);
+        hipLaunchKernelGGL(edge_select_pick(true, false, false), dim3(g2), dim3(64), 0, c->stream, a);
         hipError_t e = hipGetLastError();
         int rc = read_counters(c);
         release(c, scratch);
-        if (e != hipSuccess) return fail(c, DISCO_E_HIP, "edge_select_kernel<true>: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(c, DISCO_E_HIP, "edge_select_kernel (big rows): %s", hipGetErrorString(e));
         CHK(rc);
     }
     c->dropped = c->dropped_local = c->h_ctr[CTR_DROPPED];
@@ -3282,43 +3399,15 @@ int disco_transitive_mark(disco_ctx *c)
         CHK(grow_big_lists(c, need));
     } else
         CHK(ensure_big_cap(c, nullptr, c->d_adj_ref, TR_CAP));
-    TrArgs a;
-    a.v = view(c);
-    a.ref = c->d_adj_ref;
-    a.adj = c->d_adj;
-    a.big_list = c->d_big_list;
-    a.n_big = c->d_n_big;
-    a.big_cap = c->d_big_list.cap;
-    a.scratch = nullptr;
-    a.hcap = 0;
-    a.half = nullptr;
-    a.hcnt = nullptr;
     c->use_half = !getenv("DISCO_NO_HALF");
-    if (c->use_half) {
-        CHK(ensure(c, c->d_half, c->n * HALF_CAP));
-        CHK(ensure(c, c->d_hcnt, c->n));
-        HIPCHK(c, hipMemsetAsync(c->d_hcnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
-        CHK(ensure(c, c->d_wide, std::min<u64>(c->n, c->n / 32 + 4096)));
-        CHK(ensure(c, c->d_n_wide, 1));
-        HIPCHK(c, hipMemsetAsync(c->d_n_wide, 0, sizeof(u32), c->stream));
-        a.half = c->d_half;
-        a.hcnt = c->d_hcnt;
-    }
-    a.wide_list = c->d_wide;
-    a.n_wide = c->d_n_wide;
-    a.wide_cap = c->d_wide.cap;
+    TrArgs a;
+    CHK(tr_args_begin(c, &a));
     a.order = (c->d_order_used && c->order_q_lo == c->q_lo && c->order_q_hi == c->q_hi && !c->adj_imported && !getenv("DISCO_TR_NO_ORDER")) ? c->d_order_used : nullptr;
     /* every row needs its flags when the emission cannot rely on the survivor lists alone */
     a.all_flags = (c->adj_imported || !c->use_half || c->q_lo != 0 || c->q_hi != c->n) ? 1u : 0u;
     ph_begin(c, DISCO_PH_TRMARK);
     const bool lists = a.half && a.hcnt && !a.all_flags; /* the survivor lists are the result: the variant compiled for it */
-#if defined(TR_EXP_DEFER_SINGLE) /* timing experiment: the multi-rank variant of the kernel on one GPU's nodes */
-    if (nq && tr_small) hipLaunchKernelGGL((transitive_mark_kernel<false, true, TR_CAP_SMALL>), dim3(wq_grid(c, transitive_mark_kernel<false, true, TR_CAP_SMALL>, nq, "DISCO_TR_WAVES")), dim3(64), 0, c->stream, a);
-#else
-    if (nq && tr_small && lists) hipLaunchKernelGGL((transitive_mark_kernel<false, false, TR_CAP_SMALL, true>), dim3(wq_grid(c, transitive_mark_kernel<false, false, TR_CAP_SMALL, true>, nq, "DISCO_TR_WAVES")), dim3(64), 0, c->stream, a);
-    else if (nq && tr_small) hipLaunchKernelGGL((transitive_mark_kernel<false, false, TR_CAP_SMALL>), dim3(wq_grid(c, transitive_mark_kernel<false, false, TR_CAP_SMALL>, nq, "DISCO_TR_WAVES")), dim3(64), 0, c->stream, a);
-#endif
-    else if (nq) hipLaunchKernelGGL((transitive_mark_kernel<false, false>), dim3(wq_grid(c, transitive_mark_kernel<false, false>, nq, "DISCO_TR_WAVES")), dim3(64), 0, c->stream, a);
+    if (nq) wq_launch(c, tr_pick(false, false, tr_small, lists), nq, "DISCO_TR_WAVES", 32, a);
     ph_end(c, DISCO_PH_TRMARK);
     HIPCHK(c, hipGetLastError());
     u32 n_big = 0;
@@ -3329,27 +3418,7 @@ int disco_transitive_mark(disco_ctx *c)
     ph_collect(c);
     if (c->h_ctr[CTR_OVERFLOW]) return fail(c, DISCO_E_CAPACITY, "transitive marking: big-node list overflow (%u nodes)", n_big);
     if (n_big) {
-        /* longest list among the big nodes bounds the hash size: one reduction on the device, one read-back */
-        CHK(zero_counter(c, CTR_MAX_DEG));
-        hipLaunchKernelGGL(list_max_degree_kernel, dim3(flat_grid(c, n_big)), dim3(256), 0, c->stream, c->d_big_list, (u64)n_big, c->d_adj_ref, c->d_ctr + CTR_MAX_DEG);
-        HIPCHK(c, hipGetLastError());
-        CHK(read_counters(c));
-        const u64 maxd = c->h_ctr[CTR_MAX_DEG];
-        u64 hcap = 64;
-        while (hcap < 2 * maxd) hcap <<= 1;
-        int g2 = (int)std::min<u64>(n_big, (u64)c->n_cu * 8);
-        u64 per = hcap * 8 + hcap * 4 + hcap;
-        DevBuf<u8> scratch;
-        CHK(ensure(c, scratch, (u64)g2 * per));
-        a.scratch = (u64 *)scratch.p;
-        a.hcap = hcap;
-        HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
-        hipLaunchKernelGGL((transitive_mark_kernel<true, false>), dim3(g2), dim3(64), 0, c->stream, a);
-        hipError_t e = hipGetLastError();
-        const int rc2 = read_counters(c); /* synchronises; the big pass may have raised CTR_OVERFLOW */
-        release(c, scratch);
-        if (e != hipSuccess) return fail(c, DISCO_E_HIP, "transitive_mark_kernel (big nodes): %s", hipGetErrorString(e));
-        CHK(rc2);
+        CHK(tr_big_nodes(c, &a, n_big, false, "big nodes"));
         if (c->h_ctr[CTR_OVERFLOW]) return fail(c, DISCO_E_CAPACITY, "transitive marking (big nodes): list overflow");
     }
     if (n_big && c->use_half) HIPCHK(c, hipMemcpy(&c->n_wide, c->d_n_wide, sizeof(u32), hipMemcpyDeviceToHost));
@@ -4523,80 +4592,14 @@ static int dist_deal_reads(disco_ctx *c)
     return DISCO_OK;
 }
 
-/* the count pass of the index over the own list (ranks own loci): records and minimizer runs by POSITION in the processing order */
-static int index_count_own_list(disco_ctx *c, const DiscoView &v, ulonglong2 *rec)
-{
-    const u64 n_own = c->n_own;
-    const int nf = v.k - v.m + 1;
-    c->runs_lpr = 0;
-    c->runs_n = 0;
-    c->runs_by_pos = false;
-    const int lpr = c->S == VERIFY_SW ? runs_lpr_for(c, nf, c->max_len, n_own) : 0;
-    if (!n_own) return DISCO_OK;
-    const dim3 grid((unsigned)((n_own + 255) / 256));
-    const u64 *list = c->d_order_own;
-    if (lpr) {
-        CHK(ensure(c, c->d_runs, n_own * (u64)lpr));
-        c->runs_lpr = lpr;
-        c->runs_lo = 0;
-        c->runs_n = n_own;
-        c->runs_by_pos = true;
-#define DISCO_RUNS_LAUNCH(NF_)                                                                                                                              \
-    do {                                                                                                                                                  \
-        if (lpr == 16) hipLaunchKernelGGL((index_runs_kernel<false, NF_, 1>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, (u32 *)nullptr, (u64)0, n_own, c->d_runs, (u32 *)nullptr, (u32 *)nullptr, 0u, list); \
-        else hipLaunchKernelGGL((index_runs_kernel<false, NF_, 2>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, (u32 *)nullptr, (u64)0, n_own, c->d_runs, (u32 *)nullptr, (u32 *)nullptr, 0u, list);             \
-    } while (0)
-#define DISCO_RUNS_LAUNCH_RT(NFMAX_, LONGK_)                                                                                                                 \
-    do {                                                                                                                                                  \
-        if (lpr == 16) hipLaunchKernelGGL((index_runs_kernel<false, 0, 1, NFMAX_, LONGK_>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, (u32 *)nullptr, (u64)0, n_own, c->d_runs, (u32 *)nullptr, (u32 *)nullptr, 0u, list); \
-        else hipLaunchKernelGGL((index_runs_kernel<false, 0, 2, NFMAX_, LONGK_>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, (u32 *)nullptr, (u64)0, n_own, c->d_runs, (u32 *)nullptr, (u32 *)nullptr, 0u, list);             \
-    } while (0)
-        const bool built = v.m == RUNS_M && (nf == 7 || nf == 12 || nf == 17 || nf == 22 || nf == 27);
-        if (!built) {
-            if (c->k > 64) {
-                if (nf <= 48) DISCO_RUNS_LAUNCH_RT(48, true);
-                else DISCO_RUNS_LAUNCH_RT(64, true);
-            } else if (nf <= 8) DISCO_RUNS_LAUNCH_RT(8, false);
-            else if (nf <= 12) DISCO_RUNS_LAUNCH_RT(12, false);
-            else if (nf <= 16) DISCO_RUNS_LAUNCH_RT(16, false);
-            else if (nf <= 24) DISCO_RUNS_LAUNCH_RT(24, false);
-            else if (nf <= 32) DISCO_RUNS_LAUNCH_RT(32, false);
-            else if (nf <= 48) DISCO_RUNS_LAUNCH_RT(48, false);
-            else DISCO_RUNS_LAUNCH_RT(64, false);
-        } else
-            switch (nf) {
-            case 7: DISCO_RUNS_LAUNCH(7); break;
-            case 12: DISCO_RUNS_LAUNCH(12); break;
-            case 17: DISCO_RUNS_LAUNCH(17); break;
-            case 22: DISCO_RUNS_LAUNCH(22); break;
-            default: DISCO_RUNS_LAUNCH(27); break;
-            }
-#undef DISCO_RUNS_LAUNCH
-#undef DISCO_RUNS_LAUNCH_RT
-    } else if (c->k > 64)
-        hipLaunchKernelGGL((index_count_kernel<false, true>), grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, (u32 *)nullptr, (u64)0, n_own, (u32 *)nullptr, (u32 *)nullptr, 0u, list);
-    else
-        hipLaunchKernelGGL(index_count_kernel<false>, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, (u32 *)nullptr, (u64)0, n_own, (u32 *)nullptr, (u32 *)nullptr, 0u, list);
-    HIPCHK(c, hipGetLastError());
-    return DISCO_OK;
-}
-
 /* ---- 1. hash-partitioned index build ------------------------------------------------------------------------------- */
 static int dist_build_index(disco_ctx *c)
 {
     DISCO_TRACE("dist_build_index");
     const u32 G = (u32)c->comm->world, r = (u32)c->comm->rank;
     const u64 nloc = c->q_hi - c->q_lo;
-    u64 T = 1024;
-    int logT = 10;
-    double tscale = 2.0;
-    if (const char *e = getenv("DISCO_BUCKET_SCALE")) tscale = atof(e);
-    while ((double)T < tscale * (double)c->n && logT < 32) {
-        T <<= 1;
-        logT++;
-    }
-    c->T = T;
-    c->bshift = 64 - logT;
+    const int logT = size_bucket_table(c);
+    const u64 T = c->T;
     auto blo_of = [&](u64 g) { return (g * T + G - 1) / G; };
     const u64 blo = blo_of(r), bhi = blo_of(r + 1);
     const bool part = c->part_index;
@@ -4609,11 +4612,13 @@ static int dist_build_index(disco_ctx *c)
     c->adj_imported = false;
     ph_begin(c, DISCO_PH_INDEX);
     DiscoView v = view(c);
-    if (c->loci) CHK(index_count_own_list(c, v, c->d_rec));
-    else {
-        IndexCountPlan pl;
+    IndexCountPlan pl;
+    if (c->loci) { /* the own list: records and minimizer runs by POSITION in the processing order */
+        CHK(index_count_plan(c, v, 0, c->n_own, &pl, c->d_order_own));
+        CHK(index_count_chunk(c, v, pl, false, c->d_rec, 0, c->n_own));
+    } else {
         CHK(index_count_plan(c, v, c->q_lo, c->q_hi, &pl));
-        CHK(index_count_chunk<false>(c, v, pl, c->d_rec, c->q_lo, c->q_hi));
+        CHK(index_count_chunk(c, v, pl, false, c->d_rec, c->q_lo, c->q_hi));
         if (c->two_class && nloc) {
             /* the long reads of the rank's range — long_ids is ascending, ovf[i] counts the long reads in front of read i: they are the
              * x in [ovf[q_lo], ovf[q_hi]) — from their full rows; records by read id from q_lo (the kernel indexes rec by read id) */
@@ -4622,12 +4627,9 @@ static int dist_build_index(disco_ctx *c)
             if (c->q_hi < c->n) HIPCHK(c, hipMemcpyAsync(&xb[1], c->d_ovf + c->q_hi, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (xb[1] > xb[0]) {
-                const dim3 g((unsigned)((xb[1] - xb[0] + 255) / 256));
                 ulonglong2 *rec_by_id = c->d_rec - 2 * (ptrdiff_t)c->q_lo; /* rec_by_id[2 i] = the record of read i (never touched outside [q_lo, q_hi)) */
                 u32 *oslot_by_id = pl.oslot ? pl.oslot - (ptrdiff_t)c->q_lo : nullptr; /* (the grouping's slots: by read id too) */
-                if (c->k > 64) hipLaunchKernelGGL((index_count_kernel<false, true, true>), g, dim3(256), 0, c->stream, v, c->d_bkt, rec_by_id, c->d_okey, (u64)xb[0], (u64)xb[1], pl.ocnt, oslot_by_id, pl.oshift);
-                else hipLaunchKernelGGL((index_count_kernel<false, false, true>), g, dim3(256), 0, c->stream, v, c->d_bkt, rec_by_id, c->d_okey, (u64)xb[0], (u64)xb[1], pl.ocnt, oslot_by_id, pl.oshift);
-                HIPCHK(c, hipGetLastError());
+                CHK(index_count_long(c, v, pl, false, rec_by_id, oslot_by_id, xb[0], xb[1]));
             }
         }
     }
@@ -5019,28 +5021,10 @@ static int dist_transitive_mark(disco_ctx *c)
     const u64 need_big = nloc + 1024;
     CHK(grow_big_lists(c, need_big));
     HIPCHK(c, hipMemsetAsync(c->d_n_big, 0, sizeof(u32), c->stream));
-    TrArgs a;
-    a.v = view(c);
-    a.order = c->loci ? c->d_order_own : nullptr; /* (ranks own loci: the own nodes are the list, in the processing order of probe / verify / selection) */
-    a.ref = c->d_adj_ref;
-    a.adj = c->d_adj;
-    a.big_list = c->d_big_list;
-    a.n_big = c->d_n_big;
-    a.big_cap = c->d_big_list.cap;
-    a.scratch = nullptr;
-    a.hcap = 0;
     c->use_half = true;
-    CHK(ensure(c, c->d_half, c->n * HALF_CAP));
-    CHK(ensure(c, c->d_hcnt, c->n));
-    HIPCHK(c, hipMemsetAsync(c->d_hcnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
-    CHK(ensure(c, c->d_wide, std::min<u64>(c->n, c->n / 32 + 4096)));
-    CHK(ensure(c, c->d_n_wide, 1));
-    HIPCHK(c, hipMemsetAsync(c->d_n_wide, 0, sizeof(u32), c->stream));
-    a.half = c->d_half;
-    a.hcnt = c->d_hcnt;
-    a.wide_list = c->d_wide;
-    a.n_wide = c->d_n_wide;
-    a.wide_cap = c->d_wide.cap;
+    TrArgs a;
+    CHK(tr_args_begin(c, &a));
+    a.order = c->loci ? c->d_order_own : nullptr; /* (ranks own loci: the own nodes are the list, in the processing order of probe / verify / selection) */
     /* the transitive flags go into the rows of nodes with more than HALF_CAP survivors only, as on one GPU: everybody who judges an edge
      * — the local emission, the survivor push and its receiver — reads a narrow node's survivor LIST and a wide node's row, never a narrow
      * node's row (rounds 1-4 wrote every flag here: a quarter of this kernel's memory requests, left over from the flag exchange the
@@ -5048,8 +5032,7 @@ static int dist_transitive_mark(disco_ctx *c)
     a.all_flags = getenv("DISCO_DIST_ALL_FLAGS") ? 1u : 0u;
     ph_begin(c, DISCO_PH_TRMARK);
     /* (every node beyond the register path waits for the request-all round here, whatever the LDS arrays could hold: the small variant) */
-    if (nloc && !a.all_flags) hipLaunchKernelGGL((transitive_mark_kernel<false, true, TR_CAP_SMALL, true>), dim3(wq_grid(c, transitive_mark_kernel<false, true, TR_CAP_SMALL, true>, nloc, "DISCO_TR_WAVES")), dim3(64), 0, c->stream, a);
-    else if (nloc) hipLaunchKernelGGL((transitive_mark_kernel<false, true, TR_CAP_SMALL>), dim3(wq_grid(c, transitive_mark_kernel<false, true, TR_CAP_SMALL>, nloc, "DISCO_TR_WAVES")), dim3(64), 0, c->stream, a);
+    if (nloc) wq_launch(c, tr_pick(false, true, true, !a.all_flags), nloc, "DISCO_TR_WAVES", 32, a);
     ph_end(c, DISCO_PH_TRMARK);
     HIPCHK(c, hipGetLastError());
     u32 n_big = 0;
@@ -5062,7 +5045,7 @@ static int dist_transitive_mark(disco_ctx *c)
     c->dinfo.tr_deferred = any;
     if (any) { /* round 2 (collective): the listed nodes ask for every row they lack, then take the generic path */
         c->dinfo.tr_rounds = 2;
-        u64 bound = 0, maxd = 0;
+        u64 bound = 0;
         HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
         if (n_big) hipLaunchKernelGGL(list_degree_sum_kernel, dim3(flat_grid(c, n_big)), dim3(256), 0, c->stream, c->d_big_list, (u64)n_big, c->d_adj_ref, c->d_list_n);
         HIPCHK(c, hipMemcpyAsync(&bound, c->d_list_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
@@ -5076,26 +5059,7 @@ static int dist_transitive_mark(disco_ctx *c)
         if (c->h_ctr[CTR_OVERFLOW]) return fail(c, DISCO_E_CAPACITY, "row requests (round 2): list overflow");
         CHK(dist_fetch_rows(c, n_flat));
         if (n_big) {
-            CHK(zero_counter(c, CTR_MAX_DEG));
-            hipLaunchKernelGGL(list_max_degree_kernel, dim3(flat_grid(c, n_big)), dim3(256), 0, c->stream, c->d_big_list, (u64)n_big, c->d_adj_ref, c->d_ctr + CTR_MAX_DEG);
-            CHK(read_counters(c));
-            maxd = c->h_ctr[CTR_MAX_DEG];
-            u64 hcap = 64;
-            while (hcap < 2 * maxd) hcap <<= 1;
-            const int g2 = (int)std::min<u64>(n_big, (u64)c->n_cu * 8);
-            const u64 perb = hcap * 8 + hcap * 4 + hcap;
-            DevBuf<u8> scratch;
-            CHK(ensure(c, scratch, (u64)g2 * perb));
-            a.scratch = (u64 *)scratch.p;
-            a.hcap = hcap;
-            a.adj = c->d_adj; /* the array may have moved (adj_tail_reserve) */
-            HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
-            hipLaunchKernelGGL((transitive_mark_kernel<true, true>), dim3(g2), dim3(64), 0, c->stream, a);
-            hipError_t e = hipGetLastError();
-            int rc = read_counters(c);
-            release(c, scratch);
-            if (e != hipSuccess) return fail(c, DISCO_E_HIP, "transitive_mark_kernel (second round): %s", hipGetErrorString(e));
-            CHK(rc);
+            CHK(tr_big_nodes(c, &a, n_big, true, "second round"));
             if (c->h_ctr[CTR_OVERFLOW]) return fail(c, DISCO_E_STATE, "transitive marking: a row was still missing after the request-all round");
         }
     }

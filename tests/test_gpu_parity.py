@@ -260,6 +260,39 @@ def test_probe_window_minimum_variants_agree(monkeypatch):
         assert_parity(_gen(seed, n, lmin, cov, lmax), 40, f"lds-{seed}")
 
 
+def test_fall_back_kernel_choices_agree(monkeypatch):
+    """every fall-back knob is parity-tested in both positions. These knobs pick another instantiation of the
+    verify / selection / probe / index kernels (the host's kernel selectors own exactly these branches); each must give the oracle's graph
+    on rows of at most 160 bases (the NW = 5 kernels) and on mixed lengths with heavy containment (NW = 8). The oracle runs once per
+    read set; every run is held to what assert_parity holds it to."""
+    from tests.util import run_hip_reads
+
+    def check(reads, want, label, **kw):
+        oe, orows, oc = want
+        he, hr, hc = run_hip_reads(reads, 40, **kw)
+        (ce, cc), (oce, occ) = canon_hip(he, hr), canon_hip(oe, orows)
+        assert np.array_equal(cc, occ), f"{label}: contained rows differ ({len(cc)} vs {len(occ)})"
+        assert np.array_equal(ce, oce), f"{label}: edge list differs ({len(ce)} vs {len(oce)})"
+        for key in ("probes", "n_contained", "e_pre", "e_out", "cap_bind_sites", "asymmetric_pairs"):
+            assert hc[key] == oc[key], f"{label}: counter {key}: hip {hc[key]} oracle {oc[key]}"
+        if kw:  # two passes: contained query reads are skipped by the second one, the counter counts what was compared
+            assert 0 < hc["kmer_hits"] <= oc["kmer_hits"], label
+        else:
+            assert hc["kmer_hits"] == oc["kmer_hits"], f"{label}: counter kmer_hits: hip {hc['kmer_hits']} oracle {oc['kmer_hits']}"
+
+    knobs = (("DISCO_NO_FLAT_VERIFY", "1"), ("DISCO_VERIFY_CACHE", "0"), ("DISCO_NO_FLAT_SELECT", "1"), ("DISCO_NO_RUNS", "1"))
+    for name, reads in (("short", _gen(42, 5000, 150, 30.0, 150)), ("mixed", _gen(7, 4000, 100, 30.0, 250))):
+        want = run_oracle_reads(reads, 40)
+        for var, val in knobs:
+            monkeypatch.setenv(var, val)
+            check(reads, want, f"{name} {var}={val}")
+            monkeypatch.delenv(var)
+        if name == "mixed":  # verify_kernel<8, 1> and <8, 2>
+            monkeypatch.setenv("DISCO_NO_FLAT_VERIFY", "1")
+            check(reads, want, "mixed DISCO_NO_FLAT_VERIFY=1, two passes", flags=buildgraph.FLAG_TWO_PASS_VERIFY)
+            monkeypatch.delenv("DISCO_NO_FLAT_VERIFY")
+
+
 def test_caller_supplied_order_changes_nothing():
     """disco_set_query_order: any permutation of the query range (plain read ids) gives the same graph"""
     import torch

@@ -146,6 +146,22 @@ class DistInfo(C.Structure):
 
 PHASES = ("index", "probe_kernel", "verify", "contain", "select", "csr", "twin", "trmark", "emit", "order")
 
+# include/disco_hip_inspect.h: looks at intermediate state for tests; bound on first use, not by load()
+INSPECT_ABI = [
+    ("disco_fetch_order", C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+]
+_inspect_bound = False
+
+
+def _bind_inspect(L):
+    global _inspect_bound
+    if not _inspect_bound:
+        for name, res, args in INSPECT_ABI:
+            fn = getattr(L, name)  # AttributeError if the library does not export it
+            fn.restype = res
+            fn.argtypes = args
+        _inspect_bound = True
+
 
 def lib_path() -> str:
     return _LIBPATH
@@ -441,6 +457,19 @@ class BuildGraph:
     def probe_run_words(self) -> int:
         """32-bit words of minimizer runs per read the last index build left for the probe (16 / 32), or 0: round 2's probe"""
         return int(self.L.disco_probe_run_words(self._h))
+
+    def fetch_order(self):
+        """(order words, keys, order bits) of the grouping the last build_index made — read id | length << 32 in processing order, the reads'
+        grouping keys by read id, log2 of the bucket count; raises where that index build made no order. Tests only"""
+        _bind_inspect(self.L)
+        n, bits = C.c_uint64(0), C.c_int(0)
+        one = np.zeros(1, dtype=np.uint64)
+        rc = self.L.disco_fetch_order(self._h, one.ctypes.data, one.ctypes.data, 0, C.byref(n), C.byref(bits))  # (no room: the size)
+        if n.value == 0:
+            self._chk(rc)
+        order, keys = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros(max(n.value, 1), dtype=np.uint32)
+        self._chk(self.L.disco_fetch_order(self._h, order.ctypes.data, keys.ctypes.data, len(order), C.byref(n), C.byref(bits)))
+        return order[:n.value], keys[:n.value], bits.value
 
     def measure_hbm(self, nbytes: int = 4 << 30, reps: int = 5) -> float:
         """attainable HBM bandwidth in GB/s (read + write bytes of a streaming copy kernel)"""

@@ -36,6 +36,7 @@
 
 #include "../../include/disco_hip.h"
 #include "../../include/disco_hip_test.h"
+#include "../../include/disco_hip_inspect.h"
 #include "disco_kernels.h"
 #include "disco_dist.h"
 
@@ -254,6 +255,8 @@ struct disco_ctx {
     /* the grouping's counting pass ran inside the index pass, for the reads [lo, hi) with 2^bits buckets (d_ocnt holds the counts,
      * d_oslot the slots): the next disco_probe over exactly that range skips its own */
     bool order_counted = false;
+    bool order_items = false; /* ... as items for the partition levels (d_rec2; the binned grouping): only disco_build_index can finish it */
+    int order_id_bits = 0;    /* (bits of the read id in an item) */
     /* the big-item lists are sized from counts the producing kernels leave behind (verify: rows beyond ES_CAP; edge selection: nodes
      * beyond TR_CAP) — valid until something else changes the rows: then the counting pass (ensure_big_cap) runs as before */
     bool es_big_counted = false, tr_big_counted = false;
@@ -844,6 +847,7 @@ static bool own_order_wanted(const disco_ctx *c, u64 nq, int *bits)
     const u64 order_min = getenv("DISCO_ORDER_MIN_READS") ? (u64)atoll(getenv("DISCO_ORDER_MIN_READS")) : 4096; /* tests: 1 */
     int b = 16;
     while (b < 27 && (1ull << b) < nq) ++b;
+    if (const char *e = getenv("DISCO_ORDER_BITS")) b = std::min(std::max(atoi(e), 16), 26); /* tests: two partition levels on a small set */
     *bits = b;
     return !c->order_external && !getenv("DISCO_NO_ORDER") && nq >= order_min && nq > 0;
 }
@@ -855,6 +859,8 @@ struct IndexCountPlan {
     u64 lo = 0, hi = 0;
     int lpr = 0, nf = 0;
     u32 *ocnt = nullptr, *oslot = nullptr;
+    u64 *oitem = nullptr; /* the binned grouping: an item per read instead of a count and a slot */
+    u32 oidbits = 0;
     u32 oshift = 0;
     const u64 *list = nullptr; /* ranks own loci: position x of [lo, hi) stands for read ORDER_ID(list[x]) (records, runs, slots by position) */
 };
@@ -898,6 +904,32 @@ static bool two_class_ok(const disco_ctx *c, int S, u64 n, u64 n_long, u32 short
 static int two_class_alloc(disco_ctx *c, u64 n_long, int Sx, u32 short_max);
 
 /* (list: the own list of a rank that owns loci, [lo, hi) = its positions — it IS the processing order: no grouping to count) */
+/* does the grouping of the whole range go through the partition levels (binned_build_order)? Where the ordered path finishes the
+ * grouping inside disco_build_index: one class of rows, no list. DISCO_NO_BINNED_ORDER=1: the counting atomics, the scan of the counter
+ * table and the scatter, as before. An item is ONE word — bucket | length | read id (ORDER_ITEM) — so the three must fit: 26 + 8 + 26 bits
+ * at 5 x 10^7 reads of 150 bases, and up to 2^28 reads of up to 256 bases; what does not fit keeps the counting form. The items and the
+ * other side of their ping-pong are two stretches of d_rec2, which is idle until the record build starts: where it cannot be had, the
+ * old path. *id_bits: bits of the read id in an item */
+static bool binned_order_wanted(disco_ctx *c, u64 n, int obits, int *id_bits)
+{
+    if (getenv("DISCO_NO_BINNED_ORDER") || getenv("DISCO_NO_ORDERED_FILL") || c->two_class || n != c->n || n >= 0xFFFF0000ull) return false;
+    /* size policy: the chain is nine launches where the old path has five — index + order at 1 M reads 0.31 ms against 0.26 on the old path,
+     * at 3 M 0.77 against 0.84, at 10 M 2.33 against 2.65 (profiles/binned_order_ab.txt): from 2^21 reads up (tests: 1) */
+    const u64 binned_min = getenv("DISCO_BINNED_ORDER_MIN_READS") ? (u64)atoll(getenv("DISCO_BINNED_ORDER_MIN_READS")) : (1ull << 21);
+    if (n < binned_min) return false;
+    int idb = 1, lenb = 1;
+    while ((1ull << idb) < n) ++idb;
+    while ((1u << lenb) <= c->max_len) ++lenb;
+    if (obits + lenb + idb > 64) return false;
+    if (ensure(c, c->d_rec2, n) != DISCO_OK) { /* (n two-word records = 2 n items) */
+        (void)hipGetLastError();
+        c->err.clear();
+        return false;
+    }
+    *id_bits = idb;
+    return true;
+}
+
 static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, IndexCountPlan *pl, const u64 *list = nullptr)
 {
     const u64 nloc = hi - lo;
@@ -906,15 +938,21 @@ static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, In
     pl->hi = hi;
     pl->list = list;
     /* the counting pass of the grouping rides along when the indexed range is the query range (always, unless a caller narrows it) */
-    if (!list) c->order_counted = c->order_ready = false;
+    if (!list) c->order_counted = c->order_ready = c->order_items = false;
     int obits = 0;
     if (!list && lo == c->q_lo && hi == c->q_hi && own_order_wanted(c, nloc, &obits) && !getenv("DISCO_NO_ORDER_FUSE")) {
         const u64 order_buckets = 1ull << obits;
-        CHK(ensure(c, c->d_ocnt, order_buckets + 1));
-        CHK(ensure(c, c->d_oslot, nloc));
-        HIPCHK(c, hipMemsetAsync(c->d_ocnt, 0, (order_buckets + 1) * sizeof(u32), c->stream));
-        pl->ocnt = c->d_ocnt;
-        pl->oslot = c->d_oslot;
+        if (lo == 0 && binned_order_wanted(c, nloc, obits, &c->order_id_bits)) {
+            pl->oitem = (u64 *)c->d_rec2.p;
+            pl->oidbits = (u32)c->order_id_bits;
+            c->order_items = true;
+        } else {
+            CHK(ensure(c, c->d_ocnt, order_buckets + 1));
+            CHK(ensure(c, c->d_oslot, nloc));
+            HIPCHK(c, hipMemsetAsync(c->d_ocnt, 0, (order_buckets + 1) * sizeof(u32), c->stream));
+            pl->ocnt = c->d_ocnt;
+            pl->oslot = c->d_oslot;
+        }
         pl->oshift = 32u - (u32)obits;
         c->order_counted = true;
         c->order_counted_lo = lo;
@@ -941,8 +979,8 @@ static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, In
 /* which instantiation counts this shape — the ONLY place that names the template arguments of index_runs_kernel / index_count_kernel.
  * lpr != 0: with the minimizer runs (16 / 32 words per read: NL 1 / 2), a window of nf m-mers; long_class: the long reads of two row
  * classes, from their full rows (never with runs) */
-typedef void (*IndexRunsFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u32 *, u32, const u64 *);
-typedef void (*IndexCountFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u32, const u64 *);
+typedef void (*IndexRunsFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u32 *, u64 *, u32, u32, const u64 *);
+typedef void (*IndexCountFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u64 *, u32, u32, const u64 *);
 struct IndexCountKernel {
     IndexRunsFn runs = nullptr; /* one of the two */
     IndexCountFn plain = nullptr;
@@ -995,10 +1033,11 @@ static int index_count_chunk(disco_ctx *c, const DiscoView &v, const IndexCountP
     const dim3 grid((unsigned)((b - a + 255) / 256));
     ulonglong2 *rec = rec_base + 2 * (a - pl.lo);
     u32 *oslot = pl.oslot ? pl.oslot + (a - pl.lo) : nullptr;
+    u64 *oitem = pl.oitem ? pl.oitem + (a - pl.lo) : nullptr; /* (at the read's global position, whichever chunk brings it) */
     u32 *okey = pl.list ? nullptr : c->d_okey.p; /* (a list: the keys were made when the reads were dealt, by read id) */
     const IndexCountKernel k = index_count_pick(count, pl.nf, v.m, pl.lpr, c->k > 64, false);
-    if (k.runs) hipLaunchKernelGGL(k.runs, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, c->d_runs + (a - pl.lo) * (u64)pl.lpr, pl.ocnt, oslot, pl.oshift, pl.list);
-    else hipLaunchKernelGGL(k.plain, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, pl.ocnt, oslot, pl.oshift, pl.list);
+    if (k.runs) hipLaunchKernelGGL(k.runs, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, c->d_runs + (a - pl.lo) * (u64)pl.lpr, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.list);
+    else hipLaunchKernelGGL(k.plain, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.list);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
 }
@@ -1008,7 +1047,7 @@ static int index_count_chunk(disco_ctx *c, const DiscoView &v, const IndexCountP
 static int index_count_long(disco_ctx *c, const DiscoView &v, const IndexCountPlan &pl, bool count, ulonglong2 *rec, u32 *oslot, u64 x_lo, u64 x_hi)
 {
     const dim3 g((unsigned)((x_hi - x_lo + 255) / 256));
-    hipLaunchKernelGGL(index_count_pick(count, 0, v.m, 0, c->k > 64, true).plain, g, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, x_lo, x_hi, pl.ocnt, oslot, pl.oshift,
+    hipLaunchKernelGGL(index_count_pick(count, 0, v.m, 0, c->k > 64, true).plain, g, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, x_lo, x_hi, pl.ocnt, oslot, (u64 *)nullptr, 0u, pl.oshift,
                        (const u64 *)nullptr);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
@@ -1081,14 +1120,14 @@ static BinxPlan binx_plan(int logT)
     return b;
 }
 
-/* records rec[0 .. 2n) = {bucket << 32, payload} of the count pass (COUNT = false) -> bkt[0 .. T], ent[0 .. 2n): see "binned index build"
- * in disco_kernels.h */
-static int binned_build_index(disco_ctx *c)
+/* the partition levels over rec[0 .. total), records {bucket << 32, payload} or one-word items, whose key word holds a bucket of `bits` bits
+ * from bit kshift up (see "binned index build" in disco_kernels.h): src and dst are the two sides of the ping-pong; *out = the side the
+ * partitions end up in, *part = their starts (n_part + 1 words in d_binx) */
+template <typename R>
+static int binx_partition(disco_ctx *c, const char *what, int bits, u32 kshift, u32 total, R *src, R *dst, const R **out, const u32 **part)
 {
-    const int logT = 64 - c->bshift;
-    const BinxPlan bp = binx_plan(logT);
-    const u32 total = (u32)(2 * c->n);
-    const u32 n_part = 1u << (logT - bp.span);
+    const BinxPlan bp = binx_plan(bits);
+    const u32 n_part = 1u << (bits - bp.span);
     const u32 tiles = (total + BINX_TILE - 1u) / BINX_TILE;
     /* d_binx: seg / tb of the level at work and of the one before (n_part + 1 words each at the most), then the counts */
     u64 hist_len = 1;
@@ -1097,20 +1136,18 @@ static int binned_build_index(disco_ctx *c)
     CHK(ensure(c, c->d_binx, 4 * tab + hist_len));
     u32 *seg[2] = {c->d_binx.p, c->d_binx.p + tab}, *tb[2] = {c->d_binx.p + 2 * tab, c->d_binx.p + 3 * tab}, *hist = c->d_binx.p + 4 * tab;
     if (getenv("DISCO_VERBOSE"))
-        fprintf(stderr, "[disco] binned index build: 2^%d buckets, %u partitions of 2^%d, %d level(s) of %d / %d / %d bits\n", logT, n_part, bp.span, bp.levels, bp.bits[0], bp.bits[1], bp.bits[2]);
-    ulonglong2 *src = c->d_rec, *dst = c->d_rec2;
+        fprintf(stderr, "[disco] binned %s: 2^%d buckets, %u partitions of 2^%d, %d level(s) of %d / %d / %d bits\n", what, bits, n_part, bp.span, bp.levels, bp.bits[0], bp.bits[1], bp.bits[2]);
     u32 pseg = 1, pnb = 1;
     int cur = 0, done = 0;
     for (int l = 0; l < bp.levels; l++) {
-        const u32 nseg = 1u << done, nb = 1u << bp.bits[l], shift = (u32)(logT - done - bp.bits[l]);
+        const u32 nseg = 1u << done, nb = 1u << bp.bits[l], shift = kshift + (u32)(bits - done - bp.bits[l]);
         const u32 grid = tiles + nseg;
         const u64 hlen = (u64)grid * nb + 1;
         hipLaunchKernelGGL(binx_segs_kernel, dim3(1), dim3(1024), 0, c->stream, l ? (const u32 *)hist : (const u32 *)nullptr, (const u32 *)tb[cur ^ 1], pseg, pnb, total, seg[cur], tb[cur]);
         HIPCHK(c, hipMemsetAsync(hist, 0, hlen * sizeof(u32), c->stream));
-        hipLaunchKernelGGL(binx_hist_kernel, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const ulonglong2 *)src, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb, hist);
+        hipLaunchKernelGGL(binx_hist_kernel<R>, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const R *)src, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb, hist);
         CHK((scan_exclusive<u32, u32>(c, hist, hlen, hist, false, nullptr)));
-        hipLaunchKernelGGL(binx_scatter_kernel, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const ulonglong2 *)src, dst, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb,
-                           (const u32 *)hist);
+        hipLaunchKernelGGL(binx_scatter_kernel<R>, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const R *)src, dst, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb, (const u32 *)hist);
         HIPCHK(c, hipGetLastError());
         std::swap(src, dst);
         pseg = nseg;
@@ -1121,7 +1158,40 @@ static int binned_build_index(disco_ctx *c)
     /* the partitions' starts: the segments the last level made (no level: the one partition) */
     hipLaunchKernelGGL(binx_segs_kernel, dim3(1), dim3(1024), 0, c->stream, bp.levels ? (const u32 *)hist : (const u32 *)nullptr, (const u32 *)tb[cur ^ 1], pseg, pnb, total, seg[cur],
                        (u32 *)nullptr);
-    hipLaunchKernelGGL(binx_build_kernel, dim3(n_part), dim3(BINX_BUILD_BLOCK), 0, c->stream, (const ulonglong2 *)src, (const u32 *)seg[cur], (u32)bp.span, total, c->T, c->d_bkt.p, c->d_ent.p);
+    HIPCHK(c, hipGetLastError());
+    *out = src;
+    *part = seg[cur];
+    return DISCO_OK;
+}
+
+/* records rec[0 .. 2n) = {bucket << 32, payload} of the count pass (COUNT = false) -> bkt[0 .. T], ent[0 .. 2n) */
+static int binned_build_index(disco_ctx *c)
+{
+    const int logT = 64 - c->bshift;
+    const u32 total = (u32)(2 * c->n);
+    const ulonglong2 *rec;
+    const u32 *part;
+    CHK(binx_partition(c, "index build", logT, 32u, total, c->d_rec.p, c->d_rec2.p, &rec, &part));
+    const int span = std::min(logT, BINX_SPAN_BITS);
+    hipLaunchKernelGGL(binx_build_kernel<ulonglong2>, dim3(1u << (logT - span)), dim3(BINX_BUILD_BLOCK), 0, c->stream, rec, part, (u32)span, 32u, 0u, total, c->T, c->d_bkt.p, c->d_ent.p);
+    HIPCHK(c, hipGetLastError());
+    return DISCO_OK;
+}
+
+/* the binned grouping: the one-word items (ORDER_ITEM) the count pass left at the start of d_rec2, one per read, -> d_order_own, the reads
+ * of equal bucket back to back. The same levels and the same build kernel as the index (the order has no bucket table); the n words
+ * behind the items are the other side of the ping-pong. Runs before the record build takes d_rec2. */
+static int binned_build_order(disco_ctx *c)
+{
+    const int bits = c->order_counted_bits;
+    const u32 total = (u32)c->n, kshift = 64u - (u32)bits;
+    u64 *items = (u64 *)c->d_rec2.p;
+    const u64 *rec;
+    const u32 *part;
+    CHK(binx_partition(c, "grouping", bits, kshift, total, items, items + c->n, &rec, &part));
+    const int span = std::min(bits, BINX_SPAN_BITS);
+    hipLaunchKernelGGL(binx_build_kernel<u64>, dim3(1u << (bits - span)), dim3(BINX_BUILD_BLOCK), 0, c->stream, rec, part, (u32)span, kshift, (u32)c->order_id_bits, total, (u64)0,
+                       (u32 *)nullptr, c->d_order_own.p);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
 }
@@ -2690,8 +2760,11 @@ int disco_build_index(disco_ctx *c)
         CHK(ensure(c, c->d_order_own, c->n));
         ph_end(c, DISCO_PH_INDEX);
         ph_begin(c, DISCO_PH_ORDER);
-        CHK((scan_exclusive<u32, u32>(c, c->d_ocnt, order_buckets + 1, c->d_ocnt, false, nullptr)));
-        hipLaunchKernelGGL(order_scatter_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_okey, c->d_oslot, c->d_ocnt, 32u - (u32)c->order_counted_bits, (u64)0, c->n, c->d_len, c->d_order_own);
+        if (c->order_items) CHK(binned_build_order(c));
+        else {
+            CHK((scan_exclusive<u32, u32>(c, c->d_ocnt, order_buckets + 1, c->d_ocnt, false, nullptr)));
+            hipLaunchKernelGGL(order_scatter_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_okey, c->d_oslot, c->d_ocnt, 32u - (u32)c->order_counted_bits, (u64)0, c->n, c->d_len, c->d_order_own);
+        }
         ph_end(c, DISCO_PH_ORDER);
         ph_begin(c, DISCO_PH_INDEX2);
         if (binned) CHK(binned_build_index(c)); /* (streams the records: no use for the order) */
@@ -2787,7 +2860,9 @@ int disco_probe(disco_ctx *c)
         a.order = nullptr;
         const u64 order_buckets = 1ull << order_bits;
         /* the index pass counted already (once: a retry of this loop finds the counters scanned and counts again) */
-        const bool counted = c->order_counted && c->order_counted_lo == c->q_lo && c->order_counted_hi == c->q_hi && c->order_counted_bits == order_bits;
+        /* (counted as items: no counts or slots to go on from — disco_build_index has finished that grouping, or it is made here) */
+        const bool counted = c->order_counted && c->order_counted_lo == c->q_lo && c->order_counted_hi == c->q_hi && c->order_counted_bits == order_bits &&
+                             (!c->order_items || c->order_ready);
         c->order_counted = false;
         if (c->loci) { /* the own list IS the processing order (grouped when the reads were dealt: dist_build_index) */
             c->d_order_used = c->d_order_own;
@@ -5386,6 +5461,21 @@ int disco_comm_init_local(disco_ctx *const *ctxs, int nranks)
 }
 
 int disco_probe_run_words(const disco_ctx *c) { return c ? c->runs_lpr : 0; }
+
+/* tests: the processing order the last disco_build_index made (ORDER_MAKE words, n of them) and the reads' grouping keys (by read id) */
+int disco_fetch_order(disco_ctx *c, uint64_t *order_words, uint32_t *keys, uint64_t cap, uint64_t *n, int *order_bits)
+{
+    if (!c || !order_words || !keys || !n || !order_bits) return DISCO_E_ARG;
+    if (!c->order_ready || !c->d_order_own || !c->d_okey) return fail(c, DISCO_E_STATE, "disco_fetch_order: disco_build_index made no order");
+    *n = c->n;
+    *order_bits = c->order_counted_bits;
+    if (cap < c->n) return fail(c, DISCO_E_ARG, "disco_fetch_order: room for %llu reads, %llu needed", (unsigned long long)cap, (unsigned long long)c->n);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(order_words, c->d_order_own, c->n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(keys, c->d_okey, c->n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DISCO_OK;
+}
 int disco_comm_rank(const disco_ctx *c) { return (c && c->comm) ? c->comm->rank : 0; }
 int disco_comm_world(const disco_ctx *c) { return (c && c->comm) ? c->comm->world : 1; }
 const char *disco_comm_kind(const disco_ctx *c) { return (c && c->comm) ? c->comm->kind() : "none"; }

@@ -89,6 +89,9 @@ enum {
 #define ORDER_MAKE(id, l) ((u64)(id) | ((u64)(l) << 32))
 #define ORDER_ID(o) ((o) & 0xFFFFFFFFull)
 #define ORDER_LEN(o) ((int)((o) >> 32))
+/* a read's item of the binned grouping, one word: order bucket (its 32 - shift bits on top) | length << idbits | read id — the host
+ * takes this form only where the three fit (binned_order_wanted) */
+#define ORDER_ITEM(key, shift, id, l, idbits) (((u64)ORDER_BUCKET(key, shift) << (32u + (shift))) | ((u64)(l) << (idbits)) | (u64)(id))
 /* the first active lane's value as a SCALAR: a value broadcast by a cross-lane shuffle is divergent to the compiler, and with it every
  * loop bound, branch and address derived from it (counters in vector registers, exec-mask loops, saveexec around uniform branches) */
 __device__ __forceinline__ u32 uniform_u32(u32 x) { return (u32)__builtin_amdgcn_readfirstlane((int)x); }
@@ -315,7 +318,8 @@ __global__ void validate_len_kernel(const u16 *__restrict__ len, u64 n, int S, i
  * records, slots and keys are indexed by position */
 template <bool COUNT, bool LONGK = false, bool LONGCLASS = false>
 __global__ void __launch_bounds__(256) index_count_kernel(DiscoView v, u32 *__restrict__ bkt, ulonglong2 *__restrict__ rec, u32 *__restrict__ okey, u64 lo, u64 hi,
-                                                          u32 *__restrict__ ocnt, u32 *__restrict__ oslot, u32 oshift, const u64 *__restrict__ list = nullptr)
+                                                          u32 *__restrict__ ocnt, u32 *__restrict__ oslot, u64 *__restrict__ oitem, u32 oidbits, u32 oshift,
+                                                          const u64 *__restrict__ list = nullptr)
 {
     /* rec[2i], rec[2i+1] = {bucket << 32 | slot inside the bucket, record} of the prefix / suffix k-mer of read i: the slot is
      * what the counting atomic returns, so the fill pass needs no second round of atomics */
@@ -370,7 +374,9 @@ __global__ void __launch_bounds__(256) index_count_kernel(DiscoView v, u32 *__re
         k2s = min(k2s, o + ((u32)(63 - (q - sfx0)) << 1));
     }
     if (okey) okey[i] = best;
-    if (ocnt) oslot[i - lo] = atomicAdd(&ocnt[ORDER_BUCKET(best, oshift)], 1u); /* the grouping's counting pass (order_count_kernel), fused */
+    /* the grouping: the read's item for the partition levels (binned grouping: no atomic, no slot), or the counting pass, fused */
+    if (oitem) oitem[i - lo] = ORDER_ITEM(best, oshift, rid, L, oidbits);
+    else if (ocnt) oslot[i - lo] = atomicAdd(&ocnt[ORDER_BUCKET(best, oshift)], 1u);
     auto resolve = [&](u32 k1, u32 k2, int j0, u32 &t, u32 &rev) {
         const int ffirst = (int)((k1 >> 1) & 63u), flast = 63 - (int)((k2 >> 1) & 63u);
         int fsel = ffirst;
@@ -399,6 +405,10 @@ __global__ void __launch_bounds__(256) index_count_kernel(DiscoView v, u32 *__re
 #define RUNS_M 23 /* minimizer length of the specialised instantiations (disco_minimizer_len gives 23 for every k from 23 to 86) */
 /* M = 0: the length is a run-time value (17 .. 31: k above 86 takes minimizers of up to 31 bases) — the mask and the place of the entering
  * complement are then scalar operands of the same instructions, and the fold of order_hash32 takes its third product */
+template <bool B>
+struct FlagConst { /* a constant flag for a generic lambda */
+    static constexpr bool value = B;
+};
 template <int M>
 struct MmerRoll {
     static_assert(M == 0 || (M > 16 && M <= 24 && (M & 1)), "two dwords, the high one partly used; a 24-bit fold in order_hash32<false>");
@@ -477,7 +487,8 @@ struct MmerRoll {
  * SCALAR test per position (every thread of the wavefront is at the same position of the same block), so the work follows nf, not NFMAX. */
 template <bool COUNT, int NF, int NL, int NFMAX = NF, bool LONGK = false>
 __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__restrict__ bkt, ulonglong2 *__restrict__ rec, u32 *__restrict__ okey, u64 lo, u64 hi,
-                                                         u32 *__restrict__ runs, u32 *__restrict__ ocnt, u32 *__restrict__ oslot, u32 oshift,
+                                                         u32 *__restrict__ runs, u32 *__restrict__ ocnt, u32 *__restrict__ oslot, u64 *__restrict__ oitem, u32 oidbits,
+                                                         u32 oshift,
                                                          const u64 *__restrict__ list = nullptr)
 {
     static_assert(NF == 0 || NF == NFMAX, "a specialised instantiation holds exactly its window");
@@ -493,9 +504,16 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
     /* two row classes: a long read is index_count_kernel's (from its full row); here it only tells the probe to take it the long way */
     const bool other_class = i < hi && v.full && v.len[rid] > DISCO_SHORT_MAX;
     if (other_class) s_runs[tid * CAP] = 0xFFFEu;
-    if (i < hi && !other_class) {
+    /* the fewest windows any read of the wavefront has (taken here, under full exec; a lane without a read stays out of it): the blocks
+     * every one of them walks in full need none of the per-lane tests against the read's end — see the two loops over the blocks below */
+    const bool mine = i < hi && !other_class;
+    const int L = mine ? (list ? ORDER_LEN(lw) : (int)v.len[rid]) : 0;
+    int npos_lo = mine ? L - v.k : 0x7FFFFFFF;
+    for (int o = 32; o; o >>= 1) npos_lo = min(npos_lo, __shfl_xor(npos_lo, o));
+    npos_lo = __builtin_amdgcn_readfirstlane(npos_lo);
+    if (mine) {
         const u64 *__restrict__ p = v.reads + rid * v.S;
-        const int L = list ? ORDER_LEN(lw) : (int)v.len[rid], k = v.k;
+        const int k = v.k;
         const int m = NF ? RUNS_M : v.m; /* (the host takes a specialised instantiation for m = RUNS_M only: runs_lpr_for) */
         const int nf = NF ? NF : k - m + 1; /* (wave uniform) */
         const int nmm = L - m + 1; /* m-mer positions */
@@ -516,9 +534,10 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
         u32 P1 = 0, P2 = 0;
         u32 *sx = s_x + tid;
         /* window w (wave uniform: every thread walks the same positions) with minima m1 / m2 over positions relative to `base`; tw = w - base */
-        auto window = [&](int w, u32 m1, u32 m2, int base, int tw) {
-            if (w <= npos) {
-                if (w == npos) { /* the suffix k-mer: its record; not one of the probe's windows. (Through LDS: as register values the three
+        /* inner (a constant): the block lies in front of every read's last windows — w < npos and q < nmm hold for the whole wavefront */
+        auto window = [&](auto inner, int w, u32 m1, u32 m2, int base, int tw) __attribute__((always_inline)) {
+            if (decltype(inner)::value || w <= npos) {
+                if (!decltype(inner)::value && w == npos) { /* the suffix k-mer: its record; not one of the probe's windows. (Through LDS: as register values the three
                                     would be merged with their old selves behind EVERY window — six copies per window and thread) */
                     sx[0] = m1;
                     sx[256] = m2;
@@ -541,10 +560,10 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
         };
         const int nblk = npos / nf + 2; /* window npos lies in block npos / nf and is complete once the next block has gone by */
         int q = 0;
-        for (int b = 0; b < nblk; ++b) {
+        auto block = [&](auto inner, int b) __attribute__((always_inline)) {
             const int base = (b - 1) * nf;
             lastm -= (u32)nf << 1;
-            if (b >= 1) window(base, s1[0], s2[0], base, 0); /* the window that IS block b - 1 */
+            if (b >= 1) window(inner, base, s1[0], s2[0], base, 0); /* the window that IS block b - 1 */
             if (b == 1) {
                 P1 = s1[0]; /* window 0: the prefix k-mer's record */
                 P2 = s2[0];
@@ -557,13 +576,13 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
                     /* past the read the order word is whatever the row holds there: never part of a window the probe uses, and kept out of the read's key */
                     roll.step();
                     const u32 h = roll.hash();
-                    best = min(best, q < nmm ? h : 0xFFFFFFFFu);
+                    best = min(best, decltype(inner)::value || q < nmm ? h : 0xFFFFFFFFu);
                     const u32 o = (h & ~0x1FFu) | roll.strand();
                     ++q;
                     hc[t] = o;
                     p1 = min(p1, o | ((u32)(nf + t) << 1));
                     p2 = min(p2, o | ((u32)(127 - (nf + t)) << 1));
-                    if (t + 1 < nf && b >= 1) window(base + t + 1, min(s1[t + 1 < NFMAX ? t + 1 : 0], p1), min(s2[t + 1 < NFMAX ? t + 1 : 0], p2), base, t + 1);
+                    if (t + 1 < nf && b >= 1) window(inner, base + t + 1, min(s1[t + 1 < NFMAX ? t + 1 : 0], p1), min(s2[t + 1 < NFMAX ? t + 1 : 0], p2), base, t + 1);
                 }
             }
             u32 a1 = 0xFFFFFFFFu, a2 = 0xFFFFFFFFu;
@@ -575,9 +594,17 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
                 s1[t] = a1;
                 s2[t] = a2;
             }
-        }
+        };
+        /* block b ends the windows up to b nf - 1 and the m-mers up to (b + 1) nf - 1 = b nf - 1 + (nmm - npos): with b nf <= npos for every
+         * read of the wavefront all of them lie inside the read and in front of window npos, and every lane is still in the loop
+         * (nblk > npos / nf + 1) — at 150 bases 7 blocks of 8. The rest, a read's last block or two, tests per lane. */
+        int b = 0;
+        for (const int inner_end = npos_lo / nf; b <= inner_end; ++b) block(FlagConst<true>(), b);
+        for (; b < nblk; ++b) block(FlagConst<false>(), b);
         if (okey) okey[i] = best;
-        if (ocnt) oslot[i - lo] = atomicAdd(&ocnt[ORDER_BUCKET(best, oshift)], 1u); /* the grouping's counting pass (order_count_kernel), fused */
+        /* the grouping: the read's item for the partition levels (binned grouping: no atomic, no slot), or the counting pass, fused */
+        if (oitem) oitem[i - lo] = ORDER_ITEM(best, oshift, rid, L, oidbits);
+        else if (ocnt) oslot[i - lo] = atomicAdd(&ocnt[ORDER_BUCKET(best, oshift)], 1u);
         if ((tie & ~1u) != 0 || cnt > (u32)CAP) my[0] = 0xFFFEu; /* (bit 0 of m1 ^ m2: the two strands of a tie may differ) */
         /* the two end k-mers' records: window_minimizer's rule on the minima of windows 0 and npos */
         auto resolve = [&](u32 k1, u32 k2, int wbase, int j0, u32 &t, u32 &rev) {
@@ -734,10 +761,15 @@ __device__ __forceinline__ bool binx_tile(const u32 *__restrict__ seg, const u32
     return true;
 }
 
-/* the digit of a level: bits [shift, shift + log2 nb) of the bucket */
-#define BINX_DIGIT(recx, shift, nb) ((u32)((recx) >> (32u + (shift))) & ((nb)-1u))
+/* what the kernels partition: the index's records {bucket << 32, payload}, or the grouping's one-word items (ORDER_ITEM); the key word
+ * holds the bucket from bit `kshift` up (records: 32) */
+__device__ __forceinline__ u64 binx_key(const ulonglong2 &r) { return r.x; }
+__device__ __forceinline__ u64 binx_key(u64 r) { return r; }
+/* the digit of a level: bits [shift, shift + log2 nb) of the key word (the host adds kshift) */
+#define BINX_DIGIT(key, shift, nb) ((u32)((key) >> (shift)) & ((nb)-1u))
 
-__global__ void __launch_bounds__(BINX_BLOCK) binx_hist_kernel(const ulonglong2 *__restrict__ rec, const u32 *__restrict__ seg, const u32 *__restrict__ tb, u32 nseg, u32 shift, u32 nb,
+template <typename R>
+__global__ void __launch_bounds__(BINX_BLOCK) binx_hist_kernel(const R *__restrict__ rec, const u32 *__restrict__ seg, const u32 *__restrict__ tb, u32 nseg, u32 shift, u32 nb,
                                                                u32 *__restrict__ hist)
 {
     __shared__ u32 s_h[1u << BINX_MAX_BITS];
@@ -745,32 +777,33 @@ __global__ void __launch_bounds__(BINX_BLOCK) binx_hist_kernel(const ulonglong2 
     if (!binx_tile(seg, tb, nseg, t0, nt, ti, lo, hi)) return;
     s_h[threadIdx.x] = 0;
     __syncthreads();
-    for (u32 i = lo + threadIdx.x; i < hi; i += BINX_BLOCK) atomicAdd(&s_h[BINX_DIGIT(rec[i].x, shift, nb)], 1u);
+    for (u32 i = lo + threadIdx.x; i < hi; i += BINX_BLOCK) atomicAdd(&s_h[BINX_DIGIT(binx_key(rec[i]), shift, nb)], 1u);
     __syncthreads();
     if (threadIdx.x < nb) hist[(u64)nb * t0 + (u64)threadIdx.x * nt + ti] = s_h[threadIdx.x];
 }
 
 /* a tile's records to their bins' places in dst: staged in LDS in bin order, written out as one run per bin */
-__global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const ulonglong2 *__restrict__ src, ulonglong2 *__restrict__ dst, const u32 *__restrict__ seg, const u32 *__restrict__ tb,
+template <typename R>
+__global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const R *__restrict__ src, R *__restrict__ dst, const u32 *__restrict__ seg, const u32 *__restrict__ tb,
                                                                   u32 nseg, u32 shift, u32 nb, const u32 *__restrict__ scan)
 {
     static_assert(BINX_BLOCK == (1u << BINX_MAX_BITS) && BINX_TILE % BINX_BLOCK == 0, "a thread per bin; whole rounds per tile");
     constexpr u32 PER = BINX_TILE / BINX_BLOCK;
-    __shared__ ulonglong2 s_rec[BINX_TILE];
+    __shared__ R s_rec[BINX_TILE];
     __shared__ u32 s_cnt[BINX_BLOCK], s_base[BINX_BLOCK], s_w[BINX_BLOCK / 64u];
     const u32 tid = threadIdx.x;
     u32 t0, nt, ti, lo, hi;
     if (!binx_tile(seg, tb, nseg, t0, nt, ti, lo, hi)) return;
     s_cnt[tid] = 0;
     __syncthreads();
-    ulonglong2 r[PER];
+    R r[PER];
     u32 rank[PER];
 #pragma unroll
     for (u32 j = 0; j < PER; j++) {
         const u32 i = lo + j * BINX_BLOCK + tid;
         if (i < hi) {
             r[j] = src[i];
-            rank[j] = atomicAdd(&s_cnt[BINX_DIGIT(r[j].x, shift, nb)], 1u);
+            rank[j] = atomicAdd(&s_cnt[BINX_DIGIT(binx_key(r[j]), shift, nb)], 1u);
         }
     }
     __syncthreads();
@@ -792,12 +825,12 @@ __global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const ulonglon
 #pragma unroll
     for (u32 j = 0; j < PER; j++) {
         const u32 i = lo + j * BINX_BLOCK + tid;
-        if (i < hi) s_rec[s_cnt[BINX_DIGIT(r[j].x, shift, nb)] + rank[j]] = r[j];
+        if (i < hi) s_rec[s_cnt[BINX_DIGIT(binx_key(r[j]), shift, nb)] + rank[j]] = r[j];
     }
     __syncthreads();
     for (u32 j = tid; j < hi - lo; j += BINX_BLOCK) {
-        const ulonglong2 x = s_rec[j];
-        dst[s_base[BINX_DIGIT(x.x, shift, nb)] + j] = x;
+        const R x = s_rec[j];
+        dst[s_base[BINX_DIGIT(binx_key(x), shift, nb)] + j] = x;
     }
 }
 
@@ -806,9 +839,15 @@ __global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const ulonglon
  * bkt[], written coalesced; an empty partition writes its starts all the same), sweep 2 hands every record its slot from the bucket's
  * cursor and places the payload: the writes of a workgroup fall into the partition's window of ent[] (about 100 KB). A partition holds
  * any number of records (copies of one read: all in one bucket); the sweeps step through it BINX_BUILD_BLOCK at a time. */
-__global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const ulonglong2 *__restrict__ rec, const u32 *__restrict__ part, u32 span, u32 total, u64 T, u32 *__restrict__ bkt,
-                                                                      u64 *__restrict__ ent)
+/* the grouping's items (R = u64, ORDER_ITEM with the read id in `idbits` bits): the same two sweeps place the order words, reads of equal
+ * bucket back to back in the partition's window of the processing order; the order has no bucket table (bkt, T: unused) */
+__device__ __forceinline__ u64 binx_payload(const ulonglong2 &r, u32, u32) { return r.y; }
+__device__ __forceinline__ u64 binx_payload(u64 r, u32 kshift, u32 idbits) { return ORDER_MAKE(r & ((1ull << idbits) - 1ull), (r << (64u - kshift)) >> (64u - kshift + idbits)); }
+template <typename R>
+__global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const R *__restrict__ rec, const u32 *__restrict__ part, u32 span, u32 kshift, u32 idbits, u32 total, u64 T,
+                                                                      u32 *__restrict__ bkt, u64 *__restrict__ ent)
 {
+    constexpr bool TABLE = sizeof(R) == sizeof(ulonglong2);
     __shared__ u32 s_c[1u << BINX_SPAN_BITS];
     __shared__ u32 s_w[16];
     const u32 tid = threadIdx.x, p = blockIdx.x;
@@ -816,7 +855,7 @@ __global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const ulon
     const u32 beg = part[p], end = part[p + 1];
     for (u32 x = tid; x < nbk; x += BINX_BUILD_BLOCK) s_c[x] = 0;
     __syncthreads();
-    for (u32 i = beg + tid; i < end; i += BINX_BUILD_BLOCK) atomicAdd(&s_c[(u32)(rec[i].x >> 32) & mask], 1u);
+    for (u32 i = beg + tid; i < end; i += BINX_BUILD_BLOCK) atomicAdd(&s_c[(u32)(binx_key(rec[i]) >> kshift) & mask], 1u);
     __syncthreads();
     u32 carry = beg;
     for (u32 base = 0; base < nbk; base += BINX_BUILD_BLOCK) { /* (nbk is a multiple of the block) */
@@ -824,14 +863,14 @@ __global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const ulon
         u32 sum;
         const u32 ex = binx_block_scan1024(x, s_w, &sum);
         s_c[base + tid] = carry + ex;
-        bkt[(u64)p * nbk + base + tid] = carry + ex;
+        if (TABLE) bkt[(u64)p * nbk + base + tid] = carry + ex;
         carry += sum;
     }
-    if ((u64)(p + 1u) * nbk == T && tid == 0) bkt[T] = total;
+    if (TABLE && (u64)(p + 1u) * nbk == T && tid == 0) bkt[T] = total;
     __syncthreads();
     for (u32 i = beg + tid; i < end; i += BINX_BUILD_BLOCK) {
-        const ulonglong2 x = rec[i];
-        ent[atomicAdd(&s_c[(u32)(x.x >> 32) & mask], 1u)] = x.y;
+        const R x = rec[i];
+        ent[atomicAdd(&s_c[(u32)(binx_key(x) >> kshift) & mask], 1u)] = binx_payload(x, kshift, idbits);
     }
 }
 

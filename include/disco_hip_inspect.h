@@ -1,0 +1,25 @@
+/*
+ * disco_hip_inspect.h — entry points of libdisco_hip.so that let a test LOOK at intermediate state no result depends on. Same library,
+ * same C rules as include/disco_hip.h; not part of the boundary a BuildGraph host binds, and not among the bench / test entry points of
+ * include/disco_hip_test.h, whose set is pinned: the Python mirror binds these on first use (disco_amd/buildgraph.py, INSPECT_ABI).
+ */
+#ifndef DISCO_HIP_INSPECT_H_
+#define DISCO_HIP_INSPECT_H_
+
+#include "disco_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* the processing order the last disco_build_index made (results do not depend on it, so only a look at it shows a grouping that stopped
+ * grouping): order_words[0 .. *n) = read id | length << 32 in the order probe / verify / selection / marking walk, keys[read] = the reads'
+ * grouping keys; reads whose (key * 0x9E3779B1) >> (32 - *order_bits) agree lie back to back. cap: room in both arrays, in entries (too
+ * little: *n and *order_bits are set, DISCO_E_ARG). DISCO_E_STATE when the last index build made no order (fewer reads than the grouping
+ * takes, two classes of rows, a caller's order, DISCO_NO_ORDER). Tests only. */
+int disco_fetch_order(disco_ctx *ctx, uint64_t *order_words, uint32_t *keys, uint64_t cap, uint64_t *n, int *order_bits);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DISCO_HIP_INSPECT_H_ */

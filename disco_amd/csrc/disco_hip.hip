@@ -291,7 +291,8 @@ struct disco_ctx {
     std::vector<u64> text_off; /* disco_format_edges: byte range of every file inside d_text */
     DevBuf<u8> d_ingest; /* the input stage's own arena (text, record arrays) when the hit buffer is allocated NEXT to it ... */
     std::thread hits_prealloc; /* ... by this thread, while the files travel and the filter runs (settle_hits_prealloc) */
-    DevBuf<u64> prealloc; /* (hipMalloc of that thread: not in hbm_bytes until settle_hits_prealloc adopts it) */
+    DevBuf<u64> prealloc; /* (hipMalloc of that thread; settle_hits_prealloc adopts or frees it) */
+    u64 prealloc_asked = 0; /* entries that thread was asked for: in hbm_bytes from the call that asks until the thread is joined */
     size_t ring_half = 0;
     hipEvent_t ev_ring[2] = {nullptr, nullptr};
     hipStream_t copy_stream = nullptr; /* disco_upload_reads: the chunks of the host buffer travel here */
@@ -901,7 +902,32 @@ static bool two_class_ok(const disco_ctx *c, int S, u64 n, u64 n_long, u32 short
     return runs_lpr_for(c, c->k - view(c).m + 1, short_max, n) != 0;
 }
 
-static int two_class_alloc(disco_ctx *c, u64 n_long, int Sx, u32 short_max);
+/* the long class's buffers for a table of n_long long reads of stride Sx whose short class has reads of up to short_max bases; the rows
+ * themselves (d_reads: [n + n_long][8]) are the caller's */
+static int two_class_alloc(disco_ctx *c, u64 n_long, int Sx, u32 short_max)
+{
+    /* (the sizes first: free_long_class accounts with them, also for what a failure below leaves behind) */
+    c->n_long = n_long;
+    c->S_ext = Sx;
+    int rc = ensure(c, c->d_ovf, c->n_alloc);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_full, n_long * (u64)Sx);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_long_ids, n_long);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_lpos, n_long);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_lmeta, n_long);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_linfo, n_long);
+    if (rc == DISCO_OK) rc = ensure(c, c->d_n_list, 1);
+    if (rc != DISCO_OK) {
+        free_long_class(c);
+        return rc;
+    }
+    c->S = VERIFY_SW;
+    c->tailb = short_max <= 160 ? 160 : 256; /* what the staged compare of the short class moves per row (verify_flat_kernel<5 / 8>) */
+    c->two_class = true;
+    if (getenv("DISCO_VERBOSE"))
+        fprintf(stderr, "[disco] two classes of rows: %llu of %llu reads are longer than 256 bases, the others up to %u: 64-byte rows + %d-word rows for those\n",
+                (unsigned long long)n_long, (unsigned long long)c->n, short_max, Sx);
+    return DISCO_OK;
+}
 
 /* (list: the own list of a rank that owns loci, [lo, hi) = its positions — it IS the processing order: no grouping to count) */
 /* does the grouping of the whole range go through the partition levels (binned_build_order)? Where the ordered path finishes the
@@ -1309,14 +1335,13 @@ static void settle_hits_prealloc(disco_ctx *c)
 {
     if (!c->hits_prealloc.joinable()) return;
     c->hits_prealloc.join();
-    if (c->prealloc) {
-        if (c->prealloc.cap > c->d_hits.cap) {
-            release(c, c->d_hits);
-            adopt(c, c->d_hits, c->prealloc);
-        } else
-            (void)hipFree(c->prealloc.p);
-        c->prealloc = DevBuf<u64>();
-    }
+    c->hbm_bytes -= std::exchange(c->prealloc_asked, 0) * 8; /* (counted when it was asked for: adopt counts what is taken over) */
+    if (c->prealloc && c->prealloc.cap > c->d_hits.cap) {
+        release(c, c->d_hits);
+        adopt(c, c->d_hits, c->prealloc);
+    } else if (c->prealloc)
+        (void)hipFree(c->prealloc.p);
+    c->prealloc = DevBuf<u64>();
 }
 
 /* ---- which instantiation serves a shape ---------------------------------------------------------------------------------------
@@ -1678,35 +1703,42 @@ static int set_reads_common(disco_ctx *c, u64 n, uint32_t stride, bool *keep = n
     if (c->crows_pending && c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
     c->crows_pending = false;
     c->cgrp_pending = false;
-    if (keep) {
-        *keep = c->reads_owned && !c->two_class && !c->dist_reads && !c->comm && c->d_reads && c->d_len && n > 0 && c->n == n && c->n_alloc == n && c->S == (int)stride &&
-                !getenv("DISCO_NO_BUFFER_REUSE");
-        if (*keep) {
-            c->h_len_ok = false; /* (not cleared: the next upload overwrites it in place) */
-            c->n_out = c->out_used = 0;
-            c->adj_total = 0;
-            c->flags_pending = false;
-            c->adj_imported = false;
-            c->ch_ready = false;
-            c->d_adj = nullptr;
-            c->d_order_used = nullptr;
-            c->dist_active = false;
-            c->q_lo = 0;
-            c->q_hi = n;
-            c->phase = 0;
-            return DISCO_OK;
-        }
+    const bool kept = keep && c->reads_owned && !c->two_class && !c->dist_reads && !c->comm && c->d_reads && c->d_len && n > 0 && c->n == n && c->n_alloc == n &&
+                      c->S == (int)stride && !getenv("DISCO_NO_BUFFER_REUSE");
+    if (keep) *keep = kept;
+    if (kept) {
+        c->h_len_ok = false; /* (not cleared: the next upload overwrites it in place) */
+        c->n_out = c->out_used = 0;
+        c->adj_total = 0;
+        c->flags_pending = false;
+        c->adj_imported = false;
+        c->ch_ready = false;
+        c->d_adj = nullptr;
+        c->d_order_used = nullptr;
+    } else {
+        free_graph_state(c);
+        free_reads(c);
+        c->n = n;
+        c->n_alloc = n;
+        c->dist_reads = false;
+        c->S = (int)stride;
     }
-    free_graph_state(c);
-    free_reads(c);
-    c->n = n;
-    c->n_alloc = n;
-    c->dist_reads = false;
     c->dist_active = false;
-    c->S = (int)stride;
     c->q_lo = 0;
     c->q_hi = n;
     c->phase = 0;
+    return DISCO_OK;
+}
+
+/* the copy stream and its events (first use) */
+static int ensure_copy_stream(disco_ctx *c)
+{
+    if (c->copy_stream) return DISCO_OK;
+    HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 3; i++) {
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_copied[i], hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_unpacked[i], hipEventDisableTiming));
+    }
     return DISCO_OK;
 }
 
@@ -1719,18 +1751,85 @@ static int copy_stream_after_stream(disco_ctx *c)
     return DISCO_OK;
 }
 
-static int validate_reads(disco_ctx *c)
+/* the device's check of the lengths of the reads [lo, hi): h_ctr[CTR_BAD_LEN / CTR_MAX_LEN / CTR_MIN_LEN (complemented)] on return */
+static int count_lengths(disco_ctx *c, u64 lo, u64 hi)
 {
     CHK(zero_counter(c, CTR_BAD_LEN));
     CHK(zero_counter(c, CTR_MAX_LEN));
     CHK(zero_counter(c, CTR_MIN_LEN));
-    if (c->n) hipLaunchKernelGGL(validate_len_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_len, c->n, c->S, (int)c->prm.min_overlap, c->d_ctr);
-    CHK(read_counters(c));
+    if (hi > lo) hipLaunchKernelGGL(validate_len_kernel, dim3(flat_grid(c, hi - lo)), dim3(256), 0, c->stream, c->d_len + lo, hi - lo, c->S, (int)c->prm.min_overlap, c->d_ctr);
+    return read_counters(c);
+}
+
+static int validate_reads(disco_ctx *c)
+{
+    CHK(count_lengths(c, 0, c->n));
     c->min_len = 0xFFFFu - (u32)c->h_ctr[CTR_MIN_LEN];
     if (c->h_ctr[CTR_BAD_LEN])
         return fail(c, DISCO_E_ARG, "%llu reads have a length outside (min_overlap=%u, min(32767, 32*stride)]", (unsigned long long)c->h_ctr[CTR_BAD_LEN], c->prm.min_overlap);
     c->max_len = (u32)c->h_ctr[CTR_MAX_LEN];
     c->phase = 1;
+    return DISCO_OK;
+}
+
+/* ---- where a read table begins -------------------------------------------------------------------------------------------------
+ * Every producer of a table comes here for the layout, the release of the old table, ownership, the buffers and the meaning of the
+ * length fields; what it then does is fill. ReadShape: what a producer knows of its reads before it touches the context (a generator
+ * knows n and the stride: validate_reads has the rest) */
+struct ReadShape {
+    u64 n = 0;
+    uint32_t stride = 0; /* words of a row that holds the longest read, padded to 64 bytes */
+    u64 n_long = 0;      /* reads of more than DISCO_SHORT_MAX bases */
+    u32 short_max = 0, longest = 0, shortest = 0; /* short_max: the longest of the others */
+};
+
+/* the length fields: under two classes of rows max_len is the SHORT class's longest read (its paths are those of a pure short set) */
+static void set_read_lengths(disco_ctx *c, u32 longest, u32 short_max, u32 shortest)
+{
+    c->max_len_all = longest;
+    c->max_len = c->two_class ? short_max : longest;
+    c->min_len = shortest;
+}
+
+/* a refused read set leaves the context with no reads: the stride of the empty table is any valid one (a bad length may ask for more
+ * than set_reads_common accepts, and its refusal would leave the PREVIOUS reads and graph in place) */
+static void drop_reads(disco_ctx *c) { (void)set_reads_common(c, 0, VERIFY_SW, nullptr); }
+
+/* the one-stride part: the old table goes (may_keep: or stays, if it is the context's own of this shape), and n_alloc rows of `stride`
+ * words (extra_rows more: the long class's tail rows) with n_alloc lengths are the context's own — flagged so only once the old table is
+ * released: an adopted one is never freed, kept or written. spare_hits: the hit buffer is in use (the input stage's arena may be it) and
+ * survives the release of the graph state of a read set of another shape */
+static int begin_rows(disco_ctx *c, u64 n, u64 n_alloc, u64 extra_rows, uint32_t stride, bool may_keep, bool spare_hits = false)
+{
+    DevBuf<u64> hits;
+    bool kept = false;
+    if (spare_hits) std::swap(hits, c->d_hits);
+    const int rc = set_reads_common(c, n, stride, may_keep ? &kept : nullptr);
+    if (spare_hits) std::swap(hits, c->d_hits);
+    CHK(rc);
+    c->reads_owned = true; /* whatever is allocated from here on is released by free_reads */
+    c->n_alloc = n_alloc;
+    return kept ? DISCO_OK : alloc_reads(c, (n_alloc + extra_rows) * (u64)stride, n_alloc);
+}
+
+/* a table of the context's own for reads of this shape, up to "the buffers exist"; an own table of the same shape is kept. A few long reads
+ * among short ones: two classes of rows (c->two_class on return) — the table of one stride, n rows as wide as the longest read, is never made */
+static int begin_read_table(disco_ctx *c, const ReadShape &s, bool spare_hits = false)
+{
+    const bool classes = two_class_ok(c, (int)s.stride, s.n, s.n_long, s.short_max, true);
+    CHK(begin_rows(c, s.n, s.n, classes ? s.n_long : 0, classes ? (uint32_t)VERIFY_SW : s.stride, !classes, spare_hits));
+    if (classes) CHK(two_class_alloc(c, s.n_long, (int)s.stride, s.short_max));
+    set_read_lengths(c, s.longest, s.short_max, s.shortest);
+    return DISCO_OK;
+}
+
+/* the long reads' numbers: ovf[i] = long reads before read i (the flags, scanned in place; CTR_SHORT_MAX takes the longest of the others)
+ * and, where asked, ids[x] = the read that is long read x. count == null: nothing waits for the device (an upload issues its chunks behind this) */
+static int number_long_reads(disco_ctx *c, u32 *ovf, u32 *ids, u64 *count)
+{
+    hipLaunchKernelGGL(class_flag_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, (const u16 *)c->d_len, c->n, ovf, c->d_ctr);
+    CHK((scan_exclusive<u32, u32>(c, ovf, c->n, ovf, false, count)));
+    if (ids) hipLaunchKernelGGL(class_ids_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, (const u16 *)c->d_len, (const u32 *)ovf, c->n, ids);
     return DISCO_OK;
 }
 
@@ -1751,8 +1850,8 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
     /* the lengths are checked where they are (the host has them): min_overlap < len <= min(32767, 32 * stride) (BG/Dataset.cpp:305,
      * BG/HashTable.cpp:531); longest / shortest decide the kernel variants of the pass, the long reads the layout; ragged: the words of
      * every chunk of CH reads */
-    std::atomic<u64> a_bad{0}, a_long{0};
-    std::atomic<u32> a_max{0}, a_min{0xFFFFu}, a_smax{0};
+    u64 n_bad = 0;
+    ReadShape shape{n, 0, 0, 0, 0, n ? 0xFFFFu : 0u};
     std::vector<u64> chunk_words(n_chunks + 1, 0);
     {
         const u32 mo = c->prm.min_overlap, cap = ragged ? 32767u : std::min<u32>(32767u, stride_words * 32u);
@@ -1774,55 +1873,31 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
                 std::lock_guard<std::mutex> lk(mu);
                 chunk_words[k + 1] += words;
             }
-            a_bad += bad;
-            a_long += nlong;
-            u32 cur = a_max.load();
-            while (mx > cur && !a_max.compare_exchange_weak(cur, mx)) {}
-            cur = a_min.load();
-            while (mn < cur && !a_min.compare_exchange_weak(cur, mn)) {}
-            cur = a_smax.load();
-            while (smx > cur && !a_smax.compare_exchange_weak(cur, smx)) {}
+            std::lock_guard<std::mutex> lk(mu);
+            n_bad += bad;
+            shape.n_long += nlong;
+            shape.longest = std::max(shape.longest, mx);
+            shape.shortest = std::min(shape.shortest, mn);
+            shape.short_max = std::max(shape.short_max, smx);
         });
         for (u64 k = 0; k < n_chunks; k++) chunk_words[k + 1] += chunk_words[k];
     }
-    if (ragged) stride_words = std::max<u32>(1, (a_max.load() + 31) / 32);
+    if (ragged) stride_words = std::max<u32>(1, (shape.longest + 31) / 32);
     t_scan = lapms();
     /* rows are padded to a multiple of 8 words = 64 B so that a candidate row fetch touches whole, aligned HBM sectors */
-    const uint32_t dstride = (stride_words + 7u) & ~7u;
-    if (a_bad.load()) {
-        /* the context is left with no reads: the stride of the empty table is any valid one (the bad length itself may ask for more
-         * than set_reads_common accepts, and its refusal would leave the PREVIOUS reads and graph in place) */
-        (void)set_reads_common(c, 0, VERIFY_SW, nullptr);
-        return fail(c, DISCO_E_ARG, "%llu reads have a length outside (min_overlap=%u, min(32767, 32*stride)]", (unsigned long long)a_bad.load(), c->prm.min_overlap);
+    const uint32_t dstride = shape.stride = (stride_words + 7u) & ~7u;
+    if (n_bad) {
+        drop_reads(c);
+        return fail(c, DISCO_E_ARG, "%llu reads have a length outside (min_overlap=%u, min(32767, 32*stride)]", (unsigned long long)n_bad, c->prm.min_overlap);
     }
-    /* a few long reads among short ones: the chunks are unpacked per class (two classes of rows, disco_kernels.h) — the table of one
-     * stride is never made on the device */
-    const u64 n_long = a_long.load();
-    const bool classes = n && two_class_ok(c, (int)dstride, n, n_long, a_smax.load(), true);
-    bool kept = false;
-    CHK(set_reads_common(c, n, classes ? (uint32_t)VERIFY_SW : dstride, classes ? nullptr : &kept));
-    c->reads_owned = true; /* the old table is gone (or kept, and then it was the context's own): whatever is allocated from here on is released by free_reads */
-    if (classes) {
-        CHK(alloc_reads(c, (n + n_long) * 8, n));
-        CHK(two_class_alloc(c, n_long, (int)dstride, a_smax.load()));
-    } else if (!kept)
-        CHK(alloc_reads(c, n * (u64)dstride, n));
-    c->reads_owned = true;
-    c->max_len = n ? (classes ? a_smax.load() : a_max.load()) : 0;
-    c->max_len_all = n ? a_max.load() : 0;
-    c->min_len = n ? a_min.load() : 0;
+    CHK(begin_read_table(c, shape));
+    const bool classes = c->two_class; /* (the chunks are then unpacked per class) */
     if (n) {
         /* The copy runs in chunks on a stream of its own; behind it, chunk by chunk on the context's stream: rows spread to the 64-byte
          * stride of the table (host rows at the words they use: 5 of 8 at 150 bp — 2.0 instead of 3.2 GB over the link; a 2-D copy of 40-byte
          * rows ran at 8.7 GB/s) and the COUNT PASS OF THE INDEX over the chunk's reads (index_runs_kernel: 9 ms at 50 M reads, hidden behind
          * the 38 ms of the copy) — disco_build_index then starts at its scan. The call returns when the host buffer is free again. */
-        if (!c->copy_stream) {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-            for (int i = 0; i < 3; i++) {
-                HIPCHK(c, hipEventCreateWithFlags(&c->ev_copied[i], hipEventDisableTiming));
-                HIPCHK(c, hipEventCreateWithFlags(&c->ev_unpacked[i], hipEventDisableTiming));
-            }
-        }
+        CHK(ensure_copy_stream(c));
         CHK(copy_stream_after_stream(c));
         const bool direct = !ragged && !classes && dstride == stride_words; /* the host rows ARE the table's rows: copied where they belong */
         /* (two classes: the index is counted by disco_build_index, over the classes) */
@@ -1840,11 +1915,7 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
             hipLaunchKernelGGL(words_per_read_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u16 *)c->d_len, n, nw);
             CHK((scan_exclusive<u32, u64>(c, nw, n, woff, false, nullptr)));
         }
-        if (classes) { /* the long reads' numbers */
-            hipLaunchKernelGGL(class_flag_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u16 *)c->d_len, n, c->d_ovf, c->d_ctr);
-            CHK((scan_exclusive<u32, u32>(c, c->d_ovf, n, c->d_ovf, false, nullptr)));
-            hipLaunchKernelGGL(class_ids_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u16 *)c->d_len, (const u32 *)c->d_ovf, n, c->d_long_ids);
-        }
+        if (classes) CHK(number_long_reads(c, c->d_ovf, c->d_long_ids, nullptr));
         t_alloc = lapms();
         IndexCountPlan pl;
         DiscoView v;
@@ -1866,8 +1937,8 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
                 hipLaunchKernelGGL(unpack_reads_kernel, dim3(flat_grid(c, (hi - lo) * (u64)c->S)), dim3(256), 0, c->stream, (const u64 *)ring, ragged ? 0 : (int)stride_words, (const u64 *)woff, w0,
                                    (const u16 *)c->d_len, lo, hi, c->S, classes ? (u32)DISCO_SHORT_MAX : 0xFFFFu, c->d_reads);
                 if (classes)
-                    hipLaunchKernelGGL(unpack_long_reads_kernel, dim3(flat_grid(c, n_long * ((u64)dstride + 8))), dim3(256), 0, c->stream, (const u64 *)ring, ragged ? 0 : (int)stride_words,
-                                       (const u64 *)woff, w0, (const u16 *)c->d_len, lo, hi, (const u32 *)c->d_long_ids, n_long, n, (int)dstride, c->tailb, c->d_full, c->d_reads);
+                    hipLaunchKernelGGL(unpack_long_reads_kernel, dim3(flat_grid(c, shape.n_long * ((u64)dstride + 8))), dim3(256), 0, c->stream, (const u64 *)ring, ragged ? 0 : (int)stride_words,
+                                       (const u64 *)woff, w0, (const u16 *)c->d_len, lo, hi, (const u32 *)c->d_long_ids, shape.n_long, n, (int)dstride, c->tailb, c->d_full, c->d_reads);
                 HIPCHK(c, hipEventRecord(c->ev_unpacked[b], c->stream));
             } else { /* (one 1-D copy per chunk: a 2-D copy whose width equals both pitches ran at a third of the rate) */
                 HIPCHK(c, hipMemcpyAsync(c->d_reads + lo * dstride, packed + lo * dstride, (hi - lo) * (u64)dstride * 8, hipMemcpyHostToDevice, c->copy_stream));
@@ -1924,31 +1995,14 @@ struct IngestFile {
     bool fastq = false;
     u64 n = 0;
     u8 *d_text = nullptr;
-    u64 text_cap = 0;
     u64 *d_start = nullptr, *d_seq = nullptr;
     u32 *d_wrap = nullptr;
     u16 *d_glen = nullptr;
     u64 n_start = 0, n_rec = 0, good = 0;
-    /* a BGZF file: n and d_text are its TEXT (known once the member chain is walked); the file itself is comp_n bytes at d_comp */
-    bool gz = false;
+    /* a BGZF file (map != null): n and d_text are its TEXT (known once the member chain is walked); the file itself is comp_n bytes at d_comp */
     const u8 *map = nullptr;
     u64 comp_n = 0;
     u8 *d_comp = nullptr;
-};
-/* the transient buffers of the input stage are carved out of ONE arena — the context's hit buffer, sized here as the probe will want it
- * (64 candidate slots per read: about three times the text): freeing 10 GB right before the pass made its first allocations take
- * 0.6 s on these boxes, and the text simply lives where the candidates will */
-struct IngestArena {
-    u8 *base = nullptr;
-    u64 cap = 0, used = 0;
-    void *take(u64 nbytes)
-    {
-        const u64 bytes = (nbytes + 255) & ~255ull;
-        if (!base || used + bytes > cap) return nullptr;
-        void *p = base + used;
-        used += bytes;
-        return p;
-    }
 };
 } // namespace
 
@@ -1999,14 +2053,7 @@ static int ingest_ring(disco_ctx *c)
         c->ring_half = HALF;
         for (int i = 0; i < 2; i++) HIPCHK(c, hipEventCreateWithFlags(&c->ev_ring[i], hipEventDisableTiming));
     }
-    if (!c->copy_stream) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 3; i++) {
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_copied[i], hipEventDisableTiming));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_unpacked[i], hipEventDisableTiming));
-        }
-    }
-    return DISCO_OK;
+    return ensure_copy_stream(c);
 }
 
 static int ingest_read_file(disco_ctx *c, int fd, u64 n, u8 *d_text, unsigned threads)
@@ -2171,380 +2218,369 @@ extern "C" int64_t disco_inflate_bgzf(disco_ctx *c, const void *bgzf, uint64_t n
     return (int64_t)total;
 }
 
+/* ---- the input stage as steps: disco_ingest_fasta (below) is a list of steps over one IngestJob. A step answers DISCO_OK, an error
+ * it has recorded with fail, or INGEST_DECLINED with the reason left in the job (an input the HOST stage reads: plain gzip, a '>' inside
+ * a line ...): only disco_ingest_fasta turns that into its message. Whatever the job holds goes with it, on every way out. */
+extern "C++" { /* (the job's `get` is a template) */
+namespace {
+constexpr int INGEST_DECLINED = 1;
+const char *const kIngestIrregular = "a '>' inside a line, an irregularly wrapped long record, or no record";
+
+struct IngestJob {
+    disco_ctx *c;
+    unsigned threads; /* of the file reader */
+    std::vector<IngestFile> F;
+    u8 *arena = nullptr; /* the transient buffers (text, record arrays) are carved out of it, 256-byte aligned (ingest_choose_arena) */
+    u64 arena_cap = 0, arena_used = 0;
+    std::vector<std::pair<void *, size_t>> owned; /* pieces that did not fit the arena: allocations of their own, in hbm_bytes */
+    u64 *d_ctr = nullptr; /* the filter's counters (FX_CTR_COUNT) */
+    FxTables tb;
+    u64 total_bytes = 0; /* text of all files as it will lie in HBM (a .gz name: an estimate) */
+    ReadShape shape{0, 0, 0, 0, 0, 0xFFFFu}; /* of the good reads, summed file by file as they are filtered */
+    u64 total_records = 0, too_long = 0;
+    float read_s = 0;
+    std::string why, where; /* of a decline */
+    const HClock::time_point t_begin = HClock::now();
+    IngestJob(disco_ctx *ctx, int n_files, uint32_t host_threads) : c(ctx), threads(host_threads ? host_threads : 16u), F((size_t)n_files) { ingest_tables(&tb); }
+    IngestJob(const IngestJob &) = delete;
+    ~IngestJob()
+    {
+        for (auto &f : F) {
+            if (f.map) munmap((void *)f.map, (size_t)f.comp_n);
+            if (f.fd >= 0) close(f.fd);
+        }
+        for (auto &o : owned) {
+            (void)hipFree(o.first);
+            c->hbm_bytes -= o.second;
+        }
+    }
+    float seconds() const { return ms_since(t_begin) * 1e-3f; }
+    int decline(const std::string &reason, const IngestFile &f) { return why = reason, where = f.path, INGEST_DECLINED; }
+    template <typename T>
+    int get(T **pp, u64 count) /* from the arena, or an allocation of its own */
+    {
+        const size_t bytes = std::max<u64>(count, 1) * sizeof(T), room = (bytes + 255) & ~(size_t)255;
+        if (arena && arena_used + room <= arena_cap) {
+            *pp = (T *)(arena + arena_used);
+            arena_used += room;
+            return DISCO_OK;
+        }
+        if (hipMalloc((void **)pp, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, DISCO_E_NOMEM, "disco_ingest_fasta: out of device memory");
+        }
+        c->hbm_bytes += bytes;
+        owned.emplace_back((void *)*pp, bytes);
+        return DISCO_OK;
+    }
+};
+} // namespace
+} // extern "C++"
+
+/* whole tiles (16-byte loads) and aligned 8-byte words behind the end of a text of n bytes */
+static u64 ingest_text_cap(u64 n) { return (n + FX_TILE + 63) / FX_TILE * FX_TILE + 64; }
+
+/* step: the files — regular, first byte '>' or '@'; under a .gz name BGZF only (plain gzip is one serial stream: the host stage's) */
+static int ingest_open(IngestJob &j, const char *const *paths)
+{
+    for (size_t fi = 0; fi < j.F.size(); fi++) {
+        IngestFile &f = j.F[fi];
+        f.path = paths[fi] ? paths[fi] : "";
+        const bool gz_name = f.path.size() >= 3 && f.path.compare(f.path.size() - 3, 3, ".gz") == 0;
+        struct stat st;
+        f.fd = open(f.path.c_str(), O_RDONLY);
+        if (f.fd < 0 && !gz_name) return j.decline("unreadable file", f);
+        if (f.fd < 0 || fstat(f.fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 1) return j.decline(gz_name ? "gzip input" : "empty or unreadable file", f);
+        if (gz_name) {
+            u32 hdr = 0, bsize = 0;
+            void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, f.fd, 0); /* for the header walk only: the readers pread */
+            if (m == MAP_FAILED) return j.decline("gzip input", f);
+            f.map = (const u8 *)m;
+            f.comp_n = (u64)st.st_size;
+            if (infl::bgzf_header(f.map, f.comp_n, 0, &hdr, &bsize)) return j.decline("gzip input", f);
+            /* the text's size is known when the chain is walked, behind the transfer: the arena is sized for five times the file (FASTA
+             * at level 6: four); a text that does not fit gets a piece of its own */
+            j.total_bytes += ((f.comp_n + 255) & ~255ull) + ingest_text_cap(f.comp_n * 5);
+            continue;
+        }
+        char first = 0;
+        if (pread(f.fd, &first, 1, 0) != 1 || pread(f.fd, &f.last, 1, st.st_size - 1) != 1) return j.decline("empty or unreadable file", f);
+        if (first != '>' && first != '@') return j.decline("neither FASTA nor FASTQ", f);
+        f.fastq = first == '@';
+        f.n = (u64)st.st_size;
+        j.total_bytes += ingest_text_cap(f.n);
+    }
+    return DISCO_OK;
+}
+
+/* step: the arena. The transient buffers of this stage (text, record arrays) come out of ONE allocation. Where memory is plentiful it
+ * is the stage's own (kept by the context: freeing 10 GB right before the pass made the pass's first allocations take 0.6 s), and the
+ * hit buffer the probe will want — 64 candidate slots per read, 28 GB at 50 M reads, 0.5-0.9 s of hipMalloc — is allocated by a
+ * thread of its own while the files travel to HBM and the filter runs (it may outlive this call: settle_hits_prealloc joins it). Where
+ * it is not (2 x 10^8 reads on one GPU), the arena IS the hit buffer, as in round 3: the text lives where the candidates will. A
+ * previous pass's results are gone either way. */
+static int ingest_choose_arena(IngestJob &j)
+{
+    disco_ctx *c = j.c;
+    if (c->phase > 1) c->phase = 1;
+    c->d_adj = nullptr;
+    c->adj_total = 0;
+    settle_hits_prealloc(c);
+    /* hit entries: 64 per read as the probe will ask, a chunk per resident wave; reads estimated at one per 150 bytes of text (shorter
+     * records: the probe grows the buffer itself) */
+    const u64 want = (j.total_bytes / 150) * 64 + (u64)c->n_cu * 32 * PR_CHUNK + (1u << 16);
+    const u64 own_bytes = j.total_bytes + (j.total_bytes / 100) * 28 + (64ull << 20); /* text + record arrays (a record per 100 bytes at worst here; more: pieces of their own) */
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) return fail(c, DISCO_E_HIP, "disco_ingest_fasta: hipMemGetInfo failed");
+    const u64 rest = (j.total_bytes / 150) * 200 + (4ull << 30); /* the read table and the index next to it */
+    if (c->arena.base && !c->comm && c->arena.used == 0 && !c->d_ingest) { /* the last call's arena, idle again: this call's text goes there */
+        /* (counted as one buffer again: the handover took it out of the sum) */
+        adopt(c, c->d_ingest, DevBuf<u8>{(u8 *)c->arena.base, c->arena.size});
+        c->arena = DevArena();
+        c->hbm_peak = std::max(c->hbm_peak, c->hbm_bytes);
+    }
+    const bool split = !getenv("DISCO_INGEST_SHARED_ARENA") && !c->arena.base && (u64)fr + c->d_hits.cap * 8 + c->d_ingest.cap > std::max(want, c->d_hits.cap) * 8 + own_bytes + rest + (16ull << 30);
+    if (split) {
+        if (own_bytes > c->d_ingest.cap && ensure(c, c->d_ingest, own_bytes) != DISCO_OK) c->err.clear();
+        if (want > c->d_hits.cap && c->d_ingest.cap) {
+            /* the buffer at hand is too small for the probe and is not this call's arena: it goes now (should the thread's allocation fail,
+             * the probe allocates its own, as on a fresh context), and what is asked for is counted now, not by the next call to join the thread */
+            release(c, c->d_hits);
+            c->hbm_bytes += (c->prealloc_asked = want) * 8;
+            c->hits_prealloc = std::thread([c, dev = c->device, want]() {
+                void *p = nullptr;
+                if (hipSetDevice(dev) == hipSuccess && hipMalloc(&p, want * 8) == hipSuccess) c->prealloc = DevBuf<u64>{(u64 *)p, want};
+                else (void)hipGetLastError();
+            });
+        }
+    }
+    if (split && c->d_ingest.cap) {
+        j.arena = c->d_ingest;
+        j.arena_cap = c->d_ingest.cap;
+    } else {
+        if (want > c->d_hits.cap && (u64)fr + c->d_hits.cap * 8 > want * 8 + rest && ensure(c, c->d_hits, want) != DISCO_OK) /* room for it next to the table and the index */
+            c->err.clear();
+        j.arena = (u8 *)c->d_hits.p;
+        j.arena_cap = c->d_hits.cap * 8;
+    }
+    return j.get(&j.d_ctr, (u64)FX_CTR_COUNT);
+}
+
+/* a BGZF file's text: the file into HBM while a host thread walks its member chain; then one wavefront per member writes the text */
+static int ingest_text_bgzf(IngestJob &j, IngestFile &f)
+{
+    disco_ctx *c = j.c;
+    const auto t_read = HClock::now();
+    CHK(j.get(&f.d_comp, f.comp_n));
+    std::vector<infl::BgzfBlock> blocks;
+    uint64_t total = 0, bad = 0;
+    const char *why = nullptr;
+    float walk_ms = 0;
+    std::thread walker([&]() {
+        const auto t0 = HClock::now();
+        why = infl::bgzf_walk(f.map, f.comp_n, blocks, &total, &bad);
+        walk_ms = ms_since(t0);
+    });
+    const int rrc = ingest_read_file(c, f.fd, f.comp_n, f.d_comp, j.threads);
+    walker.join();
+    j.read_s += ms_since(t_read) * 1e-3f;
+    CHK(rrc);
+    char msg[160];
+    if (why || total == 0) {
+        snprintf(msg, sizeof msg, "gzip input, member %llu: %s", (unsigned long long)bad, why ? why : "no text");
+        return j.decline(msg, f);
+    }
+    const auto t_inf = HClock::now();
+    f.n = total;
+    infl::BgzfBlock *d_blk = nullptr;
+    u32 *d_status = nullptr;
+    CHK(j.get(&f.d_text, ingest_text_cap(f.n)));
+    CHK(j.get(&d_blk, blocks.size()));
+    CHK(j.get(&d_status, blocks.size() + 1));
+    HIPCHK(c, hipMemsetAsync(f.d_text + f.n, 0, ingest_text_cap(f.n) - f.n, c->stream));
+    int e = infl::INFL_OK;
+    CHK(bgzf_inflate_run(c, f.d_comp, blocks, d_blk, d_status, f.d_text, &bad, &e));
+    if (e != infl::INFL_OK) {
+        snprintf(msg, sizeof msg, "BGZF member %llu: %s", (unsigned long long)bad, infl::reason(e));
+        return j.decline(msg, f);
+    }
+    char first = 0;
+    HIPCHK(c, hipMemcpy(&first, f.d_text, 1, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&f.last, f.d_text + f.n - 1, 1, hipMemcpyDeviceToHost));
+    if (getenv("DISCO_VERBOSE"))
+        fprintf(stderr, "[disco] BGZF %s: %.1f MB in %llu members -> %.1f MB of text; header walk %.1f ms (behind the transfer), inflate %.1f ms\n", f.path.c_str(), f.comp_n / 1e6,
+                (unsigned long long)blocks.size(), f.n / 1e6, walk_ms, ms_since(t_inf));
+    if (first != '>' && first != '@') return j.decline("neither FASTA nor FASTQ", f);
+    f.fastq = first == '@';
+    return DISCO_OK;
+}
+
+/* step: one file's text into HBM, plain or BGZF */
+static int ingest_text(IngestJob &j, IngestFile &f)
+{
+    if (f.map) return ingest_text_bgzf(j, f);
+    disco_ctx *c = j.c;
+    const auto t_read = HClock::now();
+    CHK(j.get(&f.d_text, ingest_text_cap(f.n)));
+    HIPCHK(c, hipMemsetAsync(f.d_text + f.n, 0, ingest_text_cap(f.n) - f.n, c->stream));
+    const int rc = ingest_read_file(c, f.fd, f.n, f.d_text, j.threads);
+    j.read_s += ms_since(t_read) * 1e-3f;
+    return rc;
+}
+
+/* step: the records of one file — FASTA: the '>' that start a line; FASTQ: every fourth line */
+static int ingest_records(IngestJob &j, IngestFile &f)
+{
+    disco_ctx *c = j.c;
+    const u64 tiles = (f.n + FX_TILE - 1) / FX_TILE;
+    u64 *d_tile_base = nullptr;
+    u32 *d_tile_cnt = nullptr;
+    CHK(j.get(&d_tile_base, tiles + 1));
+    CHK(j.get(&d_tile_cnt, tiles));
+    HIPCHK(c, hipMemsetAsync(j.d_ctr, 0, FX_CTR_COUNT * sizeof(u64), c->stream));
+    if (f.fastq) {
+        u64 n_newlines = 0;
+        hipLaunchKernelGGL(fx_lines_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, d_tile_cnt, (const u64 *)nullptr, (u64 *)nullptr);
+        CHK((scan_exclusive<u32, u64>(c, d_tile_cnt, tiles, d_tile_base, false, &n_newlines)));
+        const u64 n_lines = n_newlines + (f.last == '\n' ? 0 : 1); /* a last line without a newline is a line */
+        f.n_start = (n_lines + 3) / 4; /* the reference starts a record whenever bytes are left (BG/Dataset.cpp:255-293) */
+        f.n_rec = f.n_start;
+    } else {
+        hipLaunchKernelGGL(fx_starts_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, d_tile_cnt, (const u64 *)nullptr, (u64 *)nullptr, j.d_ctr);
+        CHK((scan_exclusive<u32, u64>(c, d_tile_cnt, tiles, d_tile_base, false, &f.n_start)));
+        /* a '>' that is the very last byte starts nothing (the reference's next getline fails) unless it is the only one; it still
+         * ends the sequence of the record before it (disco_amd/host/fastx.cpp) */
+        f.n_rec = (f.n_start > 1 && f.last == '>') ? f.n_start - 1 : f.n_start;
+    }
+    if (f.n_start == 0 || f.n_start >= (1ull << 32)) return j.decline(kIngestIrregular, f);
+    CHK(j.get(&f.d_start, f.n_start));
+    CHK(j.get(&f.d_seq, f.n_rec));
+    CHK(j.get(&f.d_glen, f.n_rec));
+    CHK(j.get(&f.d_wrap, f.n_rec));
+    if (f.fastq) hipLaunchKernelGGL(fx_lines_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, (u32 *)nullptr, (const u64 *)d_tile_base, f.d_start);
+    else hipLaunchKernelGGL(fx_starts_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, (u32 *)nullptr, (const u64 *)d_tile_base, f.d_start, j.d_ctr);
+    return DISCO_OK;
+}
+
+/* step: clean + filter the records of one file; its counters into the job's totals and the caller's per-file entry */
+static int ingest_filter(IngestJob &j, IngestFile &f, disco_ingest_file *out)
+{
+    disco_ctx *c = j.c;
+    const FxFilterArgs fa{.text = f.d_text, .n = f.n, .start = f.d_start, .n_start = f.n_start, .n_rec = f.n_rec, .min_overlap = c->prm.min_overlap, .fastq = f.fastq ? 1u : 0u,
+                          .glen = f.d_glen, .seq_begin = f.d_seq, .wrap = f.d_wrap, .ctr = j.d_ctr};
+    hipLaunchKernelGGL(fx_filter_kernel, dim3(flat_grid(c, f.n_rec)), dim3(256), 0, c->stream, fa, j.tb);
+    HIPCHK(c, hipGetLastError());
+    u64 h[FX_CTR_COUNT];
+    HIPCHK(c, hipMemcpyAsync(h, j.d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h[FX_CTR_BAD_GT] || h[FX_CTR_MULTILINE]) return j.decline(kIngestIrregular, f);
+    f.good = h[FX_CTR_GOOD];
+    j.too_long += h[FX_CTR_TOO_LONG];
+    if (f.good) {
+        j.shape.longest = std::max(j.shape.longest, (u32)h[FX_CTR_MAX_LEN]);
+        j.shape.shortest = std::min(j.shape.shortest, 0xFFFFu - (u32)h[FX_CTR_MIN_LEN_INV]);
+        j.shape.n_long += h[FX_CTR_N_LONG];
+        j.shape.short_max = std::max(j.shape.short_max, (u32)h[FX_CTR_SHORT_MAX]);
+    }
+    *out = disco_ingest_file{.first_index = j.total_records + 1, .last_index = j.total_records + f.n_rec, .good = f.good, .bad = f.n_rec - f.good};
+    j.total_records += f.n_rec;
+    j.shape.n += f.good;
+    return DISCO_OK;
+}
+
+/* step: the read table — ids in file order, rows packed straight from the text (per class where the table has two classes of rows) */
+static int ingest_build_table(IngestJob &j)
+{
+    disco_ctx *c = j.c;
+    ReadShape &s = j.shape;
+    if (s.n == 0 || s.n >= (1ull << 31)) return j.decline("no good read (or more than 2^31)", j.F[0]);
+    s.stride = (std::max<u32>(1, (s.longest + 31) / 32) + 7u) & ~7u;
+    CHK(begin_read_table(c, s, true)); /* (true: the arena may be the hit buffer) */
+    const size_t n_files = j.F.size();
+    CHK(ensure(c, c->d_rec_of_read, s.n));
+    c->ingest_id_base.assign(n_files + 1, 0);
+    c->ingest_rec_base.assign(n_files + 1, 0);
+    u64 max_rec = 0;
+    for (auto &f : j.F) max_rec = std::max(max_rec, f.n_rec);
+    u64 *d_pos = nullptr;
+    u8 *d_flag = nullptr;
+    CHK(j.get(&d_pos, max_rec + 1));
+    CHK(j.get(&d_flag, max_rec));
+    for (size_t fi = 0; fi < n_files; fi++) {
+        IngestFile &f = j.F[fi];
+        const u64 id_base = c->ingest_id_base[fi];
+        hipLaunchKernelGGL(fx_flags_kernel, dim3(flat_grid(c, f.n_rec)), dim3(256), 0, c->stream, (const u16 *)f.d_glen, f.n_rec, d_flag);
+        u64 good = 0;
+        CHK((scan_exclusive<u8, u64>(c, d_flag, f.n_rec, d_pos, false, &good)));
+        if (good != f.good) return fail(c, DISCO_E_STATE, "disco_ingest_fasta: %llu good reads counted, %llu placed", (unsigned long long)f.good, (unsigned long long)good);
+        hipLaunchKernelGGL(fx_ids_kernel, dim3(flat_grid(c, f.n_rec)), dim3(256), 0, c->stream, (const u16 *)f.d_glen, (const u64 *)d_pos, f.n_rec, id_base, c->d_rec_of_read, c->d_len);
+        if (f.good)
+            hipLaunchKernelGGL(fx_pack_kernel, dim3(flat_grid(c, f.good * (u64)c->S)), dim3(256), 0, c->stream, (const u8 *)f.d_text, (const u64 *)f.d_seq, (const u32 *)f.d_wrap, (const u32 *)c->d_rec_of_read,
+                               (const u16 *)c->d_len, id_base, f.good, c->S, c->two_class ? (u32)DISCO_SHORT_MAX : 0xFFFFu, c->d_reads);
+        HIPCHK(c, hipGetLastError());
+        c->ingest_id_base[fi + 1] = id_base + f.good;
+        c->ingest_rec_base[fi + 1] = c->ingest_rec_base[fi] + f.n_rec;
+    }
+    if (c->two_class) { /* every read has its id and length: number the long ones, then their full and tail rows, file by file */
+        u64 counted = 0;
+        CHK(number_long_reads(c, c->d_ovf, c->d_long_ids, &counted));
+        if (counted != s.n_long) return fail(c, DISCO_E_STATE, "disco_ingest_fasta: %llu long reads counted, %llu placed", (unsigned long long)s.n_long, (unsigned long long)counted);
+        for (size_t fi = 0; fi < n_files; fi++) {
+            IngestFile &f = j.F[fi];
+            if (!f.good) continue;
+            hipLaunchKernelGGL(fx_pack_long_kernel, dim3(flat_grid(c, s.n_long * ((u64)s.stride + 8))), dim3(256), 0, c->stream, (const u8 *)f.d_text, (const u64 *)f.d_seq, (const u32 *)f.d_wrap,
+                               (const u32 *)c->d_rec_of_read, (const u16 *)c->d_len, c->ingest_id_base[fi], f.good, (const u32 *)c->d_long_ids, s.n_long, s.n, (int)s.stride, c->tailb, c->d_full,
+                               c->d_reads);
+        }
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DISCO_OK;
+}
+
+/* step: the stage's own arena is free space from here on — the context's allocator serves the pass from it (its index, headers,
+ * adjacency and result buffers: a dozen device allocations of 5-10 ms each that the first pass of a fresh context otherwise waits for) */
+static void ingest_hand_over_arena(IngestJob &j)
+{
+    disco_ctx *c = j.c;
+    if (!c->d_ingest || j.arena != c->d_ingest.p || getenv("DISCO_NO_ARENA_HANDOVER")) return;
+    c->arena = DevArena();
+    c->arena.free_at[0] = c->arena.size = c->d_ingest.cap & ~(u64)255;
+    /* what the allocator serves out of it is counted buffer by buffer (dev_alloc): the arena itself leaves the sum, or every byte of
+     * it would count twice in hbm_bytes / hbm_peak */
+    c->arena.base = (char *)disown(c, c->d_ingest);
+}
+
 extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_files, uint32_t host_threads, disco_ingest_info *info, disco_ingest_file *files)
 {
     DISCO_TRACE("disco_ingest_fasta");
     if (!c || !paths || n_files < 1 || !info || !files) return c ? fail(c, DISCO_E_ARG, "disco_ingest_fasta: null argument") : DISCO_E_ARG;
     if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "disco_ingest_fasta: single-GPU contexts only");
     HIPCHK(c, hipSetDevice(c->device));
-    const auto t_begin = HClock::now();
-    std::vector<IngestFile> F((size_t)n_files);
-    struct Owned { /* pieces that did not fit the arena */
-        void *p;
-        size_t bytes;
-    };
-    std::vector<Owned> owned;
-    IngestArena arena;
-    auto cleanup = [&]() {
-        for (auto &f : F) {
-            if (f.map) munmap((void *)f.map, (size_t)f.comp_n);
-            f.map = nullptr;
-            if (f.fd >= 0) close(f.fd);
-            f.fd = -1;
-        }
-        for (auto &o : owned) {
-            (void)hipFree(o.p);
-            c->hbm_bytes -= o.bytes;
-        }
-        owned.clear();
-    };
-    auto unsupported = [&](const char *why, const std::string &path) {
-        cleanup();
-        return fail(c, DISCO_E_UNSUPPORTED, "disco_ingest_fasta: %s (%s): the host input stage takes this job", why, path.c_str());
-    };
-    /* ---- the files: regular, first byte '>' or '@'; under a .gz name BGZF only (plain gzip is one serial stream: the host stage's) ----- */
-    u64 total_bytes = 0;
-    for (int fi = 0; fi < n_files; fi++) {
-        IngestFile &f = F[(size_t)fi];
-        f.path = paths[fi] ? paths[fi] : "";
-        if (f.path.size() >= 3 && f.path.compare(f.path.size() - 3, 3, ".gz") == 0) {
-            struct stat gst;
-            u32 hdr = 0, bsize = 0;
-            f.fd = open(f.path.c_str(), O_RDONLY);
-            if (f.fd < 0 || fstat(f.fd, &gst) != 0 || !S_ISREG(gst.st_mode) || gst.st_size < 1) return unsupported("gzip input", f.path);
-            void *m = mmap(nullptr, (size_t)gst.st_size, PROT_READ, MAP_PRIVATE, f.fd, 0); /* for the header walk only: the readers pread */
-            if (m == MAP_FAILED) return unsupported("gzip input", f.path);
-            f.map = (const u8 *)m;
-            f.comp_n = (u64)gst.st_size;
-            if (infl::bgzf_header(f.map, f.comp_n, 0, &hdr, &bsize)) return unsupported("gzip input", f.path);
-            f.gz = true;
-            /* the text's size is known when the chain is walked, behind the transfer: the arena is sized for five times the file (FASTA
-             * at level 6: four); a text that does not fit gets a piece of its own */
-            total_bytes += ((f.comp_n + 255) & ~255ull) + (f.comp_n * 5 + FX_TILE + 63) / FX_TILE * FX_TILE + 64;
-            continue;
-        }
-        f.fd = open(f.path.c_str(), O_RDONLY);
-        if (f.fd < 0) return unsupported("unreadable file", f.path);
-        struct stat st;
-        char first = 0;
-        if (fstat(f.fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 1 || pread(f.fd, &first, 1, 0) != 1 || pread(f.fd, &f.last, 1, st.st_size - 1) != 1)
-            return unsupported("empty or unreadable file", f.path);
-        if (first != '>' && first != '@') return unsupported("neither FASTA nor FASTQ", f.path);
-        f.fastq = first == '@';
-        f.n = (u64)st.st_size;
-        f.text_cap = (f.n + FX_TILE + 63) / FX_TILE * FX_TILE + 64; /* whole tiles (16-byte loads) and aligned 8-byte words behind the end */
-        total_bytes += f.text_cap;
+    IngestJob job(c, n_files, host_threads);
+    int rc = ingest_open(job, paths);
+    if (rc == DISCO_OK) rc = ingest_choose_arena(job);
+    const float t_arena = job.seconds();
+    for (int fi = 0; fi < n_files && rc == DISCO_OK; fi++) { /* every file: its text into HBM, its records, clean + filter */
+        IngestFile &f = job.F[(size_t)fi];
+        rc = ingest_text(job, f);
+        if (rc == DISCO_OK) rc = ingest_records(job, f);
+        if (rc == DISCO_OK) rc = ingest_filter(job, f, &files[fi]);
     }
-    /* ---- the arena. The transient buffers of this stage (text, record arrays) come out of ONE allocation. Where memory is plentiful it
-     * is the stage's own (kept by the context: freeing 10 GB right before the pass made the pass's first allocations take 0.6 s), and the
-     * hit buffer the probe will want — 64 candidate slots per read, 28 GB at 50 M reads, 0.5-0.9 s of hipMalloc — is allocated by a
-     * thread of its own while the files travel to HBM and the filter runs. Where it is not (2 x 10^8 reads on one GPU), the arena IS
-     * the hit buffer, as in round 3: the text lives where the candidates will. A previous pass's results are gone either way. */
-    if (c->phase > 1) c->phase = 1;
-    c->d_adj = nullptr;
-    c->adj_total = 0;
-    settle_hits_prealloc(c);
-    {
-        /* hit entries: 64 per read as the probe will ask, a chunk per resident wave; reads estimated at one per 150 bytes of text (shorter
-         * records: the probe grows the buffer itself) */
-        const u64 want = (total_bytes / 150) * 64 + (u64)c->n_cu * 32 * PR_CHUNK + (1u << 16);
-        const u64 own_bytes = total_bytes + (total_bytes / 100) * 28 + (64ull << 20); /* text + record arrays (a record per 100 bytes at worst here; more: pieces of their own) */
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
-            cleanup();
-            return fail(c, DISCO_E_HIP, "disco_ingest_fasta: hipMemGetInfo failed");
-        }
-        const u64 rest = (total_bytes / 150) * 200 + (4ull << 30); /* the read table and the index next to it */
-        if (c->arena.base && !c->comm && c->arena.used == 0 && !c->d_ingest) { /* the last call's arena, idle again: this call's text goes there */
-            /* (counted as one buffer again: the handover below took it out of the sum) */
-            adopt(c, c->d_ingest, DevBuf<u8>{(u8 *)c->arena.base, c->arena.size});
-            c->arena = DevArena();
-            c->hbm_peak = std::max(c->hbm_peak, c->hbm_bytes);
-        }
-        const bool split = !getenv("DISCO_INGEST_SHARED_ARENA") && !c->arena.base && (u64)fr + c->d_hits.cap * 8 + c->d_ingest.cap > std::max(want, c->d_hits.cap) * 8 + own_bytes + rest + (16ull << 30);
-        if (split) {
-            if (own_bytes > c->d_ingest.cap && ensure(c, c->d_ingest, own_bytes) != DISCO_OK) c->err.clear();
-            if (want > c->d_hits.cap && c->d_ingest.cap) {
-                const int dev = c->device;
-                disco_ctx *cc = c;
-                c->hits_prealloc = std::thread([cc, dev, want]() {
-                    void *p = nullptr;
-                    if (hipSetDevice(dev) == hipSuccess && hipMalloc(&p, want * 8) == hipSuccess) {
-                        cc->prealloc = DevBuf<u64>{(u64 *)p, want};
-                    } else
-                        (void)hipGetLastError();
-                });
-            }
-        }
-        if (split && c->d_ingest.cap) {
-            arena.base = c->d_ingest;
-            arena.cap = c->d_ingest.cap;
-        } else {
-            if (want > c->d_hits.cap && (u64)fr + c->d_hits.cap * 8 > want * 8 + rest && ensure(c, c->d_hits, want) != DISCO_OK) /* room for it next to the table and the index */
-                c->err.clear();
-            arena.base = (u8 *)c->d_hits.p;
-            arena.cap = c->d_hits.cap * 8;
-        }
-    }
-    const float t_arena = ms_since(t_begin) * 1e-3f;
-    int rc = DISCO_OK;
-    auto get = [&](auto **pp, u64 count) -> int { /* from the arena, or an allocation of its own */
-        using T = typename std::remove_pointer<typename std::remove_pointer<decltype(pp)>::type>::type;
-        const size_t bytes = std::max<u64>(count, 1) * sizeof(T);
-        *pp = (T *)arena.take(bytes);
-        if (*pp) return DISCO_OK;
-        if (hipMalloc((void **)pp, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, DISCO_E_NOMEM, "disco_ingest_fasta: out of device memory");
-        }
-        c->hbm_bytes += bytes;
-        owned.push_back({(void *)*pp, bytes});
-        return DISCO_OK;
-    };
-    FxTables tb;
-    ingest_tables(&tb);
-    u64 *d_ctr = nullptr;
-    if ((rc = get(&d_ctr, (u64)FX_CTR_COUNT)) != DISCO_OK) {
-        cleanup();
-        return rc;
-    }
-    u64 total_records = 0, n_good = 0, too_long = 0;
-    u32 longest = 0, shortest = 0xFFFFu, short_max = 0;
-    u64 n_long_reads = 0;
-    float read_s = 0;
-    /* ---- pass A: every file into HBM, record starts, clean + filter ------------------------------------------------------------ */
-    for (int fi = 0; fi < n_files; fi++) {
-        IngestFile &f = F[(size_t)fi];
-        const auto t_read = HClock::now();
-        std::string gz_why;
-        /* a BGZF file: the file into HBM while a host thread walks its member chain; then one wavefront per member writes the text */
-        auto gz_stage = [&]() -> int {
-            CHK(get(&f.d_comp, f.comp_n));
-            std::vector<infl::BgzfBlock> blocks;
-            uint64_t total = 0, bad = 0;
-            const char *why = nullptr;
-            float walk_ms = 0;
-            std::thread walker([&]() {
-                const auto t0 = HClock::now();
-                why = infl::bgzf_walk(f.map, f.comp_n, blocks, &total, &bad);
-                walk_ms = ms_since(t0);
-            });
-            const int rrc = ingest_read_file(c, f.fd, f.comp_n, f.d_comp, host_threads ? host_threads : 16u);
-            walker.join();
-            read_s += ms_since(t_read) * 1e-3f;
-            CHK(rrc);
-            char msg[160];
-            if (why || total == 0) {
-                snprintf(msg, sizeof msg, "gzip input, member %llu: %s", (unsigned long long)bad, why ? why : "no text");
-                gz_why = msg;
-                return DISCO_E_UNSUPPORTED;
-            }
-            const auto t_inf = HClock::now();
-            f.n = total;
-            f.text_cap = (f.n + FX_TILE + 63) / FX_TILE * FX_TILE + 64;
-            infl::BgzfBlock *d_blk = nullptr;
-            u32 *d_status = nullptr;
-            CHK(get(&f.d_text, f.text_cap));
-            CHK(get(&d_blk, blocks.size()));
-            CHK(get(&d_status, blocks.size() + 1));
-            HIPCHK(c, hipMemsetAsync(f.d_text + f.n, 0, f.text_cap - f.n, c->stream));
-            int e = infl::INFL_OK;
-            CHK(bgzf_inflate_run(c, f.d_comp, blocks, d_blk, d_status, f.d_text, &bad, &e));
-            if (e != infl::INFL_OK) {
-                snprintf(msg, sizeof msg, "BGZF member %llu: %s", (unsigned long long)bad, infl::reason(e));
-                gz_why = msg;
-                return DISCO_E_UNSUPPORTED;
-            }
-            char first = 0;
-            HIPCHK(c, hipMemcpy(&first, f.d_text, 1, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(&f.last, f.d_text + f.n - 1, 1, hipMemcpyDeviceToHost));
-            if (getenv("DISCO_VERBOSE"))
-                fprintf(stderr, "[disco] BGZF %s: %.1f MB in %llu members -> %.1f MB of text; header walk %.1f ms (behind the transfer), inflate %.1f ms\n", f.path.c_str(), f.comp_n / 1e6,
-                        (unsigned long long)blocks.size(), f.n / 1e6, walk_ms, ms_since(t_inf));
-            if (first != '>' && first != '@') {
-                gz_why = "neither FASTA nor FASTQ";
-                return DISCO_E_UNSUPPORTED;
-            }
-            f.fastq = first == '@';
-            return DISCO_OK;
-        };
-        if (f.gz) {
-            rc = gz_stage();
-            if (rc == DISCO_E_UNSUPPORTED && !gz_why.empty()) return unsupported(gz_why.c_str(), f.path);
-        } else {
-            if ((rc = get(&f.d_text, f.text_cap)) == DISCO_OK && hipMemsetAsync(f.d_text + f.n, 0, f.text_cap - f.n, c->stream) != hipSuccess) rc = DISCO_E_HIP;
-            if (rc == DISCO_OK) rc = ingest_read_file(c, f.fd, f.n, f.d_text, host_threads ? host_threads : 16u);
-            read_s += ms_since(t_read) * 1e-3f;
-        }
-        const u64 tiles = (f.n + FX_TILE - 1) / FX_TILE;
-        u64 *d_tile_base = nullptr;
-        u32 *d_tile_cnt = nullptr;
-        auto body = [&]() -> int {
-            CHK(get(&d_tile_base, tiles + 1));
-            CHK(get(&d_tile_cnt, tiles));
-            HIPCHK(c, hipMemsetAsync(d_ctr, 0, FX_CTR_COUNT * sizeof(u64), c->stream));
-            if (f.fastq) {
-                u64 n_newlines = 0;
-                hipLaunchKernelGGL(fx_lines_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, d_tile_cnt, (const u64 *)nullptr, (u64 *)nullptr);
-                CHK((scan_exclusive<u32, u64>(c, d_tile_cnt, tiles, d_tile_base, false, &n_newlines)));
-                const u64 n_lines = n_newlines + (f.last == '\n' ? 0 : 1); /* a last line without a newline is a line */
-                f.n_start = (n_lines + 3) / 4; /* the reference starts a record whenever bytes are left (BG/Dataset.cpp:255-293) */
-                f.n_rec = f.n_start;
-            } else {
-                hipLaunchKernelGGL(fx_starts_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, d_tile_cnt, (const u64 *)nullptr, (u64 *)nullptr, d_ctr);
-                CHK((scan_exclusive<u32, u64>(c, d_tile_cnt, tiles, d_tile_base, false, &f.n_start)));
-                /* a '>' that is the very last byte starts nothing (the reference's next getline fails) unless it is the only one; it still
-                 * ends the sequence of the record before it (disco_amd/host/fastx.cpp) */
-                f.n_rec = (f.n_start > 1 && f.last == '>') ? f.n_start - 1 : f.n_start;
-            }
-            if (f.n_start == 0 || f.n_start >= (1ull << 32)) return DISCO_E_UNSUPPORTED;
-            CHK(get(&f.d_start, f.n_start));
-            CHK(get(&f.d_seq, f.n_rec));
-            CHK(get(&f.d_glen, f.n_rec));
-            CHK(get(&f.d_wrap, f.n_rec));
-            if (f.fastq) hipLaunchKernelGGL(fx_lines_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, (u32 *)nullptr, (const u64 *)d_tile_base, f.d_start);
-            else hipLaunchKernelGGL(fx_starts_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, (u32 *)nullptr, (const u64 *)d_tile_base, f.d_start, d_ctr);
-            FxFilterArgs fa;
-            fa.text = f.d_text;
-            fa.n = f.n;
-            fa.start = f.d_start;
-            fa.n_start = f.n_start;
-            fa.n_rec = f.n_rec;
-            fa.min_overlap = c->prm.min_overlap;
-            fa.fastq = f.fastq ? 1u : 0u;
-            fa.glen = f.d_glen;
-            fa.seq_begin = f.d_seq;
-            fa.wrap = f.d_wrap;
-            fa.ctr = d_ctr;
-            hipLaunchKernelGGL(fx_filter_kernel, dim3(flat_grid(c, f.n_rec)), dim3(256), 0, c->stream, fa, tb);
-            HIPCHK(c, hipGetLastError());
-            u64 h[FX_CTR_COUNT];
-            HIPCHK(c, hipMemcpyAsync(h, d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (h[FX_CTR_BAD_GT] || h[FX_CTR_MULTILINE]) return DISCO_E_UNSUPPORTED;
-            f.good = h[FX_CTR_GOOD];
-            too_long += h[FX_CTR_TOO_LONG];
-            if (f.good) {
-                longest = std::max(longest, (u32)h[FX_CTR_MAX_LEN]);
-                shortest = std::min(shortest, 0xFFFFu - (u32)h[FX_CTR_MIN_LEN_INV]);
-                n_long_reads += h[FX_CTR_N_LONG];
-                short_max = std::max(short_max, (u32)h[FX_CTR_SHORT_MAX]);
-            }
-            return DISCO_OK;
-        };
-        if (rc == DISCO_OK) rc = body();
-        if (rc == DISCO_E_UNSUPPORTED) return unsupported("a '>' inside a line, an irregularly wrapped long record, or no record", f.path);
-        if (rc != DISCO_OK) {
-            cleanup();
-            return rc;
-        }
-        files[fi].first_index = total_records + 1;
-        files[fi].last_index = total_records + f.n_rec;
-        files[fi].good = f.good;
-        files[fi].bad = f.n_rec - f.good;
-        total_records += f.n_rec;
-        n_good += f.good;
-    }
-    if (n_good == 0 || n_good >= (1ull << 31)) return unsupported("no good read (or more than 2^31)", F[0].path);
-    /* ---- pass B: ids in file order, rows of the read table -------------------------------------------------------------------- */
-    const uint32_t stride_words = std::max<u32>(1, (longest + 31) / 32), dstride = (stride_words + 7u) & ~7u;
-    auto pass_b = [&]() -> int {
-        DevBuf<u64> keep_hits = c->d_hits; /* set_reads_common may drop the graph state of a read set of another shape: the arena must survive it */
-        c->d_hits = DevBuf<u64>();
-        bool kept = false;
-        /* a few long reads among short ones: the rows are packed per class straight from the text (two classes of rows, disco_kernels.h) —
-         * the table of one stride, n rows as wide as the longest read, is never made */
-        const bool classes = two_class_ok(c, (int)dstride, n_good, n_long_reads, short_max, true);
-        const int src = set_reads_common(c, n_good, classes ? (uint32_t)VERIFY_SW : dstride, classes ? nullptr : &kept);
-        c->d_hits = keep_hits;
-        CHK(src);
-        c->reads_owned = true; /* (as in upload_reads_impl: only now) */
-        if (classes) {
-            CHK(alloc_reads(c, (n_good + n_long_reads) * 8, n_good));
-            CHK(two_class_alloc(c, n_long_reads, (int)dstride, short_max));
-        } else if (!kept)
-            CHK(alloc_reads(c, n_good * (u64)dstride, n_good));
-        c->reads_owned = true;
-        CHK(ensure(c, c->d_rec_of_read, n_good));
-        c->ingest_id_base.assign((size_t)n_files + 1, 0);
-        c->ingest_rec_base.assign((size_t)n_files + 1, 0);
-        u64 max_rec = 0;
-        for (auto &f : F) max_rec = std::max(max_rec, f.n_rec);
-        u64 *d_pos = nullptr;
-        u8 *d_flag = nullptr;
-        CHK(get(&d_pos, max_rec + 1));
-        CHK(get(&d_flag, max_rec));
-        u64 id_base = 0, rec_base = 0;
-        for (int fi = 0; fi < n_files; fi++) {
-            IngestFile &f = F[(size_t)fi];
-            c->ingest_id_base[(size_t)fi] = id_base;
-            c->ingest_rec_base[(size_t)fi] = rec_base;
-            hipLaunchKernelGGL(fx_flags_kernel, dim3(flat_grid(c, f.n_rec)), dim3(256), 0, c->stream, (const u16 *)f.d_glen, f.n_rec, d_flag);
-            u64 good = 0;
-            CHK((scan_exclusive<u8, u64>(c, d_flag, f.n_rec, d_pos, false, &good)));
-            if (good != f.good) return fail(c, DISCO_E_STATE, "disco_ingest_fasta: %llu good reads counted, %llu placed", (unsigned long long)f.good, (unsigned long long)good);
-            hipLaunchKernelGGL(fx_ids_kernel, dim3(flat_grid(c, f.n_rec)), dim3(256), 0, c->stream, (const u16 *)f.d_glen, (const u64 *)d_pos, f.n_rec, id_base, c->d_rec_of_read, c->d_len);
-            if (f.good)
-                hipLaunchKernelGGL(fx_pack_kernel, dim3(flat_grid(c, f.good * (u64)c->S)), dim3(256), 0, c->stream, (const u8 *)f.d_text, (const u64 *)f.d_seq, (const u32 *)f.d_wrap, (const u32 *)c->d_rec_of_read,
-                                   (const u16 *)c->d_len, id_base, f.good, c->S, classes ? (u32)DISCO_SHORT_MAX : 0xFFFFu, c->d_reads);
-            HIPCHK(c, hipGetLastError());
-            id_base += f.good;
-            rec_base += f.n_rec;
-        }
-        c->ingest_id_base[(size_t)n_files] = id_base;
-        c->ingest_rec_base[(size_t)n_files] = rec_base;
-        if (classes) { /* every read has its id and length: number the long ones, then their full and tail rows, file by file */
-            hipLaunchKernelGGL(class_flag_kernel, dim3(flat_grid(c, n_good)), dim3(256), 0, c->stream, (const u16 *)c->d_len, n_good, c->d_ovf, c->d_ctr);
-            u64 counted = 0;
-            CHK((scan_exclusive<u32, u32>(c, c->d_ovf, n_good, c->d_ovf, false, &counted)));
-            if (counted != n_long_reads) return fail(c, DISCO_E_STATE, "disco_ingest_fasta: %llu long reads counted, %llu placed", (unsigned long long)n_long_reads, (unsigned long long)counted);
-            hipLaunchKernelGGL(class_ids_kernel, dim3(flat_grid(c, n_good)), dim3(256), 0, c->stream, (const u16 *)c->d_len, (const u32 *)c->d_ovf, n_good, c->d_long_ids);
-            for (int fi = 0; fi < n_files; fi++) {
-                IngestFile &f = F[(size_t)fi];
-                if (!f.good) continue;
-                hipLaunchKernelGGL(fx_pack_long_kernel, dim3(flat_grid(c, n_long_reads * ((u64)dstride + 8))), dim3(256), 0, c->stream, (const u8 *)f.d_text, (const u64 *)f.d_seq, (const u32 *)f.d_wrap,
-                                   (const u32 *)c->d_rec_of_read, (const u16 *)c->d_len, c->ingest_id_base[(size_t)fi], f.good, (const u32 *)c->d_long_ids, n_long_reads, n_good, (int)dstride, c->tailb,
-                                   c->d_full, c->d_reads);
-            }
-            HIPCHK(c, hipGetLastError());
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return DISCO_OK;
-    };
-    const float t_pass_a = ms_since(t_begin) * 1e-3f;
-    rc = pass_b();
-    cleanup();
+    const float t_filtered = job.seconds();
+    if (rc == DISCO_OK) rc = ingest_build_table(job);
+    if (rc == INGEST_DECLINED) return fail(c, DISCO_E_UNSUPPORTED, "disco_ingest_fasta: %s (%s): the host input stage takes this job", job.why.c_str(), job.where.c_str());
     CHK(rc);
     if (getenv("DISCO_VERBOSE"))
-        fprintf(stderr, "[disco] input stage: arena of %.1f GB %.3f s, files + records + filter %.3f s (files %.3f), table + ids + rows %.3f s\n", arena.cap / 1e9, t_arena,
-                t_pass_a - t_arena, read_s, ms_since(t_begin) * 1e-3f - t_pass_a);
-    /* the stage's own arena is free space from here on: the context's allocator serves the pass from it (its index, headers, adjacency
-     * and result buffers: a dozen device allocations of 5-10 ms each that the first pass of a fresh context otherwise waits for) */
-    if (c->d_ingest && arena.base == c->d_ingest && owned.empty() && !getenv("DISCO_NO_ARENA_HANDOVER")) {
-        c->arena = DevArena();
-        c->arena.size = c->d_ingest.cap & ~(u64)255;
-        c->arena.free_at[0] = c->arena.size;
-        /* what the allocator serves out of it is counted buffer by buffer (dev_alloc): the arena itself leaves the sum, or every byte of
-         * it would count twice in hbm_bytes / hbm_peak */
-        c->arena.base = (char *)disown(c, c->d_ingest);
-    }
-    c->ingest_n = n_good;
-    if (c->two_class) {
-        c->max_len_all = longest;
-        c->max_len = short_max;
-    } else
-        c->max_len = longest;
-    c->min_len = shortest;
+        fprintf(stderr, "[disco] input stage: arena of %.1f GB %.3f s, files + records + filter %.3f s (files %.3f), table + ids + rows %.3f s\n", job.arena_cap / 1e9, t_arena,
+                t_filtered - t_arena, job.read_s, job.seconds() - t_filtered);
+    ingest_hand_over_arena(job);
+    const ReadShape &s = job.shape;
+    c->ingest_n = s.n;
     c->h_len_ok = false;
     c->phase = 1;
-    info->n_reads = n_good;
-    info->total_records = total_records;
-    info->too_long = too_long;
-    info->stride_words = stride_words;
-    info->shortest = shortest;
-    info->longest = longest;
-    info->read_s = read_s;
-    info->device_s = ms_since(t_begin) * 1e-3f - read_s;
+    *info = disco_ingest_info{.n_reads = s.n, .total_records = job.total_records, .too_long = job.too_long, .stride_words = std::max<u32>(1, (s.longest + 31) / 32),
+                              .shortest = s.shortest, .longest = s.longest, .read_s = job.read_s, .device_s = job.seconds() - job.read_s};
     return DISCO_OK;
 }
 
@@ -2591,24 +2627,27 @@ int disco_adopt_reads(disco_ctx *c, const void *d_packed, uint32_t stride_words,
     return validate_reads(c);
 }
 
+/* the generator's spec as its kernel takes it, checked, and the stride of the table it fills (words; 64-byte rows) */
+static int gen_spec(disco_ctx *c, const char *who, const disco_genspec_abi *s, disco_genspec *g, uint32_t *stride)
+{
+    memcpy(g, s, sizeof *g);
+    const uint32_t longest = std::max<uint32_t>(s->len_max, DISCO_GEN_LONG_SHARE(g) ? DISCO_GEN_LONG_LEN(g) : 0u);
+    if (s->len_min == 0 || s->len_max < s->len_min || longest > 32767 || s->n_contigs == 0 || s->contig_len < longest) return fail(c, DISCO_E_ARG, "%s: bad spec", who);
+    *stride = (((longest + 31) / 32) + 7u) & ~7u;
+    return DISCO_OK;
+}
+
 int disco_generate_reads(disco_ctx *c, const disco_genspec_abi *s)
 {
     DISCO_TRACE("disco_generate_reads");
     if (!c || !s) return c ? fail(c, DISCO_E_ARG, "disco_generate_reads: null argument") : DISCO_E_ARG;
-    disco_genspec gs;
-    memcpy(&gs, s, sizeof gs);
-    const uint32_t longest = std::max<uint32_t>(s->len_max, DISCO_GEN_LONG_SHARE(&gs) ? DISCO_GEN_LONG_LEN(&gs) : 0u);
-    if (s->len_min == 0 || s->len_max < s->len_min || longest > 32767 || s->n_contigs == 0 || s->contig_len < longest)
-        return fail(c, DISCO_E_ARG, "disco_generate_reads: bad spec");
-    HIPCHK(c, hipSetDevice(c->device));
-    uint32_t stride = (((longest + 31) / 32) + 7u) & ~7u; /* 64-B aligned rows */
-    bool kept = false;
-    CHK(set_reads_common(c, s->n_reads, stride, &kept));
-    if (!kept) CHK(alloc_reads(c, c->n * (u64)stride, c->n));
-    c->reads_owned = true;
     disco_genspec g;
-    memcpy(&g, s, sizeof g);
-    if (c->n) hipLaunchKernelGGL(generate_reads_kernel, dim3(flat_grid(c, c->n * stride)), dim3(256), 0, c->stream, g, c->d_reads, c->d_len, (int)stride, (u64)0, c->n);
+    ReadShape shape; /* (one stride here: a tail of long reads is converted at the index build, after whatever edits the table) */
+    CHK(gen_spec(c, "disco_generate_reads", s, &g, &shape.stride));
+    HIPCHK(c, hipSetDevice(c->device));
+    shape.n = s->n_reads;
+    CHK(begin_read_table(c, shape));
+    if (c->n) hipLaunchKernelGGL(generate_reads_kernel, dim3(flat_grid(c, c->n * shape.stride)), dim3(256), 0, c->stream, g, c->d_reads, c->d_len, (int)shape.stride, (u64)0, c->n);
     HIPCHK(c, hipGetLastError());
     return validate_reads(c);
 }
@@ -2667,34 +2706,6 @@ int disco_set_query_range(disco_ctx *c, uint64_t lo, uint64_t hi)
 /* one stride -> two classes of rows (disco_kernels.h), at the first index build over the table: everything that edits a table (the
  * generator's substitutions) has been and gone by then. The decision is the device's own count of the long reads; the table that is
  * given up goes back to the allocator. */
-/* the long class's buffers for a table of n_long long reads of stride Sx whose short class has reads of up to short_max bases; the rows
- * themselves (d_reads: [n + n_long][8]) are the caller's */
-static int two_class_alloc(disco_ctx *c, u64 n_long, int Sx, u32 short_max)
-{
-    /* (the sizes first: free_long_class accounts with them, also for what a failure below leaves behind) */
-    c->n_long = n_long;
-    c->S_ext = Sx;
-    int rc = DISCO_OK;
-    rc = ensure(c, c->d_ovf, c->n_alloc);
-    if (rc == DISCO_OK) rc = ensure(c, c->d_full, n_long * (u64)Sx);
-    if (rc == DISCO_OK) rc = ensure(c, c->d_long_ids, n_long);
-    if (rc == DISCO_OK) rc = ensure(c, c->d_lpos, n_long);
-    if (rc == DISCO_OK) rc = ensure(c, c->d_lmeta, n_long);
-    if (rc == DISCO_OK) rc = ensure(c, c->d_linfo, n_long);
-    if (rc == DISCO_OK) rc = ensure(c, c->d_n_list, 1);
-    if (rc != DISCO_OK) {
-        free_long_class(c);
-        return rc;
-    }
-    c->S = VERIFY_SW;
-    c->tailb = short_max <= 160 ? 160 : 256; /* what the staged compare of the short class moves per row (verify_flat_kernel<5 / 8>) */
-    c->two_class = true;
-    if (getenv("DISCO_VERBOSE"))
-        fprintf(stderr, "[disco] two classes of rows: %llu of %llu reads are longer than 256 bases, the others up to %u: 64-byte rows + %d-word rows for those\n",
-                (unsigned long long)n_long, (unsigned long long)c->n, short_max, Sx);
-    return DISCO_OK;
-}
-
 static int two_class_convert(disco_ctx *c)
 {
     if (c->two_class || !c->n || c->max_len <= (u32)DISCO_SHORT_MAX || !two_class_ok(c, c->S, c->n, 1, (u32)c->k + 1)) return DISCO_OK; /* (cheap part first) */
@@ -2702,9 +2713,8 @@ static int two_class_convert(disco_ctx *c)
     DevBuf<u32> ovf;
     CHK(ensure(c, ovf, c->n_alloc));
     CHK(zero_counter(c, CTR_SHORT_MAX));
-    hipLaunchKernelGGL(class_flag_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_len, c->n, ovf.p, c->d_ctr);
     u64 n_long = 0;
-    CHK((scan_exclusive<u32, u32>(c, ovf, c->n, ovf, false, &n_long)));
+    CHK(number_long_reads(c, ovf, nullptr, &n_long)); /* (class_split_kernel writes the ids) */
     CHK(read_counters(c));
     const u32 short_max = (u32)c->h_ctr[CTR_SHORT_MAX];
     if (!two_class_ok(c, Sx, c->n, n_long, short_max)) {
@@ -2727,8 +2737,7 @@ static int two_class_convert(disco_ctx *c)
     release(c, c->reads_own);
     c->reads_own = rows8;
     c->d_reads = c->reads_own;
-    c->max_len_all = c->max_len;
-    c->max_len = short_max;
+    set_read_lengths(c, c->max_len, short_max, c->min_len);
     return DISCO_OK;
 }
 
@@ -5494,17 +5503,14 @@ int disco_dist_range(const disco_ctx *c, uint64_t n_total, uint64_t *lo, uint64_
 static int dist_set_reads(disco_ctx *c, u64 n_total, uint32_t dstride)
 {
     if (!c->comm) return fail(c, DISCO_E_STATE, "no communicator: call disco_comm_init / disco_comm_init_local first");
-    CHK(set_reads_common(c, n_total, dstride));
     u64 per, lo, hi;
     dist_range(c, n_total, &per, &lo, &hi);
+    CHK(begin_rows(c, n_total, per * (u64)c->comm->world, 0, dstride, false));
     c->per = per;
-    c->n_alloc = per * (u64)c->comm->world;
     c->q_lo = c->home_lo = lo;
     c->q_hi = c->home_hi = hi;
-    CHK(alloc_reads(c, c->n_alloc * (u64)dstride, c->n_alloc));
     /* unused words of a row are zero (disco_device.h): the other ranks' rows arrive at their used words only */
     HIPCHK(c, hipMemsetAsync(c->d_reads, 0, c->n_alloc * (u64)dstride * 8, c->stream));
-    c->reads_owned = true;
     c->dist_reads = true;
     return DISCO_OK;
 }
@@ -5512,11 +5518,7 @@ static int dist_set_reads(disco_ctx *c, u64 n_total, uint32_t dstride)
 static int dist_validate(disco_ctx *c)
 {
     const u64 nloc = c->q_hi - c->q_lo;
-    CHK(zero_counter(c, CTR_BAD_LEN));
-    CHK(zero_counter(c, CTR_MAX_LEN));
-    CHK(zero_counter(c, CTR_MIN_LEN));
-    if (nloc) hipLaunchKernelGGL(validate_len_kernel, dim3(flat_grid(c, nloc)), dim3(256), 0, c->stream, c->d_len + c->q_lo, nloc, c->S, (int)c->prm.min_overlap, c->d_ctr);
-    CHK(read_counters(c));
+    CHK(count_lengths(c, c->q_lo, c->q_hi));
     /* the job's longest / shortest read (the shortest travels complemented, so both are a maximum over the ranks): every rank
      * then takes the same two-pass decision in disco_probe whatever its own reads or its context's history look like */
     u64 bad = c->h_ctr[CTR_BAD_LEN], ext[2] = {c->h_ctr[CTR_MAX_LEN], c->h_ctr[CTR_MIN_LEN]};
@@ -5575,12 +5577,9 @@ int disco_dist_generate_reads(disco_ctx *c, const disco_genspec_abi *s)
     DISCO_TRACE("disco_dist_generate_reads");
     if (!c || !s) return c ? fail(c, DISCO_E_ARG, "disco_dist_generate_reads: null argument") : DISCO_E_ARG;
     disco_genspec g;
-    memcpy(&g, s, sizeof g);
-    const uint32_t longest = std::max<uint32_t>(s->len_max, DISCO_GEN_LONG_SHARE(&g) ? DISCO_GEN_LONG_LEN(&g) : 0u);
-    if (s->len_min == 0 || s->len_max < s->len_min || longest > 32767 || s->n_contigs == 0 || s->contig_len < longest)
-        return fail(c, DISCO_E_ARG, "disco_dist_generate_reads: bad spec");
+    uint32_t stride = 0;
+    CHK(gen_spec(c, "disco_dist_generate_reads", s, &g, &stride));
     HIPCHK(c, hipSetDevice(c->device));
-    const uint32_t stride = (((longest + 31) / 32) + 7u) & ~7u;
     CHK(dist_set_reads(c, s->n_reads, stride));
     const u64 nloc = c->q_hi - c->q_lo;
     if (nloc) hipLaunchKernelGGL(generate_reads_kernel, dim3(flat_grid(c, nloc * stride)), dim3(256), 0, c->stream, g, c->d_reads, c->d_len, (int)stride, c->q_lo, c->q_hi);

@@ -1,15 +1,16 @@
 """differential fuzzing: HIP path (C-ABI) vs the CPU oracle on random generator settings.
    python tools/fuzz_parity.py [ITERATIONS=50] [SEED=1] [inexact | runs]
    with "inexact": every data set gets sequencing errors and a random substitution threshold (the f-4 extension, checked against
-   the oracle's statement of the same rule, substitutions per edge included); with "runs": min-overlap 30 / 35 / 40 / 45 / 50 and reads of up to 256 bases
-   throughout — the shapes that take the minimizer runs of the index pass (index_runs_kernel / probe_runs_kernel), low-complexity and
+   the oracle's statement of the same rule, substitutions per edge included); with "runs": every min-overlap from 19 to 95 (every window of
+   2 .. 64 m-mers) and reads of up to 256 bases throughout — the shapes that can take the minimizer runs of the index pass (index_runs_kernel /
+   probe_runs_kernel; a shape the rule of runs_lpr_for gives none is still a case: the `ok` line tells the run words), low-complexity and
    repeat genomes (ties of the window minimum: reads handed to probe_kernel's list pass) more often"""
 import os, sys, time, traceback
 os.environ.setdefault('DISCO_ORDER_MIN_READS', '1')  # the grouped verify order on every data set, however small
 sys.path.insert(0, '.')
 import numpy as np
 from disco_amd import readgen
-from tests.util import assert_parity
+from tests.util import assert_parity, low_complexity
 
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -20,14 +21,15 @@ fails = 0
 t0 = time.time()
 for it in range(iters):
     lmin = int(rng.choice([45, 60, 80, 100, 150, 151, 168, 200, 256, 257, 300, 500, 1000, 1025, 2000, 5000]))
-    lmax = lmin if rng.random() < 0.4 else int(lmin + rng.integers(1, 2 * lmin))
-    mo = int(rng.choice([31, 32, 33, 40, 41, 50, 64, 65, 66, 80, 88, 95]))  # (round 4: k up to 94)
+    mo = int(rng.integers(18, 96))  # every legal value: k = 17 .. 94, windows of 1 .. 64 m-mers, minimizers of 17 .. 31 bases
     if runs:
         lmin = int(rng.choice([45, 60, 80, 100, 128, 150, 151, 167, 168, 200, 250, 256]))
-        lmax = lmin if rng.random() < 0.4 else int(min(256, lmin + rng.integers(1, 2 * lmin)))
-        mo = int(rng.choice([40, 40, 30, 35, 45, 50]))  # the window lengths index_runs_kernel is built for
+        mo = int(rng.integers(19, 96))  # (the specialised windows 7 / 12 / 17 / 22 / 27 and every run-time one)
     if mo >= lmin:
-        mo = max(31, lmin - 8)
+        lmin = mo + int(rng.integers(1, 41))  # (a short set: the only shape windows of 2 .. 4 m-mers get run lists for)
+    lmax = lmin if rng.random() < 0.4 else int(lmin + rng.integers(1, 2 * lmin))
+    if runs:
+        lmax = min(lmax, 256)
     cov = float(rng.choice([3, 8, 20, 30, 60, 120, 300, 700, 1500]))
     n = int(rng.integers(300, 9000))
     if cov >= 300:
@@ -60,10 +62,8 @@ for it in range(iters):
                 b[hit] = np.frombuffer(b"ACGT", dtype=np.uint8)[r2.integers(0, 4, int(hit.sum()))]
                 out.append(b.tobytes().decode())
             reads = out
-        if runs and rng.random() < 0.15:  # low-complexity stretches: the smallest m-mer hash of a window ties
-            r4 = np.random.default_rng(seed + 2)
-            units = ["AC", "AAT", "ACGT", "A", "AGGC", "ACACG"]
-            reads = [(s[:int(len(s) * 0.3)] + (units[int(r4.integers(0, len(units)))] * 200)[:int(len(s) * 0.4)] + s[int(len(s) * 0.7):]) if r4.random() < 0.3 else s for s in reads]
+        if runs and rng.random() < 0.25:  # low-complexity stretches: the smallest m-mer hash of a window ties — at every window length
+            reads = low_complexity(reads, np.random.default_rng(seed + 2))
             label += " lowcomplexity"
         if rng.random() < (0.35 if runs else 0.2):  # a genome with repeat copies: duplicate destinations, the per-k-mer cap, one-sided pairs
             r3 = np.random.default_rng(seed + 1)
@@ -84,8 +84,10 @@ for it in range(iters):
         if rng.random() < 0.2:  # exact and reverse-complement duplicates
             comp = str.maketrans("ACGT", "TGCA")
             reads += [reads[i] if rng.random() < 0.5 else reads[i].translate(comp)[::-1] for i in rng.integers(0, len(reads), len(reads) // 10)]
-        c = assert_parity(reads, mo, label, max_substitutions=tsub)
-        print("ok  ", label, "e_pre", c["e_pre"], "e_out", c["e_out"], "contained", c["n_contained"], "cap", c["cap_bind_sites"], "asym", c["asymmetric_pairs"], flush=True)
+        seen = {}
+        c = assert_parity(reads, mo, label, max_substitutions=tsub, inspect=seen)
+        print("ok  ", label, "e_pre", c["e_pre"], "e_out", c["e_out"], "contained", c["n_contained"], "cap", c["cap_bind_sites"], "asym", c["asymmetric_pairs"],
+              "probe_run_words", seen["probe_run_words"], flush=True)
     except Exception as e:
         fails += 1
         print("FAIL", label, repr(e)[:300], flush=True)

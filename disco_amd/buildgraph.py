@@ -111,6 +111,8 @@ ABI = [
     ("disco_ingest_fasta", C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, C.c_uint32, _P, _P]),
     ("disco_ingest_fetch", C.c_int, [_P, _P, _P]),
     ("disco_inflate_bgzf", C.c_int64, [_P, _P, C.c_uint64, _P, C.c_uint64]),
+    ("disco_dist_ingest_fasta", C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, C.c_uint32, _P, _P]),
+    ("disco_dist_ingest_fetch", C.c_int, [_P, _P, _P]),
 ]
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
@@ -132,6 +134,12 @@ class IngestFile(C.Structure):
 class IngestInfo(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("total_records", C.c_uint64), ("too_long", C.c_uint64), ("stride_words", C.c_uint32), ("shortest", C.c_uint32),
                 ("longest", C.c_uint32), ("read_s", C.c_float), ("device_s", C.c_float)]
+
+
+class DistIngestInfo(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("total_records", C.c_uint64), ("too_long", C.c_uint64), ("stride_words", C.c_uint32), ("shortest", C.c_uint32),
+                ("longest", C.c_uint32), ("world", C.c_uint32), ("share_lo", C.c_uint64), ("share_hi", C.c_uint64), ("share_reads", C.c_uint64),
+                ("kept_reads", C.c_uint64), ("home_lo", C.c_uint64), ("home_hi", C.c_uint64), ("read_s", C.c_float), ("device_s", C.c_float)]
 
 
 class DistInfo(C.Structure):
@@ -581,6 +589,25 @@ class BuildGraph:
         n = self.num_reads
         ln, fi = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint64)
         self._chk(self.L.disco_ingest_fetch(self._h, ln.ctypes.data, fi.ctypes.data))
+        return ln, fi
+
+    def dist_ingest_fasta(self, paths, threads: int = 4):
+        """the input stage on every rank (disco_dist_ingest_fasta, COLLECTIVE: every rank passes the same files). Returns (info dict,
+        per-file dicts), or None — on every rank — when any rank met an input the device stage declines (last_error() names the file
+        and the reason; the contexts stay usable: dist_upload_reads is next)"""
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+        info, files = DistIngestInfo(), (IngestFile * len(paths))()
+        rc = self.L.disco_dist_ingest_fasta(self._h, arr, len(paths), threads, C.byref(info), files)
+        if rc == -6:  # DISCO_E_UNSUPPORTED
+            return None
+        self._chk(rc)
+        return ({n: getattr(info, n) for n, _ in DistIngestInfo._fields_}, [{n: getattr(f, n) for n, _ in IngestFile._fields_} for f in files])
+
+    def dist_ingest_fetch(self):
+        """(lengths, 1-based file indices) of the rank's home range after dist_ingest_fasta"""
+        lo, hi = self.dist_range(self.num_reads)
+        ln, fi = np.zeros(hi - lo, dtype=np.uint16), np.zeros(hi - lo, dtype=np.uint64)
+        self._chk(self.L.disco_dist_ingest_fetch(self._h, ln.ctypes.data, fi.ctypes.data))
         return ln, fi
 
     def dist_run_graph(self, gather_reads: bool = True, partitioned_index: bool = False):

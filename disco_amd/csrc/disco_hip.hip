@@ -2056,7 +2056,8 @@ static int ingest_ring(disco_ctx *c)
     return ensure_copy_stream(c);
 }
 
-static int ingest_read_file(disco_ctx *c, int fd, u64 n, u8 *d_text, unsigned threads)
+/* file_off: the bytes [file_off, file_off + n) of the file; own_ring: a pinned ring of the caller's (own_ring_bytes in all) instead of the context's */
+static int ingest_read_file(disco_ctx *c, int fd, u64 n, u8 *d_text, unsigned threads, u64 file_off = 0, void *own_ring = nullptr, size_t own_ring_bytes = 0)
 {
     /* The file travels through a pinned ring of RING_SLOTS slots (256 MB in all, as the two halves of rounds 3-4 were): reader threads
      * that live as long as the file — no thread is started per slot — pread piece after piece, in file order, into the next slot that is
@@ -2064,10 +2065,12 @@ static int ingest_read_file(disco_ctx *c, int fd, u64 n, u8 *d_text, unsigned th
      * copy is through. With two halves the readers waited for the copy of the half before last before they could start (0.8 of every
      * 3.3 ms: `waiting for the ring` in the DISCO_VERBOSE line of round 4); with four slots reading runs ahead of the link. */
     constexpr unsigned RING_SLOTS = 4;
-    const size_t HALF = 128u << 20, SLOT = 2 * HALF / RING_SLOTS;
-    CHK(ingest_ring(c));
+    const size_t HALF = 128u << 20, SLOT = own_ring ? own_ring_bytes / RING_SLOTS : 2 * HALF / RING_SLOTS;
+    if (own_ring) CHK(ensure_copy_stream(c));
+    else CHK(ingest_ring(c));
+    char *const h_ring = own_ring ? (char *)own_ring : (char *)c->h_ring;
     /* (the ring's slots need an event each: ev_ring has two, the upload's ev_copied — idle here — the others) */
-    hipEvent_t ev[RING_SLOTS] = {c->ev_ring[0], c->ev_ring[1], c->ev_copied[0], c->ev_copied[1]};
+    hipEvent_t ev[RING_SLOTS] = {own_ring ? c->ev_copied[2] : c->ev_ring[0], own_ring ? c->ev_unpacked[1] : c->ev_ring[1], c->ev_copied[0], c->ev_copied[1]};
     /* SIX readers whatever -t says (round 6; DISCO_INGEST_THREADS: measurement): the link, not the page cache, is what the file waits for, and
      * every reader beyond what keeps the ring full only competes with the DMA engine for the host's memory — 8.1 GB into HBM in 155-160 ms
      * with 5-6 readers, 195-280 ms with 16, 165-300 with 3-4 (16-core host of this pool, four runs each: profiles/r06_experiments.txt H) */
@@ -2098,10 +2101,10 @@ static int ingest_read_file(disco_ctx *c, int fd, u64 n, u8 *d_text, unsigned th
                 }
                 const u64 off = k * (u64)SLOT;
                 const size_t len = (size_t)std::min<u64>(SLOT, n - off);
-                char *slot = (char *)c->h_ring + (k % RING_SLOTS) * SLOT;
+                char *slot = h_ring + (k % RING_SLOTS) * SLOT;
                 size_t p0 = len * piece / threads, p1 = len * (piece + 1) / threads;
                 while (p0 < p1 && ok.load()) {
-                    const ssize_t got = pread(fd, slot + p0, p1 - p0, (off_t)(off + p0));
+                    const ssize_t got = pread(fd, slot + p0, p1 - p0, (off_t)(file_off + off + p0));
                     if (got <= 0) {
                         ok.store(false);
                         break;
@@ -2130,7 +2133,7 @@ static int ingest_read_file(disco_ctx *c, int fd, u64 n, u8 *d_text, unsigned th
         if (!ok.load()) return fail(c, DISCO_E_ARG, "disco_ingest_fasta: read error");
         const u64 off = k * (u64)SLOT;
         const size_t len = (size_t)std::min<u64>(SLOT, n - off);
-        HIPCHK(c, hipMemcpyAsync(d_text + off, (char *)c->h_ring + (k % RING_SLOTS) * SLOT, len, hipMemcpyHostToDevice, c->copy_stream));
+        HIPCHK(c, hipMemcpyAsync(d_text + off, h_ring + (k % RING_SLOTS) * SLOT, len, hipMemcpyHostToDevice, c->copy_stream));
         HIPCHK(c, hipEventRecord(ev[k % RING_SLOTS], c->copy_stream));
         tw = HClock::now();
         if (k >= 1) { /* the copy before this one: through, its slot goes back to the readers (this copy is queued behind it already) */
@@ -5512,6 +5515,7 @@ static int dist_set_reads(disco_ctx *c, u64 n_total, uint32_t dstride)
     /* unused words of a row are zero (disco_device.h): the other ranks' rows arrive at their used words only */
     HIPCHK(c, hipMemsetAsync(c->d_reads, 0, c->n_alloc * (u64)dstride * 8, c->stream));
     c->dist_reads = true;
+    c->ingest_n = 0; /* (disco_dist_ingest_fasta sets it again behind this: only its reads have record numbers to fetch) */
     return DISCO_OK;
 }
 
@@ -5585,6 +5589,454 @@ int disco_dist_generate_reads(disco_ctx *c, const disco_genspec_abi *s)
     if (nloc) hipLaunchKernelGGL(generate_reads_kernel, dim3(flat_grid(c, nloc * stride)), dim3(256), 0, c->stream, g, c->d_reads, c->d_len, (int)stride, c->q_lo, c->q_hi);
     HIPCHK(c, hipGetLastError());
     return dist_validate(c);
+}
+
+/* ---- the device input stage on every rank (include/disco_hip.h: disco_dist_ingest_fasta; kernels: disco_ingest.h, "a PIECE of a file") ----
+ * Steps of one rank, with the three places where all ranks meet:
+ *   A  its pieces into HBM; FASTA: record starts; FASTQ: newlines of the owned bytes
+ *      -- all-gather: status word + newlines per (rank, file) --
+ *   B  FASTQ: record starts from the line phase; clean + filter of the piece's records
+ *      -- all-gather: status word + the per-piece figures --
+ *   C  every rank computes the job's shape, the per-file counts and the id of every piece's first good read; table of the job's shape
+ *      (dist_set_reads); lengths, record numbers and rows of the share at their global ids
+ *      -- all-gather: status word -- all-to-all of rows, lengths, record numbers: what lies outside the home range, to its owner
+ *   dist_validate (collective, as behind an upload)
+ * A local failure or decline never returns in front of the next meeting point: it travels in the status word, and everybody leaves
+ * behind that all-gather with the same code. */
+extern "C++" {
+namespace {
+enum { DI_OK = 0, DI_DECLINE = 1, DI_ERROR = 2 };
+enum { DR_GZ = 1, DR_UNREADABLE, DR_FORM, DR_IRREGULAR, DR_NO_READ, DR_LONG_RECORD, DR_COUNT };
+const char *const kDistDecline[DR_COUNT] = {"", "gzip input (a .gz name is the host stage's under a communicator)", "empty or unreadable file", "neither FASTA nor FASTQ",
+                                            kIngestIrregular, "no good read (or more than 2^31)", "a record of 2^21 bytes or more"};
+constexpr u64 DI_TAIL = 1ull << 21; /* bytes behind a piece: the rest of its last record (a longer one declines the file on one GPU too) */
+constexpr int DI_PER_PIECE = 7;     /* figures of a piece in the second all-gather */
+enum { DP_STARTS = 0, DP_GOOD, DP_TOO_LONG, DP_MAX_LEN, DP_MIN_LEN_INV, DP_N_LONG, DP_SHORT_MAX };
+
+struct IngestPiece {
+    u64 p0 = 0, p1 = 0;                /* the owned bytes of the file */
+    u64 own_lo = 0, own_hi = 0, n = 0; /* the same in the buffer, and the buffer's bytes */
+    bool to_eof = false;               /* the buffer reaches the end of the file */
+    bool prefix_nl = true, last_nl = false; /* the byte in front of the piece / its last byte is a newline */
+    u64 own_nl = 0, tiles = 0;
+    u64 *d_tile_base = nullptr, *d_ctr = nullptr;
+    u32 *d_tile_cnt = nullptr;
+    u64 fig[DI_PER_PIECE] = {0, 0, 0, 0, 0, 0, 0};
+    IngestFile d; /* the device arrays of the piece's records */
+};
+
+inline u64 di_status(int kind, int code, size_t file) { return ((u64)kind << 60) | ((u64)file << 16) | (u64)code; }
+
+/* n values per rank -> all[world][n], in calls of at most the communicator's staging */
+int di_gather(disco_ctx *c, const std::vector<u64> &mine, std::vector<u64> &all)
+{
+    const size_t G = (size_t)c->comm->world, n = mine.size(), STEP = RcclComm::SMALL_VALUES;
+    all.assign(G * n, 0);
+    std::vector<u64> part;
+    for (size_t at = 0; at < n; at += STEP) {
+        const size_t m = std::min(STEP, n - at);
+        part.resize(G * m);
+        COMM_CHK(c, c->comm->host_all_gather((const unsigned long long *)mine.data() + at, (int)m, (unsigned long long *)part.data(), c->stream));
+        for (size_t g = 0; g < G; g++) memcpy(&all[g * n + at], &part[g * m], m * 8);
+    }
+    return DISCO_OK;
+}
+
+struct DistIngest {
+    disco_ctx *c;
+    IngestJob job;
+    std::vector<IngestPiece> P;
+    std::vector<u64> size; /* bytes of every file */
+    void *ring = nullptr;
+    size_t ring_bytes = 0;
+    u64 status = 0; /* this rank's */
+    DistIngest(disco_ctx *ctx, int n_files, uint32_t threads) : c(ctx), job(ctx, n_files, threads), P((size_t)n_files), size((size_t)n_files, 0) {}
+    ~DistIngest()
+    {
+        if (ring) (void)hipHostFree(ring);
+        release(c, c->d_ingest);
+    }
+    /* a step's answer into the status word (the first one stays) */
+    void note(int rc, int code, size_t file)
+    {
+        if (rc == DISCO_OK || status) return;
+        status = rc == INGEST_DECLINED ? di_status(DI_DECLINE, code, file) : di_status(DI_ERROR, -rc, file);
+    }
+};
+} // namespace
+} // extern "C++"
+
+/* every rank's verdict -> one for all: the error of the lowest rank that has one, else the decline of the lowest file (lowest rank) */
+static int di_verdict(DistIngest &D, const std::vector<u64> &all, size_t n_per_rank, const char *const *paths)
+{
+    disco_ctx *c = D.c;
+    const int G = c->comm->world;
+    int dec_rank = -1;
+    u64 dec = 0;
+    for (int g = 0; g < G; g++) {
+        const u64 st = all[(size_t)g * n_per_rank];
+        const int kind = (int)(st >> 60);
+        if (kind == DI_ERROR) {
+            const int rc = -(int)(st & 0xFFFFu);
+            if (g == c->comm->rank) return rc; /* (its own message stands) */
+            return fail(c, rc, "disco_dist_ingest_fasta: rank %d failed (%d) in its share of the input", g, rc);
+        }
+        if (kind == DI_DECLINE && (dec_rank < 0 || ((st >> 16) & 0xFFFFFFFFull) < ((dec >> 16) & 0xFFFFFFFFull))) {
+            dec_rank = g;
+            dec = st;
+        }
+    }
+    if (dec_rank < 0) return DISCO_OK;
+    const size_t file = (size_t)((dec >> 16) & 0xFFFFFFFFull);
+    const int code = (int)(dec & 0xFFFFu);
+    c->err.clear();
+    return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s (%s; seen by rank %d): the host input stage takes this job", kDistDecline[code > 0 && code < DR_COUNT ? code : 0],
+                paths[file] ? paths[file] : "", dec_rank);
+}
+
+/* step A, local: the files, the rank's pieces, their text in HBM, FASTA record starts / FASTQ newline counts */
+static int di_read_pieces(DistIngest &D, const char *const *paths, disco_dist_ingest_info *info)
+{
+    disco_ctx *c = D.c;
+    IngestJob &j = D.job;
+    const u64 G = (u64)c->comm->world, r = (u64)c->comm->rank;
+    const size_t F = j.F.size();
+    u64 T = 0;
+    for (size_t fi = 0; fi < F; fi++) {
+        IngestFile &f = j.F[fi];
+        f.path = paths[fi] ? paths[fi] : "";
+        if (f.path.size() >= 3 && f.path.compare(f.path.size() - 3, 3, ".gz") == 0) return D.note(INGEST_DECLINED, DR_GZ, fi), INGEST_DECLINED;
+        struct stat st;
+        f.fd = open(f.path.c_str(), O_RDONLY);
+        char first = 0;
+        if (f.fd < 0 || fstat(f.fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 1 || pread(f.fd, &first, 1, 0) != 1 || pread(f.fd, &f.last, 1, st.st_size - 1) != 1)
+            return D.note(INGEST_DECLINED, DR_UNREADABLE, fi), INGEST_DECLINED;
+        if (first != '>' && first != '@') return D.note(INGEST_DECLINED, DR_FORM, fi), INGEST_DECLINED;
+        f.fastq = first == '@';
+        f.n = D.size[fi] = (u64)st.st_size;
+        T += f.n;
+    }
+    /* (128-bit product: T * r does not fit 64 bits for nothing anybody has, but the cut must be the same arithmetic everywhere) */
+    const u64 a = (u64)((unsigned __int128)T * r / G), b = (u64)((unsigned __int128)T * (r + 1) / G);
+    info->share_lo = a;
+    info->share_hi = b;
+    u64 cum = 0, text_bytes = 0;
+    for (size_t fi = 0; fi < F; fi++) {
+        IngestPiece &p = D.P[fi];
+        const u64 n = D.size[fi];
+        p.p0 = std::min(std::max(a, cum) - cum, n);
+        p.p1 = std::min(std::max(b, cum) - cum, n);
+        cum += n;
+        if (p.p1 <= p.p0) continue;
+        const u64 pend = std::min(n, p.p1 + DI_TAIL);
+        p.to_eof = pend == n;
+        p.own_lo = p.p0 ? 1 : 16; /* the byte in front of the piece; at the top of a file 16 newlines (the copy stays aligned) */
+        p.own_hi = p.own_lo + (p.p1 - p.p0);
+        p.n = p.own_lo + (pend - p.p0);
+        text_bytes += ingest_text_cap(p.n);
+    }
+    /* the arena and the pinned ring: sized for the SHARE (text + record arrays, a record per 100 bytes at worst here; more: pieces of their own) */
+    const u64 own_bytes = text_bytes + (text_bytes / 100) * 28 + (8ull << 20);
+    CHK(ensure(c, c->d_ingest, own_bytes));
+    j.arena = c->d_ingest.p;
+    j.arena_cap = c->d_ingest.cap;
+    D.ring_bytes = (size_t)std::min<u64>(256ull << 20, std::max<u64>(1ull << 20, (text_bytes + (1ull << 20) - 1) & ~((1ull << 20) - 1)));
+    if (hipHostMalloc(&D.ring, D.ring_bytes, ring_alloc_flags()) != hipSuccess) {
+        D.ring = nullptr;
+        (void)hipGetLastError();
+        return fail(c, DISCO_E_NOMEM, "disco_dist_ingest_fasta: no pinned staging memory");
+    }
+    for (size_t fi = 0; fi < F; fi++) {
+        IngestPiece &p = D.P[fi];
+        IngestFile &f = j.F[fi];
+        if (p.p1 <= p.p0) continue;
+        const auto t_read = HClock::now();
+        CHK(j.get(&p.d.d_text, ingest_text_cap(p.n)));
+        CHK(j.get(&p.d_ctr, (u64)FX_CTR_COUNT));
+        HIPCHK(c, hipMemsetAsync(p.d_ctr, 0, FX_CTR_COUNT * sizeof(u64), c->stream));
+        HIPCHK(c, hipMemsetAsync(p.d.d_text + p.n, 0, ingest_text_cap(p.n) - p.n, c->stream));
+        if (!p.p0) HIPCHK(c, hipMemsetAsync(p.d.d_text, '\n', 16, c->stream));
+        const u64 from = p.p0 ? p.p0 - 1 : 0;
+        CHK(ingest_read_file(c, f.fd, p.n - (p.p0 ? 0 : 16), p.d.d_text + (p.p0 ? 0 : 16), j.threads, from, D.ring, D.ring_bytes));
+        j.read_s += ms_since(t_read) * 1e-3f;
+        char ch = 0;
+        if (p.p0) {
+            if (pread(f.fd, &ch, 1, (off_t)(p.p0 - 1)) != 1) return fail(c, DISCO_E_ARG, "disco_dist_ingest_fasta: read error");
+            p.prefix_nl = ch == '\n';
+        }
+        if (pread(f.fd, &ch, 1, (off_t)(p.p1 - 1)) != 1) return fail(c, DISCO_E_ARG, "disco_dist_ingest_fasta: read error");
+        p.last_nl = ch == '\n';
+        p.tiles = (p.n + FX_TILE - 1) / FX_TILE;
+        CHK(j.get(&p.d_tile_base, p.tiles + 1));
+        CHK(j.get(&p.d_tile_cnt, p.tiles));
+        if (f.fastq) {
+            hipLaunchKernelGGL(fx_piece_lines_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, p.n, p.own_lo, p.own_hi, (u64)0, p.d_tile_cnt,
+                               (const u64 *)nullptr, (u64 *)nullptr, (u64)0, (u64)0, p.d_ctr);
+            CHK((scan_exclusive<u32, u64>(c, p.d_tile_cnt, p.tiles, p.d_tile_base, false, nullptr)));
+            HIPCHK(c, hipMemcpyAsync(&p.own_nl, p.d_ctr + FX_CTR_OWN_NL, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        } else {
+            hipLaunchKernelGGL(fx_piece_starts_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, p.n, p.own_lo, p.own_hi, p.d_tile_cnt, (const u64 *)nullptr,
+                               (u64 *)nullptr, p.d_ctr);
+            CHK((scan_exclusive<u32, u64>(c, p.d_tile_cnt, p.tiles, p.d_tile_base, false, &p.d.n_start)));
+            if (p.d.n_start >= (1ull << 32)) return D.note(INGEST_DECLINED, DR_IRREGULAR, fi), INGEST_DECLINED;
+            CHK(j.get(&p.d.d_start, p.d.n_start));
+            hipLaunchKernelGGL(fx_piece_starts_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, p.n, p.own_lo, p.own_hi, (u32 *)nullptr,
+                               (const u64 *)p.d_tile_base, p.d.d_start, p.d_ctr);
+        }
+        HIPCHK(c, hipGetLastError());
+    }
+    return DISCO_OK;
+}
+
+/* step B, local: FASTQ record starts from the exchanged newline counts nl[rank][1 + file]; clean + filter of every piece's records */
+static int di_filter_pieces(DistIngest &D, const std::vector<u64> &nl, size_t per_rank)
+{
+    disco_ctx *c = D.c;
+    IngestJob &j = D.job;
+    const size_t F = j.F.size(), r = (size_t)c->comm->rank;
+    for (size_t fi = 0; fi < F; fi++) {
+        IngestPiece &p = D.P[fi];
+        IngestFile &f = j.F[fi];
+        if (p.p1 <= p.p0) continue;
+        if (f.fastq) {
+            u64 line0 = 0; /* newlines of the file in front of the piece */
+            for (size_t g = 0; g < r; g++) line0 += nl[g * per_rank + 1 + fi];
+            /* the lines that BEGIN in the owned bytes: one at the first byte if a newline stands in front of it, one behind every owned
+             * newline but the piece's last byte (that line is the next piece's, or nobody's at the end of the file) */
+            const u64 first = p.prefix_nl ? line0 : line0 + 1, lines = (p.prefix_nl ? 1 : 0) + p.own_nl - (p.last_nl ? 1 : 0);
+            const u64 rec0 = (first + 3) / 4;
+            p.d.n_start = (lines && (first + lines - 1) / 4 + 1 > rec0) ? (first + lines - 1) / 4 + 1 - rec0 : 0;
+            if (p.d.n_start >= (1ull << 32)) return D.note(INGEST_DECLINED, DR_IRREGULAR, fi), INGEST_DECLINED;
+            CHK(j.get(&p.d.d_start, p.d.n_start));
+            hipLaunchKernelGGL(fx_piece_lines_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, p.n, p.own_lo, p.own_hi, line0, (u32 *)nullptr,
+                               (const u64 *)p.d_tile_base, p.d.d_start, rec0, p.d.n_start, p.d_ctr);
+            HIPCHK(c, hipGetLastError());
+        }
+        u64 h[FX_CTR_COUNT];
+        HIPCHK(c, hipMemcpyAsync(h, p.d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h[FX_CTR_BAD_GT]) return D.note(INGEST_DECLINED, DR_IRREGULAR, fi), INGEST_DECLINED;
+        p.fig[DP_STARTS] = p.d.n_start;
+        p.d.n_rec = p.d.n_start;
+        if (!p.d.n_rec) continue;
+        /* where the last owned record ends: the first record start behind the owned bytes, or the end of the file */
+        u64 end = p.n;
+        if (h[FX_CTR_NEXT_INV]) end = ~h[FX_CTR_NEXT_INV];
+        else if (!p.to_eof) return D.note(INGEST_DECLINED, DR_LONG_RECORD, fi), INGEST_DECLINED;
+        CHK(j.get(&p.d.d_seq, p.d.n_rec));
+        CHK(j.get(&p.d.d_glen, p.d.n_rec));
+        CHK(j.get(&p.d.d_wrap, p.d.n_rec));
+        const FxFilterArgs fa{.text = p.d.d_text, .n = end, .start = p.d.d_start, .n_start = p.d.n_start, .n_rec = p.d.n_rec, .min_overlap = c->prm.min_overlap, .fastq = f.fastq ? 1u : 0u,
+                              .glen = p.d.d_glen, .seq_begin = p.d.d_seq, .wrap = p.d.d_wrap, .ctr = p.d_ctr};
+        hipLaunchKernelGGL(fx_filter_kernel, dim3(flat_grid(c, p.d.n_rec)), dim3(256), 0, c->stream, fa, j.tb);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h, p.d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h[FX_CTR_MULTILINE]) return D.note(INGEST_DECLINED, DR_IRREGULAR, fi), INGEST_DECLINED;
+        p.d.good = h[FX_CTR_GOOD];
+        p.fig[DP_GOOD] = h[FX_CTR_GOOD];
+        p.fig[DP_TOO_LONG] = h[FX_CTR_TOO_LONG];
+        p.fig[DP_MAX_LEN] = h[FX_CTR_MAX_LEN];
+        p.fig[DP_MIN_LEN_INV] = h[FX_CTR_MIN_LEN_INV];
+        p.fig[DP_N_LONG] = h[FX_CTR_N_LONG];
+        p.fig[DP_SHORT_MAX] = h[FX_CTR_SHORT_MAX];
+    }
+    return DISCO_OK;
+}
+
+/* step C, local: the job's table; lengths, record numbers (within the file) and rows of the share at their global ids.
+ * id_base[file] / rec_in_file[file]: id of the piece's first good read / records of the file in the pieces before */
+static int di_fill_table(DistIngest &D, const ReadShape &s, const std::vector<u64> &id_base, const std::vector<u64> &rec_in_file, const std::vector<u64> &n_rec)
+{
+    disco_ctx *c = D.c;
+    IngestJob &j = D.job;
+    CHK(dist_set_reads(c, s.n, s.stride));
+    CHK(ensure(c, c->d_rec_of_read, c->n_alloc));
+    u64 max_rec = 0;
+    for (auto &p : D.P) max_rec = std::max(max_rec, p.d.n_rec);
+    u64 *d_pos = nullptr;
+    u8 *d_flag = nullptr;
+    CHK(j.get(&d_pos, max_rec + 1));
+    CHK(j.get(&d_flag, max_rec));
+    for (size_t fi = 0; fi < D.P.size(); fi++) {
+        IngestPiece &p = D.P[fi];
+        const u64 nr = n_rec[fi]; /* (without a lone trailing '>': its glen is 0 anyway) */
+        if (!nr || !p.d.good) continue;
+        hipLaunchKernelGGL(fx_flags_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const u16 *)p.d.d_glen, nr, d_flag);
+        u64 good = 0;
+        CHK((scan_exclusive<u8, u64>(c, d_flag, nr, d_pos, false, &good)));
+        if (good != p.d.good) return fail(c, DISCO_E_STATE, "disco_dist_ingest_fasta: %llu good reads counted, %llu placed", (unsigned long long)p.d.good, (unsigned long long)good);
+        if (id_base[fi] + good > s.n) return fail(c, DISCO_E_STATE, "disco_dist_ingest_fasta: ids beyond the job's reads");
+        hipLaunchKernelGGL(fx_ids_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const u16 *)p.d.d_glen, (const u64 *)d_pos, nr, id_base[fi], c->d_rec_of_read.p, c->d_len);
+        hipLaunchKernelGGL(fx_pack_kernel, dim3(flat_grid(c, good * (u64)c->S)), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, (const u64 *)p.d.d_seq, (const u32 *)p.d.d_wrap,
+                           (const u32 *)c->d_rec_of_read.p, (const u16 *)c->d_len, id_base[fi], good, c->S, 0xFFFFu, c->d_reads);
+        if (rec_in_file[fi])
+            hipLaunchKernelGGL(fx_rec_add_kernel, dim3(flat_grid(c, good)), dim3(256), 0, c->stream, c->d_rec_of_read.p, id_base[fi], id_base[fi] + good, (u32)rec_in_file[fi]);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DISCO_OK;
+}
+
+/* what a rank made for ids outside its home range, to the owners: ids [share[g], share[g + 1]) are rank g's, homes are [q per, (q + 1) per).
+ * Sender and receiver keep a read at the same row of their tables, so both sides of the all-to-all are the table itself. */
+static int di_exchange(disco_ctx *c, const std::vector<u64> &share, void *table, size_t elem)
+{
+    const int G = c->comm->world, r = c->comm->rank;
+    std::vector<size_t> so((size_t)G, 0), sc((size_t)G, 0), ro((size_t)G, 0), rc((size_t)G, 0);
+    auto cut = [&](int from, int to, size_t *off, size_t *cnt) { /* ids of rank `from`'s share in rank `to`'s home range */
+        const u64 lo = std::max(share[(size_t)from], (u64)to * c->per), hi = std::min(share[(size_t)from + 1], ((u64)to + 1) * c->per);
+        *off = hi > lo ? (size_t)lo * elem : 0;
+        *cnt = hi > lo ? (size_t)(hi - lo) * elem : 0;
+    };
+    for (int p = 0; p < G; p++) {
+        if (p == r) continue;
+        cut(r, p, &so[(size_t)p], &sc[(size_t)p]);
+        cut(p, r, &ro[(size_t)p], &rc[(size_t)p]);
+    }
+    COMM_CHK(c, c->comm->all_to_all_v(table, so.data(), sc.data(), table, ro.data(), rc.data(), c->stream));
+    return DISCO_OK;
+}
+
+int disco_dist_ingest_fasta(disco_ctx *c, const char *const *paths, int n_files, uint32_t host_threads, disco_dist_ingest_info *info, disco_ingest_file *files)
+{
+    DISCO_TRACE("disco_dist_ingest_fasta");
+    if (!c || !paths || n_files < 1 || !info || !files) return c ? fail(c, DISCO_E_ARG, "disco_dist_ingest_fasta: null argument") : DISCO_E_ARG;
+    if (!c->comm) return fail(c, DISCO_E_STATE, "disco_dist_ingest_fasta: no communicator (one GPU: disco_ingest_fasta)");
+    const size_t F = (size_t)n_files, G = (size_t)c->comm->world, r = (size_t)c->comm->rank;
+    memset(info, 0, sizeof *info);
+    info->world = (uint32_t)G;
+    DistIngest D(c, n_files, host_threads);
+    IngestJob &j = D.job;
+    std::vector<u64> mine, all;
+    /* A */
+    int rc = hipSetDevice(c->device) == hipSuccess ? DISCO_OK : fail(c, DISCO_E_HIP, "hipSetDevice failed");
+    if (rc == DISCO_OK) {
+        if (c->phase > 1) c->phase = 1;
+        rc = di_read_pieces(D, paths, info);
+    }
+    D.note(rc, 0, 0);
+    mine.assign(1 + F, 0);
+    mine[0] = D.status;
+    for (size_t fi = 0; fi < F; fi++) mine[1 + fi] = D.P[fi].own_nl;
+    CHK(di_gather(c, mine, all));
+    CHK(di_verdict(D, all, 1 + F, paths));
+    /* B */
+    rc = di_filter_pieces(D, all, 1 + F);
+    D.note(rc, 0, 0);
+    const float t_filtered = j.seconds();
+    const size_t PR = 1 + F * DI_PER_PIECE;
+    mine.assign(PR, 0);
+    mine[0] = D.status;
+    for (size_t fi = 0; fi < F; fi++) memcpy(&mine[1 + fi * DI_PER_PIECE], D.P[fi].fig, sizeof D.P[fi].fig);
+    CHK(di_gather(c, mine, all));
+    CHK(di_verdict(D, all, PR, paths));
+    /* C: from here on every rank computes the same figures from the same numbers */
+    auto fig = [&](size_t g, size_t fi, int what) { return all[g * PR + 1 + fi * DI_PER_PIECE + (size_t)what]; };
+    ReadShape s{0, 0, 0, 0, 0, 0xFFFFu};
+    u64 total_records = 0, too_long = 0;
+    std::vector<u64> share(G + 1, 0), id_base(F, 0), rec_in_file(F, 0), n_rec(F, 0);
+    c->ingest_id_base.assign(F + 1, 0);
+    c->ingest_rec_base.assign(F + 1, 0);
+    for (size_t fi = 0; fi < F; fi++) {
+        u64 starts = 0, good = 0;
+        size_t last_piece = 0; /* the rank that owns the file's last byte */
+        for (size_t g = 0; g < G; g++) {
+            starts += fig(g, fi, DP_STARTS);
+            if (fig(g, fi, DP_STARTS)) last_piece = g;
+        }
+        if (starts == 0 || starts >= (1ull << 32)) { /* (every rank alike) */
+            c->err.clear();
+            return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s (%s): the host input stage takes this job", kIngestIrregular, j.F[fi].path.c_str());
+        }
+        /* a '>' that is the very last byte starts nothing unless it is the only one (it still ended the record before it) */
+        const bool lone_gt = !j.F[fi].fastq && starts > 1 && j.F[fi].last == '>';
+        u64 recs = 0;
+        for (size_t g = 0; g < G; g++) {
+            const u64 nr = fig(g, fi, DP_STARTS) - ((lone_gt && g == last_piece) ? 1 : 0);
+            if (g == r) {
+                id_base[fi] = s.n + good;
+                rec_in_file[fi] = recs;
+                n_rec[fi] = nr;
+            }
+            recs += nr;
+            const u64 gd = fig(g, fi, DP_GOOD);
+            good += gd;
+            share[g + 1] += gd;
+            too_long += fig(g, fi, DP_TOO_LONG);
+            if (gd) {
+                s.longest = std::max(s.longest, (u32)fig(g, fi, DP_MAX_LEN));
+                s.shortest = std::min(s.shortest, 0xFFFFu - (u32)fig(g, fi, DP_MIN_LEN_INV));
+                s.n_long += fig(g, fi, DP_N_LONG);
+                s.short_max = std::max(s.short_max, (u32)fig(g, fi, DP_SHORT_MAX));
+            }
+        }
+        files[fi] = disco_ingest_file{.first_index = total_records + 1, .last_index = total_records + recs, .good = good, .bad = recs - good};
+        total_records += recs;
+        s.n += good;
+        c->ingest_id_base[fi + 1] = s.n;
+        c->ingest_rec_base[fi + 1] = total_records;
+    }
+    for (size_t g = 0; g < G; g++) share[g + 1] += share[g]; /* rank g's reads are the ids [share[g], share[g + 1]): shares follow each other in file order */
+    if (s.n == 0 || s.n >= (1ull << 31)) {
+        c->err.clear();
+        return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s (%s): the host input stage takes this job", kDistDecline[DR_NO_READ], j.F[0].path.c_str());
+    }
+    s.stride = (std::max<u32>(1, (s.longest + 31) / 32) + 7u) & ~7u;
+    D.status = 0;
+    rc = di_fill_table(D, s, id_base, rec_in_file, n_rec);
+    D.note(rc, 0, 0);
+    mine.assign(1, D.status);
+    CHK(di_gather(c, mine, all));
+    CHK(di_verdict(D, all, 1, paths));
+    CHK(di_exchange(c, share, c->d_reads, (size_t)c->S * 8));
+    CHK(di_exchange(c, share, c->d_len, sizeof(u16)));
+    CHK(di_exchange(c, share, c->d_rec_of_read.p, sizeof(u32)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ingest_n = s.n;
+    c->h_len_ok = false;
+    info->n_reads = s.n;
+    info->total_records = total_records;
+    info->too_long = too_long;
+    info->stride_words = std::max<u32>(1, (s.longest + 31) / 32);
+    info->shortest = s.shortest;
+    info->longest = s.longest;
+    info->share_reads = share[r + 1] - share[r];
+    info->home_lo = c->home_lo;
+    info->home_hi = c->home_hi;
+    {
+        const u64 lo = std::max(share[r], c->home_lo), hi = std::min(share[r + 1], c->home_hi);
+        info->kept_reads = hi > lo ? hi - lo : 0;
+    }
+    const int vrc = dist_validate(c);
+    info->read_s = j.read_s;
+    info->device_s = j.seconds() - j.read_s;
+    if (getenv("DISCO_VERBOSE"))
+        fprintf(stderr, "[disco] input stage on rank %zu of %zu: bytes [%llu, %llu) of the input, %llu reads of %llu, %llu kept at home; files %.3f s, records + filter %.3f s, "
+                        "table + rows + exchange %.3f s\n",
+                r, G, (unsigned long long)info->share_lo, (unsigned long long)info->share_hi, (unsigned long long)info->share_reads, (unsigned long long)s.n,
+                (unsigned long long)info->kept_reads, j.read_s, t_filtered - j.read_s, j.seconds() - t_filtered);
+    return vrc;
+}
+
+int disco_dist_ingest_fetch(disco_ctx *c, uint16_t *len, uint64_t *file_index)
+{
+    if (!c || !len || !file_index) return c ? fail(c, DISCO_E_ARG, "disco_dist_ingest_fetch: null argument") : DISCO_E_ARG;
+    if (!c->comm || !c->dist_reads || c->phase < 1 || c->ingest_n == 0 || c->ingest_n != c->n)
+        return fail(c, DISCO_E_STATE, "disco_dist_ingest_fetch: the reads of the context did not come from disco_dist_ingest_fasta");
+    HIPCHK(c, hipSetDevice(c->device));
+    const u64 lo = c->home_lo, hi = c->home_hi, n = hi - lo;
+    if (!n) return DISCO_OK;
+    std::vector<u32> rec(n);
+    HIPCHK(c, hipMemcpyAsync(len, c->d_len + lo, n * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_rec_of_read.p + lo, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t fi = 0; fi + 1 < c->ingest_id_base.size(); fi++) {
+        const u64 a = std::max(lo, c->ingest_id_base[fi]), b = std::min(hi, c->ingest_id_base[fi + 1]), rb = c->ingest_rec_base[fi];
+        for (u64 i = a; i < b; i++) file_index[i - lo] = rb + (u64)rec[i - lo] + 1; /* BG/Dataset.cpp:294: every record counts */
+    }
+    return DISCO_OK;
 }
 
 static int dist_run_graph_pass(disco_ctx *c, uint32_t flags, bool allow_loci, bool *retry_with_id_ranges);

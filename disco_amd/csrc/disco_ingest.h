@@ -28,8 +28,9 @@
 #define FX_WRAP_IRREGULAR 0xFFFFFFFFu
 
 /* counters of one ingest (u64 each) */
-enum { FX_CTR_BAD_GT = 0, FX_CTR_MULTILINE, FX_CTR_TOO_LONG, FX_CTR_MAX_LEN, FX_CTR_MIN_LEN_INV, FX_CTR_GOOD, FX_CTR_N_LONG, FX_CTR_SHORT_MAX, FX_CTR_COUNT };
-/* (N_LONG / SHORT_MAX: good reads of more than DISCO_SHORT_MAX bases, and the longest of the others — the table may get two classes of rows) */
+enum { FX_CTR_BAD_GT = 0, FX_CTR_MULTILINE, FX_CTR_TOO_LONG, FX_CTR_MAX_LEN, FX_CTR_MIN_LEN_INV, FX_CTR_GOOD, FX_CTR_N_LONG, FX_CTR_SHORT_MAX, FX_CTR_NEXT_INV, FX_CTR_OWN_NL, FX_CTR_COUNT };
+/* (N_LONG / SHORT_MAX: good reads of more than DISCO_SHORT_MAX bases, and the longest of the others — the table may get two classes of rows;
+ * NEXT_INV / OWN_NL: pieces of a file, below — ~position of the first record start behind the owned bytes (0: none), newlines of the owned bytes) */
 
 struct FxTables { /* Dataset::testRead's patterns (read_filter_tables.h), prepared by the host */
     u64 rep58[FX_MAX_REPEATS]; /* the 29-mers that may be neither prefix nor suffix of a read, 2 bits per base */
@@ -418,6 +419,130 @@ __global__ void __launch_bounds__(256) fx_pack_long_kernel(const u8 *__restrict_
             rows8[(n + j) * 8 + tw] = 32u * tw < (u32)tailb ? fx_pack_word(tx, seq_begin[rec], wrap[rec], L, L - (u32)tailb + 32u * tw) : 0ull;
         }
     }
+}
+
+/* ---- a PIECE of a file (disco_dist_ingest_fasta: every rank reads its share of the bytes) ----------------------------------------------
+ * The buffer holds the byte in front of the piece (a '\n' where the piece begins the file), the bytes the rank owns — [own_lo, own_hi) —
+ * and behind them the rest of the last record that starts there (up to 2^21 bytes, or the end of the file): n bytes in all. A record
+ * belongs to the piece that holds its first byte; the first record start BEHIND the owned bytes ends the last owned record: its position
+ * goes to FX_CTR_NEXT_INV, complemented (atomicMax over a zeroed counter = the smallest position; 0: no start in the buffer). */
+
+/* fx_starts_kernel over a piece: only the '>' of the owned bytes are counted / placed / found inside a line */
+__global__ void __launch_bounds__(256) fx_piece_starts_kernel(const u8 *__restrict__ text, u64 n, u64 own_lo, u64 own_hi, u32 *__restrict__ count,
+                                                              const u64 *__restrict__ base, u64 *__restrict__ pos, u64 *__restrict__ ctr)
+{
+    __shared__ u32 s_w[4];
+    const u64 tile = blockIdx.x;
+    const u64 p0 = tile * FX_TILE + (u64)threadIdx.x * 16u;
+    u32 mask = 0, bad = 0;
+    u64 next = ~0ull;
+    if (p0 < n && p0 + 16u > own_lo) {
+        const uint4 q = *(const uint4 *)(text + p0); /* (padded buffer) */
+        const u32 wds[4] = {q.x, q.y, q.z, q.w};
+        u32 prev = p0 ? text[p0 - 1] : (u32)'\n';
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const u32 c = (wds[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+            const u64 p = p0 + i;
+            if (p >= own_lo && p < n && c == '>') {
+                if (p < own_hi) {
+                    if (prev == '\n') mask |= 1u << i;
+                    else bad = 1;
+                } else if (prev == '\n' && next == ~0ull)
+                    next = p;
+            }
+            prev = c;
+        }
+    }
+    if (count) { /* (once, in the counting pass) */
+        if (bad) atomicAdd(&ctr[FX_CTR_BAD_GT], 1ull);
+        if (next != ~0ull) atomicMax(&ctr[FX_CTR_NEXT_INV], ~next);
+    }
+    const u32 mine = (u32)__popc(mask);
+    u32 incl = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const u32 y = (u32)__shfl_up((int)incl, o);
+        if ((int)(threadIdx.x & 63) >= o) incl += y;
+    }
+    if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    u32 off = incl - mine;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) off += s_w[w];
+    if (count) {
+        if (threadIdx.x == 255) count[tile] = off + mine;
+    } else {
+        u64 at = base[tile] + off;
+        u32 m = mask;
+        while (m) {
+            const int i = __ffs((int)m) - 1;
+            m &= m - 1;
+            pos[at++] = p0 + (u64)i;
+        }
+    }
+}
+
+/* fx_lines_kernel over a piece. Pass 1 (count != nullptr): newlines per tile from own_lo on, and those of the owned bytes summed into
+ * FX_CTR_OWN_NL — what the ranks exchange: line0, the newlines of the file in front of the piece, is the sum over the pieces before it.
+ * Pass 2: the line that begins at byte p has the index line0 + newlines in [own_lo, p); a multiple of 4 starts record index / 4, which
+ * goes to pos[index / 4 - rec0] (n_pos slots: the owned record starts) or, behind the owned bytes, to FX_CTR_NEXT_INV. */
+__global__ void __launch_bounds__(256) fx_piece_lines_kernel(const u8 *__restrict__ text, u64 n, u64 own_lo, u64 own_hi, u64 line0, u32 *__restrict__ count,
+                                                             const u64 *__restrict__ base, u64 *__restrict__ pos, u64 rec0, u64 n_pos, u64 *__restrict__ ctr)
+{
+    __shared__ u32 s_w[4];
+    const u64 tile = blockIdx.x;
+    const u64 p0 = tile * FX_TILE + (u64)threadIdx.x * 16u;
+    u32 nlmask = 0, ownmask = 0;
+    u32 wds[4] = {0, 0, 0, 0};
+    if (p0 < n && p0 + 16u > own_lo) {
+        const uint4 q = *(const uint4 *)(text + p0);
+        wds[0] = q.x, wds[1] = q.y, wds[2] = q.z, wds[3] = q.w;
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const u64 p = p0 + i;
+            if (p >= own_lo && p < n && ((wds[i >> 2] >> (8 * (i & 3))) & 0xFFu) == '\n') {
+                nlmask |= 1u << i;
+                if (p < own_hi) ownmask |= 1u << i;
+            }
+        }
+    }
+    const u32 mine = (u32)__popc(nlmask);
+    u32 incl = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const u32 y = (u32)__shfl_up((int)incl, o);
+        if ((int)(threadIdx.x & 63) >= o) incl += y;
+    }
+    if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    u32 off = incl - mine;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) off += s_w[w];
+    if (count) {
+        if (threadIdx.x == 255) count[tile] = off + mine;
+        u32 own = (u32)__popc(ownmask);
+        for (int o = 32; o > 0; o >>= 1) own += (u32)__shfl_down((int)own, o);
+        if ((threadIdx.x & 63) == 0 && own) atomicAdd(&ctr[FX_CTR_OWN_NL], (u64)own);
+        return;
+    }
+    if (p0 >= n || p0 + 16u <= own_lo) return;
+    u64 before = line0 + base[tile] + off;
+    u32 prev = p0 ? text[p0 - 1] : (u32)'\n';
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const u64 p = p0 + i;
+        if (p >= own_lo && p < n && prev == '\n' && (before & 3ull) == 0) {
+            const u64 slot = (before >> 2) - rec0;
+            if (p >= own_hi) atomicMax(&ctr[FX_CTR_NEXT_INV], ~p);
+            else if ((before >> 2) >= rec0 && slot < n_pos) pos[slot] = p;
+        }
+        if (nlmask & (1u << i)) before++;
+        prev = (wds[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+    }
+}
+
+/* record numbers of the reads [lo, hi): piece-local (what fx_pack_kernel looks the sequence up by) -> numbers within the file */
+__global__ void fx_rec_add_kernel(u32 *__restrict__ rec_of_read, u64 lo, u64 hi, u32 add)
+{
+    u64 i = lo + (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i < hi; i += (u64)gridDim.x * blockDim.x) rec_of_read[i] += add;
 }
 
 #endif

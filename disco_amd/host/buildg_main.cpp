@@ -27,6 +27,7 @@
 #include <cstring>
 #include <thread>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <memory>
 #include <sstream>
@@ -356,6 +357,151 @@ int main(int argc, char **argv)
         else if (getenv("DISCO_VERBOSE"))
             fprintf(stderr, "[disco host] %s\n", disco_last_error(ctx1));
     }
+    /* --gpus N: the contexts, the communicator and the watchdog exist BEFORE the input stage, because every rank reads its share of the
+     * files itself (disco_dist_ingest_fasta: the bytes of the files laid end to end, cut into N shares; records, filter and rows on the
+     * rank's GPU, rows of other ranks' home ranges sent to their owners). DISCO_E_UNSUPPORTED — on every rank alike: a .gz name, a '>'
+     * inside a line, an irregularly wrapped long record, an unreadable file — leaves the job to the host stage below, inside the same
+     * run and on the same contexts. Asked for with DISCO_DIST_DEVICE_INPUT=1 (below: why not by default); DISCO_HOST_INPUT=1: the host stage always. */
+    std::vector<disco_ctx *> ctx;
+    unsigned char uid[DISCO_UNIQUE_ID_BYTES];
+    bool comm_joined = false; /* (RCCL: the ranks joined the communicator in front of the device input stage) */
+    /* Watchdog of the multi-rank stage (bench.py has its twin): every rank thread names the call it is in; when NO rank has moved for
+     * DISCO_WATCHDOG_S seconds (default 900; 0: off) — a collective one rank never entered, a link that went away — the process says
+     * where every rank stands and exits non-zero. Never a re-exec, never a silent hang: runDisco.sh does not check the status, but
+     * the missing GC=Complete line makes the next run start over. */
+    enum { ST_START = 0, ST_COMM_INIT, ST_INGEST, ST_INGEST_FETCH, ST_HOST_INPUT, ST_UPLOAD, ST_FRONT_OF_PASS, ST_PASS, ST_FETCH_CONTAINED, ST_FETCH_EDGES, ST_DONE };
+    static const char *const kStage[] = {"start", "disco_comm_init", "disco_dist_ingest_fasta", "disco_dist_ingest_fetch", "the host input stage (between the rank threads)",
+                                         "disco_dist_upload_reads", "front of disco_dist_run_graph (never entered it)", "disco_dist_run_graph",
+                                         "disco_fetch_contained", "disco_fetch_edges", "done"};
+    std::vector<std::atomic<int>> stage((size_t)gpus);
+    for (auto &st : stage) st.store(ST_START);
+    std::atomic<bool> ranks_done{false};
+    const long wd_s = getenv("DISCO_WATCHDOG_S") ? atol(getenv("DISCO_WATCHDOG_S")) : 900;
+    std::atomic<bool> wd_paused{false}; /* the host stage runs on the main thread: no rank moves, and nobody waits for one */
+    std::thread watchdog;
+    struct WatchdogJoin {
+        std::atomic<bool> &done;
+        std::thread &t;
+        ~WatchdogJoin()
+        {
+            done.store(true);
+            if (t.joinable()) t.join();
+        }
+    } watchdog_join{ranks_done, watchdog};
+    /* the ranks' contexts, the communicator (in-process: joined here; RCCL: its id) and the watchdog; "" or what went wrong */
+    auto make_ranks = [&]() -> std::string {
+        const disco_params prm0{min_overlap, 4, getenv("DISCO_EXACT_COUNTERS") ? 0u : DISCO_FLAG_TWO_PASS_VERIFY, max_subs};
+        ctx.assign((size_t)gpus, nullptr);
+        for (int r = 0; r < gpus; r++)
+            if (disco_create(same_device ? gpu : gpu + r, &prm0, &ctx[(size_t)r]) < 0)
+                return std::string("disco_create (rank ") + std::to_string(r) + "): " + disco_last_error(nullptr) +
+                       (same_device ? "" : " — one GPU per rank is needed; --same-device runs all ranks on one GPU");
+        if (same_device) {
+            if (disco_comm_init_local(ctx.data(), gpus) < 0) return "disco_comm_init_local failed";
+        } else if (disco_comm_unique_id(uid, sizeof uid) < 0)
+            return std::string("disco_comm_unique_id: ") + disco_last_error(nullptr);
+        watchdog = std::thread([&]() {
+            if (wd_s <= 0) return;
+            std::vector<int> last((size_t)gpus, -1);
+            auto moved_at = Clock::now();
+            while (!ranks_done.load()) {
+                std::this_thread::sleep_for(std::chrono::milliseconds(200));
+                bool moved = wd_paused.load();
+                for (int r = 0; r < gpus; r++) {
+                    const int x = stage[(size_t)r].load();
+                    moved = moved || x != last[(size_t)r];
+                    last[(size_t)r] = x;
+                }
+                if (moved) moved_at = Clock::now();
+                else if (secs(moved_at) > (double)wd_s) {
+                    std::cout << "\nError: no rank has made progress for " << wd_s << " seconds:";
+                    for (int r = 0; r < gpus; r++) std::cout << " rank " << r << " in " << kStage[last[(size_t)r]] << ";";
+                    std::cout << " giving up (DISCO_WATCHDOG_S sets the patience)." << std::endl;
+                    _exit(3);
+                }
+            }
+        });
+        return "";
+    };
+    /* Measured (profiles/dist_ingest.txt): four ranks on ONE device, 5 M reads — the device stage on the ranks is not faster than the host
+     * stage there (the ranks share one GPU and one link), so the host stage stays the default under --gpus N and
+     * DISCO_DIST_DEVICE_INPUT=1 asks for the device stage; what one GPU per rank gains is a measurement this pool cannot make. */
+    const char *ddi = getenv("DISCO_DIST_DEVICE_INPUT");
+    if (gpus > 1 && ddi && strcmp(ddi, "0") != 0 && !getenv("DISCO_HOST_INPUT")) {
+        if (const std::string e = make_ranks(); !e.empty()) return die(e);
+        std::vector<const char *> paths;
+        for (auto &f : pe) paths.push_back(f.c_str());
+        for (auto &f : se) paths.push_back(f.c_str());
+        /* reader threads per rank: all ranks together stay within 16 (one GPU: six keep the ring full, buildg's host has 16 cores). The
+         * right figure for N links is a measurement nobody can make on this pool (its ranks share one device and one link). */
+        const uint32_t readers = (uint32_t)std::max(1, std::min(threads, 16) / gpus);
+        std::vector<int> irc((size_t)gpus, 0);
+        std::vector<disco_dist_ingest_info> dii((size_t)gpus);
+        std::vector<std::vector<disco_ingest_file>> ifiles((size_t)gpus, std::vector<disco_ingest_file>(paths.size()));
+        auto on_ranks = [&](const std::function<void(int)> &fn) {
+            std::vector<std::thread> th;
+            for (int r = 0; r < gpus; r++) th.emplace_back(fn, r);
+            for (auto &t : th) t.join();
+        };
+        on_ranks([&](int r) {
+            disco_ctx *c = ctx[(size_t)r];
+            stage[(size_t)r].store(ST_COMM_INIT);
+            if (!same_device && disco_comm_init(c, uid, gpus, r) < 0) {
+                /* the other ranks wait for this one inside a collective: there is nothing to unwind to */
+                std::cout << "\nError (rank " << r << "): disco_comm_init: " << disco_last_error(c) << std::endl;
+                _exit(2);
+            }
+            stage[(size_t)r].store(ST_INGEST);
+            irc[(size_t)r] = disco_dist_ingest_fasta(c, paths.data(), (int)paths.size(), readers, &dii[(size_t)r], ifiles[(size_t)r].data());
+        });
+        comm_joined = true;
+        bool all_ok = true, all_declined = true;
+        for (int r = 0; r < gpus; r++) {
+            all_ok = all_ok && irc[(size_t)r] == DISCO_OK;
+            all_declined = all_declined && irc[(size_t)r] == DISCO_E_UNSUPPORTED;
+        }
+        if (all_ok) {
+            const disco_dist_ingest_info &ii = dii[0];
+            rs.n_reads = ii.n_reads;
+            rs.stride_words = ii.stride_words;
+            rs.total_records = ii.total_records;
+            rs.too_long = ii.too_long;
+            rs.shortest = ii.shortest;
+            rs.longest = ii.longest;
+            rs.len.resize(ii.n_reads);
+            rs.file_index.resize(ii.n_reads);
+            /* the ranks' home ranges, one behind the other, are the job's reads: lengths and file indices for _ReadIDMap.txt and the writers */
+            on_ranks([&](int r) {
+                stage[(size_t)r].store(ST_INGEST_FETCH);
+                const disco_dist_ingest_info &d = dii[(size_t)r];
+                if (d.home_hi > d.home_lo) irc[(size_t)r] = disco_dist_ingest_fetch(ctx[(size_t)r], rs.len.data() + d.home_lo, rs.file_index.data() + d.home_lo);
+            });
+            for (int r = 0; r < gpus; r++)
+                if (irc[(size_t)r] < 0) return die(std::string("disco_dist_ingest_fetch: ") + disco_last_error(ctx[(size_t)r]));
+            for (size_t i = 0; i < paths.size(); i++) {
+                disco::FileRange fr;
+                fr.name = paths[i];
+                fr.paired = i < pe.size();
+                fr.first_index = ifiles[0][i].first_index;
+                fr.last_index = ifiles[0][i].last_index;
+                fr.good = ifiles[0][i].good;
+                fr.bad = ifiles[0][i].bad;
+                rs.files.push_back(fr);
+            }
+            ingested = true;
+            if (getenv("DISCO_VERBOSE"))
+                for (int r = 0; r < gpus; r++)
+                    fprintf(stderr, "[disco host] input stage on the GPU of rank %d: its bytes into HBM %.3f s, records + filter + ids + rows + exchange %.3f s\n", r, dii[(size_t)r].read_s,
+                            dii[(size_t)r].device_s);
+        } else if (!all_declined) {
+            for (int r = 0; r < gpus; r++)
+                if (irc[(size_t)r] != DISCO_OK && irc[(size_t)r] != DISCO_E_UNSUPPORTED) return die(std::string("disco_dist_ingest_fasta (rank ") + std::to_string(r) + "): " + disco_last_error(ctx[(size_t)r]));
+            return die("disco_dist_ingest_fasta: the ranks disagree about the input");
+        } else if (getenv("DISCO_VERBOSE"))
+            fprintf(stderr, "[disco host] %s\n", disco_last_error(ctx[0]));
+        for (auto &st : stage) st.store(ST_HOST_INPUT);
+    }
+    wd_paused.store(true);
     if (!ingested && !disco::load_reads(pe, se, min_overlap, threads, rs, err, pinned)) return die(err);
     for (auto &fr : rs.files) {
         std::cout << "File name: " << fr.name << "\n"
@@ -534,59 +680,12 @@ int main(int argc, char **argv)
     } else {
         /* one rank per GPU, one host thread per rank (replaces mpirun -np N of runDisco-MPI.sh:214-258): rank r holds the reads
          * [r*per, (r+1)*per), every exchange is an RCCL collective inside libdisco_hip.so */
-        std::vector<disco_ctx *> ctx((size_t)gpus, nullptr);
-        for (int r = 0; r < gpus; r++)
-            if (disco_create(same_device ? gpu : gpu + r, &prm, &ctx[(size_t)r]) < 0)
-                return die(std::string("disco_create (rank ") + std::to_string(r) + "): " + disco_last_error(nullptr) +
-                           (same_device ? "" : " — one GPU per rank is needed; --same-device runs all ranks on one GPU"));
-        unsigned char uid[DISCO_UNIQUE_ID_BYTES];
-        if (same_device) {
-            if (disco_comm_init_local(ctx.data(), gpus) < 0) return die("disco_comm_init_local failed");
-        } else if (disco_comm_unique_id(uid, sizeof uid) < 0)
-            return die(std::string("disco_comm_unique_id: ") + disco_last_error(nullptr));
         std::vector<RankResult> res((size_t)gpus);
         std::vector<std::thread> th;
-        const std::vector<uint64_t> woff = rs.word_offsets();
-        /* Watchdog of the multi-rank stage (bench.py has its twin): every rank thread names the call it is in; when NO rank has moved for
-         * DISCO_WATCHDOG_S seconds (default 900; 0: off) — a collective one rank never entered, a link that went away — the process says
-         * where every rank stands and exits non-zero. Never a re-exec, never a silent hang: runDisco.sh does not check the status, but
-         * the missing GC=Complete line makes the next run start over. */
-        static const char *const kStage[] = {"start", "disco_comm_init", "disco_dist_upload_reads", "front of disco_dist_run_graph (never entered it)", "disco_dist_run_graph",
-                                             "disco_fetch_contained", "disco_fetch_edges", "done"};
-        std::vector<std::atomic<int>> stage((size_t)gpus);
-        for (auto &st : stage) st.store(0);
-        std::atomic<bool> ranks_done{false};
-        const long wd_s = getenv("DISCO_WATCHDOG_S") ? atol(getenv("DISCO_WATCHDOG_S")) : 900;
-        std::thread watchdog([&]() {
-            if (wd_s <= 0) return;
-            std::vector<int> last((size_t)gpus, -1);
-            auto moved_at = Clock::now();
-            while (!ranks_done.load()) {
-                std::this_thread::sleep_for(std::chrono::milliseconds(200));
-                bool moved = false;
-                for (int r = 0; r < gpus; r++) {
-                    const int x = stage[(size_t)r].load();
-                    moved = moved || x != last[(size_t)r];
-                    last[(size_t)r] = x;
-                }
-                if (moved) moved_at = Clock::now();
-                else if (secs(moved_at) > (double)wd_s) {
-                    std::cout << "\nError: no rank has made progress for " << wd_s << " seconds:";
-                    for (int r = 0; r < gpus; r++) std::cout << " rank " << r << " in " << kStage[last[(size_t)r]] << ";";
-                    std::cout << " giving up (DISCO_WATCHDOG_S sets the patience)." << std::endl;
-                    _exit(3);
-                }
-            }
-        });
-        struct WatchdogJoin {
-            std::atomic<bool> &done;
-            std::thread &t;
-            ~WatchdogJoin()
-            {
-                done.store(true);
-                if (t.joinable()) t.join();
-            }
-        } watchdog_join{ranks_done, watchdog};
+        const std::vector<uint64_t> woff = ingested ? std::vector<uint64_t>() : rs.word_offsets();
+        if (ctx.empty())
+            if (const std::string e = make_ranks(); !e.empty()) return die(e);
+        wd_paused.store(false);
         for (int r = 0; r < gpus; r++)
             th.emplace_back([&, r]() {
                 RankResult &R = res[(size_t)r];
@@ -598,28 +697,30 @@ int main(int argc, char **argv)
                     std::cout << "\nError (rank " << r << "): " << R.err << std::endl;
                     _exit(2);
                 };
-                at(1);
-                if (!same_device && disco_comm_init(c, uid, gpus, r) < 0) bail("disco_comm_init");
-                uint64_t lo = 0, hi = 0;
-                if (disco_dist_range(c, rs.size(), &lo, &hi) < 0) bail("disco_dist_range");
-                at(2);
-                {
+                if (!comm_joined) {
+                    at(ST_COMM_INIT);
+                    if (!same_device && disco_comm_init(c, uid, gpus, r) < 0) bail("disco_comm_init");
+                }
+                if (!ingested) { /* (the device input stage left the rank's home range in place, as the upload does) */
+                    uint64_t lo = 0, hi = 0;
+                    if (disco_dist_range(c, rs.size(), &lo, &hi) < 0) bail("disco_dist_range");
+                    at(ST_UPLOAD);
                     const std::vector<uint64_t> own = rs.rows(lo, hi, woff); /* (the multi-GPU table has one stride: the rank's rows at it) */
                     if (disco_dist_upload_reads(c, own.data(), rs.stride_words, rs.len.data() + lo, rs.size()) < 0) bail("disco_dist_upload_reads");
                 }
-                at(3);
+                at(ST_FRONT_OF_PASS);
                 /* (tests: a rank that never enters the pass; DISCO_TEST_STALL_FIRST_TRY: in the launcher's first child only) */
                 if (getenv("DISCO_TEST_STALL_RANK") && atoi(getenv("DISCO_TEST_STALL_RANK")) == r &&
                     (!getenv("DISCO_TEST_STALL_FIRST_TRY") || !getenv("DISCO_BUILDG_CHILD") || !strcmp(getenv("DISCO_BUILDG_CHILD"), "1")))
                     for (;;) std::this_thread::sleep_for(std::chrono::seconds(1));
-                at(4);
+                at(ST_PASS);
                 if (disco_dist_run_graph(c, DISCO_DIST_GATHER_READS | (partitioned_index ? DISCO_DIST_KEEP_INDEX_PARTITIONED : 0)) < 0) bail("disco_dist_run_graph");
                 if (disco_dist_get_info(c, &R.info) < 0) bail("disco_dist_get_info");
                 if (verbose && r == 0) fprintf(stderr, "[disco host] transport %s, %d ranks\n", disco_comm_kind(c), gpus);
-                at(5);
+                at(ST_FETCH_CONTAINED);
                 R.rows.resize(R.info.n_contained_local);
                 if (R.info.n_contained_local && disco_fetch_contained(c, R.rows.data(), R.info.n_contained_local) < 0) bail("disco_fetch_contained");
-                at(6);
+                at(ST_FETCH_EDGES);
                 R.n_edges = R.info.e_out_local;
                 R.edges.reset(new disco_edge[std::max<uint64_t>(R.n_edges, 1)]);
                 if (R.n_edges && disco_fetch_edges(c, R.edges.get(), R.n_edges) < 0) bail("disco_fetch_edges");
@@ -627,7 +728,7 @@ int main(int argc, char **argv)
                     R.subs.reset(new uint16_t[std::max<uint64_t>(R.n_edges, 1)]);
                     if (R.n_edges && disco_fetch_edge_substitutions(c, R.subs.get(), R.n_edges) < 0) bail("disco_fetch_edge_substitutions");
                 }
-                at(7);
+                at(ST_DONE);
             });
         for (auto &t : th) t.join();
         ranks_done.store(true);

@@ -271,6 +271,7 @@ const char *disco_comm_kind(const disco_ctx *ctx);
 int disco_dist_range(const disco_ctx *ctx, uint64_t n_total, uint64_t *lo, uint64_t *hi);
 /* this rank's reads = rows [lo, hi) of the job's n_total reads (replaces the per-rank file pass of MPI/Dataset.cpp:153-170) */
 int disco_dist_upload_reads(disco_ctx *ctx, const uint64_t *packed_own, uint32_t stride_words, const uint16_t *len_own, uint64_t n_total);
+/* ... or the ranks read the files themselves: disco_dist_ingest_fasta, with the input stage on the GPU below */
 /* one whole pass; afterwards disco_fetch_edges / disco_fetch_contained / disco_fetch_edge_files return THIS rank's share */
 int disco_dist_run_graph(disco_ctx *ctx, uint32_t flags);
 int disco_dist_get_info(disco_ctx *ctx, disco_dist_info *out);
@@ -309,6 +310,33 @@ int64_t disco_inflate_bgzf(disco_ctx *ctx, const void *bgzf, uint64_t n_bytes, v
  * thread drives a pass on the same context (it works on the copy stream and shares only the mirrored lengths, under a lock); its
  * error text, if any, goes to the context's error buffer like everybody's — read it after joining the thread */
 int disco_ingest_fetch(disco_ctx *ctx, uint16_t *len, uint64_t *file_index);
+/* The device input stage on every rank (COLLECTIVE: every rank passes the same file list). The files laid end to end are T bytes; rank r
+ * reads the bytes [T r / G, T (r + 1) / G) — one piece per file it touches, the byte in front of each piece and, behind it, the rest
+ * of the last record that starts there (at most 2^21 bytes) — and finds, cleans, filters and packs the records whose FIRST byte lies in its
+ * pieces, exactly as disco_ingest_fasta does for whole files (FASTA: a '>' behind a newline; FASTQ: the lines whose index in the file is a
+ * multiple of 4, from the newline counts of the pieces before, exchanged; a lone trailing '>', the per-file counts and the read ids, which
+ * are those of disco_ingest_fasta, come from the all-gathered per-piece counts). The rows, lengths and record numbers a rank made for
+ * ids outside its home range travel to their owners in one all-to-all each. Afterwards the context is in the state
+ * disco_dist_upload_reads leaves it in: disco_dist_run_graph(ctx, DISCO_DIST_GATHER_READS | ...) is next.
+ * Every rank returns the same code: DISCO_E_UNSUPPORTED — each context stays usable, the caller runs its host stage and
+ * disco_dist_upload_reads — when ANY rank met something the device stage does not take (what disco_ingest_fasta declines, and under a
+ * communicator every .gz name, BGZF or not); disco_last_error names the file and the reason on every rank. A rank that fails (a file it
+ * cannot read, no memory, a HIP error) says so in the status word all ranks exchange and leaves with them: an error anywhere is an
+ * error everywhere, and no rank waits inside a collective for one that left. files[n_files]: as disco_ingest_fasta fills them, on every rank. */
+typedef struct disco_dist_ingest_info {
+    uint64_t n_reads, total_records, too_long; /* whole job, as disco_ingest_info */
+    uint32_t stride_words, shortest, longest;  /* whole job */
+    uint32_t world;
+    uint64_t share_lo, share_hi;               /* this rank's bytes of the files laid end to end */
+    uint64_t share_reads;                      /* good reads whose record starts in this rank's bytes */
+    uint64_t kept_reads;                       /* ... of which in its own home range (the others went to their owners) */
+    uint64_t home_lo, home_hi;                 /* the rank's home range of read ids (disco_dist_range) */
+    float read_s, device_s;                    /* host wall on this rank: its bytes into HBM / everything after */
+} disco_dist_ingest_info;
+int disco_dist_ingest_fasta(disco_ctx *ctx, const char *const *paths, int n_files, uint32_t host_threads, disco_dist_ingest_info *info, disco_ingest_file *files);
+/* lengths and 1-based file indices of the rank's HOME range after disco_dist_ingest_fasta: len[home_hi - home_lo], file_index[home_hi - home_lo]
+ * (the ranks' ranges, one behind the other, are what disco_ingest_fetch returns on one GPU). Local, not collective. */
+int disco_dist_ingest_fetch(disco_ctx *ctx, uint16_t *len, uint64_t *file_index);
 
 /* ---- results --------------------------------------------------------------------------------------------------- */
 /* optional: the rows start their way to the host NOW, on a side stream (grouped != 0: also in the contained-read files' order),

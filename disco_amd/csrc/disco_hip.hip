@@ -1988,21 +1988,37 @@ int disco_upload_reads_ragged(disco_ctx *c, const uint64_t *words, const uint16_
  * input stage on the GPU (kernels: disco_ingest.h)
  * ============================================================================================================== */
 namespace {
+/* figures of a piece's records: what its filter leaves and, under a communicator, what the ranks exchange */
+enum { DP_STARTS = 0, DP_GOOD, DP_TOO_LONG, DP_MAX_LEN, DP_MIN_LEN_INV, DP_N_LONG, DP_SHORT_MAX, DP_COUNT };
+
+/* the part of a file one job works on (kernels: disco_ingest.h). One GPU: the whole file; under a communicator: the rank's share of its bytes */
+struct IngestPiece {
+    u64 p0 = 0, p1 = 0;                /* the owned bytes of the file */
+    u64 own_lo = 0, own_hi = 0, n = 0; /* the same in the buffer, and the buffer's bytes */
+    bool to_eof = false;               /* the buffer reaches the end of the file */
+    bool prefix_nl = true, last_nl = false; /* the byte in front of the piece (the file's first byte: nothing counts as one) / its last byte is a newline */
+    u64 own_nl = 0, tiles = 0;
+    u8 *d_text = nullptr;
+    u64 *d_tile_base = nullptr, *d_ctr = nullptr; /* d_ctr: the kernels' counters (FX_CTR_COUNT) */
+    u32 *d_tile_cnt = nullptr;
+    u64 *d_start = nullptr, *d_seq = nullptr; /* the piece's records: n_start of them */
+    u32 *d_wrap = nullptr;
+    u16 *d_glen = nullptr;
+    u64 n_start = 0, good = 0;
+    u64 fig[DP_COUNT] = {0, 0, 0, 0, 0, 0, 0};
+};
+
 struct IngestFile {
     std::string path;
     int fd = -1;
     char last = 0;
     bool fastq = false;
-    u64 n = 0;
-    u8 *d_text = nullptr;
-    u64 *d_start = nullptr, *d_seq = nullptr;
-    u32 *d_wrap = nullptr;
-    u16 *d_glen = nullptr;
-    u64 n_start = 0, n_rec = 0, good = 0;
-    /* a BGZF file (map != null): n and d_text are its TEXT (known once the member chain is walked); the file itself is comp_n bytes at d_comp */
+    u64 n = 0; /* bytes of text */
+    /* a BGZF file (map != null): n and the piece's text are its TEXT (known once the member chain is walked); the file itself is comp_n bytes at d_comp */
     const u8 *map = nullptr;
     u64 comp_n = 0;
     u8 *d_comp = nullptr;
+    IngestPiece p;
 };
 } // namespace
 
@@ -2221,30 +2237,36 @@ extern "C" int64_t disco_inflate_bgzf(disco_ctx *c, const void *bgzf, uint64_t n
     return (int64_t)total;
 }
 
-/* ---- the input stage as steps: disco_ingest_fasta (below) is a list of steps over one IngestJob. A step answers DISCO_OK, an error
- * it has recorded with fail, or INGEST_DECLINED with the reason left in the job (an input the HOST stage reads: plain gzip, a '>' inside
- * a line ...): only disco_ingest_fasta turns that into its message. Whatever the job holds goes with it, on every way out. */
+/* ---- the input stage as steps over one IngestJob, with two drivers: disco_ingest_fasta (below: one piece per file, no exchange) and
+ * disco_dist_ingest_fasta (multi-GPU section: the pieces of the rank's share, all-gathers and an all-to-all between the steps). A step
+ * answers DISCO_OK, an error it has recorded with fail, or INGEST_DECLINED with the reason left in the job (an input the HOST stage reads:
+ * plain gzip, a '>' inside a line ...): only the drivers turn that into their message. Whatever the job holds goes with it, on every way out. */
 extern "C++" { /* (the job's `get` is a template) */
 namespace {
 constexpr int INGEST_DECLINED = 1;
-const char *const kIngestIrregular = "a '>' inside a line, an irregularly wrapped long record, or no record";
+/* why the stage leaves a job to the host stage (the ranks of a communicator tell each other by code). One condition has two codes: a plain
+ * file that cannot be opened is DR_NO_OPEN on one GPU and DR_UNREADABLE under a communicator — the words each entry point had before */
+enum { DR_NONE = 0, DR_GZ, DR_GZ_MEMBER, DR_BGZF_MEMBER, DR_GZ_COMM, DR_NO_OPEN, DR_UNREADABLE, DR_FORM, DR_IRREGULAR, DR_NO_READ, DR_LONG_RECORD, DR_COUNT };
+const char *const kIngestDecline[DR_COUNT] = {"", "gzip input", "gzip input,", "BGZF", /* (the last two: + "member N: ...", IngestJob::decline's detail) */
+                                              "gzip input (a .gz name is the host stage's under a communicator)", "unreadable file", "empty or unreadable file", "neither FASTA nor FASTQ",
+                                              "a '>' inside a line, an irregularly wrapped long record, or no record", "no good read (or more than 2^31)", "a record of 2^21 bytes or more"};
 
 struct IngestJob {
     disco_ctx *c;
+    const char *who; /* the entry point, for messages */
     unsigned threads; /* of the file reader */
     std::vector<IngestFile> F;
-    u8 *arena = nullptr; /* the transient buffers (text, record arrays) are carved out of it, 256-byte aligned (ingest_choose_arena) */
+    u8 *arena = nullptr; /* the transient buffers (text, record arrays) are carved out of it, 256-byte aligned */
     u64 arena_cap = 0, arena_used = 0;
     std::vector<std::pair<void *, size_t>> owned; /* pieces that did not fit the arena: allocations of their own, in hbm_bytes */
-    u64 *d_ctr = nullptr; /* the filter's counters (FX_CTR_COUNT) */
     FxTables tb;
     u64 total_bytes = 0; /* text of all files as it will lie in HBM (a .gz name: an estimate) */
-    ReadShape shape{0, 0, 0, 0, 0, 0xFFFFu}; /* of the good reads, summed file by file as they are filtered */
-    u64 total_records = 0, too_long = 0;
     float read_s = 0;
-    std::string why, where; /* of a decline */
+    int why_code = DR_NONE; /* of a decline: the code, the file's number, and both in words */
+    size_t why_file = 0;
+    std::string why, where;
     const HClock::time_point t_begin = HClock::now();
-    IngestJob(disco_ctx *ctx, int n_files, uint32_t host_threads) : c(ctx), threads(host_threads ? host_threads : 16u), F((size_t)n_files) { ingest_tables(&tb); }
+    IngestJob(disco_ctx *ctx, const char *entry, int n_files, uint32_t host_threads) : c(ctx), who(entry), threads(host_threads ? host_threads : 16u), F((size_t)n_files) { ingest_tables(&tb); }
     IngestJob(const IngestJob &) = delete;
     ~IngestJob()
     {
@@ -2258,7 +2280,12 @@ struct IngestJob {
         }
     }
     float seconds() const { return ms_since(t_begin) * 1e-3f; }
-    int decline(const std::string &reason, const IngestFile &f) { return why = reason, where = f.path, INGEST_DECLINED; }
+    int decline(int code, const IngestFile &f, const char *detail = nullptr)
+    {
+        why_code = code, why_file = (size_t)(&f - F.data()), where = f.path;
+        why = detail ? std::string(kIngestDecline[code]) + " " + detail : kIngestDecline[code];
+        return INGEST_DECLINED;
+    }
     template <typename T>
     int get(T **pp, u64 count) /* from the arena, or an allocation of its own */
     {
@@ -2277,41 +2304,57 @@ struct IngestJob {
         return DISCO_OK;
     }
 };
+
+/* what the figures of all pieces fold into (ingest_fold) */
+struct IngestFold {
+    ReadShape shape{0, 0, 0, 0, 0, 0xFFFFu}; /* of the job's good reads */
+    u64 total_records = 0, too_long = 0;
+    std::vector<u64> share; /* rank g's good reads are the ids [share[g], share[g + 1]): shares follow each other in file order */
+    std::vector<u64> file_id_base, file_rec_base; /* per file: first read id, records before the file (the context's ingest_id_base / ingest_rec_base once the table is begun) */
+    std::vector<u64> id_base, rec_in_file, n_rec; /* per file, of THIS rank's piece: id of its first good read / records of the file in the pieces before / its records */
+};
 } // namespace
 } // extern "C++"
 
 /* whole tiles (16-byte loads) and aligned 8-byte words behind the end of a text of n bytes */
 static u64 ingest_text_cap(u64 n) { return (n + FX_TILE + 63) / FX_TILE * FX_TILE + 64; }
 
-/* step: the files — regular, first byte '>' or '@'; under a .gz name BGZF only (plain gzip is one serial stream: the host stage's) */
+/* a file opened and classified — regular, first byte '>' or '@'. Under a .gz name: BGZF only where the caller decodes it (may_bgzf: one
+ * GPU; plain gzip is one serial stream, the host stage's), a decline otherwise. Answers a decline code */
+static int ingest_open_file(IngestFile &f, const char *path, bool may_bgzf)
+{
+    f.path = path ? path : "";
+    const bool gz_name = f.path.size() >= 3 && f.path.compare(f.path.size() - 3, 3, ".gz") == 0;
+    if (gz_name && !may_bgzf) return DR_GZ_COMM;
+    struct stat st;
+    f.fd = open(f.path.c_str(), O_RDONLY);
+    if (f.fd < 0 && !gz_name) return may_bgzf ? DR_NO_OPEN : DR_UNREADABLE; /* (the words each entry point has always had for it) */
+    if (f.fd < 0 || fstat(f.fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 1) return gz_name ? DR_GZ : DR_UNREADABLE;
+    if (gz_name) {
+        u32 hdr = 0, bsize = 0;
+        void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, f.fd, 0); /* for the header walk only: the readers pread */
+        if (m == MAP_FAILED) return DR_GZ;
+        f.map = (const u8 *)m;
+        f.comp_n = (u64)st.st_size;
+        return infl::bgzf_header(f.map, f.comp_n, 0, &hdr, &bsize) ? DR_GZ : DR_NONE;
+    }
+    char first = 0;
+    if (pread(f.fd, &first, 1, 0) != 1 || pread(f.fd, &f.last, 1, st.st_size - 1) != 1) return DR_UNREADABLE;
+    if (first != '>' && first != '@') return DR_FORM;
+    f.fastq = first == '@';
+    f.n = (u64)st.st_size;
+    return DR_NONE;
+}
+
+/* step (one GPU): the files, and the bytes their text will take in HBM */
 static int ingest_open(IngestJob &j, const char *const *paths)
 {
     for (size_t fi = 0; fi < j.F.size(); fi++) {
         IngestFile &f = j.F[fi];
-        f.path = paths[fi] ? paths[fi] : "";
-        const bool gz_name = f.path.size() >= 3 && f.path.compare(f.path.size() - 3, 3, ".gz") == 0;
-        struct stat st;
-        f.fd = open(f.path.c_str(), O_RDONLY);
-        if (f.fd < 0 && !gz_name) return j.decline("unreadable file", f);
-        if (f.fd < 0 || fstat(f.fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 1) return j.decline(gz_name ? "gzip input" : "empty or unreadable file", f);
-        if (gz_name) {
-            u32 hdr = 0, bsize = 0;
-            void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, f.fd, 0); /* for the header walk only: the readers pread */
-            if (m == MAP_FAILED) return j.decline("gzip input", f);
-            f.map = (const u8 *)m;
-            f.comp_n = (u64)st.st_size;
-            if (infl::bgzf_header(f.map, f.comp_n, 0, &hdr, &bsize)) return j.decline("gzip input", f);
-            /* the text's size is known when the chain is walked, behind the transfer: the arena is sized for five times the file (FASTA
-             * at level 6: four); a text that does not fit gets a piece of its own */
-            j.total_bytes += ((f.comp_n + 255) & ~255ull) + ingest_text_cap(f.comp_n * 5);
-            continue;
-        }
-        char first = 0;
-        if (pread(f.fd, &first, 1, 0) != 1 || pread(f.fd, &f.last, 1, st.st_size - 1) != 1) return j.decline("empty or unreadable file", f);
-        if (first != '>' && first != '@') return j.decline("neither FASTA nor FASTQ", f);
-        f.fastq = first == '@';
-        f.n = (u64)st.st_size;
-        j.total_bytes += ingest_text_cap(f.n);
+        if (const int code = ingest_open_file(f, paths[fi], true)) return j.decline(code, f);
+        /* BGZF: the text's size is known when the chain is walked, behind the transfer: the arena is sized for five times the file (FASTA
+         * at level 6: four); a text that does not fit gets a piece of its own */
+        j.total_bytes += f.map ? ((f.comp_n + 255) & ~255ull) + ingest_text_cap(f.comp_n * 5) : ingest_text_cap(f.n);
     }
     return DISCO_OK;
 }
@@ -2366,7 +2409,7 @@ static int ingest_choose_arena(IngestJob &j)
         j.arena = (u8 *)c->d_hits.p;
         j.arena_cap = c->d_hits.cap * 8;
     }
-    return j.get(&j.d_ctr, (u64)FX_CTR_COUNT);
+    return DISCO_OK;
 }
 
 /* a BGZF file's text: the file into HBM while a host thread walks its member chain; then one wavefront per member writes the text */
@@ -2390,149 +2433,264 @@ static int ingest_text_bgzf(IngestJob &j, IngestFile &f)
     CHK(rrc);
     char msg[160];
     if (why || total == 0) {
-        snprintf(msg, sizeof msg, "gzip input, member %llu: %s", (unsigned long long)bad, why ? why : "no text");
-        return j.decline(msg, f);
+        snprintf(msg, sizeof msg, "member %llu: %s", (unsigned long long)bad, why ? why : "no text");
+        return j.decline(DR_GZ_MEMBER, f, msg);
     }
     const auto t_inf = HClock::now();
     f.n = total;
     infl::BgzfBlock *d_blk = nullptr;
     u32 *d_status = nullptr;
-    CHK(j.get(&f.d_text, ingest_text_cap(f.n)));
+    CHK(j.get(&f.p.d_text, ingest_text_cap(f.n)));
     CHK(j.get(&d_blk, blocks.size()));
     CHK(j.get(&d_status, blocks.size() + 1));
-    HIPCHK(c, hipMemsetAsync(f.d_text + f.n, 0, ingest_text_cap(f.n) - f.n, c->stream));
+    HIPCHK(c, hipMemsetAsync(f.p.d_text + f.n, 0, ingest_text_cap(f.n) - f.n, c->stream));
     int e = infl::INFL_OK;
-    CHK(bgzf_inflate_run(c, f.d_comp, blocks, d_blk, d_status, f.d_text, &bad, &e));
+    CHK(bgzf_inflate_run(c, f.d_comp, blocks, d_blk, d_status, f.p.d_text, &bad, &e));
     if (e != infl::INFL_OK) {
-        snprintf(msg, sizeof msg, "BGZF member %llu: %s", (unsigned long long)bad, infl::reason(e));
-        return j.decline(msg, f);
+        snprintf(msg, sizeof msg, "member %llu: %s", (unsigned long long)bad, infl::reason(e));
+        return j.decline(DR_BGZF_MEMBER, f, msg);
     }
     char first = 0;
-    HIPCHK(c, hipMemcpy(&first, f.d_text, 1, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&f.last, f.d_text + f.n - 1, 1, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&first, f.p.d_text, 1, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&f.last, f.p.d_text + f.n - 1, 1, hipMemcpyDeviceToHost));
     if (getenv("DISCO_VERBOSE"))
         fprintf(stderr, "[disco] BGZF %s: %.1f MB in %llu members -> %.1f MB of text; header walk %.1f ms (behind the transfer), inflate %.1f ms\n", f.path.c_str(), f.comp_n / 1e6,
                 (unsigned long long)blocks.size(), f.n / 1e6, walk_ms, ms_since(t_inf));
-    if (first != '>' && first != '@') return j.decline("neither FASTA nor FASTQ", f);
+    if (first != '>' && first != '@') return j.decline(DR_FORM, f);
     f.fastq = first == '@';
     return DISCO_OK;
 }
 
-/* step: one file's text into HBM, plain or BGZF */
-static int ingest_text(IngestJob &j, IngestFile &f)
+/* step: the bytes of a piece into HBM — the byte in front of it (own_lo = 1; none at the top of a file), the owned bytes and what follows
+ * them up to p.n. ring: the caller's pinned ring instead of the context's */
+static int ingest_piece_text(IngestJob &j, IngestFile &f, void *ring = nullptr, size_t ring_bytes = 0)
 {
-    if (f.map) return ingest_text_bgzf(j, f);
     disco_ctx *c = j.c;
+    IngestPiece &p = f.p;
     const auto t_read = HClock::now();
-    CHK(j.get(&f.d_text, ingest_text_cap(f.n)));
-    HIPCHK(c, hipMemsetAsync(f.d_text + f.n, 0, ingest_text_cap(f.n) - f.n, c->stream));
-    const int rc = ingest_read_file(c, f.fd, f.n, f.d_text, j.threads);
+    CHK(j.get(&p.d_text, ingest_text_cap(p.n)));
+    HIPCHK(c, hipMemsetAsync(p.d_text + p.n, 0, ingest_text_cap(p.n) - p.n, c->stream));
+    const int rc = ingest_read_file(c, f.fd, p.n, p.d_text, j.threads, p.p0 - p.own_lo, ring, ring_bytes);
     j.read_s += ms_since(t_read) * 1e-3f;
     return rc;
 }
 
-/* step: the records of one file — FASTA: the '>' that start a line; FASTQ: every fourth line */
-static int ingest_records(IngestJob &j, IngestFile &f)
+/* step (one GPU): one file's text into HBM, plain or BGZF — the piece that owns every byte, with nothing in front and nothing behind */
+static int ingest_text(IngestJob &j, IngestFile &f)
+{
+    if (f.map) CHK(ingest_text_bgzf(j, f));
+    IngestPiece &p = f.p;
+    p.p0 = p.own_lo = 0;
+    p.p1 = p.own_hi = p.n = f.n;
+    p.to_eof = p.prefix_nl = true;
+    p.last_nl = f.last == '\n';
+    return f.map ? DISCO_OK : ingest_piece_text(j, f);
+}
+
+/* step: the record starts of a piece, placed. FASTQ: line0 = newlines of the file in front of the piece (a whole file: 0) */
+static int ingest_place_starts(IngestJob &j, IngestFile &f, u64 line0)
 {
     disco_ctx *c = j.c;
-    const u64 tiles = (f.n + FX_TILE - 1) / FX_TILE;
-    u64 *d_tile_base = nullptr;
-    u32 *d_tile_cnt = nullptr;
-    CHK(j.get(&d_tile_base, tiles + 1));
-    CHK(j.get(&d_tile_cnt, tiles));
-    HIPCHK(c, hipMemsetAsync(j.d_ctr, 0, FX_CTR_COUNT * sizeof(u64), c->stream));
+    IngestPiece &p = f.p;
+    u64 rec0 = 0; /* FASTQ: the file's records that start in front of the piece */
     if (f.fastq) {
-        u64 n_newlines = 0;
-        hipLaunchKernelGGL(fx_lines_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, d_tile_cnt, (const u64 *)nullptr, (u64 *)nullptr);
-        CHK((scan_exclusive<u32, u64>(c, d_tile_cnt, tiles, d_tile_base, false, &n_newlines)));
-        const u64 n_lines = n_newlines + (f.last == '\n' ? 0 : 1); /* a last line without a newline is a line */
-        f.n_start = (n_lines + 3) / 4; /* the reference starts a record whenever bytes are left (BG/Dataset.cpp:255-293) */
-        f.n_rec = f.n_start;
-    } else {
-        hipLaunchKernelGGL(fx_starts_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, d_tile_cnt, (const u64 *)nullptr, (u64 *)nullptr, j.d_ctr);
-        CHK((scan_exclusive<u32, u64>(c, d_tile_cnt, tiles, d_tile_base, false, &f.n_start)));
+        /* the lines that BEGIN in the owned bytes: one at the first byte if a newline stands in front of it, one behind every owned
+         * newline but the piece's last byte (that line is the next piece's, or nobody's at the end of the file: a last line without a
+         * newline is a line). Line l of the file begins record l / 4 where l is a multiple of 4: the reference starts a record whenever
+         * bytes are left (BG/Dataset.cpp:255-293) */
+        const u64 first = p.prefix_nl ? line0 : line0 + 1, lines = (p.prefix_nl ? 1 : 0) + p.own_nl - (p.last_nl ? 1 : 0);
+        rec0 = (first + 3) / 4;
+        p.n_start = (lines && (first + lines - 1) / 4 + 1 > rec0) ? (first + lines - 1) / 4 + 1 - rec0 : 0;
+    }
+    if (p.n_start >= (1ull << 32)) return j.decline(DR_IRREGULAR, f);
+    CHK(j.get(&p.d_start, p.n_start));
+    if (f.fastq)
+        hipLaunchKernelGGL(fx_lines_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d_text, p.n, p.own_lo, p.own_hi, line0, (u32 *)nullptr, (const u64 *)p.d_tile_base,
+                           p.d_start, rec0, p.n_start, p.d_ctr);
+    else
+        hipLaunchKernelGGL(fx_starts_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d_text, p.n, p.own_lo, p.own_hi, (u32 *)nullptr, (const u64 *)p.d_tile_base, p.d_start,
+                           p.d_ctr);
+    HIPCHK(c, hipGetLastError());
+    return DISCO_OK;
+}
+
+/* step: the record starts of a piece, counted — FASTA: the '>' that start a line, which are placed right away; FASTQ: the owned
+ * newlines (a record is every fourth LINE of the file: ingest_place_starts, once the lines in front of the piece are known) */
+static int ingest_count_starts(IngestJob &j, IngestFile &f)
+{
+    disco_ctx *c = j.c;
+    IngestPiece &p = f.p;
+    p.tiles = (p.n + FX_TILE - 1) / FX_TILE;
+    CHK(j.get(&p.d_tile_base, p.tiles + 1));
+    CHK(j.get(&p.d_tile_cnt, p.tiles));
+    CHK(j.get(&p.d_ctr, (u64)FX_CTR_COUNT));
+    HIPCHK(c, hipMemsetAsync(p.d_ctr, 0, FX_CTR_COUNT * sizeof(u64), c->stream));
+    u64 total = 0;
+    if (f.fastq)
+        hipLaunchKernelGGL(fx_lines_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d_text, p.n, p.own_lo, p.own_hi, (u64)0, p.d_tile_cnt, (const u64 *)nullptr,
+                           (u64 *)nullptr, (u64)0, (u64)0, p.d_ctr);
+    else
+        hipLaunchKernelGGL(fx_starts_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d_text, p.n, p.own_lo, p.own_hi, p.d_tile_cnt, (const u64 *)nullptr, (u64 *)nullptr,
+                           p.d_ctr);
+    CHK((scan_exclusive<u32, u64>(c, p.d_tile_cnt, p.tiles, p.d_tile_base, false, &total)));
+    if (!f.fastq) {
+        p.n_start = total;
+        return ingest_place_starts(j, f, 0);
+    }
+    p.own_nl = total; /* the newlines from own_lo on: the owned ones where nothing follows the owned bytes, else the kernel has summed those */
+    if (p.own_hi < p.n) {
+        HIPCHK(c, hipMemcpyAsync(&p.own_nl, p.d_ctr + FX_CTR_OWN_NL, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return DISCO_OK;
+}
+
+/* step: clean + filter the records of a piece; what is left of them as the piece's figures */
+static int ingest_filter_piece(IngestJob &j, IngestFile &f)
+{
+    disco_ctx *c = j.c;
+    IngestPiece &p = f.p;
+    u64 h[FX_CTR_COUNT] = {0};
+    /* where the last owned record ends: the first record start behind the owned bytes, or the end of the file. A piece that ends its
+     * buffer (a whole file) has nothing behind it: its counters are read once, with the filter's */
+    if (p.own_hi < p.n || !p.n_start) {
+        HIPCHK(c, hipMemcpyAsync(h, p.d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h[FX_CTR_BAD_GT]) return j.decline(DR_IRREGULAR, f);
+    }
+    p.fig[DP_STARTS] = p.n_start;
+    if (!p.n_start) return DISCO_OK;
+    u64 end = p.n;
+    if (h[FX_CTR_NEXT_INV]) end = ~h[FX_CTR_NEXT_INV];
+    else if (!p.to_eof) return j.decline(DR_LONG_RECORD, f);
+    CHK(j.get(&p.d_seq, p.n_start));
+    CHK(j.get(&p.d_glen, p.n_start));
+    CHK(j.get(&p.d_wrap, p.n_start));
+    /* (a '>' that is the file's very last byte is filtered as a record of no bases: never good, never counted — ingest_fold) */
+    const FxFilterArgs fa{.text = p.d_text, .n = end, .start = p.d_start, .n_start = p.n_start, .n_rec = p.n_start, .min_overlap = c->prm.min_overlap, .fastq = f.fastq ? 1u : 0u,
+                          .glen = p.d_glen, .seq_begin = p.d_seq, .wrap = p.d_wrap, .ctr = p.d_ctr};
+    hipLaunchKernelGGL(fx_filter_kernel, dim3(flat_grid(c, p.n_start)), dim3(256), 0, c->stream, fa, j.tb);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h, p.d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h[FX_CTR_BAD_GT] || h[FX_CTR_MULTILINE]) return j.decline(DR_IRREGULAR, f);
+    const int from[DP_COUNT] = {-1, FX_CTR_GOOD, FX_CTR_TOO_LONG, FX_CTR_MAX_LEN, FX_CTR_MIN_LEN_INV, FX_CTR_N_LONG, FX_CTR_SHORT_MAX}; /* (DP_STARTS: above) */
+    for (int k = DP_GOOD; k < DP_COUNT; k++) p.fig[k] = h[from[k]];
+    p.good = p.fig[DP_GOOD];
+    return DISCO_OK;
+}
+
+/* this job's figures as they travel: a status word (the communicator's), then DP_COUNT figures per file */
+static std::vector<u64> ingest_figures(const IngestJob &j, u64 status)
+{
+    std::vector<u64> v(1 + j.F.size() * DP_COUNT, status); /* (every other word is written below) */
+    for (size_t fi = 0; fi < j.F.size(); fi++) memcpy(&v[1 + fi * DP_COUNT], j.F[fi].p.fig, sizeof j.F[fi].p.fig);
+    return v;
+}
+
+/* the figures of every rank's pieces, all[rank][ingest_figures] (one GPU: world = 1) -> the job: the shape of its reads, the per-file
+ * counts, the ids of every rank's share and where this rank's pieces lie in them. Every rank computes the same from the same numbers */
+static int ingest_fold(IngestJob &j, const std::vector<u64> &all, size_t world, size_t rank, disco_ingest_file *files, IngestFold *o)
+{
+    const size_t F = j.F.size(), PR = 1 + F * DP_COUNT;
+    auto fig = [&](size_t g, size_t fi, int what) { return all[g * PR + 1 + fi * DP_COUNT + (size_t)what]; };
+    ReadShape &s = o->shape;
+    o->share.assign(world + 1, 0);
+    o->id_base = o->rec_in_file = o->n_rec = std::vector<u64>(F, 0);
+    o->file_id_base = o->file_rec_base = std::vector<u64>(F + 1, 0);
+    for (size_t fi = 0; fi < F; fi++) {
+        u64 starts = 0, good = 0;
+        size_t last_piece = 0; /* the rank that owns the file's last record start */
+        for (size_t g = 0; g < world; g++) {
+            starts += fig(g, fi, DP_STARTS);
+            if (fig(g, fi, DP_STARTS)) last_piece = g;
+        }
+        if (starts == 0 || starts >= (1ull << 32)) return j.decline(DR_IRREGULAR, j.F[fi]);
         /* a '>' that is the very last byte starts nothing (the reference's next getline fails) unless it is the only one; it still
          * ends the sequence of the record before it (disco_amd/host/fastx.cpp) */
-        f.n_rec = (f.n_start > 1 && f.last == '>') ? f.n_start - 1 : f.n_start;
+        const bool lone_gt = !j.F[fi].fastq && starts > 1 && j.F[fi].last == '>';
+        u64 recs = 0;
+        for (size_t g = 0; g < world; g++) {
+            const u64 nr = fig(g, fi, DP_STARTS) - ((lone_gt && g == last_piece) ? 1 : 0);
+            if (g == rank) {
+                o->id_base[fi] = s.n + good;
+                o->rec_in_file[fi] = recs;
+                o->n_rec[fi] = nr;
+            }
+            recs += nr;
+            const u64 gd = fig(g, fi, DP_GOOD);
+            good += gd;
+            o->share[g + 1] += gd;
+            o->too_long += fig(g, fi, DP_TOO_LONG);
+            if (gd) {
+                s.longest = std::max(s.longest, (u32)fig(g, fi, DP_MAX_LEN));
+                s.shortest = std::min(s.shortest, 0xFFFFu - (u32)fig(g, fi, DP_MIN_LEN_INV));
+                s.n_long += fig(g, fi, DP_N_LONG);
+                s.short_max = std::max(s.short_max, (u32)fig(g, fi, DP_SHORT_MAX));
+            }
+        }
+        files[fi] = disco_ingest_file{.first_index = o->total_records + 1, .last_index = o->total_records + recs, .good = good, .bad = recs - good};
+        o->total_records += recs;
+        s.n += good;
+        o->file_id_base[fi + 1] = s.n;
+        o->file_rec_base[fi + 1] = o->total_records;
     }
-    if (f.n_start == 0 || f.n_start >= (1ull << 32)) return j.decline(kIngestIrregular, f);
-    CHK(j.get(&f.d_start, f.n_start));
-    CHK(j.get(&f.d_seq, f.n_rec));
-    CHK(j.get(&f.d_glen, f.n_rec));
-    CHK(j.get(&f.d_wrap, f.n_rec));
-    if (f.fastq) hipLaunchKernelGGL(fx_lines_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, (u32 *)nullptr, (const u64 *)d_tile_base, f.d_start);
-    else hipLaunchKernelGGL(fx_starts_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const u8 *)f.d_text, f.n, (u32 *)nullptr, (const u64 *)d_tile_base, f.d_start, j.d_ctr);
-    return DISCO_OK;
-}
-
-/* step: clean + filter the records of one file; its counters into the job's totals and the caller's per-file entry */
-static int ingest_filter(IngestJob &j, IngestFile &f, disco_ingest_file *out)
-{
-    disco_ctx *c = j.c;
-    const FxFilterArgs fa{.text = f.d_text, .n = f.n, .start = f.d_start, .n_start = f.n_start, .n_rec = f.n_rec, .min_overlap = c->prm.min_overlap, .fastq = f.fastq ? 1u : 0u,
-                          .glen = f.d_glen, .seq_begin = f.d_seq, .wrap = f.d_wrap, .ctr = j.d_ctr};
-    hipLaunchKernelGGL(fx_filter_kernel, dim3(flat_grid(c, f.n_rec)), dim3(256), 0, c->stream, fa, j.tb);
-    HIPCHK(c, hipGetLastError());
-    u64 h[FX_CTR_COUNT];
-    HIPCHK(c, hipMemcpyAsync(h, j.d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (h[FX_CTR_BAD_GT] || h[FX_CTR_MULTILINE]) return j.decline(kIngestIrregular, f);
-    f.good = h[FX_CTR_GOOD];
-    j.too_long += h[FX_CTR_TOO_LONG];
-    if (f.good) {
-        j.shape.longest = std::max(j.shape.longest, (u32)h[FX_CTR_MAX_LEN]);
-        j.shape.shortest = std::min(j.shape.shortest, 0xFFFFu - (u32)h[FX_CTR_MIN_LEN_INV]);
-        j.shape.n_long += h[FX_CTR_N_LONG];
-        j.shape.short_max = std::max(j.shape.short_max, (u32)h[FX_CTR_SHORT_MAX]);
-    }
-    *out = disco_ingest_file{.first_index = j.total_records + 1, .last_index = j.total_records + f.n_rec, .good = f.good, .bad = f.n_rec - f.good};
-    j.total_records += f.n_rec;
-    j.shape.n += f.good;
-    return DISCO_OK;
-}
-
-/* step: the read table — ids in file order, rows packed straight from the text (per class where the table has two classes of rows) */
-static int ingest_build_table(IngestJob &j)
-{
-    disco_ctx *c = j.c;
-    ReadShape &s = j.shape;
-    if (s.n == 0 || s.n >= (1ull << 31)) return j.decline("no good read (or more than 2^31)", j.F[0]);
+    for (size_t g = 0; g < world; g++) o->share[g + 1] += o->share[g];
+    if (s.n == 0 || s.n >= (1ull << 31)) return j.decline(DR_NO_READ, j.F[0]);
     s.stride = (std::max<u32>(1, (s.longest + 31) / 32) + 7u) & ~7u;
-    CHK(begin_read_table(c, s, true)); /* (true: the arena may be the hit buffer) */
-    const size_t n_files = j.F.size();
-    CHK(ensure(c, c->d_rec_of_read, s.n));
-    c->ingest_id_base.assign(n_files + 1, 0);
-    c->ingest_rec_base.assign(n_files + 1, 0);
+    return DISCO_OK;
+}
+
+/* step: the good reads of this job's pieces into the table the driver has begun, at their ids — lengths, record numbers within the
+ * file, rows packed straight from the text (the short class's where the table has two classes of rows). Nothing waits for the device */
+static int ingest_place_reads(IngestJob &j, const IngestFold &o)
+{
+    disco_ctx *c = j.c;
+    c->ingest_id_base = o.file_id_base; /* (here, not in the fold: a declined job leaves the context what the fetch calls read) */
+    c->ingest_rec_base = o.file_rec_base;
     u64 max_rec = 0;
-    for (auto &f : j.F) max_rec = std::max(max_rec, f.n_rec);
+    for (auto &f : j.F) max_rec = std::max(max_rec, f.p.n_start);
     u64 *d_pos = nullptr;
     u8 *d_flag = nullptr;
     CHK(j.get(&d_pos, max_rec + 1));
     CHK(j.get(&d_flag, max_rec));
-    for (size_t fi = 0; fi < n_files; fi++) {
-        IngestFile &f = j.F[fi];
-        const u64 id_base = c->ingest_id_base[fi];
-        hipLaunchKernelGGL(fx_flags_kernel, dim3(flat_grid(c, f.n_rec)), dim3(256), 0, c->stream, (const u16 *)f.d_glen, f.n_rec, d_flag);
+    for (size_t fi = 0; fi < j.F.size(); fi++) {
+        const IngestPiece &p = j.F[fi].p;
+        const u64 nr = o.n_rec[fi], id_base = o.id_base[fi];
+        if (!nr) continue;
+        hipLaunchKernelGGL(fx_flags_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const u16 *)p.d_glen, nr, d_flag);
         u64 good = 0;
-        CHK((scan_exclusive<u8, u64>(c, d_flag, f.n_rec, d_pos, false, &good)));
-        if (good != f.good) return fail(c, DISCO_E_STATE, "disco_ingest_fasta: %llu good reads counted, %llu placed", (unsigned long long)f.good, (unsigned long long)good);
-        hipLaunchKernelGGL(fx_ids_kernel, dim3(flat_grid(c, f.n_rec)), dim3(256), 0, c->stream, (const u16 *)f.d_glen, (const u64 *)d_pos, f.n_rec, id_base, c->d_rec_of_read, c->d_len);
-        if (f.good)
-            hipLaunchKernelGGL(fx_pack_kernel, dim3(flat_grid(c, f.good * (u64)c->S)), dim3(256), 0, c->stream, (const u8 *)f.d_text, (const u64 *)f.d_seq, (const u32 *)f.d_wrap, (const u32 *)c->d_rec_of_read,
-                               (const u16 *)c->d_len, id_base, f.good, c->S, c->two_class ? (u32)DISCO_SHORT_MAX : 0xFFFFu, c->d_reads);
+        CHK((scan_exclusive<u8, u64>(c, d_flag, nr, d_pos, false, &good)));
+        if (good != p.good) return fail(c, DISCO_E_STATE, "%s: %llu good reads counted, %llu placed", j.who, (unsigned long long)p.good, (unsigned long long)good);
+        if (id_base + good > o.shape.n) return fail(c, DISCO_E_STATE, "%s: ids beyond the job's reads", j.who);
+        if (!good) continue;
+        hipLaunchKernelGGL(fx_ids_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const u16 *)p.d_glen, (const u64 *)d_pos, nr, id_base, c->d_rec_of_read.p, c->d_len);
+        hipLaunchKernelGGL(fx_pack_kernel, dim3(flat_grid(c, good * (u64)c->S)), dim3(256), 0, c->stream, (const u8 *)p.d_text, (const u64 *)p.d_seq, (const u32 *)p.d_wrap,
+                           (const u32 *)c->d_rec_of_read.p, (const u16 *)c->d_len, id_base, good, c->S, c->two_class ? (u32)DISCO_SHORT_MAX : 0xFFFFu, c->d_reads);
+        if (o.rec_in_file[fi])
+            hipLaunchKernelGGL(fx_rec_add_kernel, dim3(flat_grid(c, good)), dim3(256), 0, c->stream, c->d_rec_of_read.p, id_base, id_base + good, (u32)o.rec_in_file[fi]);
         HIPCHK(c, hipGetLastError());
-        c->ingest_id_base[fi + 1] = id_base + f.good;
-        c->ingest_rec_base[fi + 1] = c->ingest_rec_base[fi] + f.n_rec;
     }
+    return DISCO_OK;
+}
+
+/* step (one GPU): the read table — every file's reads in file order, then the long class's rows where the table has two classes */
+static int ingest_build_table(IngestJob &j, const IngestFold &o)
+{
+    disco_ctx *c = j.c;
+    const ReadShape &s = o.shape;
+    CHK(begin_read_table(c, s, true)); /* (true: the arena may be the hit buffer) */
+    CHK(ensure(c, c->d_rec_of_read, s.n));
+    CHK(ingest_place_reads(j, o));
     if (c->two_class) { /* every read has its id and length: number the long ones, then their full and tail rows, file by file */
         u64 counted = 0;
         CHK(number_long_reads(c, c->d_ovf, c->d_long_ids, &counted));
         if (counted != s.n_long) return fail(c, DISCO_E_STATE, "disco_ingest_fasta: %llu long reads counted, %llu placed", (unsigned long long)s.n_long, (unsigned long long)counted);
-        for (size_t fi = 0; fi < n_files; fi++) {
-            IngestFile &f = j.F[fi];
-            if (!f.good) continue;
-            hipLaunchKernelGGL(fx_pack_long_kernel, dim3(flat_grid(c, s.n_long * ((u64)s.stride + 8))), dim3(256), 0, c->stream, (const u8 *)f.d_text, (const u64 *)f.d_seq, (const u32 *)f.d_wrap,
-                               (const u32 *)c->d_rec_of_read, (const u16 *)c->d_len, c->ingest_id_base[fi], f.good, (const u32 *)c->d_long_ids, s.n_long, s.n, (int)s.stride, c->tailb, c->d_full,
+        for (size_t fi = 0; fi < j.F.size(); fi++) {
+            const IngestPiece &p = j.F[fi].p;
+            if (!p.good) continue;
+            hipLaunchKernelGGL(fx_pack_long_kernel, dim3(flat_grid(c, s.n_long * ((u64)s.stride + 8))), dim3(256), 0, c->stream, (const u8 *)p.d_text, (const u64 *)p.d_seq, (const u32 *)p.d_wrap,
+                               (const u32 *)c->d_rec_of_read, (const u16 *)c->d_len, c->ingest_id_base[fi], p.good, (const u32 *)c->d_long_ids, s.n_long, s.n, (int)s.stride, c->tailb, c->d_full,
                                c->d_reads);
         }
         HIPCHK(c, hipGetLastError());
@@ -2560,30 +2718,54 @@ extern "C" int disco_ingest_fasta(disco_ctx *c, const char *const *paths, int n_
     if (!c || !paths || n_files < 1 || !info || !files) return c ? fail(c, DISCO_E_ARG, "disco_ingest_fasta: null argument") : DISCO_E_ARG;
     if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "disco_ingest_fasta: single-GPU contexts only");
     HIPCHK(c, hipSetDevice(c->device));
-    IngestJob job(c, n_files, host_threads);
+    IngestJob job(c, "disco_ingest_fasta", n_files, host_threads);
+    IngestFold o;
     int rc = ingest_open(job, paths);
     if (rc == DISCO_OK) rc = ingest_choose_arena(job);
     const float t_arena = job.seconds();
-    for (int fi = 0; fi < n_files && rc == DISCO_OK; fi++) { /* every file: its text into HBM, its records, clean + filter */
+    for (int fi = 0; fi < n_files && rc == DISCO_OK; fi++) { /* every file, as one piece: its text into HBM, its records, clean + filter */
         IngestFile &f = job.F[(size_t)fi];
         rc = ingest_text(job, f);
-        if (rc == DISCO_OK) rc = ingest_records(job, f);
-        if (rc == DISCO_OK) rc = ingest_filter(job, f, &files[fi]);
+        if (rc == DISCO_OK) rc = ingest_count_starts(job, f);
+        if (rc == DISCO_OK && f.fastq) rc = ingest_place_starts(job, f, 0);
+        if (rc == DISCO_OK) rc = ingest_filter_piece(job, f);
     }
+    if (rc == DISCO_OK) rc = ingest_fold(job, ingest_figures(job, 0), 1, 0, files, &o);
     const float t_filtered = job.seconds();
-    if (rc == DISCO_OK) rc = ingest_build_table(job);
+    if (rc == DISCO_OK) rc = ingest_build_table(job, o);
     if (rc == INGEST_DECLINED) return fail(c, DISCO_E_UNSUPPORTED, "disco_ingest_fasta: %s (%s): the host input stage takes this job", job.why.c_str(), job.where.c_str());
     CHK(rc);
     if (getenv("DISCO_VERBOSE"))
         fprintf(stderr, "[disco] input stage: arena of %.1f GB %.3f s, files + records + filter %.3f s (files %.3f), table + ids + rows %.3f s\n", job.arena_cap / 1e9, t_arena,
                 t_filtered - t_arena, job.read_s, job.seconds() - t_filtered);
     ingest_hand_over_arena(job);
-    const ReadShape &s = job.shape;
+    const ReadShape &s = o.shape;
     c->ingest_n = s.n;
     c->h_len_ok = false;
     c->phase = 1;
-    *info = disco_ingest_info{.n_reads = s.n, .total_records = job.total_records, .too_long = job.too_long, .stride_words = std::max<u32>(1, (s.longest + 31) / 32),
+    *info = disco_ingest_info{.n_reads = s.n, .total_records = o.total_records, .too_long = o.too_long, .stride_words = std::max<u32>(1, (s.longest + 31) / 32),
                               .shortest = s.shortest, .longest = s.longest, .read_s = job.read_s, .device_s = job.seconds() - job.read_s};
+    return DISCO_OK;
+}
+
+/* lengths and file indices of the reads [lo, hi) of a table the input stage made, to len[0 ..) and file_index[0 ..): a read's record
+ * number within its file -> the 1-based number of the record among all records of the job */
+static int ingest_fetch_range(disco_ctx *c, u64 lo, u64 hi, hipStream_t st, uint16_t *len, uint64_t *file_index)
+{
+    if (hi <= lo) return DISCO_OK;
+    const u64 n = hi - lo;
+    std::unique_ptr<u32[]> rec(new u32[n]);
+    HIPCHK(c, hipMemcpyAsync(len, c->d_len + lo, n * 2, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(rec.get(), c->d_rec_of_read.p + lo, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const u32 *r = rec.get();
+    for (size_t fi = 0; fi + 1 < c->ingest_id_base.size(); fi++) {
+        const u64 a = std::max(lo, c->ingest_id_base[fi]), b = std::min(hi, c->ingest_id_base[fi + 1]), rb = c->ingest_rec_base[fi];
+        if (b > a)
+            parallel_for(b - a, [&, a, rb](u64 x, u64 y) {
+                for (u64 i = a + x; i < a + y; i++) file_index[i - lo] = rb + (u64)r[i - lo] + 1; /* BG/Dataset.cpp:294: every record counts */
+            });
+    }
     return DISCO_OK;
 }
 
@@ -2593,20 +2775,9 @@ extern "C" int disco_ingest_fetch(disco_ctx *c, uint16_t *len, uint64_t *file_in
     if (c->phase < 1 || c->ingest_n == 0 || c->ingest_n != c->n) return fail(c, DISCO_E_STATE, "disco_ingest_fetch: the reads of the context did not come from disco_ingest_fasta");
     HIPCHK(c, hipSetDevice(c->device));
     const u64 n = c->n;
-    std::unique_ptr<u32[]> rec(new u32[n]);
     /* on the copy stream: the call may run on a host thread of its own while the context's stream is busy with the pass (buildG does
      * that: the per-read arrays are only needed by the writers) */
-    hipStream_t st = c->copy_stream ? c->copy_stream : c->stream;
-    HIPCHK(c, hipMemcpyAsync(len, c->d_len, n * 2, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(rec.get(), c->d_rec_of_read, n * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    const u32 *r = rec.get();
-    for (size_t fi = 0; fi + 1 < c->ingest_id_base.size(); fi++) {
-        const u64 lo = c->ingest_id_base[fi], hi = c->ingest_id_base[fi + 1], rb = c->ingest_rec_base[fi];
-        parallel_for(hi - lo, [&, lo, rb](u64 b, u64 e_) {
-            for (u64 i = lo + b; i < lo + e_; i++) file_index[i] = rb + (u64)r[i] + 1; /* BG/Dataset.cpp:294: every record counts */
-        });
-    }
+    CHK(ingest_fetch_range(c, 0, n, c->copy_stream ? c->copy_stream : c->stream, len, file_index));
     {
         std::lock_guard<std::mutex> lk(c->h_len_mu);
         if (!(c->h_len_ok && c->h_len.size() == n)) { /* (ensure_host_len may have mirrored them meanwhile) */
@@ -5591,14 +5762,15 @@ int disco_dist_generate_reads(disco_ctx *c, const disco_genspec_abi *s)
     return dist_validate(c);
 }
 
-/* ---- the device input stage on every rank (include/disco_hip.h: disco_dist_ingest_fasta; kernels: disco_ingest.h, "a PIECE of a file") ----
- * Steps of one rank, with the three places where all ranks meet:
+/* ---- the device input stage on every rank (include/disco_hip.h: disco_dist_ingest_fasta): the second driver of the input stage's steps
+ * ("input stage on the GPU" above; kernels: disco_ingest.h). Particular to it: the byte shares, a pinned ring of the call's own, the
+ * tail behind a piece, and the three places where all ranks meet:
  *   A  its pieces into HBM; FASTA: record starts; FASTQ: newlines of the owned bytes
  *      -- all-gather: status word + newlines per (rank, file) --
  *   B  FASTQ: record starts from the line phase; clean + filter of the piece's records
  *      -- all-gather: status word + the per-piece figures --
- *   C  every rank computes the job's shape, the per-file counts and the id of every piece's first good read; table of the job's shape
- *      (dist_set_reads); lengths, record numbers and rows of the share at their global ids
+ *   C  every rank folds the same figures (ingest_fold); table of the job's shape (dist_set_reads); lengths, record numbers and rows of
+ *      the share at their global ids
  *      -- all-gather: status word -- all-to-all of rows, lengths, record numbers: what lies outside the home range, to its owner
  *   dist_validate (collective, as behind an upload)
  * A local failure or decline never returns in front of the next meeting point: it travels in the status word, and everybody leaves
@@ -5606,24 +5778,7 @@ int disco_dist_generate_reads(disco_ctx *c, const disco_genspec_abi *s)
 extern "C++" {
 namespace {
 enum { DI_OK = 0, DI_DECLINE = 1, DI_ERROR = 2 };
-enum { DR_GZ = 1, DR_UNREADABLE, DR_FORM, DR_IRREGULAR, DR_NO_READ, DR_LONG_RECORD, DR_COUNT };
-const char *const kDistDecline[DR_COUNT] = {"", "gzip input (a .gz name is the host stage's under a communicator)", "empty or unreadable file", "neither FASTA nor FASTQ",
-                                            kIngestIrregular, "no good read (or more than 2^31)", "a record of 2^21 bytes or more"};
 constexpr u64 DI_TAIL = 1ull << 21; /* bytes behind a piece: the rest of its last record (a longer one declines the file on one GPU too) */
-constexpr int DI_PER_PIECE = 7;     /* figures of a piece in the second all-gather */
-enum { DP_STARTS = 0, DP_GOOD, DP_TOO_LONG, DP_MAX_LEN, DP_MIN_LEN_INV, DP_N_LONG, DP_SHORT_MAX };
-
-struct IngestPiece {
-    u64 p0 = 0, p1 = 0;                /* the owned bytes of the file */
-    u64 own_lo = 0, own_hi = 0, n = 0; /* the same in the buffer, and the buffer's bytes */
-    bool to_eof = false;               /* the buffer reaches the end of the file */
-    bool prefix_nl = true, last_nl = false; /* the byte in front of the piece / its last byte is a newline */
-    u64 own_nl = 0, tiles = 0;
-    u64 *d_tile_base = nullptr, *d_ctr = nullptr;
-    u32 *d_tile_cnt = nullptr;
-    u64 fig[DI_PER_PIECE] = {0, 0, 0, 0, 0, 0, 0};
-    IngestFile d; /* the device arrays of the piece's records */
-};
 
 inline u64 di_status(int kind, int code, size_t file) { return ((u64)kind << 60) | ((u64)file << 16) | (u64)code; }
 
@@ -5645,22 +5800,20 @@ int di_gather(disco_ctx *c, const std::vector<u64> &mine, std::vector<u64> &all)
 struct DistIngest {
     disco_ctx *c;
     IngestJob job;
-    std::vector<IngestPiece> P;
-    std::vector<u64> size; /* bytes of every file */
     void *ring = nullptr;
     size_t ring_bytes = 0;
     u64 status = 0; /* this rank's */
-    DistIngest(disco_ctx *ctx, int n_files, uint32_t threads) : c(ctx), job(ctx, n_files, threads), P((size_t)n_files), size((size_t)n_files, 0) {}
+    DistIngest(disco_ctx *ctx, int n_files, uint32_t threads) : c(ctx), job(ctx, "disco_dist_ingest_fasta", n_files, threads) {}
     ~DistIngest()
     {
         if (ring) (void)hipHostFree(ring);
         release(c, c->d_ingest);
     }
     /* a step's answer into the status word (the first one stays) */
-    void note(int rc, int code, size_t file)
+    void note(int rc)
     {
         if (rc == DISCO_OK || status) return;
-        status = rc == INGEST_DECLINED ? di_status(DI_DECLINE, code, file) : di_status(DI_ERROR, -rc, file);
+        status = rc == INGEST_DECLINED ? di_status(DI_DECLINE, job.why_code, job.why_file) : di_status(DI_ERROR, -rc, 0);
     }
 };
 } // namespace
@@ -5690,50 +5843,43 @@ static int di_verdict(DistIngest &D, const std::vector<u64> &all, size_t n_per_r
     const size_t file = (size_t)((dec >> 16) & 0xFFFFFFFFull);
     const int code = (int)(dec & 0xFFFFu);
     c->err.clear();
-    return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s (%s; seen by rank %d): the host input stage takes this job", kDistDecline[code > 0 && code < DR_COUNT ? code : 0],
+    return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s (%s; seen by rank %d): the host input stage takes this job", kIngestDecline[code > 0 && code < DR_COUNT ? code : 0],
                 paths[file] ? paths[file] : "", dec_rank);
 }
 
-/* step A, local: the files, the rank's pieces, their text in HBM, FASTA record starts / FASTQ newline counts */
+/* step A, local: the files, the rank's pieces of them, their text in HBM, FASTA record starts / FASTQ newline counts */
 static int di_read_pieces(DistIngest &D, const char *const *paths, disco_dist_ingest_info *info)
 {
     disco_ctx *c = D.c;
     IngestJob &j = D.job;
     const u64 G = (u64)c->comm->world, r = (u64)c->comm->rank;
-    const size_t F = j.F.size();
     u64 T = 0;
-    for (size_t fi = 0; fi < F; fi++) {
-        IngestFile &f = j.F[fi];
-        f.path = paths[fi] ? paths[fi] : "";
-        if (f.path.size() >= 3 && f.path.compare(f.path.size() - 3, 3, ".gz") == 0) return D.note(INGEST_DECLINED, DR_GZ, fi), INGEST_DECLINED;
-        struct stat st;
-        f.fd = open(f.path.c_str(), O_RDONLY);
-        char first = 0;
-        if (f.fd < 0 || fstat(f.fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 1 || pread(f.fd, &first, 1, 0) != 1 || pread(f.fd, &f.last, 1, st.st_size - 1) != 1)
-            return D.note(INGEST_DECLINED, DR_UNREADABLE, fi), INGEST_DECLINED;
-        if (first != '>' && first != '@') return D.note(INGEST_DECLINED, DR_FORM, fi), INGEST_DECLINED;
-        f.fastq = first == '@';
-        f.n = D.size[fi] = (u64)st.st_size;
-        T += f.n;
+    for (size_t fi = 0; fi < j.F.size(); fi++) {
+        if (const int code = ingest_open_file(j.F[fi], paths[fi], false)) return j.decline(code, j.F[fi]);
+        T += j.F[fi].n;
     }
-    /* (128-bit product: T * r does not fit 64 bits for nothing anybody has, but the cut must be the same arithmetic everywhere) */
+    /* the rank's share: bytes [a, b) of the files laid end to end
+     * (128-bit product: T * r does not fit 64 bits for nothing anybody has, but the cut must be the same arithmetic everywhere) */
     const u64 a = (u64)((unsigned __int128)T * r / G), b = (u64)((unsigned __int128)T * (r + 1) / G);
     info->share_lo = a;
     info->share_hi = b;
     u64 cum = 0, text_bytes = 0;
-    for (size_t fi = 0; fi < F; fi++) {
-        IngestPiece &p = D.P[fi];
-        const u64 n = D.size[fi];
-        p.p0 = std::min(std::max(a, cum) - cum, n);
-        p.p1 = std::min(std::max(b, cum) - cum, n);
-        cum += n;
+    for (IngestFile &f : j.F) {
+        IngestPiece &p = f.p;
+        p.p0 = std::min(std::max(a, cum) - cum, f.n);
+        p.p1 = std::min(std::max(b, cum) - cum, f.n);
+        cum += f.n;
         if (p.p1 <= p.p0) continue;
-        const u64 pend = std::min(n, p.p1 + DI_TAIL);
-        p.to_eof = pend == n;
-        p.own_lo = p.p0 ? 1 : 16; /* the byte in front of the piece; at the top of a file 16 newlines (the copy stays aligned) */
+        const u64 pend = std::min(f.n, p.p1 + DI_TAIL);
+        p.to_eof = pend == f.n;
+        p.own_lo = p.p0 ? 1 : 0; /* the byte in front of the piece travels with it; the top of a file has none (the kernels count one: a newline) */
         p.own_hi = p.own_lo + (p.p1 - p.p0);
         p.n = p.own_lo + (pend - p.p0);
         text_bytes += ingest_text_cap(p.n);
+        char ch[2] = {'\n', 0};
+        if ((p.p0 && pread(f.fd, &ch[0], 1, (off_t)(p.p0 - 1)) != 1) || pread(f.fd, &ch[1], 1, (off_t)(p.p1 - 1)) != 1) return fail(c, DISCO_E_ARG, "disco_dist_ingest_fasta: read error");
+        p.prefix_nl = ch[0] == '\n';
+        p.last_nl = ch[1] == '\n';
     }
     /* the arena and the pinned ring: sized for the SHARE (text + record arrays, a record per 100 bytes at worst here; more: pieces of their own) */
     const u64 own_bytes = text_bytes + (text_bytes / 100) * 28 + (8ull << 20);
@@ -5746,45 +5892,10 @@ static int di_read_pieces(DistIngest &D, const char *const *paths, disco_dist_in
         (void)hipGetLastError();
         return fail(c, DISCO_E_NOMEM, "disco_dist_ingest_fasta: no pinned staging memory");
     }
-    for (size_t fi = 0; fi < F; fi++) {
-        IngestPiece &p = D.P[fi];
-        IngestFile &f = j.F[fi];
-        if (p.p1 <= p.p0) continue;
-        const auto t_read = HClock::now();
-        CHK(j.get(&p.d.d_text, ingest_text_cap(p.n)));
-        CHK(j.get(&p.d_ctr, (u64)FX_CTR_COUNT));
-        HIPCHK(c, hipMemsetAsync(p.d_ctr, 0, FX_CTR_COUNT * sizeof(u64), c->stream));
-        HIPCHK(c, hipMemsetAsync(p.d.d_text + p.n, 0, ingest_text_cap(p.n) - p.n, c->stream));
-        if (!p.p0) HIPCHK(c, hipMemsetAsync(p.d.d_text, '\n', 16, c->stream));
-        const u64 from = p.p0 ? p.p0 - 1 : 0;
-        CHK(ingest_read_file(c, f.fd, p.n - (p.p0 ? 0 : 16), p.d.d_text + (p.p0 ? 0 : 16), j.threads, from, D.ring, D.ring_bytes));
-        j.read_s += ms_since(t_read) * 1e-3f;
-        char ch = 0;
-        if (p.p0) {
-            if (pread(f.fd, &ch, 1, (off_t)(p.p0 - 1)) != 1) return fail(c, DISCO_E_ARG, "disco_dist_ingest_fasta: read error");
-            p.prefix_nl = ch == '\n';
-        }
-        if (pread(f.fd, &ch, 1, (off_t)(p.p1 - 1)) != 1) return fail(c, DISCO_E_ARG, "disco_dist_ingest_fasta: read error");
-        p.last_nl = ch == '\n';
-        p.tiles = (p.n + FX_TILE - 1) / FX_TILE;
-        CHK(j.get(&p.d_tile_base, p.tiles + 1));
-        CHK(j.get(&p.d_tile_cnt, p.tiles));
-        if (f.fastq) {
-            hipLaunchKernelGGL(fx_piece_lines_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, p.n, p.own_lo, p.own_hi, (u64)0, p.d_tile_cnt,
-                               (const u64 *)nullptr, (u64 *)nullptr, (u64)0, (u64)0, p.d_ctr);
-            CHK((scan_exclusive<u32, u64>(c, p.d_tile_cnt, p.tiles, p.d_tile_base, false, nullptr)));
-            HIPCHK(c, hipMemcpyAsync(&p.own_nl, p.d_ctr + FX_CTR_OWN_NL, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        } else {
-            hipLaunchKernelGGL(fx_piece_starts_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, p.n, p.own_lo, p.own_hi, p.d_tile_cnt, (const u64 *)nullptr,
-                               (u64 *)nullptr, p.d_ctr);
-            CHK((scan_exclusive<u32, u64>(c, p.d_tile_cnt, p.tiles, p.d_tile_base, false, &p.d.n_start)));
-            if (p.d.n_start >= (1ull << 32)) return D.note(INGEST_DECLINED, DR_IRREGULAR, fi), INGEST_DECLINED;
-            CHK(j.get(&p.d.d_start, p.d.n_start));
-            hipLaunchKernelGGL(fx_piece_starts_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, p.n, p.own_lo, p.own_hi, (u32 *)nullptr,
-                               (const u64 *)p.d_tile_base, p.d.d_start, p.d_ctr);
-        }
-        HIPCHK(c, hipGetLastError());
+    for (IngestFile &f : j.F) {
+        if (f.p.p1 <= f.p.p0) continue;
+        CHK(ingest_piece_text(j, f, D.ring, D.ring_bytes));
+        CHK(ingest_count_starts(j, f));
     }
     return DISCO_OK;
 }
@@ -5792,89 +5903,28 @@ static int di_read_pieces(DistIngest &D, const char *const *paths, disco_dist_in
 /* step B, local: FASTQ record starts from the exchanged newline counts nl[rank][1 + file]; clean + filter of every piece's records */
 static int di_filter_pieces(DistIngest &D, const std::vector<u64> &nl, size_t per_rank)
 {
-    disco_ctx *c = D.c;
     IngestJob &j = D.job;
-    const size_t F = j.F.size(), r = (size_t)c->comm->rank;
-    for (size_t fi = 0; fi < F; fi++) {
-        IngestPiece &p = D.P[fi];
+    const size_t r = (size_t)D.c->comm->rank;
+    for (size_t fi = 0; fi < j.F.size(); fi++) {
         IngestFile &f = j.F[fi];
-        if (p.p1 <= p.p0) continue;
+        if (f.p.p1 <= f.p.p0) continue;
         if (f.fastq) {
             u64 line0 = 0; /* newlines of the file in front of the piece */
             for (size_t g = 0; g < r; g++) line0 += nl[g * per_rank + 1 + fi];
-            /* the lines that BEGIN in the owned bytes: one at the first byte if a newline stands in front of it, one behind every owned
-             * newline but the piece's last byte (that line is the next piece's, or nobody's at the end of the file) */
-            const u64 first = p.prefix_nl ? line0 : line0 + 1, lines = (p.prefix_nl ? 1 : 0) + p.own_nl - (p.last_nl ? 1 : 0);
-            const u64 rec0 = (first + 3) / 4;
-            p.d.n_start = (lines && (first + lines - 1) / 4 + 1 > rec0) ? (first + lines - 1) / 4 + 1 - rec0 : 0;
-            if (p.d.n_start >= (1ull << 32)) return D.note(INGEST_DECLINED, DR_IRREGULAR, fi), INGEST_DECLINED;
-            CHK(j.get(&p.d.d_start, p.d.n_start));
-            hipLaunchKernelGGL(fx_piece_lines_kernel, dim3((unsigned)p.tiles), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, p.n, p.own_lo, p.own_hi, line0, (u32 *)nullptr,
-                               (const u64 *)p.d_tile_base, p.d.d_start, rec0, p.d.n_start, p.d_ctr);
-            HIPCHK(c, hipGetLastError());
+            CHK(ingest_place_starts(j, f, line0));
         }
-        u64 h[FX_CTR_COUNT];
-        HIPCHK(c, hipMemcpyAsync(h, p.d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (h[FX_CTR_BAD_GT]) return D.note(INGEST_DECLINED, DR_IRREGULAR, fi), INGEST_DECLINED;
-        p.fig[DP_STARTS] = p.d.n_start;
-        p.d.n_rec = p.d.n_start;
-        if (!p.d.n_rec) continue;
-        /* where the last owned record ends: the first record start behind the owned bytes, or the end of the file */
-        u64 end = p.n;
-        if (h[FX_CTR_NEXT_INV]) end = ~h[FX_CTR_NEXT_INV];
-        else if (!p.to_eof) return D.note(INGEST_DECLINED, DR_LONG_RECORD, fi), INGEST_DECLINED;
-        CHK(j.get(&p.d.d_seq, p.d.n_rec));
-        CHK(j.get(&p.d.d_glen, p.d.n_rec));
-        CHK(j.get(&p.d.d_wrap, p.d.n_rec));
-        const FxFilterArgs fa{.text = p.d.d_text, .n = end, .start = p.d.d_start, .n_start = p.d.n_start, .n_rec = p.d.n_rec, .min_overlap = c->prm.min_overlap, .fastq = f.fastq ? 1u : 0u,
-                              .glen = p.d.d_glen, .seq_begin = p.d.d_seq, .wrap = p.d.d_wrap, .ctr = p.d_ctr};
-        hipLaunchKernelGGL(fx_filter_kernel, dim3(flat_grid(c, p.d.n_rec)), dim3(256), 0, c->stream, fa, j.tb);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h, p.d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (h[FX_CTR_MULTILINE]) return D.note(INGEST_DECLINED, DR_IRREGULAR, fi), INGEST_DECLINED;
-        p.d.good = h[FX_CTR_GOOD];
-        p.fig[DP_GOOD] = h[FX_CTR_GOOD];
-        p.fig[DP_TOO_LONG] = h[FX_CTR_TOO_LONG];
-        p.fig[DP_MAX_LEN] = h[FX_CTR_MAX_LEN];
-        p.fig[DP_MIN_LEN_INV] = h[FX_CTR_MIN_LEN_INV];
-        p.fig[DP_N_LONG] = h[FX_CTR_N_LONG];
-        p.fig[DP_SHORT_MAX] = h[FX_CTR_SHORT_MAX];
+        CHK(ingest_filter_piece(j, f));
     }
     return DISCO_OK;
 }
 
-/* step C, local: the job's table; lengths, record numbers (within the file) and rows of the share at their global ids.
- * id_base[file] / rec_in_file[file]: id of the piece's first good read / records of the file in the pieces before */
-static int di_fill_table(DistIngest &D, const ReadShape &s, const std::vector<u64> &id_base, const std::vector<u64> &rec_in_file, const std::vector<u64> &n_rec)
+/* step C, local: the job's table; lengths, record numbers (within the file) and rows of the share at their global ids */
+static int di_fill_table(DistIngest &D, const IngestFold &o)
 {
     disco_ctx *c = D.c;
-    IngestJob &j = D.job;
-    CHK(dist_set_reads(c, s.n, s.stride));
+    CHK(dist_set_reads(c, o.shape.n, o.shape.stride));
     CHK(ensure(c, c->d_rec_of_read, c->n_alloc));
-    u64 max_rec = 0;
-    for (auto &p : D.P) max_rec = std::max(max_rec, p.d.n_rec);
-    u64 *d_pos = nullptr;
-    u8 *d_flag = nullptr;
-    CHK(j.get(&d_pos, max_rec + 1));
-    CHK(j.get(&d_flag, max_rec));
-    for (size_t fi = 0; fi < D.P.size(); fi++) {
-        IngestPiece &p = D.P[fi];
-        const u64 nr = n_rec[fi]; /* (without a lone trailing '>': its glen is 0 anyway) */
-        if (!nr || !p.d.good) continue;
-        hipLaunchKernelGGL(fx_flags_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const u16 *)p.d.d_glen, nr, d_flag);
-        u64 good = 0;
-        CHK((scan_exclusive<u8, u64>(c, d_flag, nr, d_pos, false, &good)));
-        if (good != p.d.good) return fail(c, DISCO_E_STATE, "disco_dist_ingest_fasta: %llu good reads counted, %llu placed", (unsigned long long)p.d.good, (unsigned long long)good);
-        if (id_base[fi] + good > s.n) return fail(c, DISCO_E_STATE, "disco_dist_ingest_fasta: ids beyond the job's reads");
-        hipLaunchKernelGGL(fx_ids_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const u16 *)p.d.d_glen, (const u64 *)d_pos, nr, id_base[fi], c->d_rec_of_read.p, c->d_len);
-        hipLaunchKernelGGL(fx_pack_kernel, dim3(flat_grid(c, good * (u64)c->S)), dim3(256), 0, c->stream, (const u8 *)p.d.d_text, (const u64 *)p.d.d_seq, (const u32 *)p.d.d_wrap,
-                           (const u32 *)c->d_rec_of_read.p, (const u16 *)c->d_len, id_base[fi], good, c->S, 0xFFFFu, c->d_reads);
-        if (rec_in_file[fi])
-            hipLaunchKernelGGL(fx_rec_add_kernel, dim3(flat_grid(c, good)), dim3(256), 0, c->stream, c->d_rec_of_read.p, id_base[fi], id_base[fi] + good, (u32)rec_in_file[fi]);
-        HIPCHK(c, hipGetLastError());
-    }
+    CHK(ingest_place_reads(D.job, o));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DISCO_OK;
 }
@@ -5916,97 +5966,47 @@ int disco_dist_ingest_fasta(disco_ctx *c, const char *const *paths, int n_files,
         if (c->phase > 1) c->phase = 1;
         rc = di_read_pieces(D, paths, info);
     }
-    D.note(rc, 0, 0);
+    D.note(rc);
     mine.assign(1 + F, 0);
     mine[0] = D.status;
-    for (size_t fi = 0; fi < F; fi++) mine[1 + fi] = D.P[fi].own_nl;
+    for (size_t fi = 0; fi < F; fi++) mine[1 + fi] = j.F[fi].p.own_nl;
     CHK(di_gather(c, mine, all));
     CHK(di_verdict(D, all, 1 + F, paths));
     /* B */
-    rc = di_filter_pieces(D, all, 1 + F);
-    D.note(rc, 0, 0);
+    D.note(di_filter_pieces(D, all, 1 + F));
     const float t_filtered = j.seconds();
-    const size_t PR = 1 + F * DI_PER_PIECE;
-    mine.assign(PR, 0);
-    mine[0] = D.status;
-    for (size_t fi = 0; fi < F; fi++) memcpy(&mine[1 + fi * DI_PER_PIECE], D.P[fi].fig, sizeof D.P[fi].fig);
+    mine = ingest_figures(j, D.status);
     CHK(di_gather(c, mine, all));
-    CHK(di_verdict(D, all, PR, paths));
-    /* C: from here on every rank computes the same figures from the same numbers */
-    auto fig = [&](size_t g, size_t fi, int what) { return all[g * PR + 1 + fi * DI_PER_PIECE + (size_t)what]; };
-    ReadShape s{0, 0, 0, 0, 0, 0xFFFFu};
-    u64 total_records = 0, too_long = 0;
-    std::vector<u64> share(G + 1, 0), id_base(F, 0), rec_in_file(F, 0), n_rec(F, 0);
-    c->ingest_id_base.assign(F + 1, 0);
-    c->ingest_rec_base.assign(F + 1, 0);
-    for (size_t fi = 0; fi < F; fi++) {
-        u64 starts = 0, good = 0;
-        size_t last_piece = 0; /* the rank that owns the file's last byte */
-        for (size_t g = 0; g < G; g++) {
-            starts += fig(g, fi, DP_STARTS);
-            if (fig(g, fi, DP_STARTS)) last_piece = g;
-        }
-        if (starts == 0 || starts >= (1ull << 32)) { /* (every rank alike) */
-            c->err.clear();
-            return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s (%s): the host input stage takes this job", kIngestIrregular, j.F[fi].path.c_str());
-        }
-        /* a '>' that is the very last byte starts nothing unless it is the only one (it still ended the record before it) */
-        const bool lone_gt = !j.F[fi].fastq && starts > 1 && j.F[fi].last == '>';
-        u64 recs = 0;
-        for (size_t g = 0; g < G; g++) {
-            const u64 nr = fig(g, fi, DP_STARTS) - ((lone_gt && g == last_piece) ? 1 : 0);
-            if (g == r) {
-                id_base[fi] = s.n + good;
-                rec_in_file[fi] = recs;
-                n_rec[fi] = nr;
-            }
-            recs += nr;
-            const u64 gd = fig(g, fi, DP_GOOD);
-            good += gd;
-            share[g + 1] += gd;
-            too_long += fig(g, fi, DP_TOO_LONG);
-            if (gd) {
-                s.longest = std::max(s.longest, (u32)fig(g, fi, DP_MAX_LEN));
-                s.shortest = std::min(s.shortest, 0xFFFFu - (u32)fig(g, fi, DP_MIN_LEN_INV));
-                s.n_long += fig(g, fi, DP_N_LONG);
-                s.short_max = std::max(s.short_max, (u32)fig(g, fi, DP_SHORT_MAX));
-            }
-        }
-        files[fi] = disco_ingest_file{.first_index = total_records + 1, .last_index = total_records + recs, .good = good, .bad = recs - good};
-        total_records += recs;
-        s.n += good;
-        c->ingest_id_base[fi + 1] = s.n;
-        c->ingest_rec_base[fi + 1] = total_records;
-    }
-    for (size_t g = 0; g < G; g++) share[g + 1] += share[g]; /* rank g's reads are the ids [share[g], share[g + 1]): shares follow each other in file order */
-    if (s.n == 0 || s.n >= (1ull << 31)) {
+    CHK(di_verdict(D, all, mine.size(), paths));
+    /* C: from here on every rank computes the same figures from the same numbers, a decline among them */
+    IngestFold o;
+    if (ingest_fold(j, all, G, r, files, &o) == INGEST_DECLINED) {
         c->err.clear();
-        return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s (%s): the host input stage takes this job", kDistDecline[DR_NO_READ], j.F[0].path.c_str());
+        return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s (%s): the host input stage takes this job", j.why.c_str(), j.where.c_str());
     }
-    s.stride = (std::max<u32>(1, (s.longest + 31) / 32) + 7u) & ~7u;
+    const ReadShape &s = o.shape;
     D.status = 0;
-    rc = di_fill_table(D, s, id_base, rec_in_file, n_rec);
-    D.note(rc, 0, 0);
+    D.note(di_fill_table(D, o));
     mine.assign(1, D.status);
     CHK(di_gather(c, mine, all));
     CHK(di_verdict(D, all, 1, paths));
-    CHK(di_exchange(c, share, c->d_reads, (size_t)c->S * 8));
-    CHK(di_exchange(c, share, c->d_len, sizeof(u16)));
-    CHK(di_exchange(c, share, c->d_rec_of_read.p, sizeof(u32)));
+    CHK(di_exchange(c, o.share, c->d_reads, (size_t)c->S * 8));
+    CHK(di_exchange(c, o.share, c->d_len, sizeof(u16)));
+    CHK(di_exchange(c, o.share, c->d_rec_of_read.p, sizeof(u32)));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->ingest_n = s.n;
     c->h_len_ok = false;
     info->n_reads = s.n;
-    info->total_records = total_records;
-    info->too_long = too_long;
+    info->total_records = o.total_records;
+    info->too_long = o.too_long;
     info->stride_words = std::max<u32>(1, (s.longest + 31) / 32);
     info->shortest = s.shortest;
     info->longest = s.longest;
-    info->share_reads = share[r + 1] - share[r];
+    info->share_reads = o.share[r + 1] - o.share[r];
     info->home_lo = c->home_lo;
     info->home_hi = c->home_hi;
     {
-        const u64 lo = std::max(share[r], c->home_lo), hi = std::min(share[r + 1], c->home_hi);
+        const u64 lo = std::max(o.share[r], c->home_lo), hi = std::min(o.share[r + 1], c->home_hi);
         info->kept_reads = hi > lo ? hi - lo : 0;
     }
     const int vrc = dist_validate(c);
@@ -6026,17 +6026,7 @@ int disco_dist_ingest_fetch(disco_ctx *c, uint16_t *len, uint64_t *file_index)
     if (!c->comm || !c->dist_reads || c->phase < 1 || c->ingest_n == 0 || c->ingest_n != c->n)
         return fail(c, DISCO_E_STATE, "disco_dist_ingest_fetch: the reads of the context did not come from disco_dist_ingest_fasta");
     HIPCHK(c, hipSetDevice(c->device));
-    const u64 lo = c->home_lo, hi = c->home_hi, n = hi - lo;
-    if (!n) return DISCO_OK;
-    std::vector<u32> rec(n);
-    HIPCHK(c, hipMemcpyAsync(len, c->d_len + lo, n * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rec.data(), c->d_rec_of_read.p + lo, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t fi = 0; fi + 1 < c->ingest_id_base.size(); fi++) {
-        const u64 a = std::max(lo, c->ingest_id_base[fi]), b = std::min(hi, c->ingest_id_base[fi + 1]), rb = c->ingest_rec_base[fi];
-        for (u64 i = a; i < b; i++) file_index[i - lo] = rb + (u64)rec[i - lo] + 1; /* BG/Dataset.cpp:294: every record counts */
-    }
-    return DISCO_OK;
+    return ingest_fetch_range(c, c->home_lo, c->home_hi, c->stream, len, file_index);
 }
 
 static int dist_run_graph_pass(disco_ctx *c, uint32_t flags, bool allow_loci, bool *retry_with_id_ranges);

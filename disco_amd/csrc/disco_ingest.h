@@ -3,7 +3,8 @@
  * Dataset::testRead per record -> ids of the good reads in file order -> 2-bit rows of the read table. Replaces, for the files it
  * accepts, the host pass of disco_amd/host/fastx.cpp (which stays for .gz, FASTQ and any FASTA it declines), i.e.
  * Dataset::readDataset / testRead (BG/Dataset.cpp:161-380,403-452) and the packing of HashTable::insertIntoTable
- * (BG/HashTable.cpp:456-477). Host side: disco_hip.hip "input stage on the GPU".
+ * (BG/HashTable.cpp:456-477). Host side: disco_hip.hip "input stage on the GPU" — one stage over PIECES of files with two drivers:
+ * disco_ingest_fasta (one GPU: every file is one piece) and disco_dist_ingest_fasta (every rank takes the pieces of its share of the bytes).
  *
  * Accepted forms (decided on the device, per file; anything else makes the caller fall back to the host stage, which follows the
  * reference's getline calls literally): FASTA — the file starts with '>' and every '>' is the first byte of a line; a record is its
@@ -21,7 +22,7 @@
 
 #include "disco_device.h"
 
-#define FX_TILE 4096 /* bytes of text per block of fx_starts_kernel */
+#define FX_TILE 4096 /* bytes of text per block of fx_starts_kernel / fx_lines_kernel */
 #define FX_MAX_MOTIFS 16
 #define FX_MAX_REPEATS 40
 #define FX_WALK_MAX 4096u /* bases of an irregularly wrapped record the device stage still addresses by walking its bytes */
@@ -30,7 +31,8 @@
 /* counters of one ingest (u64 each) */
 enum { FX_CTR_BAD_GT = 0, FX_CTR_MULTILINE, FX_CTR_TOO_LONG, FX_CTR_MAX_LEN, FX_CTR_MIN_LEN_INV, FX_CTR_GOOD, FX_CTR_N_LONG, FX_CTR_SHORT_MAX, FX_CTR_NEXT_INV, FX_CTR_OWN_NL, FX_CTR_COUNT };
 /* (N_LONG / SHORT_MAX: good reads of more than DISCO_SHORT_MAX bases, and the longest of the others — the table may get two classes of rows;
- * NEXT_INV / OWN_NL: pieces of a file, below — ~position of the first record start behind the owned bytes (0: none), newlines of the owned bytes) */
+ * NEXT_INV / OWN_NL: a piece that does not end its buffer, below — ~position of the first record start behind the owned bytes (0: none), newlines of the
+ * owned bytes) */
 
 struct FxTables { /* Dataset::testRead's patterns (read_filter_tables.h), prepared by the host */
     u64 rep58[FX_MAX_REPEATS]; /* the 29-mers that may be neither prefix nor suffix of a read, 2 bits per base */
@@ -62,32 +64,18 @@ __device__ __forceinline__ u32 fx_upper(u32 c) { return (c >= 'a' && c <= 'z') ?
 /* A0 C1 G2 T3 (BG/HashTable.h:16-24), anything else 4 */
 __device__ __forceinline__ u32 fx_code(u32 c) { return c == 'A' ? 0u : (c == 'C' ? 1u : (c == 'G' ? 2u : (c == 'T' ? 3u : 4u))); }
 
-/* record starts: '>' at the first byte of a line. count != nullptr: starts per tile; pos != nullptr: their positions at
- * base[tile] + rank inside the tile. A '>' anywhere else raises FX_CTR_BAD_GT (the file is not of the accepted form). */
-__global__ void __launch_bounds__(256) fx_starts_kernel(const u8 *__restrict__ text, u64 n, u32 *__restrict__ count, const u64 *__restrict__ base,
-                                                        u64 *__restrict__ pos, u64 *__restrict__ ctr)
+/* ---- record starts of a PIECE of a file ----------------------------------------------------------------------------------------------
+ * The unit of the stage is a piece: the buffer holds the byte in front of the piece (nothing where the piece begins the file: the byte in
+ * front of position 0 counts as a '\n'), the bytes the piece owns — [own_lo, own_hi) — and behind them the rest of the last record that
+ * starts there (up to 2^21 bytes, or the end of the file): n bytes in all. A whole file (disco_ingest_fasta) is the piece that owns every
+ * byte: own_lo = 0, own_hi = n. A record belongs to the piece that holds its first byte; the first record start BEHIND the owned bytes
+ * ends the last owned record: its position goes to FX_CTR_NEXT_INV, complemented (atomicMax over a zeroed counter = the smallest
+ * position; 0: no start in the buffer). Both kernels run twice: count != nullptr counts per tile (FX_TILE bytes, 16 per lane), the
+ * second pass places the positions behind the scanned counts. */
+
+/* exclusive prefix of `mine` over the block of 256 lanes (s_w: a word of LDS per wave) */
+__device__ __forceinline__ u32 fx_block_prefix(u32 mine, u32 *s_w)
 {
-    __shared__ u32 s_w[4];
-    const u64 tile = blockIdx.x;
-    const u64 p0 = tile * FX_TILE + (u64)threadIdx.x * 16u;
-    u32 mask = 0, bad = 0; /* bit i: byte p0 + i starts a record */
-    if (p0 < n) {
-        const uint4 q = *(const uint4 *)(text + p0); /* (padded buffer) */
-        const u32 wds[4] = {q.x, q.y, q.z, q.w};
-        u32 prev = p0 ? text[p0 - 1] : (u32)'\n';
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const u32 c = (wds[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-            if (p0 + i < n && c == '>') {
-                if (prev == '\n') mask |= 1u << i;
-                else bad = 1;
-            }
-            prev = c;
-        }
-    }
-    if (bad) atomicAdd(&ctr[FX_CTR_BAD_GT], 1ull);
-    const u32 mine = (u32)__popc(mask);
-    /* exclusive prefix of `mine` over the block */
     u32 incl = mine;
     for (int o = 1; o < 64; o <<= 1) {
         const u32 y = (u32)__shfl_up((int)incl, o);
@@ -97,6 +85,48 @@ __global__ void __launch_bounds__(256) fx_starts_kernel(const u8 *__restrict__ t
     __syncthreads();
     u32 off = incl - mine;
     for (int w = 0; w < (int)(threadIdx.x >> 6); w++) off += s_w[w];
+    return off;
+}
+
+/* the 16 bytes of a lane as masks, bit i for byte p0 + i: the bytes equal to ch / the bytes inside [lo, hi). The window costs a lane two
+ * of these, not three 64-bit compares per byte: the kernels below run at the speed of HBM, and a whole file must not pay for pieces */
+__device__ __forceinline__ u32 fx_eq_mask(const uint4 &q, u32 ch)
+{
+    const u32 wds[4] = {q.x, q.y, q.z, q.w};
+    u32 m = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) m |= (u32)(((wds[i >> 2] >> (8 * (i & 3))) & 0xFFu) == ch) << i;
+    return m;
+}
+__device__ __forceinline__ u32 fx_window(u64 p0, u64 lo, u64 hi)
+{
+    const u32 a = lo > p0 ? (u32)min(lo - p0, (u64)16) : 0u, b = hi > p0 ? (u32)min(hi - p0, (u64)16) : 0u;
+    return b > a ? ((1u << b) - 1u) & ~((1u << a) - 1u) : 0u;
+}
+
+/* FASTA: a record starts at a '>' that is the first byte of a line. Pass 1: owned starts per tile; a '>' of the owned bytes anywhere
+ * else raises FX_CTR_BAD_GT (the file is not of the accepted form). Pass 2: their positions at base[tile] + rank inside the tile. */
+__global__ void __launch_bounds__(256) fx_starts_kernel(const u8 *__restrict__ text, u64 n, u64 own_lo, u64 own_hi, u32 *__restrict__ count,
+                                                        const u64 *__restrict__ base, u64 *__restrict__ pos, u64 *__restrict__ ctr)
+{
+    __shared__ u32 s_w[4];
+    const u64 tile = blockIdx.x;
+    const u64 p0 = tile * FX_TILE + (u64)threadIdx.x * 16u;
+    u32 mask = 0, bad = 0, behind = 0; /* bit i: byte p0 + i starts an owned record / is an owned '>' inside a line / starts a record behind the owned bytes */
+    if (p0 < n && p0 + 16u > own_lo) {
+        const uint4 q = *(const uint4 *)(text + p0); /* (padded buffer) */
+        const u32 at_line = (fx_eq_mask(q, '\n') << 1) | (u32)(p0 ? text[p0 - 1] == '\n' : 1); /* the byte in front is a newline */
+        const u32 gt = fx_eq_mask(q, '>') & fx_window(p0, own_lo, n), own = fx_window(p0, own_lo, own_hi);
+        mask = gt & own & at_line;
+        bad = gt & own & ~at_line;
+        behind = gt & ~own & at_line;
+    }
+    if (count) { /* (once, in the counting pass) */
+        if (bad) atomicAdd(&ctr[FX_CTR_BAD_GT], 1ull);
+        if (behind) atomicMax(&ctr[FX_CTR_NEXT_INV], ~(p0 + (u64)(__ffs((int)behind) - 1)));
+    }
+    const u32 mine = (u32)__popc(mask);
+    const u32 off = fx_block_prefix(mine, s_w);
     if (count) {
         if (threadIdx.x == 255) count[tile] = off + mine;
     } else {
@@ -111,48 +141,44 @@ __global__ void __launch_bounds__(256) fx_starts_kernel(const u8 *__restrict__ t
 }
 
 /* FASTQ: a record is four lines (header, sequence, '+', qualities: the reference reads them with four getline calls,
- * BG/Dataset.cpp:255-293 — a quality line may well begin with '@', so only the line COUNT says where a record starts). Pass 1
- * (count != nullptr): newlines per tile. Pass 2: base[tile] = newlines before the tile; every byte that begins a line (byte 0, or the
- * byte behind a '\n') whose line index is a multiple of 4 is a record start: its position goes to pos[line / 4]. */
-__global__ void __launch_bounds__(256) fx_lines_kernel(const u8 *__restrict__ text, u64 n, u32 *__restrict__ count, const u64 *__restrict__ base,
-                                                       u64 *__restrict__ pos)
+ * BG/Dataset.cpp:255-293 — a quality line may well begin with '@', so only the line COUNT says where a record starts). Pass 1: newlines
+ * per tile from own_lo on. Their sum over the tiles is the owned newlines where the owned bytes end the buffer (a whole file: no atomic);
+ * where bytes follow them, the owned ones are summed into FX_CTR_OWN_NL — what the ranks exchange: line0, the newlines of the file in
+ * front of the piece, is the sum over the pieces before it. Pass 2: the line that begins at byte p (byte 0 of a file, or the byte behind
+ * a '\n') has the index line0 + newlines in [own_lo, p); a multiple of 4 starts record index / 4, which goes to pos[index / 4 - rec0]
+ * (n_pos slots: the owned record starts) or, behind the owned bytes, to FX_CTR_NEXT_INV. */
+__global__ void __launch_bounds__(256) fx_lines_kernel(const u8 *__restrict__ text, u64 n, u64 own_lo, u64 own_hi, u64 line0, u32 *__restrict__ count,
+                                                       const u64 *__restrict__ base, u64 *__restrict__ pos, u64 rec0, u64 n_pos, u64 *__restrict__ ctr)
 {
     __shared__ u32 s_w[4];
     const u64 tile = blockIdx.x;
     const u64 p0 = tile * FX_TILE + (u64)threadIdx.x * 16u;
-    u32 nlmask = 0; /* bit i: byte p0 + i is a newline */
-    if (p0 < n) {
-        const uint4 q = *(const uint4 *)(text + p0);
-        const u32 wds[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int i = 0; i < 16; i++)
-            if (p0 + i < n && ((wds[i >> 2] >> (8 * (i & 3))) & 0xFFu) == '\n') nlmask |= 1u << i;
+    u32 nl = 0, seen = 0; /* bit i: byte p0 + i is a newline / lies in [own_lo, n) */
+    if (p0 < n && p0 + 16u > own_lo) {
+        nl = fx_eq_mask(*(const uint4 *)(text + p0), '\n');
+        seen = fx_window(p0, own_lo, n);
     }
-    const u32 mine = (u32)__popc(nlmask);
-    u32 incl = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 y = (u32)__shfl_up((int)incl, o);
-        if ((int)(threadIdx.x & 63) >= o) incl += y;
-    }
-    if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    u32 off = incl - mine;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) off += s_w[w];
+    const u32 nlmask = nl & seen, mine = (u32)__popc(nlmask);
+    const u32 off = fx_block_prefix(mine, s_w);
     if (count) {
         if (threadIdx.x == 255) count[tile] = off + mine;
+        if (own_hi < n) { /* (uniform) */
+            u32 own = (u32)__popc(nlmask & fx_window(p0, own_lo, own_hi));
+            for (int o = 32; o > 0; o >>= 1) own += (u32)__shfl_down((int)own, o);
+            if ((threadIdx.x & 63) == 0 && own) atomicAdd(&ctr[FX_CTR_OWN_NL], (u64)own);
+        }
         return;
     }
-    if (p0 >= n) return;
-    /* line index of the line that BEGINS at byte p0 + i = newlines before that byte */
-    u64 before = base[tile] + off;
-    const bool starts_line = p0 == 0 || text[p0 - 1] == '\n';
-    if (starts_line && (before & 3ull) == 0) pos[before >> 2] = p0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        if (nlmask & (1u << i)) {
-            before++;
-            if (p0 + i + 1 < n && (before & 3ull) == 0) pos[before >> 2] = p0 + (u64)i + 1; /* the byte behind this newline begins a line */
-        }
+    if (!seen) return;
+    const u64 before = line0 + base[tile] + off;
+    u32 begins = ((nl << 1) | (u32)(p0 ? text[p0 - 1] == '\n' : 1)) & seen; /* bit i: a line begins at byte p0 + i */
+    while (begins) {
+        const int i = __ffs((int)begins) - 1;
+        begins &= begins - 1;
+        const u64 p = p0 + (u64)i, line = before + (u64)__popc(nlmask & ((1u << i) - 1u));
+        if (line & 3ull) continue;
+        if (p >= own_hi) atomicMax(&ctr[FX_CTR_NEXT_INV], ~p);
+        else if ((line >> 2) >= rec0 && (line >> 2) - rec0 < n_pos) pos[(line >> 2) - rec0] = p;
     }
 }
 
@@ -418,123 +444,6 @@ __global__ void __launch_bounds__(256) fx_pack_long_kernel(const u8 *__restrict_
             const u32 tw = w - (u32)SL;
             rows8[(n + j) * 8 + tw] = 32u * tw < (u32)tailb ? fx_pack_word(tx, seq_begin[rec], wrap[rec], L, L - (u32)tailb + 32u * tw) : 0ull;
         }
-    }
-}
-
-/* ---- a PIECE of a file (disco_dist_ingest_fasta: every rank reads its share of the bytes) ----------------------------------------------
- * The buffer holds the byte in front of the piece (a '\n' where the piece begins the file), the bytes the rank owns — [own_lo, own_hi) —
- * and behind them the rest of the last record that starts there (up to 2^21 bytes, or the end of the file): n bytes in all. A record
- * belongs to the piece that holds its first byte; the first record start BEHIND the owned bytes ends the last owned record: its position
- * goes to FX_CTR_NEXT_INV, complemented (atomicMax over a zeroed counter = the smallest position; 0: no start in the buffer). */
-
-/* fx_starts_kernel over a piece: only the '>' of the owned bytes are counted / placed / found inside a line */
-__global__ void __launch_bounds__(256) fx_piece_starts_kernel(const u8 *__restrict__ text, u64 n, u64 own_lo, u64 own_hi, u32 *__restrict__ count,
-                                                              const u64 *__restrict__ base, u64 *__restrict__ pos, u64 *__restrict__ ctr)
-{
-    __shared__ u32 s_w[4];
-    const u64 tile = blockIdx.x;
-    const u64 p0 = tile * FX_TILE + (u64)threadIdx.x * 16u;
-    u32 mask = 0, bad = 0;
-    u64 next = ~0ull;
-    if (p0 < n && p0 + 16u > own_lo) {
-        const uint4 q = *(const uint4 *)(text + p0); /* (padded buffer) */
-        const u32 wds[4] = {q.x, q.y, q.z, q.w};
-        u32 prev = p0 ? text[p0 - 1] : (u32)'\n';
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const u32 c = (wds[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-            const u64 p = p0 + i;
-            if (p >= own_lo && p < n && c == '>') {
-                if (p < own_hi) {
-                    if (prev == '\n') mask |= 1u << i;
-                    else bad = 1;
-                } else if (prev == '\n' && next == ~0ull)
-                    next = p;
-            }
-            prev = c;
-        }
-    }
-    if (count) { /* (once, in the counting pass) */
-        if (bad) atomicAdd(&ctr[FX_CTR_BAD_GT], 1ull);
-        if (next != ~0ull) atomicMax(&ctr[FX_CTR_NEXT_INV], ~next);
-    }
-    const u32 mine = (u32)__popc(mask);
-    u32 incl = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 y = (u32)__shfl_up((int)incl, o);
-        if ((int)(threadIdx.x & 63) >= o) incl += y;
-    }
-    if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    u32 off = incl - mine;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) off += s_w[w];
-    if (count) {
-        if (threadIdx.x == 255) count[tile] = off + mine;
-    } else {
-        u64 at = base[tile] + off;
-        u32 m = mask;
-        while (m) {
-            const int i = __ffs((int)m) - 1;
-            m &= m - 1;
-            pos[at++] = p0 + (u64)i;
-        }
-    }
-}
-
-/* fx_lines_kernel over a piece. Pass 1 (count != nullptr): newlines per tile from own_lo on, and those of the owned bytes summed into
- * FX_CTR_OWN_NL — what the ranks exchange: line0, the newlines of the file in front of the piece, is the sum over the pieces before it.
- * Pass 2: the line that begins at byte p has the index line0 + newlines in [own_lo, p); a multiple of 4 starts record index / 4, which
- * goes to pos[index / 4 - rec0] (n_pos slots: the owned record starts) or, behind the owned bytes, to FX_CTR_NEXT_INV. */
-__global__ void __launch_bounds__(256) fx_piece_lines_kernel(const u8 *__restrict__ text, u64 n, u64 own_lo, u64 own_hi, u64 line0, u32 *__restrict__ count,
-                                                             const u64 *__restrict__ base, u64 *__restrict__ pos, u64 rec0, u64 n_pos, u64 *__restrict__ ctr)
-{
-    __shared__ u32 s_w[4];
-    const u64 tile = blockIdx.x;
-    const u64 p0 = tile * FX_TILE + (u64)threadIdx.x * 16u;
-    u32 nlmask = 0, ownmask = 0;
-    u32 wds[4] = {0, 0, 0, 0};
-    if (p0 < n && p0 + 16u > own_lo) {
-        const uint4 q = *(const uint4 *)(text + p0);
-        wds[0] = q.x, wds[1] = q.y, wds[2] = q.z, wds[3] = q.w;
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const u64 p = p0 + i;
-            if (p >= own_lo && p < n && ((wds[i >> 2] >> (8 * (i & 3))) & 0xFFu) == '\n') {
-                nlmask |= 1u << i;
-                if (p < own_hi) ownmask |= 1u << i;
-            }
-        }
-    }
-    const u32 mine = (u32)__popc(nlmask);
-    u32 incl = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 y = (u32)__shfl_up((int)incl, o);
-        if ((int)(threadIdx.x & 63) >= o) incl += y;
-    }
-    if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    u32 off = incl - mine;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) off += s_w[w];
-    if (count) {
-        if (threadIdx.x == 255) count[tile] = off + mine;
-        u32 own = (u32)__popc(ownmask);
-        for (int o = 32; o > 0; o >>= 1) own += (u32)__shfl_down((int)own, o);
-        if ((threadIdx.x & 63) == 0 && own) atomicAdd(&ctr[FX_CTR_OWN_NL], (u64)own);
-        return;
-    }
-    if (p0 >= n || p0 + 16u <= own_lo) return;
-    u64 before = line0 + base[tile] + off;
-    u32 prev = p0 ? text[p0 - 1] : (u32)'\n';
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const u64 p = p0 + i;
-        if (p >= own_lo && p < n && prev == '\n' && (before & 3ull) == 0) {
-            const u64 slot = (before >> 2) - rec0;
-            if (p >= own_hi) atomicMax(&ctr[FX_CTR_NEXT_INV], ~p);
-            else if ((before >> 2) >= rec0 && slot < n_pos) pos[slot] = p;
-        }
-        if (nlmask & (1u << i)) before++;
-        prev = (wds[i >> 2] >> (8 * (i & 3))) & 0xFFu;
     }
 }
 

@@ -14,6 +14,7 @@ import pytest
 
 from disco_amd import buildgraph, readgen
 from oracle import pyoracle
+from tests.ingest_edges import EDGE_DECLINED, edge_files, edge_want
 from tests.test_gpu_ingest import _adversarial, _decode, _wrapped
 from tests.util import canon_hip, run_oracle_reads
 
@@ -426,3 +427,61 @@ def test_buildg_reads_its_files_on_every_rank(tmp_path, args):
             assert out["device"][k] == out[how][k], (how, k)
         assert out["device_log"] == out[how + "_log"] and len(out["device_log"]) == 4 * 3 + 2
     assert out["device"]["_ReadIDMap.txt"].count(b"\n") >= 3
+
+
+# ---- 8. the seams of the record-finding kernels, and one rank against one GPU -------------------------------------------------------------
+@pytest.mark.parametrize("G", (2, 3))
+def test_block_and_lane_edges_under_a_communicator(tmp_path, G):
+    """the files of tests/test_gpu_ingest.py::test_record_starts_on_block_and_lane_edges through G ranks: the top piece of a file begins
+    its buffer as a whole file does; the other pieces see the same seams one byte further on"""
+    mo = 33
+    files = edge_files(tmp_path)
+    names = list(files)
+
+    def work(g, r):  # the same contexts take one input after the other
+        out = {}
+        for name in names:
+            got = g.dist_ingest_fasta([files[name][0]], threads=2)
+            if name == EDGE_DECLINED:
+                out[name] = (got, g.last_error())
+                continue
+            assert got is not None, (name, g.last_error())
+            out[name] = {"info": got[0], "files": got[1], "home": _home(g)}
+        return out
+
+    res = _ranks(G, mo, work)
+    for name in names:
+        want, wfidx, wtotal = edge_want(files[name][0], mo)
+        if name == EDGE_DECLINED:
+            assert want == [] and all(o[name][0] is None and "no good read (or more than 2^31)" in o[name][1] for o in res), name
+            continue
+        infos = _check_homes([o[name] for o in res], want, wfidx)
+        assert infos[0]["total_records"] == wtotal and len(want) > 10, name
+
+
+def test_a_communicator_of_one_rank_makes_the_table_one_gpu_makes(tmp_path):
+    reads, rng = _pool(61, 1500, 500)
+    fa, fq = tmp_path / "one.fasta", tmp_path / "one.fastq"
+    fa.write_text(_fasta(reads))
+    fq.write_text(_fastq(reads, rng))
+    mo = 33
+    for p in (str(fa), str(fq)):
+        def work(g, r):
+            got = g.dist_ingest_fasta([p], threads=2)
+            assert got is not None, g.last_error()
+            ln, fi = g.dist_ingest_fetch()
+            packed, lens = g.download_reads()
+            return got[0], got[1], ln, fi, packed, lens
+
+        (dinfo, dfiles, dln, dfi, dpacked, dlens), = _ranks(1, mo, work)
+        with buildgraph.BuildGraph(min_overlap=mo) as g:
+            info, files = g.ingest_fasta([p], threads=2)
+            ln, fi = g.ingest_fetch()
+            packed, lens = g.download_reads()
+        assert len(ln) > 1500
+        for k in ("n_reads", "total_records", "too_long"):
+            assert dinfo[k] == info[k], k
+        assert dfiles == files
+        assert np.array_equal(dln, ln) and np.array_equal(dlens, lens) and np.array_equal(dfi, fi)
+        m = min(dpacked.shape[1], packed.shape[1])  # (the row strides may differ: words behind a read are zero in both)
+        assert np.array_equal(dpacked[:, :m], packed[:, :m]) and not dpacked[:, m:].any() and not packed[:, m:].any()

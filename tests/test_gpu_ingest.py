@@ -13,6 +13,7 @@ import pytest
 from disco_amd import build, buildgraph
 from oracle import pyoracle
 from tests import golden_util as gu
+from tests.ingest_edges import EDGE_DECLINED, EDGE_OFFSETS, edge_files, edge_want
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -321,3 +322,31 @@ def test_ingest_packs_a_tail_of_long_reads_per_class(tmp_path, wrapped):
     oe, orows, oc = run_oracle_reads(want, 40)
     a, b = canon_hip(he, hr), canon_hip(oe, orows)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and hc["kmer_hits"] == oc["kmer_hits"]
+
+
+# ---- block and lane edges of the record-finding kernels (tests/ingest_edges.py) ---------------------------------------------------------------
+def test_record_starts_on_block_and_lane_edges(tmp_path):
+    """the record-finding kernels at their seams, one context through every file of edge_files, against the parser"""
+    mo = 33
+    files = edge_files(tmp_path)
+    assert list(files)[-1] == EDGE_DECLINED  # (behind files that were read: what a decline must leave alone is there)
+    assert len(files) == 2 * (2 * len(EDGE_OFFSETS) + 2) + 4
+    with buildgraph.BuildGraph(min_overlap=mo) as g:
+        for name, (path, fastq) in files.items():
+            want, wfidx, wtotal = edge_want(path, mo)
+            res = g.ingest_fasta([path], threads=2)
+            if name == EDGE_DECLINED:
+                assert want == [] and res is None, name
+                assert g.last_error() == f"disco_ingest_fasta: no good read (or more than 2^31) ({path}): the host input stage takes this job"
+                # a declined call leaves the context the reads it had: the fetch still answers for the file before
+                ln2, fi2 = g.ingest_fetch()
+                assert np.array_equal(ln2, before[0]) and np.array_equal(fi2, before[1]) and len(fi2) > 10 and fi2.min() >= 1
+                continue
+            assert res is not None, (name, g.last_error())
+            info, per_file = res
+            ln, fi = g.ingest_fetch()
+            packed, lens = g.download_reads()
+            assert np.array_equal(ln, lens) and info["n_reads"] == len(want) > 10, name
+            assert info["total_records"] == wtotal and per_file[0]["good"] + per_file[0]["bad"] == wtotal, name
+            assert _decode(packed, lens) == want and np.array_equal(fi.astype(np.int64), wfidx), name
+            before = (ln, fi)

@@ -113,6 +113,7 @@ ABI = [
     ("disco_inflate_bgzf", C.c_int64, [_P, _P, C.c_uint64, _P, C.c_uint64]),
     ("disco_dist_ingest_fasta", C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, C.c_uint32, _P, _P]),
     ("disco_dist_ingest_fetch", C.c_int, [_P, _P, _P]),
+    ("disco_inflate_bgzf_window", C.c_int64, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint64, _P]),
 ]
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
@@ -580,6 +581,17 @@ class BuildGraph:
         if n == -6:
             return None
         return out.raw[:self._chk(n)]
+
+    def inflate_bgzf_window(self, data: bytes, lo: int, n: int):
+        """the bytes [lo, lo + n) of a BGZF buffer's text — what of them the text has — decoded on the device from the members that hold
+        them (disco_inflate_bgzf_window), or None when the buffer is not BGZF or a member of the window is corrupt — last_error() then
+        names the member by its number in the file"""
+        data = bytes(data)
+        out = C.create_string_buffer(max(n, 1))
+        got = self.L.disco_inflate_bgzf_window(self._h, data, len(data), lo, n, out)
+        if got == -6:  # DISCO_E_UNSUPPORTED
+            return None
+        return out.raw[:self._chk(got)]
 
     def last_error(self) -> str:
         return self.L.disco_last_error(self._h).decode()

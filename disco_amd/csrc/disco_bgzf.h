@@ -9,6 +9,9 @@
  * The CRC32 is taken over the window — a chunk per lane, the registers moved to the end by multiplying with x^(8 n) mod P and
  * XORed over the wave — and only a member that is sound is written out, 16 bytes a lane where source and destination allow it (the
  * window is laid into LDS at the destination's misalignment, so they always do between the first and the last few bytes).
+ * A launch writes a WINDOW of the file's text: a member is decoded and checked whole, and of its bytes those inside the window are
+ * stored, at text + (out_off + i - win_lo) — a whole file is the window [0, its text); a rank's piece of it is decoded from the
+ * members that overlap the piece, the first and the last of them clipped.
  * Nothing the wave has stored is read back through global memory.
  */
 #ifndef DISCO_BGZF_H_
@@ -18,10 +21,11 @@
 #include "disco_inflate.h"
 
 struct BgzfArgs {
-    const u8 *comp;              /* the file                                                    */
-    const infl::BgzfBlock *blk;  /* its members                                                 */
+    const u8 *comp;              /* the compressed bytes of the launched members: in_off counts from here */
+    const infl::BgzfBlock *blk;  /* the launched members; out_off is a member's place in the FILE's text  */
     u32 n_blk;
-    u8 *text;                    /* out_off of every member counts from here                    */
+    u8 *text;                    /* the window's first byte: text[0, win_n) is all a launch may write     */
+    u64 win_lo, win_n;           /* the window of the file's text (a whole file: 0 and its text's size)   */
     u32 *status;                 /* [n_blk] INFL_* of every member, then one word: members with an error */
 };
 
@@ -66,8 +70,13 @@ __global__ void __launch_bounds__(64) bgzf_inflate_kernel(BgzfArgs a)
     const u32 m = blockIdx.x, lane = threadIdx.x;
     if (m >= a.n_blk) return;
     const infl::BgzfBlock b = a.blk[m];
-    u8 *dst = a.text + b.out_off;
-    const u32 mis = (u32)((uintptr_t)dst & 15u);
+    /* where the member's first byte would lie, as a number: in front of `text` where the window cuts the member's front, and never dereferenced there */
+    const uintptr_t dst = (uintptr_t)a.text + (uintptr_t)(b.out_off - a.win_lo);
+    const u32 mis = (u32)(dst & 15u);
+    /* the member's bytes [c0, c1) lie in the window: dst + i is inside text[0, win_n) exactly for them (known in front of the decode, so
+     * that the window does not stay in registers through it) */
+    const u64 m_lo = b.out_off, m_hi = m_lo + b.isize, w_hi = a.win_lo + a.win_n;
+    const u32 c0 = (u32)(min(max(m_lo, a.win_lo), m_hi) - m_lo), c1 = (u32)(max(min(m_hi, w_hi), m_lo + c0) - m_lo);
     WaveSink sink = {win + mis, 0, lane, 0, 0};
     u32 used = 0, made = 0;
     int err = infl::inflate_raw(a.comp + b.in_off, b.in_len, b.isize, sink, tab, lane, 64, &used, &made);
@@ -82,10 +91,10 @@ __global__ void __launch_bounds__(64) bgzf_inflate_kernel(BgzfArgs a)
     }
     if (!err) {
         const u8 *w = sink.w;
-        const u32 n = b.isize, head = min(n, (16u - mis) & 15u), body = (n - head) / 16;
-        if (lane < head) dst[lane] = w[lane];
-        for (u32 i = lane; i < body; i += 64) ((uint4 *)(dst + head))[i] = *(const uint4 *)(w + head + 16 * i);
-        for (u32 i = head + 16 * body + lane; i < n; i += 64) dst[i] = w[i];
+        const u32 n = c1 - c0, head = min(n, (16u - ((mis + c0) & 15u)) & 15u), body = (n - head) / 16;
+        if (lane < head) *(u8 *)(dst + c0 + lane) = w[c0 + lane];
+        for (u32 i = lane; i < body; i += 64) *(uint4 *)(dst + c0 + head + 16 * i) = *(const uint4 *)(w + c0 + head + 16 * i);
+        for (u32 i = c0 + head + 16 * body + lane; i < c1; i += 64) *(u8 *)(dst + i) = w[i];
     }
     if (lane == 0) {
         a.status[m] = (u32)err;

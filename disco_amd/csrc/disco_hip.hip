@@ -2018,6 +2018,9 @@ struct IngestFile {
     const u8 *map = nullptr;
     u64 comp_n = 0;
     u8 *d_comp = nullptr;
+    /* under a communicator: the member chain, walked by every rank, and the members [m_first, m_first + m_count) that hold the rank's piece */
+    std::vector<infl::BgzfBlock> blocks;
+    uint64_t m_first = 0, m_count = 0;
     IngestPiece p;
 };
 } // namespace
@@ -2167,21 +2170,25 @@ static int ingest_read_file(disco_ctx *c, int fd, u64 n, u8 *d_text, unsigned th
 }
 
 /* ---- BGZF: the members of a compressed file decoded on the device (kernel: disco_bgzf.h, decoder: disco_inflate.h) ------------------- */
-/* one wavefront per member on the context's stream, waited for. d_blk: room for the member table, d_status: a word per member and one
- * more. *why = INFL_OK, or the error of member *bad, the first one the kernel did not accept (its text is then not written) */
-static int bgzf_inflate_run(disco_ctx *c, const u8 *d_comp, const std::vector<infl::BgzfBlock> &blocks, infl::BgzfBlock *d_blk, u32 *d_status, u8 *d_text, uint64_t *bad, int *why)
+/* one wavefront per member on the context's stream, waited for: the nb members blk[] — whose payloads lie at d_comp + in_off — write
+ * what they hold of the window [win_lo, win_lo + win_n) of the file's text to d_text[0, win_n). d_blk: room for the member table,
+ * d_status: a word per member and one more. *why = INFL_OK, or the error of member *bad OF THE LAUNCH, the first one the kernel did
+ * not accept (its text is then not written) */
+static int bgzf_inflate_run(disco_ctx *c, const u8 *d_comp, const infl::BgzfBlock *blk, u64 nb, infl::BgzfBlock *d_blk, u32 *d_status, u8 *d_text, u64 win_lo, u64 win_n, uint64_t *bad,
+                            int *why)
 {
-    const u64 nb = blocks.size();
     *why = infl::INFL_OK;
     *bad = 0;
     if (nb == 0 || nb >= (1ull << 31)) return fail(c, DISCO_E_ARG, "BGZF: %llu members out of range", (unsigned long long)nb);
-    HIPCHK(c, hipMemcpyAsync(d_blk, blocks.data(), nb * sizeof(infl::BgzfBlock), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_blk, blk, nb * sizeof(infl::BgzfBlock), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_status, 0, (nb + 1) * sizeof(u32), c->stream));
     BgzfArgs a;
     a.comp = d_comp;
     a.blk = d_blk;
     a.n_blk = (u32)nb;
     a.text = d_text;
+    a.win_lo = win_lo;
+    a.win_n = win_n;
     a.status = d_status;
     hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)nb), dim3(64), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
@@ -2223,7 +2230,7 @@ extern "C" int64_t disco_inflate_bgzf(disco_ctx *c, const void *bgzf, uint64_t n
         CHK(ensure(c, d_blk, blocks.size()));
         CHK(ensure(c, d_status, blocks.size() + 1));
         HIPCHK(c, hipMemcpyAsync(d_comp.p, bgzf, n_bytes, hipMemcpyHostToDevice, c->stream));
-        CHK(bgzf_inflate_run(c, d_comp, blocks, d_blk, d_status, d_text, &bad, &e));
+        CHK(bgzf_inflate_run(c, d_comp, blocks.data(), blocks.size(), d_blk, d_status, d_text, 0, total, &bad, &e));
         if (e == infl::INFL_OK && total) HIPCHK(c, hipMemcpy(out, d_text.p, total, hipMemcpyDeviceToHost));
         return DISCO_OK;
     };
@@ -2235,6 +2242,43 @@ extern "C" int64_t disco_inflate_bgzf(disco_ctx *c, const void *bgzf, uint64_t n
     CHK(rc);
     if (e != infl::INFL_OK) return fail(c, DISCO_E_UNSUPPORTED, "disco_inflate_bgzf: member %llu: %s", (unsigned long long)bad, infl::reason(e));
     return (int64_t)total;
+}
+
+extern "C" int64_t disco_inflate_bgzf_window(disco_ctx *c, const void *bgzf, uint64_t n_bytes, uint64_t text_lo, uint64_t text_n, void *out)
+{
+    DISCO_TRACE("disco_inflate_bgzf_window");
+    if (!c || !bgzf) return c ? fail(c, DISCO_E_ARG, "disco_inflate_bgzf_window: null argument") : DISCO_E_ARG;
+    std::vector<infl::BgzfBlock> blocks, sub;
+    uint64_t total = 0, bad = 0, first = 0, count = 0, comp_lo = 0, comp_n = 0;
+    if (const char *why = infl::bgzf_walk((const u8 *)bgzf, n_bytes, blocks, &total, &bad))
+        return fail(c, DISCO_E_UNSUPPORTED, "disco_inflate_bgzf_window: member %llu: %s", (unsigned long long)bad, why);
+    const uint64_t n = text_lo < total ? std::min(text_n, total - text_lo) : 0;
+    if (!out || n == 0) return (int64_t)n;
+    infl::bgzf_window_members(blocks, text_lo, n, &first, &count);
+    infl::bgzf_rebase(blocks, first, count, sub, &comp_lo, &comp_n);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<u8> d_comp, d_text;
+    DevBuf<infl::BgzfBlock> d_blk;
+    DevBuf<u32> d_status;
+    int e = infl::INFL_OK;
+    auto body = [&]() -> int {
+        CHK(ensure(c, d_comp, comp_n));
+        CHK(ensure(c, d_text, n));
+        CHK(ensure(c, d_blk, sub.size()));
+        CHK(ensure(c, d_status, sub.size() + 1));
+        HIPCHK(c, hipMemcpyAsync(d_comp.p, (const u8 *)bgzf + comp_lo, comp_n, hipMemcpyHostToDevice, c->stream));
+        CHK(bgzf_inflate_run(c, d_comp, sub.data(), sub.size(), d_blk, d_status, d_text, text_lo, n, &bad, &e));
+        if (e == infl::INFL_OK) HIPCHK(c, hipMemcpy(out, d_text.p, n, hipMemcpyDeviceToHost));
+        return DISCO_OK;
+    };
+    const int rc = body();
+    release(c, d_comp);
+    release(c, d_text);
+    release(c, d_blk);
+    release(c, d_status);
+    CHK(rc);
+    if (e != infl::INFL_OK) return fail(c, DISCO_E_UNSUPPORTED, "disco_inflate_bgzf_window: member %llu: %s", (unsigned long long)(first + bad), infl::reason(e));
+    return (int64_t)n;
 }
 
 /* ---- the input stage as steps over one IngestJob, with two drivers: disco_ingest_fasta (below: one piece per file, no exchange) and
@@ -2320,7 +2364,8 @@ struct IngestFold {
 static u64 ingest_text_cap(u64 n) { return (n + FX_TILE + 63) / FX_TILE * FX_TILE + 64; }
 
 /* a file opened and classified — regular, first byte '>' or '@'. Under a .gz name: BGZF only where the caller decodes it (may_bgzf: one
- * GPU; plain gzip is one serial stream, the host stage's), a decline otherwise. Answers a decline code */
+ * GPU, and the ranks of a communicator that were told to with DISCO_DIST_BGZF=1; plain gzip is one serial stream, the host stage's), a
+ * decline otherwise. A BGZF file is mapped and left unclassified: its text is known once its members are. Answers a decline code */
 static int ingest_open_file(IngestFile &f, const char *path, bool may_bgzf)
 {
     f.path = path ? path : "";
@@ -2445,7 +2490,7 @@ static int ingest_text_bgzf(IngestJob &j, IngestFile &f)
     CHK(j.get(&d_status, blocks.size() + 1));
     HIPCHK(c, hipMemsetAsync(f.p.d_text + f.n, 0, ingest_text_cap(f.n) - f.n, c->stream));
     int e = infl::INFL_OK;
-    CHK(bgzf_inflate_run(c, f.d_comp, blocks, d_blk, d_status, f.p.d_text, &bad, &e));
+    CHK(bgzf_inflate_run(c, f.d_comp, blocks.data(), blocks.size(), d_blk, d_status, f.p.d_text, 0, f.n, &bad, &e));
     if (e != infl::INFL_OK) {
         snprintf(msg, sizeof msg, "member %llu: %s", (unsigned long long)bad, infl::reason(e));
         return j.decline(DR_BGZF_MEMBER, f, msg);
@@ -5774,7 +5819,10 @@ int disco_dist_generate_reads(disco_ctx *c, const disco_genspec_abi *s)
  *      -- all-gather: status word -- all-to-all of rows, lengths, record numbers: what lies outside the home range, to its owner
  *   dist_validate (collective, as behind an upload)
  * A local failure or decline never returns in front of the next meeting point: it travels in the status word, and everybody leaves
- * behind that all-gather with the same code. */
+ * behind that all-gather with the same code.
+ * DISCO_DIST_BGZF=1: a BGZF file is a file whose bytes are those of its TEXT. Every rank walks its member chain in front of the shares
+ * (di_walk_bgzf), and in step A a piece's text is decoded from the members that hold it (ingest_piece_text_bgzf) instead of read; from
+ * ingest_count_starts on nothing knows the difference. */
 extern "C++" {
 namespace {
 enum { DI_OK = 0, DI_DECLINE = 1, DI_ERROR = 2 };
@@ -5803,6 +5851,8 @@ struct DistIngest {
     void *ring = nullptr;
     size_t ring_bytes = 0;
     u64 status = 0; /* this rank's */
+    size_t n_bgzf = 0; /* BGZF files of the job, and what walking their member chains took on this rank */
+    float walk_ms = 0;
     DistIngest(disco_ctx *ctx, int n_files, uint32_t threads) : c(ctx), job(ctx, "disco_dist_ingest_fasta", n_files, threads) {}
     ~DistIngest()
     {
@@ -5843,8 +5893,83 @@ static int di_verdict(DistIngest &D, const std::vector<u64> &all, size_t n_per_r
     const size_t file = (size_t)((dec >> 16) & 0xFFFFFFFFull);
     const int code = (int)(dec & 0xFFFFu);
     c->err.clear();
-    return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s (%s; seen by rank %d): the host input stage takes this job", kIngestDecline[code > 0 && code < DR_COUNT ? code : 0],
+    /* (which member and why is known to the rank that met it — its DISCO_VERBOSE line says so; the status word carries the code) */
+    const char *const more = code == DR_GZ_MEMBER ? " a member chain that does not hold" : (code == DR_BGZF_MEMBER ? ": a member the decoder or its CRC32 refuses" : "");
+    return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_ingest_fasta: %s%s (%s; seen by rank %d): the host input stage takes this job", kIngestDecline[code > 0 && code < DR_COUNT ? code : 0], more,
                 paths[file] ? paths[file] : "", dec_rank);
+}
+
+/* step (every rank, DISCO_DIST_BGZF=1): a BGZF file's member chain, the size of its text and — what every rank must know of a file
+ * before it counts anything — its first and its last text byte, from the first and the last member that have text, decoded here on
+ * the host by the kernel's own functions and checked as the kernel checks them. Every rank sees the same file: a decline is everybody's */
+static int di_walk_bgzf(IngestJob &j, IngestFile &f, float *walk_ms)
+{
+    const auto t0 = HClock::now();
+    uint64_t total = 0, bad = 0;
+    const char *why = infl::bgzf_walk(f.map, f.comp_n, f.blocks, &total, &bad);
+    *walk_ms += ms_since(t0);
+    char msg[160];
+    if (why || total == 0) {
+        snprintf(msg, sizeof msg, "member %llu: %s", (unsigned long long)bad, why ? why : "no text");
+        return j.decline(DR_GZ_MEMBER, f, msg);
+    }
+    f.n = total;
+    size_t k0 = 0, k1 = f.blocks.size() - 1;
+    while (f.blocks[k0].isize == 0) k0++;
+    while (f.blocks[k1].isize == 0) k1--;
+    std::vector<u8> text(INFL_MAX_ISIZE);
+    std::unique_ptr<infl::Tables> tab(new infl::Tables);
+    char first = 0;
+    for (size_t k = k0;; k = k1) { /* (one member with text: decoded once) */
+        if (const int e = infl::bgzf_member_host(f.map, f.blocks[k], text.data(), *tab)) {
+            snprintf(msg, sizeof msg, "member %llu: %s", (unsigned long long)k, infl::reason(e));
+            return j.decline(DR_BGZF_MEMBER, f, msg);
+        }
+        if (k == k0) first = (char)text[0];
+        f.last = (char)text[f.blocks[k].isize - 1];
+        if (k == k1) break;
+    }
+    if (first != '>' && first != '@') return j.decline(DR_FORM, f);
+    f.fastq = first == '@';
+    return DISCO_OK;
+}
+
+/* step: the text of a piece of a BGZF file — the window [p0 - own_lo, pend) of the file's text — out of the members that hold it: their
+ * compressed bytes into HBM (ONE range of the file), the table counted from there, one wavefront per member, the first and the last
+ * one clipped to the window. Behind it the piece is what ingest_piece_text leaves of a plain file; the byte in front of the owned
+ * bytes and their last one are looked at in the decoded text */
+static int ingest_piece_text_bgzf(IngestJob &j, IngestFile &f, void *ring, size_t ring_bytes)
+{
+    disco_ctx *c = j.c;
+    IngestPiece &p = f.p;
+    const auto t_read = HClock::now();
+    std::vector<infl::BgzfBlock> sub;
+    uint64_t comp_lo = 0, comp_n = 0, bad = 0;
+    infl::bgzf_rebase(f.blocks, f.m_first, f.m_count, sub, &comp_lo, &comp_n);
+    if (sub.empty()) return fail(c, DISCO_E_STATE, "disco_dist_ingest_fasta: a piece of %s without a member", f.path.c_str());
+    infl::BgzfBlock *d_blk = nullptr;
+    u32 *d_status = nullptr;
+    CHK(j.get(&p.d_text, ingest_text_cap(p.n)));
+    CHK(j.get(&f.d_comp, comp_n));
+    CHK(j.get(&d_blk, sub.size()));
+    CHK(j.get(&d_status, sub.size() + 1));
+    HIPCHK(c, hipMemsetAsync(p.d_text + p.n, 0, ingest_text_cap(p.n) - p.n, c->stream));
+    const int rc = ingest_read_file(c, f.fd, comp_n, f.d_comp, j.threads, comp_lo, ring, ring_bytes);
+    j.read_s += ms_since(t_read) * 1e-3f;
+    CHK(rc);
+    int e = infl::INFL_OK;
+    CHK(bgzf_inflate_run(c, f.d_comp, sub.data(), sub.size(), d_blk, d_status, p.d_text, p.p0 - p.own_lo, p.n, &bad, &e));
+    if (e != infl::INFL_OK) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "member %llu: %s", (unsigned long long)(f.m_first + bad), infl::reason(e));
+        return j.decline(DR_BGZF_MEMBER, f, msg);
+    }
+    char ch[2] = {'\n', 0};
+    if (p.own_lo) HIPCHK(c, hipMemcpy(&ch[0], p.d_text, 1, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&ch[1], p.d_text + p.own_hi - 1, 1, hipMemcpyDeviceToHost));
+    p.prefix_nl = ch[0] == '\n';
+    p.last_nl = ch[1] == '\n';
+    return DISCO_OK;
 }
 
 /* step A, local: the files, the rank's pieces of them, their text in HBM, FASTA record starts / FASTQ newline counts */
@@ -5854,9 +5979,17 @@ static int di_read_pieces(DistIngest &D, const char *const *paths, disco_dist_in
     IngestJob &j = D.job;
     const u64 G = (u64)c->comm->world, r = (u64)c->comm->rank;
     u64 T = 0;
+    /* DISCO_DIST_BGZF=1: a .gz name is opened as one GPU opens it, and a BGZF file is T bytes of TEXT like any other: shares, pieces and
+     * tails are cut over text bytes. Without it every .gz name declines (DR_GZ_COMM), on this rank and so on all */
+    const bool may_bgzf = env_int("DISCO_DIST_BGZF", 0) == 1;
     for (size_t fi = 0; fi < j.F.size(); fi++) {
-        if (const int code = ingest_open_file(j.F[fi], paths[fi], false)) return j.decline(code, j.F[fi]);
-        T += j.F[fi].n;
+        IngestFile &f = j.F[fi];
+        if (const int code = ingest_open_file(f, paths[fi], may_bgzf)) return j.decline(code == DR_NO_OPEN ? DR_UNREADABLE : code, f);
+        if (f.map) {
+            if (const int rc = di_walk_bgzf(j, f, &D.walk_ms)) return rc;
+            D.n_bgzf++;
+        }
+        T += f.n;
     }
     /* the rank's share: bytes [a, b) of the files laid end to end
      * (128-bit product: T * r does not fit 64 bits for nothing anybody has, but the cut must be the same arithmetic everywhere) */
@@ -5876,6 +6009,12 @@ static int di_read_pieces(DistIngest &D, const char *const *paths, disco_dist_in
         p.own_hi = p.own_lo + (p.p1 - p.p0);
         p.n = p.own_lo + (pend - p.p0);
         text_bytes += ingest_text_cap(p.n);
+        if (f.map) { /* the members that hold the piece: their compressed bytes and their table lie in the arena next to its text */
+            infl::bgzf_window_members(f.blocks, p.p0 - p.own_lo, p.n, &f.m_first, &f.m_count);
+            const infl::BgzfBlock &m0 = f.blocks[f.m_first], &m1 = f.blocks[f.m_first + f.m_count - 1];
+            text_bytes += ((m1.in_off + m1.in_len - m0.in_off + 255) & ~255ull) + ((f.m_count * sizeof(infl::BgzfBlock) + 255) & ~255ull) + (((f.m_count + 1) * 4 + 255) & ~255ull);
+            continue; /* (the byte in front and the last owned one: read in the decoded text) */
+        }
         char ch[2] = {'\n', 0};
         if ((p.p0 && pread(f.fd, &ch[0], 1, (off_t)(p.p0 - 1)) != 1) || pread(f.fd, &ch[1], 1, (off_t)(p.p1 - 1)) != 1) return fail(c, DISCO_E_ARG, "disco_dist_ingest_fasta: read error");
         p.prefix_nl = ch[0] == '\n';
@@ -5894,7 +6033,10 @@ static int di_read_pieces(DistIngest &D, const char *const *paths, disco_dist_in
     }
     for (IngestFile &f : j.F) {
         if (f.p.p1 <= f.p.p0) continue;
-        CHK(ingest_piece_text(j, f, D.ring, D.ring_bytes));
+        if (f.map) {
+            if (const int rc = ingest_piece_text_bgzf(j, f, D.ring, D.ring_bytes)) return rc;
+        } else
+            CHK(ingest_piece_text(j, f, D.ring, D.ring_bytes));
         CHK(ingest_count_starts(j, f));
     }
     return DISCO_OK;
@@ -5966,6 +6108,8 @@ int disco_dist_ingest_fasta(disco_ctx *c, const char *const *paths, int n_files,
         if (c->phase > 1) c->phase = 1;
         rc = di_read_pieces(D, paths, info);
     }
+    /* (which member of a BGZF file, and why: the status word has no room for it) */
+    if (rc == INGEST_DECLINED && (j.why_code == DR_GZ_MEMBER || j.why_code == DR_BGZF_MEMBER) && getenv("DISCO_VERBOSE")) fprintf(stderr, "[disco] rank %zu declines: %s (%s)\n", r, j.why.c_str(), j.where.c_str());
     D.note(rc);
     mine.assign(1 + F, 0);
     mine[0] = D.status;
@@ -6012,11 +6156,14 @@ int disco_dist_ingest_fasta(disco_ctx *c, const char *const *paths, int n_files,
     const int vrc = dist_validate(c);
     info->read_s = j.read_s;
     info->device_s = j.seconds() - j.read_s;
-    if (getenv("DISCO_VERBOSE"))
+    if (getenv("DISCO_VERBOSE")) {
+        char bgzf[96] = "";
+        if (D.n_bgzf) snprintf(bgzf, sizeof bgzf, "; %zu BGZF files, member chains walked in %.1f ms", D.n_bgzf, D.walk_ms);
         fprintf(stderr, "[disco] input stage on rank %zu of %zu: bytes [%llu, %llu) of the input, %llu reads of %llu, %llu kept at home; files %.3f s, records + filter %.3f s, "
-                        "table + rows + exchange %.3f s\n",
+                        "table + rows + exchange %.3f s%s\n",
                 r, G, (unsigned long long)info->share_lo, (unsigned long long)info->share_hi, (unsigned long long)info->share_reads, (unsigned long long)s.n,
-                (unsigned long long)info->kept_reads, j.read_s, t_filtered - j.read_s, j.seconds() - t_filtered);
+                (unsigned long long)info->kept_reads, j.read_s, t_filtered - j.read_s, j.seconds() - t_filtered, bgzf);
+    }
     return vrc;
 }
 

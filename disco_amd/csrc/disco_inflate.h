@@ -430,5 +430,81 @@ inline const char *bgzf_walk(const uint8_t *d, uint64_t n, Vec &blocks, uint64_t
     return k ? nullptr : "empty file";
 }
 
+/* the members that hold the window [lo, lo + n) of the text: blocks [*first, *first + *count), ONE range of the chain (out_off never
+ * decreases along it). Its first and its last member hold a byte of the window; empty members between them belong to it, empty members
+ * on its edges do not. count 0: the window is empty or lies behind the text. Blocks: anything with size() and [] of BgzfBlock. */
+template <class Blocks>
+inline void bgzf_window_members(const Blocks &blocks, uint64_t lo, uint64_t n, uint64_t *first, uint64_t *count)
+{
+    const uint64_t nb = blocks.size(), hi = n > ~0ull - lo ? ~0ull : lo + n;
+    uint64_t a = 0, b = nb;
+    while (a < b) { /* the first member that ends behind lo */
+        const uint64_t m = a + (b - a) / 2;
+        if (blocks[m].out_off + blocks[m].isize > lo) b = m;
+        else a = m + 1;
+    }
+    *first = a;
+    for (b = nb; a < b;) { /* the first member that begins at or behind hi */
+        const uint64_t m = a + (b - a) / 2;
+        if (blocks[m].out_off >= hi) b = m;
+        else a = m + 1;
+    }
+    while (a > *first && blocks[a - 1].isize == 0) a--;
+    *count = a > *first && n ? a - *first : 0;
+}
+
+/* the table of a launch (or of the host tool's loop) over the members [first, first + count): in_off counts from the first one's
+ * payload, whose offset in the file is *comp_lo; the members' compressed bytes, headers and trailers between them included, are
+ * [*comp_lo, *comp_lo + *comp_n) of the file. out_off stays what it is: the member's place in the file's text */
+template <class Blocks, class Vec>
+inline void bgzf_rebase(const Blocks &blocks, uint64_t first, uint64_t count, Vec &out, uint64_t *comp_lo, uint64_t *comp_n)
+{
+    out.clear();
+    *comp_lo = count ? blocks[first].in_off : 0;
+    *comp_n = count ? blocks[first + count - 1].in_off + blocks[first + count - 1].in_len - *comp_lo : 0;
+    for (uint64_t k = first; k < first + count; k++) {
+        BgzfBlock b = blocks[k];
+        b.in_off -= *comp_lo;
+        out.push_back(b);
+    }
+}
+
+/* ---- one member on the host: a serial byte sink, the CRC32 by the lanes' chunks (inflate_check; the first and the last byte of a file
+ * for the ranks of disco_dist_ingest_fasta) ------------------------------------------------------------------------------------------ */
+struct ByteSink {
+    uint8_t *out;
+    uint32_t p = 0;
+    void lit(uint8_t c) { out[p++] = c; }
+    void match(uint32_t len, uint32_t dist)
+    {
+        for (uint32_t i = 0; i < len; i++) out[p + i] = out[p - dist + (i < dist ? i : i % dist)]; /* the lanes' formula */
+        p += len;
+    }
+    void raw(const uint8_t *s, uint32_t n)
+    {
+        memcpy(out + p, s, n);
+        p += n;
+    }
+};
+
+inline uint32_t crc_by_chunks(const uint8_t *p, uint32_t n)
+{
+    uint32_t x = 0;
+    for (uint32_t lane = 0; lane < 64; lane++) x ^= crc_lane(p, n, lane, 64);
+    return ~x;
+}
+
+/* member b, whose payload lies at comp + b.in_off, decoded whole into out[0, b.isize) and checked as the kernel checks it: INFL_* */
+inline int bgzf_member_host(const uint8_t *comp, const BgzfBlock &b, uint8_t *out, Tables &tab)
+{
+    ByteSink sink{out};
+    uint32_t used = 0, made = 0;
+    int e = inflate_raw(comp + b.in_off, b.in_len, b.isize, sink, tab, 0, 1, &used, &made);
+    if (!e && made != b.isize) e = INFL_E_SHORT;
+    if (!e && used != b.in_len) e = INFL_E_TRAIL;
+    if (!e && crc_by_chunks(out, b.isize) != b.crc) e = INFL_E_CRC;
+    return e;
+}
+
 } // namespace infl
 #endif

@@ -359,7 +359,7 @@ int main(int argc, char **argv)
     }
     /* --gpus N: the contexts, the communicator and the watchdog exist BEFORE the input stage, because every rank reads its share of the
      * files itself (disco_dist_ingest_fasta: the bytes of the files laid end to end, cut into N shares; records, filter and rows on the
-     * rank's GPU, rows of other ranks' home ranges sent to their owners). DISCO_E_UNSUPPORTED — on every rank alike: a .gz name, a '>'
+     * rank's GPU, rows of other ranks' home ranges sent to their owners). DISCO_E_UNSUPPORTED — on every rank alike: a .gz name (BGZF too, unless DISCO_DIST_BGZF=1 asks the ranks to decode it), a '>'
      * inside a line, an irregularly wrapped long record, an unreadable file — leaves the job to the host stage below, inside the same
      * run and on the same contexts. Asked for with DISCO_DIST_DEVICE_INPUT=1 (below: why not by default); DISCO_HOST_INPUT=1: the host stage always. */
     std::vector<disco_ctx *> ctx;

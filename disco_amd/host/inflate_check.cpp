@@ -1,6 +1,8 @@
-/* inflate_check FILE — decodes a BGZF file with the decode core of the device input stage (disco_amd/csrc/disco_inflate.h) on the host,
- * one member after the other with a serial byte sink, checks every member's CRC32 and ISIZE and writes the text to stdout.
+/* inflate_check [--window LO N] FILE — decodes a BGZF file with the decode core of the device input stage (disco_amd/csrc/disco_inflate.h)
+ * on the host, one member after the other with a serial byte sink, checks every member's CRC32 and ISIZE and writes the text to stdout.
  * Exit 0, or 3 with `block N: reason` on stderr for anything it does not accept (2: usage / unreadable file).
+ * --window LO N: only the bytes [LO, LO + N) of the text (what of them the text has), from the members that hold them — chosen, rebased
+ * and clipped by the functions disco_inflate_bgzf_window runs; a member outside the window is not looked at, the chain is walked whole.
  *
  * The members are found as the device stage finds them: by the BSIZE chain, every payload decoded inside its own bounds and to its
  * last byte. Where the chain itself does not hold (a BSIZE that is not the member's size), the file is read once more the way zlib
@@ -8,33 +10,14 @@
  * is valid gzip, the device stage declines it and the host stage reads it. */
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../csrc/disco_inflate.h"
 
 namespace {
-struct ByteSink {
-    uint8_t *out;
-    uint32_t p = 0;
-    void lit(uint8_t c) { out[p++] = c; }
-    void match(uint32_t len, uint32_t dist)
-    {
-        for (uint32_t i = 0; i < len; i++) out[p + i] = out[p - dist + (i < dist ? i : i % dist)]; /* the lanes' formula */
-        p += len;
-    }
-    void raw(const uint8_t *s, uint32_t n)
-    {
-        memcpy(out + p, s, n);
-        p += n;
-    }
-};
-
-uint32_t crc_by_chunks(const uint8_t *p, uint32_t n)
-{
-    uint32_t x = 0;
-    for (uint32_t lane = 0; lane < 64; lane++) x ^= infl::crc_lane(p, n, lane, 64);
-    return ~x;
-}
+using infl::ByteSink;
+using infl::crc_by_chunks;
 
 int refuse(uint64_t block, const char *why)
 {
@@ -67,17 +50,43 @@ int read_as_gzip(const std::vector<uint8_t> &f, std::vector<uint8_t> &text)
     }
     return k ? 0 : refuse(0, "empty file");
 }
+
+/* the window [lo, lo + n) of the text to stdout: its members out of a buffer that holds their compressed bytes only, by the rebased
+ * table; each one decoded and checked whole, clipped to the window as the kernel clips it */
+int write_window(const std::vector<uint8_t> &f, const std::vector<infl::BgzfBlock> &blocks, uint64_t lo, uint64_t n)
+{
+    static infl::Tables tab;
+    uint64_t first = 0, count = 0, comp_lo = 0, comp_n = 0;
+    infl::bgzf_window_members(blocks, lo, n, &first, &count);
+    std::vector<infl::BgzfBlock> sub;
+    infl::bgzf_rebase(blocks, first, count, sub, &comp_lo, &comp_n);
+    const std::vector<uint8_t> comp(f.begin() + comp_lo, f.begin() + comp_lo + comp_n); /* a copy: a read outside it is one outside an allocation */
+    std::vector<uint8_t> member(INFL_MAX_ISIZE), text;
+    const uint64_t hi = n > ~0ull - lo ? ~0ull : lo + n;
+    for (size_t k = 0; k < sub.size(); k++) {
+        const infl::BgzfBlock &b = sub[k];
+        if (const int e = infl::bgzf_member_host(comp.data(), b, member.data(), tab)) return refuse(first + k, infl::reason(e));
+        const uint64_t c0 = (lo > b.out_off ? lo : b.out_off) - b.out_off, end = b.out_off + b.isize, c1 = (hi < end ? hi : end) - b.out_off;
+        if (c1 > c0) text.insert(text.end(), member.begin() + c0, member.begin() + c1);
+    }
+    if (!text.empty() && fwrite(text.data(), 1, text.size(), stdout) != text.size()) return 2;
+    return 0;
+}
 } // namespace
 
 int main(int argc, char **argv)
 {
-    if (argc != 2) {
-        fprintf(stderr, "usage: inflate_check FILE.gz\n");
+    const bool window = argc == 5 && strcmp(argv[1], "--window") == 0;
+    char *e1 = nullptr, *e2 = nullptr;
+    const uint64_t win_lo = window ? strtoull(argv[2], &e1, 10) : 0, win_n = window ? strtoull(argv[3], &e2, 10) : 0;
+    if (!(argc == 2 || (window && *argv[2] && *argv[3] && !*e1 && !*e2))) {
+        fprintf(stderr, "usage: inflate_check [--window LO N] FILE.gz\n");
         return 2;
     }
-    FILE *fp = fopen(argv[1], "rb");
+    const char *path = argv[argc - 1];
+    FILE *fp = fopen(path, "rb");
     if (!fp) {
-        perror(argv[1]);
+        perror(path);
         return 2;
     }
     std::vector<uint8_t> f;
@@ -89,7 +98,12 @@ int main(int argc, char **argv)
     std::vector<uint8_t> text;
     uint64_t total = 0, bad = 0;
     int rc = 0;
-    if (const char *why = infl::bgzf_walk(f.data(), f.size(), blocks, &total, &bad)) {
+    const char *why = infl::bgzf_walk(f.data(), f.size(), blocks, &total, &bad);
+    if (window) {
+        if (why) return refuse(bad, why);
+        return write_window(f, blocks, win_lo, win_n);
+    }
+    if (why) {
         uint32_t hdr, bsize;
         /* a file that begins as BGZF and whose chain breaks later: once more as plain gzip members. Anything else is refused as it stands */
         if (infl::bgzf_header(f.data(), f.size(), 0, &hdr, &bsize)) return refuse(bad, why);
@@ -100,13 +114,7 @@ int main(int argc, char **argv)
         text.resize(total);
         for (size_t k = 0; k < blocks.size(); k++) {
             const infl::BgzfBlock &b = blocks[k];
-            ByteSink sink{text.data() + b.out_off};
-            uint32_t used = 0, made = 0;
-            int e = infl::inflate_raw(f.data() + b.in_off, b.in_len, b.isize, sink, tab, 0, 1, &used, &made);
-            if (!e && made != b.isize) e = infl::INFL_E_SHORT;
-            if (!e && used != b.in_len) e = infl::INFL_E_TRAIL;
-            if (!e && crc_by_chunks(text.data() + b.out_off, b.isize) != b.crc) e = infl::INFL_E_CRC;
-            if (e) return refuse(k, infl::reason(e));
+            if (const int e = infl::bgzf_member_host(f.data(), b, text.data() + b.out_off, tab)) return refuse(k, infl::reason(e));
         }
     }
     if (!text.empty() && fwrite(text.data(), 1, text.size(), stdout) != text.size()) return 2;

@@ -320,14 +320,20 @@ int disco_ingest_fetch(disco_ctx *ctx, uint16_t *len, uint64_t *file_index);
  * disco_dist_upload_reads leaves it in: disco_dist_run_graph(ctx, DISCO_DIST_GATHER_READS | ...) is next.
  * Every rank returns the same code: DISCO_E_UNSUPPORTED — each context stays usable, the caller runs its host stage and
  * disco_dist_upload_reads — when ANY rank met something the device stage does not take (what disco_ingest_fasta declines, and under a
- * communicator every .gz name, BGZF or not); disco_last_error names the file and the reason on every rank. A rank that fails (a file it
+ * communicator every .gz name, BGZF or not, unless DISCO_DIST_BGZF=1 — below); disco_last_error names the file and the reason on every rank. A rank that fails (a file it
  * cannot read, no memory, a HIP error) says so in the status word all ranks exchange and leaves with them: an error anywhere is an
- * error everywhere, and no rank waits inside a collective for one that left. files[n_files]: as disco_ingest_fasta fills them, on every rank. */
+ * error everywhere, and no rank waits inside a collective for one that left. files[n_files]: as disco_ingest_fasta fills them, on every rank.
+ * DISCO_DIST_BGZF=1 in a rank's environment (opt-in; a rank without it declines a .gz name, and with it everybody): a BGZF file counts
+ * with the bytes of its TEXT — every rank walks its member chain — so T, the shares, the pieces, the ids and the per-file figures are
+ * those of the same text in plain files, and plain and BGZF files mix freely. A rank's piece is decoded on its GPU from the members that
+ * hold it (one range of the file: only their compressed bytes are read), the first and the last of them clipped to the piece; every
+ * member of the file is decoded and CRC32-checked by at least one rank. Declines: plain gzip, a member chain that does not hold, a text
+ * that starts with neither '>' nor '@', a member the decoder or its CRC32 refuses (seen by the rank whose piece holds it, known to all). */
 typedef struct disco_dist_ingest_info {
     uint64_t n_reads, total_records, too_long; /* whole job, as disco_ingest_info */
     uint32_t stride_words, shortest, longest;  /* whole job */
     uint32_t world;
-    uint64_t share_lo, share_hi;               /* this rank's bytes of the files laid end to end */
+    uint64_t share_lo, share_hi;               /* this rank's bytes of the files laid end to end: TEXT bytes (a BGZF file counts with its text) */
     uint64_t share_reads;                      /* good reads whose record starts in this rank's bytes */
     uint64_t kept_reads;                       /* ... of which in its own home range (the others went to their owners) */
     uint64_t home_lo, home_hi;                 /* the rank's home range of read ids (disco_dist_range) */
@@ -429,6 +435,15 @@ int disco_fetch_chains(disco_ctx *ctx, disco_chain_edge *comp, disco_chain_link 
 
 /* device-to-device copy on the context's stream (staging for caller-side collectives) */
 int disco_memcpy_d2d(disco_ctx *ctx, void *dst, const void *src, uint64_t bytes);
+
+/* a window of a BGZF buffer's text, decoded on the device: the bytes [text_lo, text_lo + text_n) of the text — what of them the text has:
+ * min(text_n, total - text_lo) bytes go to `out`, and that count is returned; a window at or beyond the end of the text returns 0
+ * (out == NULL: the count only, nothing decoded). The member chain is walked whole; only the compressed bytes of the members that hold
+ * the window travel to the device and only those are decoded — each one whole and CRC32-checked, the first and the last one written
+ * from / up to the window's edge. Errors as disco_inflate_bgzf: DISCO_E_UNSUPPORTED when the buffer is not BGZF, or when a member OF THE
+ * WINDOW is corrupt — disco_last_error names it by its number in the file; a corrupt member outside the window is not looked at.
+ * (What a rank of disco_dist_ingest_fasta does with its piece of a BGZF file, on a buffer the caller holds.) */
+int64_t disco_inflate_bgzf_window(disco_ctx *ctx, const void *bgzf, uint64_t n_bytes, uint64_t text_lo, uint64_t text_n, void *out);
 
 #ifdef __cplusplus
 }

@@ -114,6 +114,9 @@ ABI = [
     ("disco_dist_ingest_fasta", C.c_int, [_P, C.POINTER(C.c_char_p), C.c_int, C.c_uint32, _P, _P]),
     ("disco_dist_ingest_fetch", C.c_int, [_P, _P, _P]),
     ("disco_inflate_bgzf_window", C.c_int64, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint64, _P]),
+    ("disco_format_contained", C.c_int64, [_P, C.c_uint32, _P, _P]),
+    ("disco_fetch_contained_text", C.c_int, [_P, _P, C.c_uint64]),
+    ("disco_write_contained_text", C.c_int, [_P, _P, C.c_uint32, C.c_uint32]),
 ]
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
@@ -404,6 +407,21 @@ class BuildGraph:
         """the text of the last format_edges straight from the device into open files: fds[f] receives file f (disco_write_edge_text)"""
         arr = (C.c_int * len(fds))(*fds)
         self._chk(self.L.disco_write_edge_text(self._h, arr, len(fds), threads))
+
+    def format_contained(self, n_files: int = 1, file_index=None):
+        """the lines of the contained-read files, grouped, sorted and formatted on the GPU (disco_format_contained): (text bytes,
+        offsets [n_files + 1]); file t = the containing reads s with s * n_files // n == t"""
+        off = np.zeros(n_files + 1, dtype=np.uint64)
+        fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
+        nb = self._chk(self.L.disco_format_contained(self._h, n_files, None if fi is None else fi.ctypes.data, off.ctypes.data))
+        buf = np.empty(max(nb, 1), dtype=np.uint8)
+        self._chk(self.L.disco_fetch_contained_text(self._h, buf.ctypes.data, nb))
+        return buf[:nb].tobytes(), off
+
+    def write_contained_text(self, fds, threads: int = 8):
+        """the text of the last format_contained straight from the device into open files: fds[f] receives file f (disco_write_contained_text)"""
+        arr = (C.c_int * len(fds))(*fds)
+        self._chk(self.L.disco_write_contained_text(self._h, arr, len(fds), threads))
 
     def start_contained_rows(self, grouped: bool = False):
         """the contained rows start their way to the host now (between mark_contained and the fetch)"""

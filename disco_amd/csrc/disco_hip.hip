@@ -289,6 +289,11 @@ struct disco_ctx {
     u64 ingest_n = 0;
     void *h_ring = nullptr; /* pinned: two halves of the text staging ring */
     std::vector<u64> text_off; /* disco_format_edges: byte range of every file inside d_text */
+    /* disco_format_contained: the lines of the contained-read files, their byte range per file — state of its own, so that either text
+     * may be formatted first */
+    DevBuf<char> d_ctext;
+    std::vector<u64> ctext_off;
+    u64 ctext_bytes = 0;
     DevBuf<u8> d_ingest; /* the input stage's own arena (text, record arrays) when the hit buffer is allocated NEXT to it ... */
     std::thread hits_prealloc; /* ... by this thread, while the files travel and the filter runs (settle_hits_prealloc) */
     DevBuf<u64> prealloc; /* (hipMalloc of that thread; settle_hits_prealloc adopts or frees it) */
@@ -761,6 +766,9 @@ static void free_graph_state(disco_ctx *c)
     release(c, c->d_ch_dead);
     release(c, c->d_text);
     c->text_bytes = 0;
+    release(c, c->d_ctext);
+    c->ctext_bytes = 0;
+    c->ctext_off.clear();
     c->ch_ready = false;
     release(c, c->d_out_pos);
     release(c, c->d_out_src);
@@ -4293,40 +4301,34 @@ int disco_fetch_edge_text(disco_ctx *c, char *out, uint64_t cap)
     return DISCO_OK;
 }
 
-/* the formatted edge lines straight into the caller's open files (fds[f] receives the bytes of file f, from its offset 0): the text
+/* formatted lines straight into the caller's open files (fds[f] receives the bytes of file f, from its offset 0): the text
  * leaves the device in 128 MB pieces through the context's pinned ring, and while a piece travels host threads pwrite the one before
  * it — the mirror image of disco_ingest_fasta's file reader. (disco_fetch_edge_text into 2.5 GB of fresh pageable memory, then the
- * writer: 0.19 s at config 3; this: the link's 0.05 s.) */
-int disco_write_edge_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t host_threads)
+ * writer: 0.19 s at config 3; this: the link's 0.05 s.) d_text: the files' text one behind the other, off: n_files + 1 offsets into it */
+static int write_text_through_ring(disco_ctx *c, const char *who, const char *d_text, const std::vector<u64> &off, const int *fds, uint32_t n_files)
 {
-    DISCO_TRACE("disco_write_edge_text");
-    if (!c || !fds) return DISCO_E_ARG;
-    if (c->text_off.size() != (size_t)n_files + 1) return fail(c, DISCO_E_STATE, "disco_write_edge_text: run disco_format_edges for %u files first", n_files);
-    HIPCHK(c, hipSetDevice(c->device));
-    const u64 n = c->text_bytes;
-    if (n == 0) return DISCO_OK;
     const size_t HALF = 128u << 20;
     CHK(ring_back_from_rows(c));
     if (!c->h_ring) {
         if (hipHostMalloc(&c->h_ring, 2 * HALF, ring_alloc_flags()) != hipSuccess) {
             c->h_ring = nullptr;
             (void)hipGetLastError();
-            return fail(c, DISCO_E_NOMEM, "disco_write_edge_text: no pinned staging memory");
+            return fail(c, DISCO_E_NOMEM, "%s: no pinned staging memory", who);
         }
         c->ring_half = HALF;
         for (int i = 0; i < 2; i++) HIPCHK(c, hipEventCreateWithFlags(&c->ev_ring[i], hipEventDisableTiming));
     }
-    (void)host_threads; /* one writer per file and round: writes to ONE file serialise on its inode lock (16 threads on one file: 12 GB/s;
-                           one thread on each of 16 files: the link's rate) */
+    /* one writer per file and round: writes to ONE file serialise on its inode lock (16 threads on one file: 12 GB/s; one thread on each
+     * of 16 files: the link's rate) */
     std::atomic<bool> ok{true};
     /* a round moves one slice of every file: slice r of file f = bytes [r S, (r + 1) S) of it, S = the ring half divided among the files */
     const size_t S = (HALF / n_files) & ~(size_t)4095;
-    if (S == 0) return fail(c, DISCO_E_UNSUPPORTED, "disco_write_edge_text: too many files for the staging ring");
+    if (S == 0) return fail(c, DISCO_E_UNSUPPORTED, "%s: too many files for the staging ring", who);
     u64 longest = 0;
-    for (uint32_t f = 0; f < n_files; f++) longest = std::max(longest, c->text_off[f + 1] - c->text_off[f]);
+    for (uint32_t f = 0; f < n_files; f++) longest = std::max(longest, off[f + 1] - off[f]);
     const u64 rounds = (longest + S - 1) / S;
     auto slice = [&](uint32_t f, u64 r, u64 &lo, size_t &len) { /* file-local byte range of the slice */
-        const u64 fl = c->text_off[f + 1] - c->text_off[f];
+        const u64 fl = off[f + 1] - off[f];
         lo = std::min<u64>(r * S, fl);
         len = (size_t)(std::min<u64>((r + 1) * S, fl) - lo);
     };
@@ -4357,15 +4359,146 @@ int disco_write_edge_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32
             u64 lo;
             size_t len;
             slice(f, r, lo, len);
-            if (len) HIPCHK(c, hipMemcpyAsync(half + (size_t)f * S, c->d_text + c->text_off[f] + lo, len, hipMemcpyDeviceToHost, c->stream));
+            if (len) HIPCHK(c, hipMemcpyAsync(half + (size_t)f * S, d_text + off[f] + lo, len, hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(c, hipEventRecord(c->ev_ring[r & 1], c->stream));
         if (r >= 1) drain(r - 1, (const char *)c->h_ring + ((r - 1) & 1) * HALF); /* (its copies were waited for below, one round ago) */
         HIPCHK(c, hipEventSynchronize(c->ev_ring[r & 1]));
     }
     if (rounds) drain(rounds - 1, (const char *)c->h_ring + ((rounds - 1) & 1) * HALF);
-    if (!ok.load()) return fail(c, DISCO_E_ARG, "disco_write_edge_text: write error");
+    if (!ok.load()) return fail(c, DISCO_E_ARG, "%s: write error", who);
     return DISCO_OK;
+}
+
+int disco_write_edge_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t host_threads)
+{
+    DISCO_TRACE("disco_write_edge_text");
+    if (!c || !fds) return DISCO_E_ARG;
+    if (c->text_off.size() != (size_t)n_files + 1) return fail(c, DISCO_E_STATE, "disco_write_edge_text: run disco_format_edges for %u files first", n_files);
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)host_threads;
+    if (c->text_bytes == 0) return DISCO_OK;
+    return write_text_through_ring(c, "disco_write_edge_text", c->d_text, c->text_off, fds, n_files);
+}
+
+/* ---- the lines of the contained-read files, grouped, sorted and formatted where the keys are (disco_text.h) ------------------ */
+int64_t disco_format_contained(disco_ctx *c, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets)
+{
+    DISCO_TRACE("disco_format_contained");
+    if (!c || !file_offsets || n_files == 0) return DISCO_E_ARG;
+    if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "disco_format_contained: a rank's rows are not grouped across ranks (the host writer formats)");
+    if (c->phase < 4) return fail(c, DISCO_E_STATE, "disco_format_contained: run disco_mark_contained first");
+    if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_format_contained: more than 2^31 reads");
+    HIPCHK(c, hipSetDevice(c->device));
+    const u64 nc = c->n_contained, n = c->n;
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
+    c->ctext_bytes = 0;
+    c->ctext_off.assign((size_t)n_files + 1, 0);
+    if (nc == 0) return 0;
+    CHK(settle_keys(c));
+    DevBuf<u32> cnt, gend, sup, list, ctr;
+    DevBuf<u64> word, place, d_findex, d_off;
+    DevBuf<u8> bytes;
+    u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
+    auto body = [&]() -> int {
+        /* 1. grouped by containing read */
+        CgrpLists L;
+        L.cap = (u32)(nc / (CROW_GROUP_MAX + 1) + 1); /* (a listed group has more than CROW_GROUP_MAX rows) */
+        CHK(ensure(c, cnt, n + 1));
+        CHK(ensure(c, gend, n + 1));
+        CHK(ensure(c, word, nc));
+        CHK(ensure(c, sup, nc));
+        CHK(ensure(c, list, 2 * (u64)L.cap));
+        CHK(ensure(c, ctr, CGRP_CTRS));
+        L.lds = list;
+        L.glb = list.p + L.cap;
+        L.ctr = ctr;
+        HIPCHK(c, hipMemsetAsync(cnt, 0, (n + 1) * sizeof(u32), c->stream));
+        HIPCHK(c, hipMemsetAsync(ctr, 0, CGRP_CTRS * sizeof(u32), c->stream));
+        hipLaunchKernelGGL(cgrp_count_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, (const u8 *)c->d_contained, n, cnt.p, ctr.p);
+        CHK((scan_exclusive<u32, u32>(c, cnt, n + 1, gend, false, nullptr)));
+        hipLaunchKernelGGL(cgrp_place_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, (const u8 *)c->d_contained, n, nc, gend.p, word.p, sup.p);
+        /* 2. every group in (j, contained read) order: by its size */
+        hipLaunchKernelGGL(cgrp_sort_small_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u32 *)gend, n, word.p, L);
+        const int big_grid = (int)std::min<u64>(L.cap, (u64)c->n_cu * 4);
+        hipLaunchKernelGGL(cgrp_sort_lds_kernel, dim3(big_grid), dim3(CGRP_BLOCK), 0, c->stream, (const u32 *)gend, word.p, L);
+        hipLaunchKernelGGL(cgrp_sort_global_kernel, dim3(big_grid), dim3(CGRP_BLOCK), 0, c->stream, (const u32 *)gend, word.p, L);
+        HIPCHK(c, hipGetLastError());
+        release(c, cnt);
+        /* 3. measure -> scan -> write */
+        CTextView g;
+        g.word = word;
+        g.sup = sup;
+        g.len = c->d_len;
+        g.nc = nc;
+        g.k = (u32)c->k;
+        if (file_index) {
+            CHK(ensure(c, d_findex, n));
+            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, n * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        g.file_index = d_findex;
+        CHK(ensure(c, bytes, nc));
+        CHK(ensure(c, place, nc + 1));
+        CHK(ensure(c, d_off, (u64)n_files + 1));
+        hipLaunchKernelGGL(ctext_measure_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, g, bytes.p);
+        u64 total = 0;
+        CHK((scan_exclusive<u8, u64>(c, bytes, nc, place, true, &total)));
+        hipLaunchKernelGGL(ctext_offsets_kernel, dim3(flat_grid(c, (u64)n_files + 1)), dim3(256), 0, c->stream, (const u32 *)gend, n, nc, (const u64 *)place, n_files, d_off.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->ctext_off.data(), d_off, ((size_t)n_files + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "disco_format_contained: %u contained reads have a key that names no containing read", h_ctr[CGRP_BAD_KEYS]);
+        CHK(ensure(c, c->d_ctext, std::max<u64>(total, 1)));
+        hipLaunchKernelGGL(ctext_write_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, g, (const u64 *)place, c->d_ctext.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->ctext_bytes = total;
+        return DISCO_OK;
+    };
+    const int rc = body();
+    release(c, cnt);
+    release(c, gend);
+    release(c, sup);
+    release(c, list);
+    release(c, ctr);
+    release(c, word);
+    release(c, place);
+    release(c, d_findex);
+    release(c, d_off);
+    release(c, bytes);
+    if (rc != DISCO_OK) {
+        c->ctext_off.assign((size_t)n_files + 1, 0);
+        return rc;
+    }
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = c->ctext_off[f];
+    if (getenv("DISCO_VERBOSE"))
+        fprintf(stderr, "[disco] contained lines: %llu rows, %llu bytes; groups of more than %d rows: %u sorted in LDS, %u through global memory, the largest of %u rows\n",
+                (unsigned long long)nc, (unsigned long long)c->ctext_bytes, CROW_GROUP_MAX, h_ctr[CGRP_N_LDS], h_ctr[CGRP_N_GLOBAL], h_ctr[CGRP_LARGEST]);
+    return (int64_t)c->ctext_bytes;
+}
+
+int disco_fetch_contained_text(disco_ctx *c, char *out, uint64_t cap)
+{
+    if (!c || (!out && c->ctext_bytes)) return DISCO_E_ARG;
+    if (cap < c->ctext_bytes) return fail(c, DISCO_E_ARG, "disco_fetch_contained_text: need room for %llu bytes", (unsigned long long)c->ctext_bytes);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->ctext_bytes) {
+        HIPCHK(c, hipMemcpyAsync(out, c->d_ctext, c->ctext_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return DISCO_OK;
+}
+
+int disco_write_contained_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t host_threads)
+{
+    DISCO_TRACE("disco_write_contained_text");
+    if (!c || !fds) return DISCO_E_ARG;
+    if (c->ctext_off.size() != (size_t)n_files + 1) return fail(c, DISCO_E_STATE, "disco_write_contained_text: run disco_format_contained for %u files first", n_files);
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)host_threads;
+    if (c->ctext_bytes == 0) return DISCO_OK;
+    return write_text_through_ring(c, "disco_write_contained_text", c->d_ctext, c->ctext_off, fds, n_files);
 }
 
 /* the contained rows of the current flags start their way to the host now, on a side stream (grouped: also in the order of the

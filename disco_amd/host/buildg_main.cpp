@@ -559,7 +559,7 @@ int main(int argc, char **argv)
     auto t1 = Clock::now();
     /* what the writer thread captures by reference comes FIRST: locals die in reverse order of declaration, so the holders below join
      * their threads before any of these goes away on an early return */
-    bool contained_early = false, contained_ok = true, edge_text_streamed = false;
+    bool contained_early = false, contained_ok = true, edge_text_streamed = false, contained_on_gpu = false;
     std::string contained_err;
     const disco::FileTags ctags_early = mpi_names ? disco::FileTags::mpi_contained(gpus, threads) : disco::FileTags::plain(threads);
     /* (threads declared before anything that may return early: their holders join on the way out) */
@@ -586,8 +586,11 @@ int main(int argc, char **argv)
         DISCO_CALL(ctx, disco_mark_contained(ctx, &n_cont));
         std::cout << "\n" << (rs.size() - n_cont) << " Non-contained reads. (Keep as is)\n"
                   << n_cont << " contained reads. (Need to change their mate-pair information)" << std::endl;
-        /* the contained rows leave now, grouped for their files, while the edges are selected and reduced */
-        if (n_cont && !getenv("DISCO_HOST_ROW_SORT") && !getenv("DISCO_LATE_ROWS")) (void)disco_start_contained_rows(ctx, 1);
+        /* the contained-read files from the GPU (disco_format_contained: rows grouped, sorted and formatted where the keys are, the lines
+         * through the pinned ring into the files) — or, where the rows are wanted on the host (binary side output, no text, DISCO_HOST_TEXT
+         * / DISCO_HOST_CONTAINED_TEXT=1), the rows leave now, grouped for their files, while the edges are selected and reduced */
+        bool gpu_contained = !no_text && !binary_out && !getenv("DISCO_HOST_TEXT") && !getenv("DISCO_HOST_CONTAINED_TEXT");
+        if (!gpu_contained && n_cont && !getenv("DISCO_HOST_ROW_SORT") && !getenv("DISCO_LATE_ROWS")) (void)disco_start_contained_rows(ctx, 1);
         DISCO_CALL(ctx, disco_build_edges(ctx, &e_pre));
         DISCO_CALL(ctx, disco_transitive_reduce(ctx, &e_out));
         t_graph = secs(t0);
@@ -607,8 +610,32 @@ int main(int argc, char **argv)
         t1 = Clock::now();
         if (!join_ingest_fetch()) return die(disco_last_error(ctx));
         lap("wait for lengths + file indices");
-        rows.resize(n_cont);
-        if (n_cont) { /* in the files' order where the device grouped them during the pass; by id (sorted by the writer) otherwise */
+        if (gpu_contained) {
+            /* right behind the reduction: the ring is free, and nothing of the rows crosses to the host */
+            const int ncf = (int)ctags_early.tag.size();
+            const bool identity = rs.total_records == rs.size(); /* no record was filtered: file index = read id + 1 */
+            std::vector<uint64_t> coff((size_t)ncf + 1, 0);
+            const int64_t nb = disco_format_contained(ctx, (uint32_t)ncf, identity ? nullptr : rs.file_index.data(), coff.data());
+            if (nb == DISCO_E_NOMEM || nb == DISCO_E_UNSUPPORTED) {
+                if (verbose) fprintf(stderr, "[disco host] contained lines by the host writer: %s\n", disco_last_error(ctx));
+                gpu_contained = false;
+            } else if (nb < 0)
+                return die(disco_last_error(ctx));
+            else {
+                lap("format contained lines on the GPU");
+                std::vector<int> fds((size_t)ncf, -1);
+                std::string ferr;
+                if (!disco::open_contained_files(prefix, ncf, &ctags_early, fds.data(), ferr)) return die(ferr);
+                const int wrc = disco_write_contained_text(ctx, fds.data(), (uint32_t)ncf, (uint32_t)threads);
+                for (int fd : fds)
+                    if (fd >= 0) close(fd);
+                if (wrc < 0) return die(disco_last_error(ctx));
+                lap("contained lines into the files");
+            }
+            contained_on_gpu = gpu_contained;
+        }
+        if (!gpu_contained) rows.resize(n_cont);
+        if (n_cont && !gpu_contained) { /* in the files' order where the device grouped them during the pass; by id (sorted by the writer) otherwise */
             const int64_t grc = getenv("DISCO_HOST_ROW_SORT") ? (int64_t)DISCO_E_UNSUPPORTED : disco_fetch_contained_grouped(ctx, rows.data(), n_cont);
             rows_grouped = grc >= 0;
             if (grc < 0 && grc != DISCO_E_UNSUPPORTED) return die(disco_last_error(ctx));
@@ -617,7 +644,7 @@ int main(int argc, char **argv)
         lap("fetch contained rows");
         /* the contained-read files are written by a thread of their own while the device partitions and formats the edges (their rows
          * have been final since the contained flags were fixed); joined before the checkpoint is written */
-        if (!no_text && !binary_out) {
+        if (!no_text && !binary_out && !gpu_contained) {
             contained_early = true;
             contained_writer = std::thread([&]() {
                 std::string e2;
@@ -822,7 +849,8 @@ int main(int argc, char **argv)
         rows.clear();
         e_out = 0;
     }
-    if (contained_early) {
+    if (contained_on_gpu) { /* written while the text left the device */
+    } else if (contained_early) {
         contained_writer.join();
         if (!contained_ok) return die(contained_err);
     } else if (!disco::write_contained(prefix, (int)ctags.tag.size(), rows, rs, err, &ctags, rows_grouped))

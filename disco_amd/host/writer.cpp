@@ -414,6 +414,21 @@ bool open_edge_files(const std::string &prefix, int n_files, const FileTags *tag
     return true;
 }
 
+/* the contained-read files, created empty and handed back open (disco_write_contained_text fills them) */
+bool open_contained_files(const std::string &prefix, int n_files, const FileTags *tags, int *fds, std::string &err)
+{
+    for (int t = 0; t < n_files; t++) {
+        const std::string path = prefix + "_" + tag_of(tags, t) + "_containedReads.txt";
+        fds[t] = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fds[t] < 0) {
+            err = "Unable to write file: " + path;
+            for (int x = 0; x < t; x++) close(fds[x]);
+            return false;
+        }
+    }
+    return true;
+}
+
 namespace {
 struct BinHeader {
     char magic[8];

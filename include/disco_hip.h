@@ -445,6 +445,20 @@ int disco_memcpy_d2d(disco_ctx *ctx, void *dst, const void *src, uint64_t bytes)
  * (What a rank of disco_dist_ingest_fasta does with its piece of a BGZF file, on a buffer the caller holds.) */
 int64_t disco_inflate_bgzf_window(disco_ctx *ctx, const void *bgzf, uint64_t n_bytes, uint64_t text_lo, uint64_t text_n, void *out);
 
+/* ---- the lines of the contained-read files, formatted on the GPU ------------------------------------------------------------------ */
+/* the lines of <prefix>_<t>_containedReads.txt (BG/OverlapGraph.cpp:438-447; disco_amd/host/writer.cpp write_contained) formatted on the GPU:
+ * "contained \t super \t orient,len2,0,0,len2,0,len2,len1,start,start+len2" for every contained read, in ascending (containing read, j,
+ * contained read) — the rows are grouped and sorted on the device, whatever the size of a group, and never reach the host. file_index
+ * as for disco_format_edges (null: read id + 1). File t holds the containing reads s with floor(s * n_files / n) == t, n =
+ * disco_num_reads: its text is bytes [file_offsets[t], file_offsets[t + 1]) of what disco_fetch_contained_text copies out (empty
+ * files have equal offsets; any number of files). Returns the total number of bytes, 0 with all offsets 0 when nothing is contained.
+ * Callable from disco_mark_contained on, before or after disco_format_edges: the two texts are kept apart. DISCO_E_UNSUPPORTED on a
+ * context with a communicator, DISCO_E_STATE before disco_mark_contained, DISCO_E_NOMEM when the text does not fit. */
+int64_t disco_format_contained(disco_ctx *ctx, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets);
+int     disco_fetch_contained_text(disco_ctx *ctx, char *out, uint64_t cap);
+/* ... or straight into the caller's open files, through the pinned ring as disco_write_edge_text */
+int     disco_write_contained_text(disco_ctx *ctx, const int *fds, uint32_t n_files, uint32_t host_threads);
+
 #ifdef __cplusplus
 }
 #endif

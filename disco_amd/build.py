@@ -111,6 +111,14 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+    # the self-delimiting survivor lists of the marking on the host: the header the kernels include, as plain C++
+    sv = os.path.join(HERE, "bin", "survivor_check")
+    ssrc = [os.path.join(HERE, "host", "survivor_check.cpp"), os.path.join(HERE, "csrc", "disco_survivor.h")]
+    if force or _stale(sv, ssrc):
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", sv, ssrc[0]]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
     return BUILDG
 
 

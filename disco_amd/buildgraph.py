@@ -161,6 +161,7 @@ PHASES = ("index", "probe_kernel", "verify", "contain", "select", "csr", "twin",
 # include/disco_hip_inspect.h: looks at intermediate state for tests; bound on first use, not by load()
 INSPECT_ABI = [
     ("disco_fetch_order", C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    ("disco_fetch_survivor_layout", C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
 ]
 _inspect_bound = False
 
@@ -497,6 +498,20 @@ class BuildGraph:
         order, keys = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros(max(n.value, 1), dtype=np.uint32)
         self._chk(self.L.disco_fetch_order(self._h, order.ctypes.data, keys.ctypes.data, len(order), C.byref(n), C.byref(bits)))
         return order[:n.value], keys[:n.value], bits.value
+
+    def fetch_survivor_layout(self, lengths: bool = True):
+        """(list lengths or None, dense, out_used) of the last transitive_reduce: the decoded length of every node's self-delimiting
+        survivor list (0..4, 5 = wide, 255 = no row this pass), whether the emission wrote its edges back to back, and the slots it wrote.
+        lengths=False where the marking kept counts instead (DISCO_NO_HALF, sharded flows). Tests only"""
+        _bind_inspect(self.L)
+        n, dense, used = C.c_uint64(0), C.c_int(0), C.c_uint64(0)
+        self._chk(self.L.disco_fetch_survivor_layout(self._h, None, 0, C.byref(n), C.byref(dense), C.byref(used)))
+        lens = None
+        if lengths:
+            lens = np.zeros(max(n.value, 1), dtype=np.uint8)
+            self._chk(self.L.disco_fetch_survivor_layout(self._h, lens.ctypes.data, len(lens), C.byref(n), C.byref(dense), C.byref(used)))
+            lens = lens[:n.value]
+        return lens, bool(dense.value), used.value
 
     def measure_hbm(self, nbytes: int = 4 << 30, reps: int = 5) -> float:
         """attainable HBM bandwidth in GB/s (read + write bytes of a streaming copy kernel)"""

@@ -32,7 +32,7 @@ struct ChainView {
 
 __device__ __forceinline__ bool ch_kept(const ChainView &g, u64 s)
 {
-    if (!g.valid[s]) return false;
+    if (g.valid && !g.valid[s]) return false;
     return (u32)g.len[g.src[s]] - ADJ_OFF(g.ent[s]) >= g.min_ovl;
 }
 __device__ __forceinline__ u32 ch_src(const ChainView &g, u32 h) { return (h & 1) ? (u32)ADJ_DST(g.ent[h >> 1]) : (u32)g.src[h >> 1]; }
@@ -128,7 +128,7 @@ __global__ void ch_jump_kernel(const ChRank *__restrict__ old, ChRank *__restric
 
 /* which direction of the chain a slot lies in builds the composite edge: the one whose FIRST half-edge is the smaller of the chain's
  * two end half-edges, numbered by the edge's rank in fetch order — the rule of the host pass, whose edges are in that order */
-__device__ __forceinline__ u64 ch_rankid(const ChainView &g, u32 h) { return 2 * g.pos[h >> 1] + (h & 1u); }
+__device__ __forceinline__ u64 ch_rankid(const ChainView &g, u32 h) { return 2 * (g.pos ? g.pos[h >> 1] : (u64)(h >> 1)) + (h & 1u); }
 
 struct ChSlot { /* what a slot of a chain knows after the ranking */
     u32 head;  /* first half-edge of the chain in the building direction */
@@ -165,7 +165,7 @@ __global__ void ch_heads_kernel(ChainView g, const u8 *__restrict__ internal, co
         const bool head = c.in_chain && c.index == 0;
         is_head[s] = head ? 1 : 0;
         links_of[s] = head ? r[c.head].cnt : 0u;
-        if (c.in_chain) dead[g.pos[s]] = 1;
+        if (c.in_chain) dead[g.pos ? g.pos[s] : s] = 1;
     }
 }
 

@@ -16,6 +16,8 @@ typedef unsigned int u32;
 typedef unsigned short u16;
 typedef unsigned char u8;
 
+#include "disco_survivor.h" /* the self-delimiting survivor lists of the marking (host and device) */
+
 #define DISCO_WAVE 64
 /* 'not contained': largest value that is also positive as int64, so that a signed all-reduce(MIN) orders keys correctly */
 #define DISCO_NOKEY 0x7FFFFFFFFFFFFFFFull

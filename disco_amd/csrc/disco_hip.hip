@@ -335,6 +335,7 @@ struct disco_ctx {
     bool adj_imported = false;
     u64 adj_span = 0;          /* size of the position space of d_adj in the sharded flow (compact: adj_total, padded: world*max) */
     bool half_complete = false; /* half/hcnt hold the survivor lists of ALL nodes */
+    bool half_selfdel = false;  /* the lists carry their own end (disco_survivor.h) and hcnt was not written: the whole-table pass of one GPU */
     DevBuf<u32> d_extra_cnt;
     DevBuf<u64> d_extra_node, d_extra_key; /* (grow together) */
     u32 *d_n_extra = nullptr;
@@ -363,6 +364,7 @@ struct disco_ctx {
     u64 text_bytes = 0;
     DevBuf<u64> d_out_src, d_out_ent; /* (grow together) */
     u64 out_used = 0; /* chunk slots written by the emission (survivors + ~0 tails) */
+    bool out_dense = false; /* the last emission wrote no tails: slot i is edge i, out_used == n_out, d_out_valid / d_out_pos are not there */
     u64 n_out = 0;
 
     /* live kernel timing (HIP events on the stream the kernels are launched on) */
@@ -1471,8 +1473,8 @@ static TrFn tr_pick(bool big, bool defer, bool small, bool lists)
 }
 
 /* the fields of TrArgs both marking drivers fill alike, after the big-node list has its size; c->use_half: the survivor lists and the
- * list of wide nodes, cleared (order and all_flags are the caller's) */
-static int tr_args_begin(disco_ctx *c, TrArgs *a)
+ * list of wide nodes, cleared (order and all_flags are the caller's); selfdel: the lists carry their own end, no count is kept */
+static int tr_args_begin(disco_ctx *c, TrArgs *a, bool selfdel = false)
 {
     a->v = view(c);
     a->ref = c->d_adj_ref;
@@ -1486,14 +1488,17 @@ static int tr_args_begin(disco_ctx *c, TrArgs *a)
     a->hcnt = nullptr;
     if (c->use_half) {
         CHK(ensure(c, c->d_half, c->n * HALF_CAP));
-        CHK(ensure(c, c->d_hcnt, c->n));
-        HIPCHK(c, hipMemsetAsync(c->d_hcnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
+        if (!selfdel) { /* (self-delimiting lists: no count — neither the 4 bytes per node nor their clearing every pass) */
+            CHK(ensure(c, c->d_hcnt, c->n));
+            HIPCHK(c, hipMemsetAsync(c->d_hcnt, 0, std::max<u64>(c->n, 1) * sizeof(u32), c->stream));
+        }
         CHK(ensure(c, c->d_wide, std::min<u64>(c->n, c->n / 32 + 4096)));
         CHK(ensure(c, c->d_n_wide, 1));
         HIPCHK(c, hipMemsetAsync(c->d_n_wide, 0, sizeof(u32), c->stream));
         a->half = c->d_half;
-        a->hcnt = c->d_hcnt;
+        a->hcnt = selfdel ? nullptr : (u32 *)c->d_hcnt;
     }
+    c->half_selfdel = c->use_half && selfdel;
     a->wide_list = c->d_wide;
     a->n_wide = c->d_n_wide;
     a->wide_cap = c->d_wide.cap;
@@ -3711,13 +3716,14 @@ int disco_transitive_mark(disco_ctx *c)
     } else
         CHK(ensure_big_cap(c, nullptr, c->d_adj_ref, TR_CAP));
     c->use_half = !getenv("DISCO_NO_HALF");
-    TrArgs a;
-    CHK(tr_args_begin(c, &a));
-    a.order = (c->d_order_used && c->order_q_lo == c->q_lo && c->order_q_hi == c->q_hi && !c->adj_imported && !getenv("DISCO_TR_NO_ORDER")) ? c->d_order_used : nullptr;
     /* every row needs its flags when the emission cannot rely on the survivor lists alone */
-    a.all_flags = (c->adj_imported || !c->use_half || c->q_lo != 0 || c->q_hi != c->n) ? 1u : 0u;
+    const u32 all_flags = (c->adj_imported || !c->use_half || c->q_lo != 0 || c->q_hi != c->n) ? 1u : 0u;
+    const bool lists = c->use_half && !all_flags; /* the survivor lists are the result: self-delimiting, and the variant compiled for it */
+    TrArgs a;
+    CHK(tr_args_begin(c, &a, lists));
+    a.order = (c->d_order_used && c->order_q_lo == c->q_lo && c->order_q_hi == c->q_hi && !c->adj_imported && !getenv("DISCO_TR_NO_ORDER")) ? c->d_order_used : nullptr;
+    a.all_flags = all_flags;
     ph_begin(c, DISCO_PH_TRMARK);
-    const bool lists = a.half && a.hcnt && !a.all_flags; /* the survivor lists are the result: the variant compiled for it */
     if (nq) wq_launch(c, tr_pick(false, false, tr_small, lists), nq, "DISCO_TR_WAVES", 32, a);
     ph_end(c, DISCO_PH_TRMARK);
     HIPCHK(c, hipGetLastError());
@@ -3747,7 +3753,7 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
     HIPCHK(c, hipSetDevice(c->device));
     const u64 nq = c->q_hi - c->q_lo;
     ph_begin(c, DISCO_PH_EMIT);
-    const int grid = wq_grid(c, emit_kernel, nq, "DISCO_EMIT_WAVES");
+    const int grid = wq_grid(c, emit_kernel<false>, nq, "DISCO_EMIT_WAVES"); /* (the dense instantiation over the few wide nodes takes it too: 4 KB of LDS more) */
     const u64 n_push = c->dist_active ? c->n_push_r : 0; /* multi-GPU flow: survivors pushed by the owners of the larger endpoints */
     const int grid_push = (int)std::max<u64>(std::min<u64>((n_push + 63) / 64, (u64)c->n_cu * 16), 1);
     const u64 nwaves = (u64)grid * 2 + (n_push ? (u64)grid_push : 0); /* emit_half_kernel + emit_kernel (+ emit_push_recv_kernel) */
@@ -3756,13 +3762,17 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
         CHK(ensure_group(c, want, want, c->d_out_src, c->d_out_ent));
         HIPCHK(c, hipMemsetAsync(c->d_bump, 0, sizeof(u64), c->stream));
         const bool half_emit = c->use_half && c->half_complete; /* else: rows + flags of every node (sharded fallback) */
+        /* self-delimiting lists (the whole-table pass of one GPU): both emitters append exact counts — no tails, nothing to compact */
+        const bool dense = half_emit && c->half_selfdel && !c->dist_active;
+        if (half_emit && c->half_selfdel && !dense) return fail(c, DISCO_E_STATE, "disco_emit_edges: self-delimiting lists under a communicator");
+        c->out_dense = dense;
         if (half_emit && nq) {
             EmitHalfArgs h;
             h.v = view(c);
             h.ref = c->d_adj_ref;
             h.adj = c->d_adj;
             h.half = c->d_half;
-            h.hcnt = c->d_hcnt;
+            h.hcnt = dense ? nullptr : (const u32 *)c->d_hcnt;
             h.out_src = c->d_out_src;
             h.out_ent = c->d_out_ent;
             h.out_cap = c->d_out_src.cap;
@@ -3770,14 +3780,19 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
             h.local_only = c->dist_active ? 1u : 0u;
             h.own = own_set(c);
             h.order = nullptr; /* (tried for one GPU, round 5: the nodes in processing order — 5.3 instead of 3.4 ms: the node's own entries become the random fetches) */
-            const int gh = wq_grid(c, emit_half_kernel, (nq + 63) / 64, "DISCO_EMIT_WAVES");
-            hipLaunchKernelGGL(emit_half_kernel, dim3(gh), dim3(64), 0, c->stream, h);
+            if (dense) {
+                const int gh = wq_grid(c, emit_half_lists_kernel, (nq + 63) / 64, "DISCO_EMIT_WAVES");
+                hipLaunchKernelGGL(emit_half_lists_kernel, dim3(gh), dim3(64), 0, c->stream, h);
+            } else {
+                const int gh = wq_grid(c, emit_half_kernel, (nq + 63) / 64, "DISCO_EMIT_WAVES");
+                hipLaunchKernelGGL(emit_half_kernel, dim3(gh), dim3(64), 0, c->stream, h);
+            }
         }
         EmitArgs a;
         a.v = view(c);
         a.ref = c->d_adj_ref;
         a.adj = c->d_adj;
-        a.hcnt = half_emit ? c->d_hcnt : nullptr;
+        a.hcnt = half_emit && !dense ? (const u32 *)c->d_hcnt : nullptr;
         a.half = half_emit ? c->d_half : nullptr;
         const bool listed = half_emit && c->n_wide <= c->d_wide.cap; /* else the list overflowed: scan the whole range */
         a.list = listed ? c->d_wide : nullptr;
@@ -3789,7 +3804,10 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
         a.local_only = c->dist_active ? 1u : 0u;
         a.own = own_set(c);
         HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
-        if (nq && !(listed && c->n_wide == 0)) hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(64), 0, c->stream, a);
+        if (nq && !(listed && c->n_wide == 0)) {
+            if (dense) hipLaunchKernelGGL(emit_kernel<true>, dim3(grid), dim3(64), 0, c->stream, a);
+            else hipLaunchKernelGGL(emit_kernel<false>, dim3(grid), dim3(64), 0, c->stream, a);
+        }
         if (n_push) {
             EmitRecvArgs pr;
             pr.items = c->d_push_r;
@@ -3819,7 +3837,11 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
     }
     /* survivors = chunk slots that are not the ~0 tail marker: count them (the compaction happens at fetch time) */
     u64 total = 0;
-    if (c->out_used) {
+    if (c->out_dense) { /* the bump pointer is the number of edges; the consumers take null valid / pos as "slot i is edge i" */
+        total = c->out_used;
+        release(c, c->d_out_valid);
+        release(c, c->d_out_pos);
+    } else if (c->out_used) {
         if (c->out_used > c->d_out_valid.cap || c->out_used + 1 > c->d_out_pos.cap) { /* (grown together; sized by the output buffer) */
             release(c, c->d_out_valid);
             release(c, c->d_out_pos);
@@ -3998,6 +4020,10 @@ int64_t disco_fetch_contained_grouped(disco_ctx *c, disco_contained_row *out, ui
     return (int64_t)nc;
 }
 
+/* the slot -> edge mapping of the last emission; null: dense (slot i is edge i) */
+static const u8 *out_valid(const disco_ctx *c) { return c->out_dense ? nullptr : (const u8 *)c->d_out_valid.p; }
+static const u64 *out_pos(const disco_ctx *c) { return c->out_dense ? nullptr : (const u64 *)c->d_out_pos.p; }
+
 int64_t disco_fetch_edges(disco_ctx *c, disco_edge *out, uint64_t cap)
 {
     DISCO_TRACE("disco_fetch_edges");
@@ -4012,10 +4038,14 @@ int64_t disco_fetch_edges(disco_ctx *c, disco_edge *out, uint64_t cap)
     /* drop the unused chunk tails of the emission (into buffers the context keeps: two allocations of 0.4 GB per call cost more than the
      * copy), then copy out 12 bytes per edge — source as 32 bits, packed entry — chunk k into pinned staging memory (kept by the context)
      * while the host threads turn chunk k - 1 into disco_edge records; a copy into pageable memory ran at a third of the link's rate */
-    CHK(ensure_group(c, ne, ne + ne / 8 + 1024, c->d_fetch_src, c->d_fetch_ent));
+    /* (a dense emission has no tails to drop: the entries go out from where the emission put them, and only the sources are narrowed to
+     * 32 bits for the link — no compaction kernel, no second buffer of entries) */
+    if (c->out_dense) CHK(ensure(c, c->d_fetch_src, ne + ne / 8 + 1024));
+    else CHK(ensure_group(c, ne, ne + ne / 8 + 1024, c->d_fetch_src, c->d_fetch_ent));
     u32 *csrc = c->d_fetch_src;
-    u64 *cent = c->d_fetch_ent;
-    hipLaunchKernelGGL(emit_compact32_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos, c->out_used, csrc, cent);
+    const u64 *cent = c->out_dense ? (const u64 *)c->d_out_ent : (const u64 *)c->d_fetch_ent;
+    if (c->out_dense) hipLaunchKernelGGL(emit_src32_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, c->d_out_src, ne, csrc);
+    else hipLaunchKernelGGL(emit_compact32_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos, c->out_used, csrc, c->d_fetch_ent.p);
     const u64 CHUNK = 1ull << 22; /* 4 M edges: 48 MB per half */
     if (!c->h_stage) {
         if (hipHostMalloc((void **)&c->h_stage, 4 * CHUNK * sizeof(u64)) != hipSuccess) c->h_stage = nullptr;
@@ -4083,7 +4113,7 @@ int64_t disco_fetch_edge_substitutions(disco_ctx *c, uint16_t *out, uint64_t cap
     }
     DevBuf<u16> subs;
     CHK(ensure(c, subs, ne));
-    hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos,
+    hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c),
                        c->out_used, c->d_reads, c->d_len, c->S, subs);
     hipError_t e1 = hipMemcpyAsync(out, subs, ne * sizeof(u16), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);
@@ -4179,7 +4209,7 @@ int64_t disco_fetch_edge_files(disco_ctx *c, uint32_t n_files, uint16_t *out, ui
     const u64 ne = c->n_out;
     if (cap < ne) return fail(c, DISCO_E_ARG, "disco_fetch_edge_files: need room for %llu edges", (unsigned long long)ne);
     if (ne == 0) return 0;
-    return partition_edges(c, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos, c->out_used, ne, c->n, n_files, out);
+    return partition_edges(c, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c), c->out_used, ne, c->n, n_files, out);
 }
 
 /* the same partition for edges held by the HOST (buildG --gpus N: the edges of all ranks, concatenated): src / dst are read ids
@@ -4240,8 +4270,8 @@ int64_t disco_format_edges(disco_ctx *c, uint32_t n_files, const uint16_t *edge_
     TextView g;
     g.src = c->d_out_src;
     g.ent = c->d_out_ent;
-    g.valid = c->d_out_valid;
-    g.pos = c->d_out_pos;
+    g.valid = out_valid(c);
+    g.pos = out_pos(c);
     g.len = c->d_len;
     g.n_slots = c->out_used;
     DevBuf<u64> d_findex, within, place;
@@ -4606,7 +4636,7 @@ int disco_contract_chains(disco_ctx *c, uint32_t min_overlap_simplify, uint64_t 
         c->ch_comp_n = c->ch_links_n = c->ch_edges_n = 0;
         c->ch_ready = true;
     } else
-        CHK(contract_chains(c, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos, c->out_used, c->n_out, c->n, min_overlap_simplify));
+        CHK(contract_chains(c, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c), c->out_used, c->n_out, c->n, min_overlap_simplify));
     if (n_composite) *n_composite = c->ch_comp_n;
     if (n_links) *n_links = c->ch_links_n;
     return DISCO_OK;
@@ -5835,6 +5865,27 @@ int disco_fetch_order(disco_ctx *c, uint64_t *order_words, uint32_t *keys, uint6
     HIPCHK(c, hipMemcpyAsync(order_words, c->d_order_own, c->n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(keys, c->d_okey, c->n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DISCO_OK;
+}
+int disco_fetch_survivor_layout(disco_ctx *c, uint8_t *list_len, uint64_t cap, uint64_t *n, int *dense, uint64_t *out_used)
+{
+    if (!c || !n || !dense || !out_used) return DISCO_E_ARG;
+    if (c->phase < 8) return fail(c, DISCO_E_STATE, "disco_fetch_survivor_layout: run disco_transitive_reduce first");
+    *n = c->n;
+    *dense = c->out_dense ? 1 : 0;
+    *out_used = c->out_used;
+    if (!list_len) return DISCO_OK;
+    if (cap < c->n) return fail(c, DISCO_E_ARG, "disco_fetch_survivor_layout: room for %llu nodes, %llu needed", (unsigned long long)cap, (unsigned long long)c->n);
+    if (!c->half_selfdel || !c->d_half) return fail(c, DISCO_E_STATE, "disco_fetch_survivor_layout: the last marking kept counts, not self-delimiting lists");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<u64> half(c->n * HALF_CAP), ref(c->n);
+    if (c->n) {
+        HIPCHK(c, hipMemcpyAsync(half.data(), c->d_half, c->n * HALF_CAP * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ref.data(), c->d_adj_ref, c->n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    for (u64 v = 0; v < c->n; v++) /* (a node without a row has no list this pass: whatever an earlier pass left) */
+        list_len[v] = REF_DEG(ref[v]) ? (uint8_t)surv_len(half[4 * v], half[4 * v + 1], half[4 * v + 2], half[4 * v + 3]) : 0xFFu;
     return DISCO_OK;
 }
 int disco_comm_rank(const disco_ctx *c) { return (c && c->comm) ? c->comm->rank : 0; }

@@ -4299,12 +4299,14 @@ __global__ void __launch_bounds__(64) merge_rows_kernel(const u64 *__restrict__ 
  * the other node's business and is combined at emission.
  * ============================================================================================================== */
 #define HALF_CAP 4 /* edges of a node that survive its own marking, kept aside for the emission (almost always 2) */
+static_assert(HALF_CAP == SURV_CAP, "disco_survivor.h decodes lists of HALF_CAP slots");
 struct TrArgs {
     DiscoView v;
     const u64 *ref;
     u64 *adj;      /* only the flag bit of the node's own row is written */
     u64 *half;     /* [n][HALF_CAP] entries not flagged from this node (first HALF_CAP in list order), or null */
-    u32 *hcnt;     /* [n] how many there are (may exceed HALF_CAP: the emission then reads the row) */
+    u32 *hcnt;     /* [n] how many there are (may exceed HALF_CAP: the emission then reads the row); null with half: the lists carry
+                      their own end (disco_survivor.h) — the whole-table pass of one GPU */
     u64 *wide_list; /* nodes with more than HALF_CAP survivors */
     u32 *n_wide;
     u32 wide_cap;
@@ -4408,6 +4410,12 @@ __device__ __forceinline__ void tr_node(const TrArgs &a, u64 v, u32 d, u64 *hkey
             __syncthreads();
         }
     }
+    /* self-delimiting lists (half without hcnt): the last survivor carries the mark, so their number is needed before the first is
+     * stored — one more pass over the states, in LDS (this path sees a node in a thousand) */
+    const bool selfdel = a.half && !a.hcnt;
+    u32 ntotal = 0;
+    if (selfdel)
+        for (u32 s0 = 0; s0 < d; s0 += 64) ntotal += __popcll(__ballot((s0 + lane < d) && !hstate[sent[s0 + lane]]));
     u32 nfree = 0;
     for (u32 s0 = 0; s0 < d; s0 += 64) {
         const u32 s = s0 + lane;
@@ -4417,12 +4425,13 @@ __device__ __forceinline__ void tr_node(const TrArgs &a, u64 v, u32 d, u64 *hkey
         const u64 mk = __ballot(fr);
         if (a.half && fr) {
             const u32 r = nfree + rank_below(mk);
-            if (r < HALF_CAP) a.half[v * HALF_CAP + r] = row[s] & ~ADJ_FLAG;
+            if (r < HALF_CAP) a.half[v * HALF_CAP + r] = selfdel ? surv_encode(row[s] & ~ADJ_FLAG, r, ntotal) : (row[s] & ~ADJ_FLAG);
         }
         nfree += __popcll(mk);
     }
-    if (a.hcnt && lane == 0) {
-        a.hcnt[v] = nfree;
+    if (a.half && lane == 0) {
+        if (a.hcnt) a.hcnt[v] = nfree;
+        else if (nfree == 0) a.half[v * HALF_CAP] = SURV_NONE;
         if (nfree > HALF_CAP) {
             const u32 idx = atomicAdd(a.n_wide, 1u);
             if (idx < a.wide_cap) a.wide_list[idx] = v;
@@ -4580,12 +4589,26 @@ __device__ __forceinline__ void tr_node_small(const TrArgs &a, const TrNodeRegs 
     const bool fr = keep & (lane < d) & !fl;
     const u64 mk = __ballot(fr);
     if (fl && ((!LISTS && (a.all_flags || !a.half)) || __popcll(mk) > HALF_CAP)) a.adj[nd.vs + lane] = e | ADJ_FLAG;
+    /* LISTS on one GPU: the lists carry their own end (disco_survivor.h) — the lane of the last survivor sets the mark in the value it stores
+     * anyway, and nothing else is written per node: the count of round 5 (hcnt[v], a lane-0 store under an exec-mask branch into a
+     * second random table) is gone. What is left under a branch is wave uniform and rare: a node without a survivor stores the
+     * sentinel, a node with more than HALF_CAP of them goes on the list of wide nodes */
+    const u32 nfree = __popcll(mk);
+    /* (the multi-rank kernel keeps the count whatever LISTS says: its emission, the survivor push and its receiver read it) */
+    const bool selfdel = DEFER ? false : (LISTS || (a.half && !a.hcnt));
     if ((LISTS || a.half) && fr) {
         const u32 r = rank_below(mk);
-        if (r < HALF_CAP) a.half[(u64)nd.v * HALF_CAP + r] = e;
+        if (r < HALF_CAP) a.half[(u64)nd.v * HALF_CAP + r] = selfdel ? surv_encode(e, r, nfree) : e;
     }
-    if ((LISTS || a.hcnt) && lane == 0 && keep) {
-        const u32 nfree = __popcll(mk);
+    if (selfdel) {
+        if (nfree - 1u >= (u32)HALF_CAP && lane == 0 && keep) { /* (none, or more than HALF_CAP) */
+            if (nfree == 0) a.half[(u64)nd.v * HALF_CAP] = SURV_NONE;
+            else {
+                const u32 idx = atomicAdd(a.n_wide, 1u);
+                if (idx < a.wide_cap) a.wide_list[idx] = nd.v;
+            }
+        }
+    } else if ((LISTS || a.hcnt) && lane == 0 && keep) {
         a.hcnt[nd.v] = nfree;
         if (nfree > HALF_CAP) {
             const u32 idx = atomicAdd(a.n_wide, 1u);
@@ -4739,7 +4762,8 @@ struct EmitArgs {
     DiscoView v;
     const u64 *ref;
     const u64 *adj;
-    const u32 *hcnt; /* non-null: only nodes with more than HALF_CAP survivors (the others went through emit_half_kernel) */
+    const u32 *hcnt; /* with half: only nodes with more than HALF_CAP survivors (the others went through emit_half_kernel); null with
+                        half: the lists carry their own end */
     const u64 *half; /* with hcnt: survivor lists; a neighbour with at most HALF_CAP survivors is judged by its list (its row
                         carries no flags then, see TrArgs.all_flags) */
     const u64 *list; /* non-null: the nodes to emit (n_list of them) instead of the whole query range */
@@ -4754,9 +4778,49 @@ struct EmitArgs {
     OwnSet own; /* the nodes this launch emits from: the query range, or the rank's own nodes */
 };
 
+/* Dense output (one GPU, whole-table pass): a wavefront stages its survivors in LDS and appends them with an atomicAdd of their EXACT
+ * number, when EMIT_CHUNK are staged and once at its end — as many atomics as the chunked form, and no unused tails: the bump pointer
+ * IS the number of edges and slot i IS edge i (no validity pass, no scan, no compaction at fetch time) */
+struct EmitStage {
+    u64 *src, *ent; /* LDS, EMIT_CHUNK each */
+    u32 staged;
+    __device__ __forceinline__ void flush(u64 *bump, u64 *out_src, u64 *out_ent, u64 out_cap, u32 lane)
+    {
+        if (!staged) return; /* (wave uniform) */
+        __syncthreads();
+        u64 base = 0;
+        if (lane == 0) base = atomicAdd(bump, (u64)staged);
+        base = uniform_u64(base);
+        for (u32 i = lane; i < staged; i += 64)
+            if (base + i < out_cap) {
+                out_src[base + i] = src[i];
+                out_ent[base + i] = ent[i];
+            }
+        __syncthreads();
+        staged = 0;
+    }
+    /* mk: the vote of `keep` (at most 64 <= EMIT_CHUNK survivors a step) */
+    __device__ __forceinline__ void append(u64 mk, bool keep, u64 v, u64 e, u64 *bump, u64 *out_src, u64 *out_ent, u64 out_cap, u32 lane)
+    {
+        const u32 kc = __popcll(mk);
+        if (!kc) return;
+        if (staged + kc > EMIT_CHUNK) flush(bump, out_src, out_ent, out_cap, lane);
+        if (keep) {
+            const u32 i = staged + rank_below(mk);
+            src[i] = v;
+            ent[i] = e;
+        }
+        staged += kc;
+    }
+};
+
+template <bool DENSE>
 __global__ void __launch_bounds__(64) emit_kernel(EmitArgs a)
 {
+    __shared__ u64 s_src[DENSE ? EMIT_CHUNK : 1], s_ent[DENSE ? EMIT_CHUNK : 1];
+    EmitStage st{s_src, s_ent, 0u};
     const u32 lane = threadIdx.x;
+    const bool selfdel = a.half && !a.hcnt; /* the lists carry their own end (disco_survivor.h) */
     u64 chunk_base = 0;
     u32 chunk_used = EMIT_CHUNK; /* no chunk yet */
     bool have_chunk = false;
@@ -4776,7 +4840,11 @@ __global__ void __launch_bounds__(64) emit_kernel(EmitArgs a)
         if (a.hcnt && a.hcnt[v] <= HALF_CAP) continue;
         const u64 rv = a.ref[v];
         const u32 d = REF_DEG(rv);
-        if (d == 0) continue;
+        if (d == 0) continue; /* (self-delimiting lists: its list is whatever an earlier pass left) */
+        if (selfdel) {
+            const u64 *hv = a.half + v * HALF_CAP;
+            if (surv_len(hv[0], hv[1], hv[2], hv[3]) <= HALF_CAP) continue;
+        }
         const u64 vs = REF_POS(rv);
         const u32 Lv = a.v.len[v];
         for (u32 s0 = 0; s0 < d; s0 += 64) {
@@ -4789,10 +4857,10 @@ __global__ void __launch_bounds__(64) emit_kernel(EmitArgs a)
                 if (v < w && !(e & ADJ_FLAG) && (!a.local_only || a.own.mine(w))) {
                     const u32 Lw = ADJ_DLEN(e);
                     const u64 twin = ADJ_MAKE(Lw + ADJ_OFF(e) - Lv, v, disco_twin_orient(ADJ_ORI(e)), Lv);
-                    const u32 cw = a.hcnt ? a.hcnt[w] : HALF_CAP + 1;
+                    const u64 *hw = a.half + w * HALF_CAP;
+                    const u32 cw = a.hcnt ? a.hcnt[w] : selfdel ? surv_len(hw[0], hw[1], hw[2], hw[3]) : HALF_CAP + 1;
                     if (cw <= HALF_CAP) {
-                        const u64 *hw = a.half + w * HALF_CAP;
-                        for (u32 r = 0; r < cw; r++) keep |= (hw[r] == twin);
+                        for (u32 r = 0; r < cw; r++) keep |= (surv_entry(hw[r]) == twin); /* (with hcnt: no mark to mask) */
                     } else {
                         const u64 rw = a.ref[w];
                         const u64 *roww = a.adj + REF_POS(rw);
@@ -4802,6 +4870,10 @@ __global__ void __launch_bounds__(64) emit_kernel(EmitArgs a)
                 }
             }
             const u64 mk = __ballot(keep);
+            if (DENSE) {
+                st.append(mk, keep, v, e & ~ADJ_FLAG, a.bump, a.out_src, a.out_ent, a.out_cap, lane);
+                continue;
+            }
             const u32 cnt = __popcll(mk);
             if (cnt) {
                 if (chunk_used + cnt > EMIT_CHUNK) {
@@ -4823,7 +4895,8 @@ __global__ void __launch_bounds__(64) emit_kernel(EmitArgs a)
             }
         }
     }
-    close_chunk();
+    if (DENSE) st.flush(a.bump, a.out_src, a.out_ent, a.out_cap, lane);
+    else close_chunk();
 }
 
 /* Emission from the half-edge lists (single GPU): lane = node. A node's few edges that survived its own marking sit in
@@ -4918,6 +4991,53 @@ __global__ void __launch_bounds__(64) emit_half_kernel(EmitHalfArgs a)
     close_chunk();
 }
 
+/* The same from self-delimiting lists (one GPU, whole-table pass: disco_survivor.h), with dense output. A node's list is valid iff the
+ * node has a row (REF_DEG(ref[v]) != 0, streamed in id order like the list itself): the buffers persist across passes, and a node the
+ * marking did not write this pass holds the list of an earlier one. The length of a neighbour's list comes out of the 32-byte gather
+ * of the list itself — round 5 gathered a count first, a second random sector per pair in front of this one.
+ * (Tried: the gathers of all four slots issued before the first vote, unconditionally and with clamped addresses — 2.66-2.68 ms
+ * against 2.67-2.73 ms for this form at 50 M reads, inside the range of either: profiles/survivor_lists_ab.txt.) */
+__global__ void __launch_bounds__(64) emit_half_lists_kernel(EmitHalfArgs a)
+{
+    __shared__ u64 s_src[EMIT_CHUNK], s_ent[EMIT_CHUNK];
+    EmitStage st{s_src, s_ent, 0u};
+    const u32 lane = threadIdx.x;
+    const u64 nq = a.own.count();
+    u64 cbeg = 0, cend = 0;
+    while (wq_grab(a.v.wq, (nq + 63) / 64, cbeg, cend))
+    for (u64 blk = cbeg; blk < cend; blk++) {
+        const bool live = blk * 64 + lane < nq;
+        const u64 v = a.order ? ORDER_ID(a.order[live ? blk * 64 + lane : 0]) : a.own.node_by_id(live ? blk * 64 + lane : 0);
+        const ulonglong2 *hv = (const ulonglong2 *)(a.half + v * HALF_CAP);
+        const ulonglong2 o0 = hv[0], o1 = hv[1];
+        const u64 rv = a.ref[v];
+        const u32 Lv = (u32)a.v.len[v];
+        const u64 own[HALF_CAP] = {o0.x, o0.y, o1.x, o1.y};
+        u32 cnt = (live && REF_DEG(rv) != 0) ? surv_len(own[0], own[1], own[2], own[3]) : 0u;
+        if (cnt > HALF_CAP) cnt = 0; /* wide nodes are emitted by emit_kernel */
+#pragma unroll
+        for (u32 r = 0; r < HALF_CAP; r++) {
+            bool keep = false;
+            const u64 e = surv_entry(own[r]);
+            const u64 w = ADJ_DST(e);
+            if (r < cnt && v < w && (!a.local_only || a.own.otab || w < a.own.hi)) {
+                const u64 twin = ADJ_MAKE(ADJ_DLEN(e) + ADJ_OFF(e) - Lv, v, disco_twin_orient(ADJ_ORI(e)), Lv);
+                const ulonglong2 *hw = (const ulonglong2 *)(a.half + w * HALF_CAP);
+                const ulonglong2 h0 = hw[0], h1 = hw[1];
+                if (surv_len(h0.x, h0.y, h1.x, h1.y) <= HALF_CAP) keep = surv_has(h0.x, h0.y, h1.x, h1.y, twin);
+                else { /* neighbour with many survivors: look the twin up in its row */
+                    const u64 rw = a.ref[w];
+                    const u64 *roww = a.adj + REF_POS(rw);
+                    const int ti = adj_find(roww, REF_DEG(rw), twin);
+                    keep = (ti >= 0) && !(roww[ti] & ADJ_FLAG);
+                }
+            }
+            st.append(__ballot(keep), keep, v, e, a.bump, a.out_src, a.out_ent, a.out_cap, lane);
+        }
+    }
+    st.flush(a.bump, a.out_src, a.out_ent, a.out_cap, lane);
+}
+
 /* compact the chunked emission (drop the ~0 tails): count + gather are done on the host side of fetch via a scan */
 __global__ void emit_valid_kernel(const u64 *__restrict__ out_src, u64 n, u8 *__restrict__ valid)
 {
@@ -4937,6 +5057,13 @@ __global__ void emit_compact32_kernel(const u64 *__restrict__ out_src, const u64
         }
 }
 
+/* ... of a dense emission: nothing to drop, the entries are copied out from where they are */
+__global__ void emit_src32_kernel(const u64 *__restrict__ out_src, u64 n, u32 *__restrict__ dst_src)
+{
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i < n; i += (u64)gridDim.x * blockDim.x) dst_src[i] = (u32)out_src[i];
+}
+
 __global__ void emit_compact_kernel(const u64 *__restrict__ out_src, const u64 *__restrict__ out_ent, const u8 *__restrict__ valid,
                                     const u64 *__restrict__ pos, u64 n, u64 *__restrict__ dst_src, u64 *__restrict__ dst_ent)
 {
@@ -4948,7 +5075,8 @@ __global__ void emit_compact_kernel(const u64 *__restrict__ out_src, const u64 *
         }
 }
 
-/* substitutions of the overlap every emitted edge stands for (the third column of an edge line; 0 by construction unless the
+/* (the consumers of the emission's slots take a dense emission — slot i is edge i, no unused tails — as null valid / pos)
+ * substitutions of the overlap every emitted edge stands for (the third column of an edge line; 0 by construction unless the
  * inexact mode is on), from the edge's geometry: orient 2,3 — string2 starts at `offset` of the source; orient 0,1 — string2 ends
  * where the first len_src - offset bases of the source end; string2 = the destination (0,3) or its reverse complement (1,2)
  * (BG/Edge.h:30-34, BG/OverlapGraph.cpp:614-626,660-666) */
@@ -4958,12 +5086,12 @@ __global__ void edge_subs_kernel(const u64 *__restrict__ out_src, const u64 *__r
 {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; i < n; i += (u64)gridDim.x * blockDim.x)
-        if (valid[i]) {
+        if (!valid || valid[i]) {
             const u64 src = out_src[i], e = out_ent[i];
             const int l1 = (int)len[src], l2 = (int)ADJ_DLEN(e), off = (int)ADJ_OFF(e), ovl = l1 - off;
             const u32 o = ADJ_ORI(e);
             const u32 rev = (o == 1 || o == 2);
-            subs[pos[i]] = (u16)seg_mismatches<false>(reads + src * S, reads + ADJ_DST(e) * S, S, l2, o >= 2 ? off : 0, o >= 2 ? 0 : l2 - ovl, ovl, rev);
+            subs[pos ? pos[i] : i] = (u16)seg_mismatches<false>(reads + src * S, reads + ADJ_DST(e) * S, S, l2, o >= 2 ? off : 0, o >= 2 ? 0 : l2 - ovl, ovl, rev);
         }
 }
 
@@ -5000,7 +5128,7 @@ __global__ void uf_hook_kernel(const u64 *__restrict__ out_src, const u64 *__res
 {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; i < n_slots; i += (u64)gridDim.x * blockDim.x) {
-        if (!valid[i]) continue;
+        if (valid && !valid[i]) continue;
         u32 a = (u32)out_src[i], b = (u32)ADJ_DST(out_ent[i]);
         for (;;) {
             a = uf_find(parent, a);
@@ -5044,7 +5172,7 @@ __global__ void __launch_bounds__(256) uf_count_kernel(const u64 *__restrict__ o
     __syncthreads();
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; i < n_slots; i += (u64)gridDim.x * blockDim.x)
-        if (valid[i]) {
+        if (!valid || valid[i]) {
             const u32 root = parent[(u32)out_src[i]];
             u32 idx = (root * 0x9E3779B1u) >> 22; /* 10 bits */
             bool placed = false;
@@ -5085,11 +5213,11 @@ __global__ void uf_edge_file_kernel(const u64 *__restrict__ out_src, const u8 *_
 {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; i < n_slots; i += (u64)gridDim.x * blockDim.x)
-        if (valid[i]) {
+        if (!valid || valid[i]) {
             const u32 r = parent[(u32)out_src[i]];
             u16 f = cfile[r];
             if (f == 0xFFFFu) f = (u16)(((u64)(r * 0x9E3779B1u) * n_files) >> 32); /* small components: spread by hash */
-            edge_file[pos[i]] = f;
+            edge_file[pos ? pos[i] : i] = f;
         }
 }
 

@@ -61,10 +61,10 @@ __global__ void text_measure_kernel(TextView g, u8 *__restrict__ bytes)
 {
     u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; s < g.n_slots; s += (u64)gridDim.x * blockDim.x) {
-        if (!g.valid[s]) continue;
+        if (g.valid && !g.valid[s]) continue;
         const TextNumbers t = tx_numbers(g, s);
         /* a \t b \t o , ovl ,0,0, len1 , off , len1-1 , len2 ,0, ovl-1 ,NA,2 \n  : 20 fixed characters + the orientation digit */
-        bytes[g.pos[s]] = (u8)(tx_digits(t.a) + tx_digits(t.b) + 1 + tx_digits(t.ovl) + tx_digits(t.len1) + tx_digits(t.off) + tx_digits(t.len1 - 1) + tx_digits(t.len2) +
+        bytes[g.pos ? g.pos[s] : s] = (u8)(tx_digits(t.a) + tx_digits(t.b) + 1 + tx_digits(t.ovl) + tx_digits(t.len1) + tx_digits(t.off) + tx_digits(t.len1 - 1) + tx_digits(t.len2) +
                                tx_digits(t.ovl - 1) + 20);
     }
 }
@@ -86,9 +86,9 @@ __global__ void text_write_kernel(TextView g, const u64 *__restrict__ place, cha
 {
     u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; s < g.n_slots; s += (u64)gridDim.x * blockDim.x) {
-        if (!g.valid[s]) continue;
+        if (g.valid && !g.valid[s]) continue;
         const TextNumbers t = tx_numbers(g, s);
-        char *p = text + place[g.pos[s]];
+        char *p = text + place[g.pos ? g.pos[s] : s];
         p = tx_put(p, t.a); *p++ = '\t';
         p = tx_put(p, t.b); *p++ = '\t';
         *p++ = (char)('0' + t.orient); *p++ = ',';

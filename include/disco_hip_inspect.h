@@ -19,6 +19,14 @@ extern "C" {
  * takes, two classes of rows, a caller's order, DISCO_NO_ORDER). Tests only. */
 int disco_fetch_order(disco_ctx *ctx, uint64_t *order_words, uint32_t *keys, uint64_t cap, uint64_t *n, int *order_bits);
 
+/* how the last disco_transitive_reduce laid its survivors out (results do not depend on it): *dense = 1 if the emission wrote its edges
+ * back to back (no unused chunk tails: *out_used, the slots it wrote, is then the number of edges), list_len[v] = the decoded length of
+ * node v's self-delimiting survivor list (disco_amd/csrc/disco_survivor.h): 0..4, 5 = wide (more than four survivors, judged by its row),
+ * 0xFF = the node has no row, so the marking wrote no list for it. list_len may be null (the other three only); cap: its room, in nodes
+ * (*n is set; too little: DISCO_E_ARG). DISCO_E_STATE for the lengths when the last marking kept counts instead (flows that need every
+ * row's flags, or a communicator). Tests only. */
+int disco_fetch_survivor_layout(disco_ctx *ctx, uint8_t *list_len, uint64_t cap, uint64_t *n, int *dense, uint64_t *out_used);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,8 @@ ABI = [
     ("disco_format_contained", C.c_int64, [_P, C.c_uint32, _P, _P]),
     ("disco_fetch_contained_text", C.c_int, [_P, _P, C.c_uint64]),
     ("disco_write_contained_text", C.c_int, [_P, _P, C.c_uint32, C.c_uint32]),
+    ("disco_dist_format_contained", C.c_int64, [_P, C.c_uint32, _P, _P]),
+    ("disco_dist_format_edges", C.c_int64, [_P, C.c_uint32, _P, _P]),
 ]
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
@@ -423,6 +425,27 @@ class BuildGraph:
         """the text of the last format_contained straight from the device into open files: fds[f] receives file f (disco_write_contained_text)"""
         arr = (C.c_int * len(fds))(*fds)
         self._chk(self.L.disco_write_contained_text(self._h, arr, len(fds), threads))
+
+    def dist_format_contained(self, n_files: int = 1, file_index=None):
+        """COLLECTIVE, after dist_run_graph: this rank's contained-read files (disco_dist_format_contained) — the files f with
+        f * world // n_files == rank, the others empty: (text bytes, offsets [n_files + 1]); write_contained_text streams them"""
+        off = np.zeros(n_files + 1, dtype=np.uint64)
+        fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
+        nb = self._chk(self.L.disco_dist_format_contained(self._h, n_files, None if fi is None else fi.ctypes.data, off.ctypes.data))
+        buf = np.empty(max(nb, 1), dtype=np.uint8)
+        self._chk(self.L.disco_fetch_contained_text(self._h, buf.ctypes.data, nb))
+        return buf[:nb].tobytes(), off
+
+    def dist_format_edges(self, n_files: int = 1, file_index=None):
+        """COLLECTIVE, after dist_run_graph: this rank's edge files (disco_dist_format_edges) — the edges of all ranks cut into
+        n_files files along connected components, the lines of the files f with f * world // n_files == rank: (text bytes,
+        offsets [n_files + 1]); write_edge_text streams them"""
+        off = np.zeros(n_files + 1, dtype=np.uint64)
+        fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
+        nb = self._chk(self.L.disco_dist_format_edges(self._h, n_files, None if fi is None else fi.ctypes.data, off.ctypes.data))
+        buf = np.empty(max(nb, 1), dtype=np.uint8)
+        self._chk(self.L.disco_fetch_edge_text(self._h, buf.ctypes.data, nb))
+        return buf[:nb].tobytes(), off
 
     def start_contained_rows(self, grouped: bool = False):
         """the contained rows start their way to the host now (between mark_contained and the fetch)"""

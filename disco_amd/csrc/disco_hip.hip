@@ -4123,9 +4123,12 @@ int64_t disco_fetch_edge_substitutions(disco_ctx *c, uint16_t *out, uint64_t cap
 }
 
 /* connected components of the edges in the slots [0, n_slots) (valid[i] != 0; pos[i] = rank of the edge among the valid ones)
- * dealt out to n_files files: out[pos[i]] = file of edge i */
+ * dealt out to n_files files: out[pos[i]] = file of edge i — on the host, or, with d_out (room for ne entries), left on the device.
+ * The assignment depends on the SET of edges only, not on their order or on who computes it: a component's root is its smallest read
+ * (uf_hook_kernel), its size a count, the large ones are dealt out in (size, root) order, the others by a hash of the root — which is
+ * what lets every rank of a multi-GPU job run it on the gathered edges and arrive at the same files (disco_dist_format_edges) */
 static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent, const u8 *d_valid, const u64 *d_pos, u64 n_slots, u64 ne, u64 n,
-                               uint32_t n_files, uint16_t *out)
+                               uint32_t n_files, uint16_t *out, u16 *d_out = nullptr)
 {
     DISCO_TRACE("partition_edges");
     DevBuf<u32> parent, cnt, d_nlist;
@@ -4152,7 +4155,7 @@ static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent,
     PART_CHK(ensure(c, parent, n));
     PART_CHK(ensure(c, cnt, n));
     PART_CHK(ensure(c, cfile, n));
-    PART_CHK(ensure(c, efile, ne));
+    if (!d_out) PART_CHK(ensure(c, efile, ne));
     PART_CHK(ensure(c, list, list_cap));
     PART_CHK(ensure(c, d_nlist, 1));
     hipLaunchKernelGGL(uf_init_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, parent, n);
@@ -4190,8 +4193,8 @@ static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent,
         }
         hipLaunchKernelGGL(uf_assign_kernel, dim3((n_list + 255) / 256), dim3(256), 0, c->stream, list, n_list, cfile);
     }
-    hipLaunchKernelGGL(uf_edge_file_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, d_src, d_valid, d_pos, n_slots, parent, cfile, n_files, efile);
-    hipError_t e1 = hipMemcpyAsync(out, efile, ne * sizeof(u16), hipMemcpyDeviceToHost, c->stream);
+    hipLaunchKernelGGL(uf_edge_file_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, d_src, d_valid, d_pos, n_slots, parent, cfile, n_files, d_out ? d_out : efile.p);
+    hipError_t e1 = d_out ? hipGetLastError() : hipMemcpyAsync(out, efile, ne * sizeof(u16), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);
     cleanup();
 #undef PART_CHK
@@ -4412,42 +4415,42 @@ int disco_write_edge_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32
 }
 
 /* ---- the lines of the contained-read files, grouped, sorted and formatted where the keys are (disco_text.h) ------------------ */
-int64_t disco_format_contained(disco_ctx *c, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets)
+/* the body of disco_format_contained and disco_dist_format_contained: the rows of the containing reads [s_lo, s_hi) out of best[0, n).
+ * flags != null: the contained reads are the flagged ones and nc of them have a containing read in the range (one GPU: all of them,
+ * known since disco_mark_contained); flags == null: read off the keys, counted here (a rank of a multi-GPU job) */
+static int64_t format_contained_rows(disco_ctx *c, const char *who, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets, const u8 *flags, u64 s_lo,
+                                     u64 s_hi, u64 nc)
 {
-    DISCO_TRACE("disco_format_contained");
-    if (!c || !file_offsets || n_files == 0) return DISCO_E_ARG;
-    if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "disco_format_contained: a rank's rows are not grouped across ranks (the host writer formats)");
-    if (c->phase < 4) return fail(c, DISCO_E_STATE, "disco_format_contained: run disco_mark_contained first");
-    if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_format_contained: more than 2^31 reads");
-    HIPCHK(c, hipSetDevice(c->device));
-    const u64 nc = c->n_contained, n = c->n;
-    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
-    c->ctext_bytes = 0;
-    c->ctext_off.assign((size_t)n_files + 1, 0);
-    if (nc == 0) return 0;
-    CHK(settle_keys(c));
+    const u64 n = c->n;
     DevBuf<u32> cnt, gend, sup, list, ctr;
     DevBuf<u64> word, place, d_findex, d_off;
     DevBuf<u8> bytes;
     u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
     auto body = [&]() -> int {
         /* 1. grouped by containing read */
-        CgrpLists L;
-        L.cap = (u32)(nc / (CROW_GROUP_MAX + 1) + 1); /* (a listed group has more than CROW_GROUP_MAX rows) */
         CHK(ensure(c, cnt, n + 1));
         CHK(ensure(c, gend, n + 1));
+        CHK(ensure(c, ctr, CGRP_CTRS));
+        HIPCHK(c, hipMemsetAsync(cnt, 0, (n + 1) * sizeof(u32), c->stream));
+        HIPCHK(c, hipMemsetAsync(ctr, 0, CGRP_CTRS * sizeof(u32), c->stream));
+        if (flags) {
+            hipLaunchKernelGGL(cgrp_count_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, flags, n, cnt.p, ctr.p);
+            CHK((scan_exclusive<u32, u32>(c, cnt, n + 1, gend, false, nullptr)));
+        } else {
+            hipLaunchKernelGGL(cgrp_count_range_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, n, s_lo, s_hi, cnt.p, ctr.p);
+            CHK((scan_exclusive<u32, u32>(c, cnt, n + 1, gend, false, &nc))); /* (the rank's rows: known only now) */
+            if (nc == 0) return DISCO_OK;
+        }
+        CgrpLists L;
+        L.cap = (u32)(nc / (CROW_GROUP_MAX + 1) + 1); /* (a listed group has more than CROW_GROUP_MAX rows) */
         CHK(ensure(c, word, nc));
         CHK(ensure(c, sup, nc));
         CHK(ensure(c, list, 2 * (u64)L.cap));
-        CHK(ensure(c, ctr, CGRP_CTRS));
         L.lds = list;
         L.glb = list.p + L.cap;
         L.ctr = ctr;
-        HIPCHK(c, hipMemsetAsync(cnt, 0, (n + 1) * sizeof(u32), c->stream));
-        HIPCHK(c, hipMemsetAsync(ctr, 0, CGRP_CTRS * sizeof(u32), c->stream));
-        hipLaunchKernelGGL(cgrp_count_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, (const u8 *)c->d_contained, n, cnt.p, ctr.p);
-        CHK((scan_exclusive<u32, u32>(c, cnt, n + 1, gend, false, nullptr)));
-        hipLaunchKernelGGL(cgrp_place_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, (const u8 *)c->d_contained, n, nc, gend.p, word.p, sup.p);
+        if (flags) hipLaunchKernelGGL(cgrp_place_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, flags, n, nc, gend.p, word.p, sup.p);
+        else hipLaunchKernelGGL(cgrp_place_range_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, n, s_lo, s_hi, nc, gend.p, word.p, sup.p);
         /* 2. every group in (j, contained read) order: by its size */
         hipLaunchKernelGGL(cgrp_sort_small_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u32 *)gend, n, word.p, L);
         const int big_grid = (int)std::min<u64>(L.cap, (u64)c->n_cu * 4);
@@ -4478,7 +4481,7 @@ int64_t disco_format_contained(disco_ctx *c, uint32_t n_files, const uint64_t *f
         HIPCHK(c, hipMemcpyAsync(c->ctext_off.data(), d_off, ((size_t)n_files + 1) * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "disco_format_contained: %u contained reads have a key that names no containing read", h_ctr[CGRP_BAD_KEYS]);
+        if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "%s: %u contained reads have a key that names no containing read", who, h_ctr[CGRP_BAD_KEYS]);
         CHK(ensure(c, c->d_ctext, std::max<u64>(total, 1)));
         hipLaunchKernelGGL(ctext_write_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, g, (const u64 *)place, c->d_ctext.p);
         HIPCHK(c, hipGetLastError());
@@ -4506,6 +4509,22 @@ int64_t disco_format_contained(disco_ctx *c, uint32_t n_files, const uint64_t *f
         fprintf(stderr, "[disco] contained lines: %llu rows, %llu bytes; groups of more than %d rows: %u sorted in LDS, %u through global memory, the largest of %u rows\n",
                 (unsigned long long)nc, (unsigned long long)c->ctext_bytes, CROW_GROUP_MAX, h_ctr[CGRP_N_LDS], h_ctr[CGRP_N_GLOBAL], h_ctr[CGRP_LARGEST]);
     return (int64_t)c->ctext_bytes;
+}
+
+int64_t disco_format_contained(disco_ctx *c, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets)
+{
+    DISCO_TRACE("disco_format_contained");
+    if (!c || !file_offsets || n_files == 0) return DISCO_E_ARG;
+    if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "disco_format_contained: a rank's rows are not grouped across ranks (the host writer formats)");
+    if (c->phase < 4) return fail(c, DISCO_E_STATE, "disco_format_contained: run disco_mark_contained first");
+    if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_format_contained: more than 2^31 reads");
+    HIPCHK(c, hipSetDevice(c->device));
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
+    c->ctext_bytes = 0;
+    c->ctext_off.assign((size_t)n_files + 1, 0);
+    if (c->n_contained == 0) return 0;
+    CHK(settle_keys(c));
+    return format_contained_rows(c, "disco_format_contained", n_files, file_index, file_offsets, (const u8 *)c->d_contained, 0, c->n, c->n_contained);
 }
 
 int disco_fetch_contained_text(disco_ctx *c, char *out, uint64_t cap)
@@ -6625,6 +6644,205 @@ int disco_dist_get_info(disco_ctx *c, disco_dist_info *out)
     if (!c || !out) return DISCO_E_ARG;
     *out = c->dinfo;
     return DISCO_OK;
+}
+
+/* ---- the text files of a multi-GPU job, every rank its own (disco_text.h) -------------------------------------------------------------
+ * For F files of one kind and G ranks, rank r writes the files f with floor(f G / F) == r: the run [ceil(r F / G), ceil((r + 1) F / G)),
+ * empty for some ranks when F < G. */
+static void dist_own_files(const disco_ctx *c, uint32_t n_files, uint32_t *f_lo, uint32_t *f_hi)
+{
+    const u64 G = (u64)c->comm->world, r = (u64)c->comm->rank, F = n_files;
+    *f_lo = (uint32_t)((r * F + G - 1) / G);
+    *f_hi = (uint32_t)(((r + 1) * F + G - 1) / G);
+}
+
+/* what a rank did on its own between two collectives, agreed on: DISCO_OK when every rank says so, else the rank's own code or the
+ * first failing peer's — the ranks leave a collective entry point alike, and the caller's next collective is entered by all or by none */
+static int dist_agree(disco_ctx *c, const char *who, int rc)
+{
+    const size_t G = (size_t)c->comm->world;
+    std::vector<u64> st(G);
+    const u64 mine = (u64)(int64_t)rc;
+    const std::string own = rc != DISCO_OK ? c->err : std::string();
+    const int xrc = c->comm->host_all_gather((const unsigned long long *)&mine, 1, (unsigned long long *)st.data(), c->stream);
+    if (rc != DISCO_OK) {
+        c->err = own;
+        return rc;
+    }
+    if (xrc != DISCO_OK) return fail(c, xrc, "%s: status exchange: %s", who, c->comm->err.c_str());
+    for (size_t p = 0; p < G; p++)
+        if ((int64_t)st[p] != DISCO_OK) return fail(c, (int)(int64_t)st[p], "%s: rank %zu could not do its part (code %d): no rank keeps its text", who, p, (int)(int64_t)st[p]);
+    return DISCO_OK;
+}
+
+/* the contained-read lines: a rank's files are one range of containing reads, whose contained reads arrived anywhere. The reduced keys
+ * — every rank holds those of its home slice — are brought together by ONE all-gather (per x 8 bytes per rank, the volume of the pass's
+ * own reduce-scatter), in place: the other slices of best[] hold nothing anybody reads after the pass, and the next pass fills the table
+ * afresh. Everything behind the gather is the rank's own business; the ranks compare notes at the end */
+int64_t disco_dist_format_contained(disco_ctx *c, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets)
+{
+    DISCO_TRACE("disco_dist_format_contained");
+    if (!c || !file_offsets || n_files == 0) return DISCO_E_ARG;
+    if (!c->comm) return fail(c, DISCO_E_STATE, "disco_dist_format_contained: no communicator (one GPU: disco_format_contained)");
+    if (!c->dist_reads || c->phase < 8) return fail(c, DISCO_E_STATE, "disco_dist_format_contained: run disco_dist_run_graph first");
+    if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_format_contained: more than 2^31 reads");
+    HIPCHK(c, hipSetDevice(c->device));
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
+    c->ctext_bytes = 0;
+    c->ctext_off.assign((size_t)n_files + 1, 0);
+    const u64 G = (u64)c->comm->world, r = (u64)c->comm->rank, n = c->n, F = n_files;
+    if (c->d_best.cap < c->per * G) return fail(c, DISCO_E_STATE, "disco_dist_format_contained: the containment keys of the last pass are gone");
+    CHK(settle_keys(c));
+    COMM_CHK(c, c->comm->all_gather(c->d_best + r * c->per, c->d_best, c->per * 8, c->stream));
+    uint32_t f_lo, f_hi;
+    dist_own_files(c, n_files, &f_lo, &f_hi);
+    const u64 s_lo = ((u64)f_lo * n + F - 1) / F, s_hi = ((u64)f_hi * n + F - 1) / F; /* file t begins at the read ceil(t n / F) */
+    if (getenv("DISCO_VERBOSE"))
+        fprintf(stderr, "[disco] rank %llu of %llu: contained-read files [%u, %u) of %u, containing reads [%llu, %llu); keys gathered, %llu bytes to the other ranks\n",
+                (unsigned long long)r, (unsigned long long)G, f_lo, f_hi, n_files, (unsigned long long)s_lo, (unsigned long long)s_hi, (unsigned long long)((G - 1) * c->per * 8));
+    const int64_t nb = s_hi <= s_lo ? 0 : format_contained_rows(c, "disco_dist_format_contained", n_files, file_index, file_offsets, nullptr, s_lo, s_hi, 0);
+    const int rc = dist_agree(c, "disco_dist_format_contained", nb < 0 ? (int)nb : DISCO_OK);
+    if (rc != DISCO_OK) {
+        for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
+        c->ctext_bytes = 0;
+        c->ctext_off.assign((size_t)n_files + 1, 0);
+        return rc;
+    }
+    return nb;
+}
+
+/* the edge lines: the ranks' edges — compacted, 12 bytes each — are all-gathered, every rank cuts the same files out of the same list
+ * (partition_edges: the assignment depends on the set of edges alone), measures every line and places and writes those of its own files.
+ * What the gather needs — the rank's memory — is there before the rank enters it, and the ranks exchange a status word in front of it:
+ * either all of them gather, or none; and again at the end, for what every rank did alone behind it */
+int64_t disco_dist_format_edges(disco_ctx *c, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets)
+{
+    DISCO_TRACE("disco_dist_format_edges");
+    if (!c || !file_offsets || n_files == 0) return DISCO_E_ARG;
+    if (!c->comm) return fail(c, DISCO_E_STATE, "disco_dist_format_edges: no communicator (one GPU: disco_format_edges)");
+    if (!c->dist_reads || c->phase < 8) return fail(c, DISCO_E_STATE, "disco_dist_format_edges: run disco_dist_run_graph first");
+    if (n_files > 256) return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_format_edges: more than 256 files (one placement pass per file)");
+    if (c->prm.max_substitutions) return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_format_edges: the substitutions column is written by the host writer");
+    if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_format_edges: more than 2^31 reads");
+    HIPCHK(c, hipSetDevice(c->device));
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
+    c->text_bytes = 0;
+    c->text_off.assign((size_t)n_files + 1, 0);
+    const size_t G = (size_t)c->comm->world, r = (size_t)c->comm->rank;
+    const u64 ne_own = c->n_out;
+    /* 1. who has how many edges */
+    std::vector<u64> cnt(G);
+    {
+        const u64 mine = ne_own;
+        COMM_CHK(c, c->comm->host_all_gather((const unsigned long long *)&mine, 1, (unsigned long long *)cnt.data(), c->stream));
+    }
+    std::vector<u64> first(G + 1, 0);
+    for (size_t p = 0; p < G; p++) first[p + 1] = first[p] + cnt[p];
+    const u64 ne = first[G];
+    if (ne == 0) return 0;
+    uint32_t f_lo, f_hi;
+    dist_own_files(c, n_files, &f_lo, &f_hi);
+    DevBuf<u32> src32;
+    DevBuf<u64> src, ent, d_findex, within, place;
+    DevBuf<u8> bytes, sel;
+    DevBuf<u16> efile;
+    /* 2. everything the rank will need, and its own edges compacted to where they lie in the job's list */
+    auto prepare = [&]() -> int {
+        CHK(ensure(c, src32, ne));
+        CHK(ensure(c, ent, ne));
+        CHK(ensure(c, src, ne));
+        CHK(ensure(c, efile, ne));
+        CHK(ensure(c, bytes, ne));
+        if (f_hi > f_lo) {
+            CHK(ensure(c, sel, ne));
+            CHK(ensure(c, within, ne + 1));
+            CHK(ensure(c, place, ne));
+        }
+        if (file_index) {
+            CHK(ensure(c, d_findex, c->n));
+            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        if (ne_own) {
+            if (c->out_dense) {
+                hipLaunchKernelGGL(emit_src32_kernel, dim3(flat_grid(c, ne_own)), dim3(256), 0, c->stream, c->d_out_src, ne_own, src32.p + first[r]);
+                HIPCHK(c, hipMemcpyAsync(ent.p + first[r], c->d_out_ent, ne_own * 8, hipMemcpyDeviceToDevice, c->stream));
+            } else
+                hipLaunchKernelGGL(emit_compact32_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos, c->out_used,
+                                   src32.p + first[r], ent.p + first[r]);
+            HIPCHK(c, hipGetLastError());
+        }
+        return DISCO_OK;
+    };
+    auto body = [&](bool *gathered) -> int {
+        CHK(dist_agree(c, "disco_dist_format_edges", prepare()));
+        *gathered = true; /* (every rank is past the verdict: all of them meet again at the end) */
+        /* 3. the job's edges on every rank, in the order of the ranks */
+        std::vector<size_t> off(G), len(G);
+        for (size_t p = 0; p < G; p++) {
+            off[p] = (size_t)first[p] * 4;
+            len[p] = (size_t)cnt[p] * 4;
+        }
+        COMM_CHK(c, c->comm->all_gather_v(src32.p + first[r], src32.p, off.data(), len.data(), c->stream));
+        for (size_t p = 0; p < G; p++) {
+            off[p] *= 2;
+            len[p] *= 2;
+        }
+        COMM_CHK(c, c->comm->all_gather_v(ent.p + first[r], ent.p, off.data(), len.data(), c->stream));
+        hipLaunchKernelGGL(text_widen_src_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, (const u32 *)src32, ne, src.p);
+        HIPCHK(c, hipGetLastError());
+        /* 4. the files of the edges: on the device they stay */
+        const int64_t part = partition_edges(c, src, ent, nullptr, nullptr, ne, ne, c->n, n_files, nullptr, efile.p);
+        if (part < 0) return (int)part;
+        /* 5. all lines measured; those of the rank's files placed and written */
+        TextView g;
+        g.src = src;
+        g.ent = ent;
+        g.valid = nullptr;
+        g.pos = nullptr;
+        g.len = c->d_len;
+        g.file_index = d_findex;
+        g.n_slots = ne;
+        hipLaunchKernelGGL(text_measure_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, g, bytes.p);
+        u64 base = 0;
+        for (uint32_t f = 0; f < n_files; f++) {
+            c->text_off[f] = base;
+            if (f < f_lo || f >= f_hi) continue;
+            u64 total = 0;
+            hipLaunchKernelGGL(text_select_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, (const u8 *)bytes, (const u16 *)efile, ne, f, sel.p);
+            CHK((scan_exclusive<u8, u64>(c, sel, ne, within, false, &total)));
+            hipLaunchKernelGGL(text_place_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, (const u64 *)within, (const u16 *)efile, ne, f, base, place.p);
+            base += total;
+        }
+        c->text_off[n_files] = base;
+        CHK(ensure(c, c->d_text, std::max<u64>(base, 1)));
+        if (base) hipLaunchKernelGGL(text_write_owned_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, g, (const u64 *)place, (const u16 *)efile, f_lo, f_hi, c->d_text.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->text_bytes = base;
+        return DISCO_OK;
+    };
+    bool gathered = false;
+    int rc = body(&gathered);
+    if (gathered) rc = dist_agree(c, "disco_dist_format_edges", rc);
+    release(c, src32);
+    release(c, src);
+    release(c, ent);
+    release(c, d_findex);
+    release(c, within);
+    release(c, place);
+    release(c, bytes);
+    release(c, sel);
+    release(c, efile);
+    if (rc != DISCO_OK) {
+        c->text_bytes = 0;
+        c->text_off.assign((size_t)n_files + 1, 0);
+        return rc;
+    }
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = c->text_off[f];
+    if (getenv("DISCO_VERBOSE"))
+        fprintf(stderr, "[disco] rank %zu of %zu: edge files [%u, %u) of %u, %llu bytes of %llu edges' lines; edges gathered, %llu bytes to the other ranks\n", r, G, f_lo, f_hi, n_files,
+                (unsigned long long)c->text_bytes, (unsigned long long)ne, (unsigned long long)((G - 1) * ne_own * 12));
+    return (int64_t)c->text_bytes;
 }
 
 } /* extern "C" */

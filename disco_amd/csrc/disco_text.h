@@ -82,22 +82,48 @@ __global__ void text_place_kernel(const u64 *__restrict__ within, const u16 *__r
         if (efile[i] == file) place[i] = base + within[i];
 }
 
+/* one edge line at p */
+__device__ __forceinline__ void tx_put_line(char *p, const TextNumbers &t)
+{
+    p = tx_put(p, t.a); *p++ = '\t';
+    p = tx_put(p, t.b); *p++ = '\t';
+    *p++ = (char)('0' + t.orient); *p++ = ',';
+    p = tx_put(p, t.ovl); *p++ = ','; *p++ = '0'; *p++ = ','; *p++ = '0'; *p++ = ','; /* :815-816 substitutions, edits */
+    p = tx_put(p, t.len1); *p++ = ',';
+    p = tx_put(p, t.off); *p++ = ',';
+    p = tx_put(p, t.len1 - 1); *p++ = ',';
+    p = tx_put(p, t.len2); *p++ = ','; *p++ = '0'; *p++ = ',';
+    p = tx_put(p, t.ovl - 1); *p++ = ','; *p++ = 'N'; *p++ = 'A'; *p++ = ','; *p++ = '2'; *p++ = '\n';
+}
+
 __global__ void text_write_kernel(TextView g, const u64 *__restrict__ place, char *__restrict__ text)
 {
     u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; s < g.n_slots; s += (u64)gridDim.x * blockDim.x) {
         if (g.valid && !g.valid[s]) continue;
         const TextNumbers t = tx_numbers(g, s);
-        char *p = text + place[g.pos ? g.pos[s] : s];
-        p = tx_put(p, t.a); *p++ = '\t';
-        p = tx_put(p, t.b); *p++ = '\t';
-        *p++ = (char)('0' + t.orient); *p++ = ',';
-        p = tx_put(p, t.ovl); *p++ = ','; *p++ = '0'; *p++ = ','; *p++ = '0'; *p++ = ','; /* :815-816 substitutions, edits */
-        p = tx_put(p, t.len1); *p++ = ',';
-        p = tx_put(p, t.off); *p++ = ',';
-        p = tx_put(p, t.len1 - 1); *p++ = ',';
-        p = tx_put(p, t.len2); *p++ = ','; *p++ = '0'; *p++ = ',';
-        p = tx_put(p, t.ovl - 1); *p++ = ','; *p++ = 'N'; *p++ = 'A'; *p++ = ','; *p++ = '2'; *p++ = '\n';
+        tx_put_line(text + place[g.pos ? g.pos[s] : s], t);
+    }
+}
+
+/* ---- a rank of a multi-GPU job writes the files [f_lo, f_hi) only (disco_dist_format_edges): the edges of all ranks lie on every rank,
+ * gathered with their sources as 32 bits; every line is measured, the lines of the rank's files are placed and written ---- */
+__global__ void text_widen_src_kernel(const u32 *__restrict__ src32, u64 ne, u64 *__restrict__ src)
+{
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i < ne; i += (u64)gridDim.x * blockDim.x) src[i] = src32[i];
+}
+/* text_write_kernel behind a file-ownership mask: place[] of an edge of another rank's file was never set, and is never read */
+__global__ void text_write_owned_kernel(TextView g, const u64 *__restrict__ place, const u16 *__restrict__ efile, u32 f_lo, u32 f_hi, char *__restrict__ text)
+{
+    u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; s < g.n_slots; s += (u64)gridDim.x * blockDim.x) {
+        if (g.valid && !g.valid[s]) continue;
+        const u64 e = g.pos ? g.pos[s] : s;
+        const u32 f = efile[e];
+        if (f < f_lo || f >= f_hi) continue;
+        const TextNumbers t = tx_numbers(g, s);
+        tx_put_line(text + place[e], t);
     }
 }
 
@@ -146,6 +172,36 @@ __global__ void cgrp_place_kernel(const u64 *__restrict__ best, const u8 *__rest
             word[at] = CWORD_MAKE(CKEY_J(key), i, CKEY_SUFFIX(key), CKEY_REV(key));
             sup[at] = (u32)s;
         }
+}
+
+/* the range-restricted forms (disco_dist_format_contained): a rank of a multi-GPU job groups the rows whose containing read lies in
+ * [s_lo, s_hi) — the reads of the files it writes — out of the keys of ALL reads, all-gathered. Who is contained is read off the key
+ * (the flags of a rank cover its home range only); cnt / cursor stay indexed by read id, zero outside the range, so that everything
+ * behind them (the sorts, ctext_offsets_kernel) runs unchanged and a file of another rank comes out empty */
+__global__ void cgrp_count_range_kernel(const u64 *__restrict__ best, u64 n, u64 s_lo, u64 s_hi, u32 *__restrict__ cnt, u32 *__restrict__ ctr)
+{
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const u64 key = best[i];
+        if (key == DISCO_NOKEY) continue;
+        const u64 s = CKEY_SUPER(key);
+        if (s >= n) atomicAdd(&ctr[CGRP_BAD_KEYS], 1u);
+        else if (s >= s_lo && s < s_hi) atomicAdd(&cnt[s], 1u);
+    }
+}
+__global__ void cgrp_place_range_kernel(const u64 *__restrict__ best, u64 n, u64 s_lo, u64 s_hi, u64 nc, u32 *__restrict__ cursor, u64 *__restrict__ word, u32 *__restrict__ sup)
+{
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const u64 key = best[i];
+        if (key == DISCO_NOKEY) continue;
+        const u64 s = CKEY_SUPER(key);
+        if (s < s_lo || s >= s_hi) continue; /* (s_hi <= n) */
+        const u32 at = atomicAdd(&cursor[s], 1u);
+        if (at >= nc) continue;
+        word[at] = CWORD_MAKE(CKEY_J(key), i, CKEY_SUFFIX(key), CKEY_REV(key));
+        sup[at] = (u32)s;
+    }
 }
 
 struct CgrpLists {

@@ -129,6 +129,12 @@ static bool read_min_overlap(const std::string &path, uint32_t &mo, std::string 
     return true;
 }
 
+/* buildG --gpus N: DISCO_DIST_GPU_TEXT=1 makes every rank write its share of the text files from its GPU. Measured with four ranks on ONE
+ * device (profiles/dist_text.txt): from "Graph construction complete" to files closed the device path is slower at 5 M reads (each rank
+ * pins a 256 MB staging ring for a few MB of text, one rank after the other) and faster at 50 M; the whole process is faster at both. Slower
+ * at either size means opt-in; what one GPU and one link per rank gain is a measurement this pool cannot make. */
+static const bool DIST_GPU_TEXT_DEFAULT = false;
+
 static int die(const std::string &msg)
 {
     std::cout << "\nError: " << msg << std::endl; /* the reference prints and exits 0 (BG/Common.h:64); we exit non-zero */
@@ -147,6 +153,10 @@ struct RankResult {
     uint64_t n_edges = 0;
     disco_dist_info info{};
     std::string err;
+    /* the rank wrote its share of the files from its GPU (disco_dist_format_contained / disco_dist_format_edges): the library makes
+     * the ranks agree, so these are the same on every rank */
+    bool dev_contained = false, dev_edges = false;
+    Clock::time_point pass_end{};
 };
 
 int main(int argc, char **argv)
@@ -369,10 +379,11 @@ int main(int argc, char **argv)
      * DISCO_WATCHDOG_S seconds (default 900; 0: off) — a collective one rank never entered, a link that went away — the process says
      * where every rank stands and exits non-zero. Never a re-exec, never a silent hang: runDisco.sh does not check the status, but
      * the missing GC=Complete line makes the next run start over. */
-    enum { ST_START = 0, ST_COMM_INIT, ST_INGEST, ST_INGEST_FETCH, ST_HOST_INPUT, ST_UPLOAD, ST_FRONT_OF_PASS, ST_PASS, ST_FETCH_CONTAINED, ST_FETCH_EDGES, ST_DONE };
+    enum { ST_START = 0, ST_COMM_INIT, ST_INGEST, ST_INGEST_FETCH, ST_HOST_INPUT, ST_UPLOAD, ST_FRONT_OF_PASS, ST_PASS, ST_FETCH_CONTAINED, ST_FETCH_EDGES, ST_FORMAT_CONTAINED, ST_WRITE_CONTAINED, ST_FORMAT_EDGES, ST_WRITE_EDGES, ST_DONE };
     static const char *const kStage[] = {"start", "disco_comm_init", "disco_dist_ingest_fasta", "disco_dist_ingest_fetch", "the host input stage (between the rank threads)",
                                          "disco_dist_upload_reads", "front of disco_dist_run_graph (never entered it)", "disco_dist_run_graph",
-                                         "disco_fetch_contained", "disco_fetch_edges", "done"};
+                                         "disco_fetch_contained", "disco_fetch_edges", "disco_dist_format_contained", "disco_write_contained_text (its contained-read files)",
+                                         "disco_dist_format_edges", "disco_write_edge_text (its edge files)", "done"};
     std::vector<std::atomic<int>> stage((size_t)gpus);
     for (auto &st : stage) st.store(ST_START);
     std::atomic<bool> ranks_done{false};
@@ -709,6 +720,15 @@ int main(int argc, char **argv)
          * [r*per, (r+1)*per), every exchange is an RCCL collective inside libdisco_hip.so */
         std::vector<RankResult> res((size_t)gpus);
         std::vector<std::thread> th;
+        /* every rank writes its share of the text files from its GPU — under the conditions of the single-GPU device path: text is wanted and
+         * nothing else needs the records on the host (no binary side output, no partial simplification), exact overlaps, at most 256 edge
+         * files, no DISCO_HOST_TEXT (DISCO_HOST_CONTAINED_TEXT: the contained files alone stay with the host writer).
+         * Opt-in: DISCO_DIST_GPU_TEXT=1 (DIST_GPU_TEXT_DEFAULT above says why); unset or 0: the host writer for both kinds */
+        const char *dgt = getenv("DISCO_DIST_GPU_TEXT");
+        const bool dev_text_wanted = (dgt ? strcmp(dgt, "0") != 0 : DIST_GPU_TEXT_DEFAULT) && !no_text && !binary_out && par_simple.empty() && !max_subs && !getenv("DISCO_HOST_TEXT") &&
+                                     !getenv("DISCO_TEXT_VIA_HOST");
+        const bool dev_contained_wanted = dev_text_wanted && !getenv("DISCO_HOST_CONTAINED_TEXT");
+        const bool dev_edges_wanted = dev_text_wanted && n_edge_files <= 256;
         const std::vector<uint64_t> woff = ingested ? std::vector<uint64_t>() : rs.word_offsets();
         if (ctx.empty())
             if (const std::string e = make_ranks(); !e.empty()) return die(e);
@@ -744,22 +764,109 @@ int main(int argc, char **argv)
                 if (disco_dist_run_graph(c, DISCO_DIST_GATHER_READS | (partitioned_index ? DISCO_DIST_KEEP_INDEX_PARTITIONED : 0)) < 0) bail("disco_dist_run_graph");
                 if (disco_dist_get_info(c, &R.info) < 0) bail("disco_dist_get_info");
                 if (verbose && r == 0) fprintf(stderr, "[disco host] transport %s, %d ranks\n", disco_comm_kind(c), gpus);
-                at(ST_FETCH_CONTAINED);
-                R.rows.resize(R.info.n_contained_local);
-                if (R.info.n_contained_local && disco_fetch_contained(c, R.rows.data(), R.info.n_contained_local) < 0) bail("disco_fetch_contained");
-                at(ST_FETCH_EDGES);
-                R.n_edges = R.info.e_out_local;
-                R.edges.reset(new disco_edge[std::max<uint64_t>(R.n_edges, 1)]);
-                if (R.n_edges && disco_fetch_edges(c, R.edges.get(), R.n_edges) < 0) bail("disco_fetch_edges");
-                if (max_subs) {
-                    R.subs.reset(new uint16_t[std::max<uint64_t>(R.n_edges, 1)]);
-                    if (R.n_edges && disco_fetch_edge_substitutions(c, R.subs.get(), R.n_edges) < 0) bail("disco_fetch_edge_substitutions");
+                R.pass_end = Clock::now();
+                /* The rank's share of the files from its GPU: the files f of a kind with floor(f gpus / files) == r. Both calls are collective
+                 * and end alike on every rank, so the ranks take the same way without asking each other: all of them write their files, or —
+                 * DISCO_E_UNSUPPORTED / DISCO_E_NOMEM — all of them hand their rows / edges to the host writer below, in the same run */
+                auto t_lap = Clock::now();
+                auto rank_lap = [&](const char *what) {
+                    if (verbose) fprintf(stderr, "[disco host] rank %d: %-36s %.3f s\n", r, what, secs(t_lap));
+                    t_lap = Clock::now();
+                };
+                const bool identity = rs.total_records == rs.size(); /* no record was filtered: file index = read id + 1 */
+                auto own_files = [&](int n_files, int *lo, int *hi) {
+                    *lo = (int)(((int64_t)r * n_files + gpus - 1) / gpus);
+                    *hi = (int)(((int64_t)(r + 1) * n_files + gpus - 1) / gpus);
+                };
+                auto close_all = [](std::vector<int> &fds) {
+                    for (int fd : fds)
+                        if (fd >= 0) close(fd);
+                };
+                R.dev_contained = dev_contained_wanted;
+                if (R.dev_contained) {
+                    at(ST_FORMAT_CONTAINED);
+                    const int ncf = (int)ctags_early.tag.size();
+                    std::vector<uint64_t> coff((size_t)ncf + 1, 0);
+                    const int64_t nb = disco_dist_format_contained(c, (uint32_t)ncf, identity ? nullptr : rs.file_index.data(), coff.data());
+                    if (nb == DISCO_E_NOMEM || nb == DISCO_E_UNSUPPORTED) {
+                        if (verbose) fprintf(stderr, "[disco host] rank %d: contained lines by the host writer: %s\n", r, disco_last_error(c));
+                        R.dev_contained = false;
+                    } else if (nb < 0)
+                        bail("disco_dist_format_contained");
+                    else {
+                        rank_lap("format contained lines on the GPU");
+                        at(ST_WRITE_CONTAINED);
+                        int lo, hi;
+                        own_files(ncf, &lo, &hi);
+                        std::vector<int> fds((size_t)ncf, -1);
+                        std::string ferr;
+                        if (!disco::open_contained_files(prefix, ncf, &ctags_early, fds.data(), ferr, lo, hi)) {
+                            std::cout << "\nError (rank " << r << "): " << ferr << std::endl;
+                            _exit(2);
+                        }
+                        const int wrc = disco_write_contained_text(c, fds.data(), (uint32_t)ncf, (uint32_t)threads);
+                        close_all(fds);
+                        if (wrc < 0) bail("disco_write_contained_text");
+                        rank_lap("contained lines into the files");
+                    }
+                }
+                if (!R.dev_contained) {
+                    at(ST_FETCH_CONTAINED);
+                    R.rows.resize(R.info.n_contained_local);
+                    if (R.info.n_contained_local && disco_fetch_contained(c, R.rows.data(), R.info.n_contained_local) < 0) bail("disco_fetch_contained");
+                }
+                R.dev_edges = dev_edges_wanted;
+                if (R.dev_edges) {
+                    at(ST_FORMAT_EDGES);
+                    std::vector<uint64_t> eoff((size_t)n_edge_files + 1, 0);
+                    const int64_t nb = disco_dist_format_edges(c, (uint32_t)n_edge_files, identity ? nullptr : rs.file_index.data(), eoff.data());
+                    if (nb == DISCO_E_NOMEM || nb == DISCO_E_UNSUPPORTED) {
+                        if (verbose) fprintf(stderr, "[disco host] rank %d: edge lines by the host writer: %s\n", r, disco_last_error(c));
+                        R.dev_edges = false;
+                    } else if (nb < 0)
+                        bail("disco_dist_format_edges");
+                    else {
+                        rank_lap("partition + format edge lines on the GPU");
+                        at(ST_WRITE_EDGES);
+                        int lo, hi;
+                        own_files(n_edge_files, &lo, &hi);
+                        const disco::FileTags et = mpi_names ? disco::FileTags::mpi_edges(gpus, threads) : disco::FileTags::plain(threads);
+                        std::vector<int> fds((size_t)n_edge_files, -1);
+                        std::string ferr;
+                        if (!disco::open_edge_files(prefix, n_edge_files, &et, rs.size(), fds.data(), ferr, lo, hi)) {
+                            std::cout << "\nError (rank " << r << "): " << ferr << std::endl;
+                            _exit(2);
+                        }
+                        const int wrc = disco_write_edge_text(c, fds.data(), (uint32_t)n_edge_files, (uint32_t)threads);
+                        close_all(fds);
+                        if (wrc < 0) bail("disco_write_edge_text");
+                        rank_lap("edge lines into the files");
+                    }
+                }
+                if (!R.dev_edges) {
+                    at(ST_FETCH_EDGES);
+                    R.n_edges = R.info.e_out_local;
+                    R.edges.reset(new disco_edge[std::max<uint64_t>(R.n_edges, 1)]);
+                    if (R.n_edges && disco_fetch_edges(c, R.edges.get(), R.n_edges) < 0) bail("disco_fetch_edges");
+                    if (max_subs) {
+                        R.subs.reset(new uint16_t[std::max<uint64_t>(R.n_edges, 1)]);
+                        if (R.n_edges && disco_fetch_edge_substitutions(c, R.subs.get(), R.n_edges) < 0) bail("disco_fetch_edge_substitutions");
+                    }
                 }
                 at(ST_DONE);
             });
         for (auto &t : th) t.join();
         ranks_done.store(true);
-        t_graph = secs(t0);
+        const bool dev_contained = res[0].dev_contained, dev_edges = res[0].dev_edges;
+        for (auto &R : res)
+            if (R.dev_contained != dev_contained || R.dev_edges != dev_edges) return die("the ranks disagree about who writes the text files");
+        /* (where the ranks wrote files, the graph was complete when the last rank left the pass: what they did behind it is output stage) */
+        auto t_pass_end = Clock::now();
+        if (dev_contained || dev_edges) {
+            t_pass_end = res[0].pass_end;
+            for (auto &R : res) t_pass_end = std::max(t_pass_end, R.pass_end);
+        }
+        t_graph = std::chrono::duration<double>(t_pass_end - t0).count();
         const disco_dist_info &di = res[0].info;
         n_cont = di.n_contained;
         e_pre = di.e_pre;
@@ -780,15 +887,18 @@ int main(int argc, char **argv)
             std::cout << "Note: this input is in the order-dependent regime of the reference (edge cap per k-mer reached or overlaps found from one "
                          "side only); the reference's own result varies with its thread count here."
                       << std::endl;
-        t0 = Clock::now();
+        t0 = dev_contained || dev_edges ? t_pass_end : Clock::now();
         t1 = Clock::now();
+        if (verbose && (dev_contained || dev_edges)) fprintf(stderr, "[disco host] %-28s %.3f s\n", "text files by the ranks", secs(t_pass_end));
+        contained_on_gpu = dev_contained;
+        edge_text_streamed = dev_edges;
         /* the ranks' shares side by side: contained rows of rank r's reads, edges whose smaller endpoint rank r owns */
         uint64_t nr = 0, ne = 0;
         for (auto &R : res) {
             nr += R.rows.size();
             ne += R.n_edges;
         }
-        if (nr != n_cont || ne != e_out) return die("the ranks' shares do not add up to the job's totals");
+        if ((!dev_contained && nr != n_cont) || (!dev_edges && ne != e_out)) return die("the ranks' shares do not add up to the job's totals");
         rows.reserve(nr);
         for (auto &R : res) {
             rows.insert(rows.end(), R.rows.begin(), R.rows.end());
@@ -805,9 +915,11 @@ int main(int argc, char **argv)
             R.subs.reset();
         }
         lap("gather the ranks' shares");
-        edge_file.reset(new uint16_t[std::max<uint64_t>(e_out, 1)]);
-        if (e_out && disco_partition_edges(ctx[0], edges.get(), e_out, rs.size(), (uint32_t)n_edge_files, edge_file.get()) < 0) return die(disco_last_error(ctx[0]));
-        lap("partition edges into files");
+        if (!dev_edges) {
+            edge_file.reset(new uint16_t[std::max<uint64_t>(e_out, 1)]);
+            if (e_out && disco_partition_edges(ctx[0], edges.get(), e_out, rs.size(), (uint32_t)n_edge_files, edge_file.get()) < 0) return die(disco_last_error(ctx[0]));
+            lap("partition edges into files");
+        }
         if (gpu_chains && e_out) { /* the ranks' edges lie on the host: rank 0's context, which holds every read's length, contracts them */
             uint64_t nc = 0, nl = 0;
             DISCO_CALL(ctx[0], disco_contract_chains_of(ctx[0], edges.get(), e_out, min_overlap_simplify, &nc, &nl));

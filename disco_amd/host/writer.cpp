@@ -397,14 +397,16 @@ bool write_edge_text(const std::string &prefix, int n_files, const char *text, c
 
 /* the edge files of write_edge_text, created empty and handed back open (disco_write_edge_text fills them), with their
  * <prefix>_<tag>_startRead.txt (layout compatibility: one start id per file, BG/OverlapGraph.cpp:211) */
-bool open_edge_files(const std::string &prefix, int n_files, const FileTags *tags, uint64_t n_reads, int *fds, std::string &err)
+bool open_edge_files(const std::string &prefix, int n_files, const FileTags *tags, uint64_t n_reads, int *fds, std::string &err, int t_lo, int t_hi)
 {
-    for (int t = 0; t < n_files; t++) {
+    if (t_hi < 0) t_hi = n_files;
+    for (int t = 0; t < n_files; t++) fds[t] = -1;
+    for (int t = t_lo; t < t_hi; t++) {
         const std::string path = prefix + "_" + tag_of(tags, t) + "_parGraph.txt";
         fds[t] = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (fds[t] < 0) {
             err = "Unable to write file: " + path;
-            for (int x = 0; x < t; x++) close(fds[x]);
+            for (int x = t_lo; x < t; x++) close(fds[x]);
             return false;
         }
         std::string e2;
@@ -415,14 +417,16 @@ bool open_edge_files(const std::string &prefix, int n_files, const FileTags *tag
 }
 
 /* the contained-read files, created empty and handed back open (disco_write_contained_text fills them) */
-bool open_contained_files(const std::string &prefix, int n_files, const FileTags *tags, int *fds, std::string &err)
+bool open_contained_files(const std::string &prefix, int n_files, const FileTags *tags, int *fds, std::string &err, int t_lo, int t_hi)
 {
-    for (int t = 0; t < n_files; t++) {
+    if (t_hi < 0) t_hi = n_files;
+    for (int t = 0; t < n_files; t++) fds[t] = -1;
+    for (int t = t_lo; t < t_hi; t++) {
         const std::string path = prefix + "_" + tag_of(tags, t) + "_containedReads.txt";
         fds[t] = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (fds[t] < 0) {
             err = "Unable to write file: " + path;
-            for (int x = 0; x < t; x++) close(fds[x]);
+            for (int x = t_lo; x < t; x++) close(fds[x]);
             return false;
         }
     }

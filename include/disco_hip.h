@@ -459,6 +459,25 @@ int     disco_fetch_contained_text(disco_ctx *ctx, char *out, uint64_t cap);
 /* ... or straight into the caller's open files, through the pinned ring as disco_write_edge_text */
 int     disco_write_contained_text(disco_ctx *ctx, const int *fds, uint32_t n_files, uint32_t host_threads);
 
+/* ---- the text files of a multi-GPU job, every rank its own ------------------------------------------------------------------------ */
+/* COLLECTIVE, after disco_dist_run_graph, every rank with the same n_files (and the same file_index, or null on all). For F files of
+ * one kind and G ranks, rank r holds the text of the files f with floor(f G / F) == r — a contiguous run, empty for some ranks when
+ * F < G — and file_offsets[F + 1] has equal offsets for every other file; the return value is the number of bytes THIS rank holds.
+ * disco_fetch_contained_text / disco_write_contained_text and disco_fetch_edge_text / disco_write_edge_text then deliver them as on
+ * one GPU (the writers skip empty files: a rank hands over descriptors for its own files only, or for all).
+ * disco_dist_format_contained: the lines of disco_format_contained. A rank's files are the containing reads [ceil(f_lo n / F),
+ * ceil(f_hi n / F)); the reduced containment keys — a rank holds its home slice — are all-gathered (per x 8 bytes per rank, in place:
+ * disco_fetch_contained still returns the rank's home rows afterwards, and a later pass is not disturbed), the rows of the range are
+ * grouped, sorted and formatted on the rank's device. Byte for byte the single-GPU files.
+ * disco_dist_format_edges: the lines of disco_format_edges for ALL edges of the job, in files cut along connected components as
+ * disco_fetch_edge_files / disco_partition_edges cut them (the same assignment: it depends on the set of edges only). The ranks'
+ * edges are all-gathered (12 bytes per edge) and every rank computes the partition on its own device; the order of the lines inside
+ * a file is the order of the ranks, then of disco_fetch_edges. At most 256 files, exact overlaps, fewer than 2^31 reads — otherwise
+ * DISCO_E_UNSUPPORTED on every rank alike, before anything is exchanged. A rank that cannot allocate says so before the gather and
+ * every rank returns its code: no rank is left inside a collective. */
+int64_t disco_dist_format_contained(disco_ctx *ctx, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets);
+int64_t disco_dist_format_edges(disco_ctx *ctx, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,7 +74,8 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     srcs = [s for s in HOST_SOURCES if os.path.exists(s)]
     if not srcs:
         return ""
-    deps = srcs + [os.path.join(HERE, "host", f) for f in os.listdir(os.path.join(HERE, "host")) if f.endswith(".h")] + [LIB]
+    partext = os.path.join(HERE, "csrc", "disco_partext.h")  # parsimple.cpp formats with the kernels' item functions when it has no device
+    deps = srcs + [os.path.join(HERE, "host", f) for f in os.listdir(os.path.join(HERE, "host")) if f.endswith(".h")] + [LIB, partext]
     if force or _stale(BUILDG, deps):
         os.makedirs(os.path.dirname(BUILDG), exist_ok=True)
         cmd = ["g++", "-O2", "-std=c++17", "-fopenmp", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", BUILDG] + srcs + [
@@ -91,7 +92,7 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
         subprocess.check_call(cmd)
     ps = os.path.join(HERE, "bin", "parsimplify")
     psrc = [os.path.join(HERE, "host", f) for f in ("parsimplify_main.cpp", "parsimple.cpp", "fastx.cpp", "writer.cpp")]
-    if force or _stale(ps, psrc + [os.path.join(HERE, "host", f) for f in ("parsimple.h", "writer.h", "fastx.h")]):
+    if force or _stale(ps, psrc + [os.path.join(HERE, "host", f) for f in ("parsimple.h", "writer.h", "fastx.h")] + [partext]):
         cmd = ["g++", "-O2", "-std=c++17", "-fopenmp", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", ps] + psrc + ["-lz"]
         if verbose:
             print(" ".join(cmd))
@@ -116,6 +117,14 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     ssrc = [os.path.join(HERE, "host", "survivor_check.cpp"), os.path.join(HERE, "csrc", "disco_survivor.h")]
     if force or _stale(sv, ssrc):
         cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", sv, ssrc[0]]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    # the item functions behind the ParSimpleEdges lines on the host: the header the kernels include, as plain C++
+    pc = os.path.join(HERE, "bin", "partext_check")
+    pcsrc = [os.path.join(HERE, "host", "partext_check.cpp"), partext, os.path.join(ROOT, "include", "disco_hip.h")]
+    if force or _stale(pc, pcsrc):
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", pc, pcsrc[0]]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

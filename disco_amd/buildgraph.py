@@ -119,6 +119,12 @@ ABI = [
     ("disco_write_contained_text", C.c_int, [_P, _P, C.c_uint32, C.c_uint32]),
     ("disco_dist_format_contained", C.c_int64, [_P, C.c_uint32, _P, _P]),
     ("disco_dist_format_edges", C.c_int64, [_P, C.c_uint32, _P, _P]),
+    ("disco_fetch_chain_residue", C.c_int64, [_P, _P, _P, C.c_uint64]),
+    ("disco_fetch_chain_first_edges", C.c_int, [_P, _P]),
+    ("disco_fetch_chain_end_links", C.c_int, [_P, _P, _P]),
+    ("disco_format_par_simple", C.c_int64, [_P, C.c_uint32, _P, _P, C.c_uint64, _P, C.c_uint64, _P]),
+    ("disco_fetch_par_simple_text", C.c_int, [_P, _P, C.c_uint64]),
+    ("disco_write_par_simple_text", C.c_int, [_P, _P, C.c_uint32, C.c_uint32]),
 ]
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
@@ -131,6 +137,21 @@ DIST_KEEP_INDEX_PARTITIONED = 2
 
 CHAIN_EDGE_DTYPE = np.dtype([("a", "<u8"), ("b", "<u8"), ("offset", "<u8"), ("orient", "<u4"), ("n_links", "<u4"), ("first_link", "<u8")])
 CHAIN_LINK_DTYPE = np.dtype([("to", "<u4"), ("offset", "<u4"), ("orient", "<u4")])
+
+
+class PsEdge(C.Structure):  # disco_ps_edge: a final edge of the partial simplification, in printing direction
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("offset", C.c_uint64), ("orient", C.c_uint32), ("file", C.c_uint32),
+                ("first_piece", C.c_uint64), ("n_pieces", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class PsPiece(C.Structure):  # disco_ps_piece: kind 0 an inline link into read a, 1 / 2 all links of composite edge a forward / reversed
+    _fields_ = [("kind", C.c_uint32), ("a", C.c_uint32), ("offset", C.c_uint32), ("orient", C.c_uint32)]
+
+
+# the same two records as numpy dtypes (arrays of them are what format_par_simple takes)
+PS_EDGE_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("offset", "<u8"), ("orient", "<u4"), ("file", "<u4"), ("first_piece", "<u8"), ("n_pieces", "<u4"), ("pad", "<u4")])
+PS_PIECE_DTYPE = np.dtype([("kind", "<u4"), ("a", "<u4"), ("offset", "<u4"), ("orient", "<u4")])
+assert PS_EDGE_DTYPE.itemsize == C.sizeof(PsEdge) and PS_PIECE_DTYPE.itemsize == C.sizeof(PsPiece)
 
 
 class IngestFile(C.Structure):
@@ -468,6 +489,51 @@ class BuildGraph:
         self._chk(self.L.disco_fetch_chains(self._h, comp.ctypes.data if len(comp) else None, links.ctypes.data if len(links) else None,
                                             absorbed.ctypes.data if ne else None))
         return comp, links, absorbed
+
+    def chain_residue(self, records: bool = True):
+        """what the last contract_chains left for the host (disco_fetch_chain_residue): the positions, in fetch order, of the edges that
+        pass the overlap filter and went into no composite edge, and (records=True; only after contract_chains without `edges`) their
+        records [EDGE_DTYPE]: (edge_index, edges or None)"""
+        n = self._chk(self.L.disco_fetch_chain_residue(self._h, None, None, 0))
+        idx = np.zeros(n, dtype=np.uint64)
+        rec = np.zeros(n, dtype=EDGE_DTYPE) if records else None
+        got = self._chk(self.L.disco_fetch_chain_residue(self._h, idx.ctypes.data, rec.ctypes.data if records else None, n))
+        assert got == n
+        return idx, rec
+
+    def chain_first_edges(self, n_composite: int) -> np.ndarray:
+        """for every composite edge of the last contract_chains the fetch-order position of the edge behind its first link"""
+        out = np.zeros(n_composite, dtype=np.uint64)
+        self._chk(self.L.disco_fetch_chain_first_edges(self._h, out.ctypes.data if n_composite else None))
+        return out
+
+    def chain_end_links(self, n_composite: int):
+        """the first link every composite edge prints, forward and turned round (disco_fetch_chain_end_links): two CHAIN_LINK_DTYPE arrays"""
+        first, last_rev = np.zeros(n_composite, dtype=CHAIN_LINK_DTYPE), np.zeros(n_composite, dtype=CHAIN_LINK_DTYPE)
+        self._chk(self.L.disco_fetch_chain_end_links(self._h, first.ctypes.data if n_composite else None, last_rev.ctypes.data if n_composite else None))
+        return first, last_rev
+
+    def format_par_simple(self, edges, pieces, n_files: int = 1, file_index=None):
+        """the lines of the ParSimpleEdges files from a description (PS_EDGE_DTYPE, PS_PIECE_DTYPE) and the device's link arrays
+        (disco_format_par_simple): offsets [n_files + 1]; fetch_par_simple_text / write_par_simple_text deliver the text"""
+        edges = np.ascontiguousarray(edges, dtype=PS_EDGE_DTYPE)
+        pieces = np.ascontiguousarray(pieces, dtype=PS_PIECE_DTYPE)
+        off = np.zeros(n_files + 1, dtype=np.uint64)
+        fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
+        self._chk(self.L.disco_format_par_simple(self._h, n_files, None if fi is None else fi.ctypes.data, edges.ctypes.data if len(edges) else None, len(edges),
+                                                 pieces.ctypes.data if len(pieces) else None, len(pieces), off.ctypes.data))
+        return off
+
+    def fetch_par_simple_text(self, n_bytes: int) -> bytes:
+        """the text of the last format_par_simple (n_bytes = its last offset)"""
+        buf = np.empty(max(int(n_bytes), 1), dtype=np.uint8)
+        self._chk(self.L.disco_fetch_par_simple_text(self._h, buf.ctypes.data, int(n_bytes)))
+        return buf[:int(n_bytes)].tobytes()
+
+    def write_par_simple_text(self, fds, threads: int = 8):
+        """the text of the last format_par_simple straight from the device into open files: fds[f] receives file f"""
+        arr = (C.c_int * len(fds))(*fds)
+        self._chk(self.L.disco_write_par_simple_text(self._h, arr, len(fds), threads))
 
     def fetch_edge_substitutions(self) -> np.ndarray:
         """substitutions of every edge's overlap, in the order of fetch_edges (all 0 unless max_substitutions > 0)"""

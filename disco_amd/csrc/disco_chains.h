@@ -179,7 +179,7 @@ struct ChainLinkOut { /* = disco_chain_link: the overlap INTO read `to` along th
 };
 
 __global__ void ch_emit_kernel(ChainView g, const u8 *__restrict__ internal, const ChRank *__restrict__ r, const u64 *__restrict__ comp_id,
-                               const u64 *__restrict__ link_start, ChainEdgeOut *__restrict__ comp, ChainLinkOut *__restrict__ links)
+                               const u64 *__restrict__ link_start, ChainEdgeOut *__restrict__ comp, ChainLinkOut *__restrict__ links, u64 *__restrict__ first_edge)
 {
     u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; s < g.n_slots; s += (u64)gridDim.x * blockDim.x) {
@@ -202,7 +202,65 @@ __global__ void ch_emit_kernel(ChainView g, const u8 *__restrict__ internal, con
             e.n_links = rh.cnt;
             e.first_link = first;
             comp[comp_id[hs]] = e;
+            first_edge[comp_id[hs]] = g.pos ? g.pos[s] : s; /* (index 0: this slot holds the first link) */
         }
+    }
+}
+
+/* the residue: the edges that pass the filter and went into no composite edge. Slot order is fetch order, so a flag per slot, its
+ * exclusive scan and a scatter compact them in that order */
+__global__ void ch_residue_flag_kernel(ChainView g, const u8 *__restrict__ dead, u8 *__restrict__ flag)
+{
+    u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; s < g.n_slots; s += (u64)gridDim.x * blockDim.x) flag[s] = (ch_kept(g, s) && !dead[g.pos ? g.pos[s] : s]) ? 1 : 0;
+}
+__global__ void ch_residue_scatter_kernel(ChainView g, const u8 *__restrict__ flag, const u64 *__restrict__ at, u64 *__restrict__ res_pos, u64 *__restrict__ res_slot)
+{
+    u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; s < g.n_slots; s += (u64)gridDim.x * blockDim.x)
+        if (flag[s]) {
+            res_pos[at[s]] = g.pos ? g.pos[s] : s;
+            res_slot[at[s]] = s;
+        }
+}
+/* the first link of every composite edge in either direction: links[0], and the reverse of its last link (as disco_partext.h turns a
+ * composite edge round). The host pass orders parallel edges that agree in everything a header shows by the first link they print. */
+__global__ void ch_end_links_kernel(const ChainEdgeOut *__restrict__ comp, const ChainLinkOut *__restrict__ links, const u16 *__restrict__ len, u64 n_comp,
+                                    ChainLinkOut *__restrict__ first, ChainLinkOut *__restrict__ last_rev)
+{
+    u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; k < n_comp; k += (u64)gridDim.x * blockDim.x) {
+        const ChainEdgeOut c = comp[k];
+        first[k] = links[c.first_link];
+        const ChainLinkOut l = links[c.first_link + c.n_links - 1];
+        const u32 from = c.n_links > 1 ? links[c.first_link + c.n_links - 2].to : (u32)c.a;
+        ChainLinkOut r;
+        r.to = from;
+        r.offset = (u32)((int)len[l.to] + (int)l.offset - (int)len[from]);
+        r.orient = ch_twin(l.orient);
+        last_rev[k] = r;
+    }
+}
+
+struct ChEdgeOut { /* = disco_edge */
+    u64 src, dst;
+    u32 orient, offset, len_src, len_dst;
+};
+/* the residue's records, gathered from the emission's slots (disco_fetch_edges' decoding) */
+__global__ void ch_residue_records_kernel(const u64 *__restrict__ src, const u64 *__restrict__ ent, const u16 *__restrict__ len, const u64 *__restrict__ res_slot, u64 n_res,
+                                          ChEdgeOut *__restrict__ out)
+{
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i < n_res; i += (u64)gridDim.x * blockDim.x) {
+        const u64 s = res_slot[i], e = ent[s];
+        ChEdgeOut o;
+        o.src = src[s];
+        o.dst = ADJ_DST(e);
+        o.orient = ADJ_ORI(e);
+        o.offset = ADJ_OFF(e);
+        o.len_src = len[o.src];
+        o.len_dst = ADJ_DLEN(e);
+        out[i] = o;
     }
 }
 

@@ -43,6 +43,7 @@
 #define DROP_LIST_CAP (1u << 20) /* dropped hits edge selection writes down for the twin search (16 MB); more than that: the bitmap search */
 #include "disco_chains.h"
 #include "disco_text.h"
+#include "disco_partext.h"
 #include "disco_ingest.h"
 #include "disco_bgzf.h"
 #include "read_filter_tables.h"
@@ -360,6 +361,15 @@ struct disco_ctx {
     DevBuf<u8> d_ch_dead;
     u64 ch_comp_n = 0, ch_links_n = 0, ch_edges_n = 0;
     bool ch_ready = false;
+    /* ... and what the host pass needs of it (disco_fetch_chain_residue / _first_edges): the edges no composite took, by fetch-order
+     * position and by slot, and the position of the edge behind every composite's first link */
+    DevBuf<u64> d_ch_first, d_ch_res_pos, d_ch_res_slot;
+    u64 ch_res_n = 0;
+    bool ch_resident = false; /* contracted from the emission's slots (disco_contract_chains), which still hold the records */
+    /* disco_format_par_simple: the lines of the ParSimpleEdges files, kept apart from the two other texts */
+    DevBuf<char> d_ptext;
+    std::vector<u64> ptext_off;
+    u64 ptext_bytes = 0;
     DevBuf<char> d_text; /* disco_format_edges: the edge lines of all files, file after file */
     u64 text_bytes = 0;
     DevBuf<u64> d_out_src, d_out_ent; /* (grow together) */
@@ -766,6 +776,13 @@ static void free_graph_state(disco_ctx *c)
     release(c, c->d_ch_comp);
     release(c, c->d_ch_links);
     release(c, c->d_ch_dead);
+    release(c, c->d_ch_first);
+    release(c, c->d_ch_res_pos);
+    release(c, c->d_ch_res_slot);
+    c->ch_res_n = 0;
+    release(c, c->d_ptext);
+    c->ptext_bytes = 0;
+    c->ptext_off.clear();
     release(c, c->d_text);
     c->text_bytes = 0;
     release(c, c->d_ctext);
@@ -4568,6 +4585,8 @@ static int contract_chains(disco_ctx *c, const u64 *d_src, const u64 *d_ent, con
 {
     DISCO_TRACE("contract_chains");
     c->ch_ready = false;
+    c->ptext_bytes = 0; /* (a text formatted from the contraction before this one names composite edges that are gone) */
+    c->ptext_off.clear();
     if (n_slots >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "chain contraction: more than 2^31 edge slots");
     ChainView g;
     g.src = d_src;
@@ -4623,9 +4642,21 @@ static int contract_chains(disco_ctx *c, const u64 *d_src, const u64 *d_ent, con
         CHK((scan_exclusive<u32, u64>(c, links_of, n_slots, link_start, false, &n_links)));
         CHK(ensure(c, c->d_ch_comp, std::max<u64>(n_comp, 1)));
         CHK(ensure(c, c->d_ch_links, std::max<u64>(n_links, 1)));
-        hipLaunchKernelGGL(ch_emit_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, ra, comp_id, link_start, c->d_ch_comp, c->d_ch_links);
+        CHK(ensure(c, c->d_ch_first, std::max<u64>(n_comp, 1)));
+        hipLaunchKernelGGL(ch_emit_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, ra, comp_id, link_start, c->d_ch_comp, c->d_ch_links,
+                           c->d_ch_first);
+        HIPCHK(c, hipGetLastError());
+        /* the residue, compacted in fetch order (the flags and the scan reuse the buffers of the heads, which the emission is through with) */
+        u64 n_res = 0;
+        hipLaunchKernelGGL(ch_residue_flag_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, (const u8 *)c->d_ch_dead, is_head.p);
+        CHK((scan_exclusive<u8, u64>(c, is_head, n_slots, comp_id, false, &n_res)));
+        CHK(ensure(c, c->d_ch_res_pos, std::max<u64>(n_res, 1)));
+        CHK(ensure(c, c->d_ch_res_slot, std::max<u64>(n_res, 1)));
+        hipLaunchKernelGGL(ch_residue_scatter_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, (const u8 *)is_head, (const u64 *)comp_id, c->d_ch_res_pos.p,
+                           c->d_ch_res_slot.p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->ch_res_n = n_res;
         c->ch_comp_n = n_comp;
         c->ch_links_n = n_links;
         c->ch_edges_n = ne;
@@ -4652,10 +4683,11 @@ int disco_contract_chains(disco_ctx *c, uint32_t min_overlap_simplify, uint64_t 
     if (c->phase < 8) return fail(c, DISCO_E_STATE, "disco_contract_chains: run disco_transitive_reduce first");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n_out == 0) {
-        c->ch_comp_n = c->ch_links_n = c->ch_edges_n = 0;
+        c->ch_comp_n = c->ch_links_n = c->ch_edges_n = c->ch_res_n = 0;
         c->ch_ready = true;
     } else
         CHK(contract_chains(c, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c), c->out_used, c->n_out, c->n, min_overlap_simplify));
+    c->ch_resident = true;
     if (n_composite) *n_composite = c->ch_comp_n;
     if (n_links) *n_links = c->ch_links_n;
     return DISCO_OK;
@@ -4667,8 +4699,9 @@ int disco_contract_chains_of(disco_ctx *c, const disco_edge *edges, uint64_t n_e
     if (c->phase < 1) return fail(c, DISCO_E_STATE, "disco_contract_chains_of: the context holds no reads (their lengths are needed)");
     HIPCHK(c, hipSetDevice(c->device));
     c->ch_ready = false;
+    c->ch_resident = false;
     if (n_edges == 0) {
-        c->ch_comp_n = c->ch_links_n = c->ch_edges_n = 0;
+        c->ch_comp_n = c->ch_links_n = c->ch_edges_n = c->ch_res_n = 0;
         c->ch_ready = true;
     } else {
         DevBuf<u64> d_src, d_ent, d_pos;
@@ -4720,6 +4753,204 @@ int disco_fetch_chains(disco_ctx *c, disco_chain_edge *comp, disco_chain_link *l
     if (edge_absorbed && c->ch_edges_n) HIPCHK(c, hipMemcpyAsync(edge_absorbed, c->d_ch_dead, c->ch_edges_n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DISCO_OK;
+}
+
+int64_t disco_fetch_chain_residue(disco_ctx *c, uint64_t *edge_index, disco_edge *edges, uint64_t cap)
+{
+    if (!c) return DISCO_E_ARG;
+    if (!c->ch_ready) return fail(c, DISCO_E_STATE, "disco_fetch_chain_residue: run disco_contract_chains first");
+    const u64 nr = c->ch_res_n;
+    if (!edge_index && !edges) return (int64_t)nr;
+    if (edges && !c->ch_resident) return fail(c, DISCO_E_STATE, "disco_fetch_chain_residue: the edges were the caller's (disco_contract_chains_of): it holds the records");
+    if (cap < nr) return fail(c, DISCO_E_ARG, "disco_fetch_chain_residue: need room for %llu edges", (unsigned long long)nr);
+    if (nr == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    static_assert(sizeof(disco_edge) == sizeof(ChEdgeOut) && sizeof(uint64_t) == sizeof(u64), "residue records");
+    DevBuf<ChEdgeOut> rec;
+    auto body = [&]() -> int {
+        if (edge_index) HIPCHK(c, hipMemcpyAsync(edge_index, c->d_ch_res_pos, nr * 8, hipMemcpyDeviceToHost, c->stream));
+        if (edges) {
+            CHK(ensure(c, rec, nr));
+            hipLaunchKernelGGL(ch_residue_records_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const u64 *)c->d_out_src, (const u64 *)c->d_out_ent, (const u16 *)c->d_len,
+                               (const u64 *)c->d_ch_res_slot, nr, rec.p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(edges, rec, nr * sizeof(ChEdgeOut), hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return DISCO_OK;
+    };
+    const int rc = body();
+    release(c, rec);
+    return rc != DISCO_OK ? rc : (int64_t)nr;
+}
+
+int disco_fetch_chain_first_edges(disco_ctx *c, uint64_t *first_edge)
+{
+    if (!c || (!first_edge && c->ch_ready && c->ch_comp_n)) return DISCO_E_ARG;
+    if (!c->ch_ready) return fail(c, DISCO_E_STATE, "disco_fetch_chain_first_edges: run disco_contract_chains first");
+    if (c->ch_comp_n == 0) return DISCO_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(first_edge, c->d_ch_first, c->ch_comp_n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DISCO_OK;
+}
+
+int disco_fetch_chain_end_links(disco_ctx *c, disco_chain_link *first, disco_chain_link *last_reversed)
+{
+    if (!c || ((!first || !last_reversed) && c->ch_ready && c->ch_comp_n)) return DISCO_E_ARG;
+    if (!c->ch_ready) return fail(c, DISCO_E_STATE, "disco_fetch_chain_end_links: run disco_contract_chains first");
+    const u64 nc = c->ch_comp_n;
+    if (nc == 0) return DISCO_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<ChainLinkOut> d;
+    auto body = [&]() -> int {
+        CHK(ensure(c, d, 2 * nc));
+        hipLaunchKernelGGL(ch_end_links_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, (const ChainEdgeOut *)c->d_ch_comp, (const ChainLinkOut *)c->d_ch_links,
+                           (const u16 *)c->d_len, nc, d.p, d.p + nc);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(first, d.p, nc * sizeof(ChainLinkOut), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(last_reversed, d.p + nc, nc * sizeof(ChainLinkOut), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return DISCO_OK;
+    };
+    const int rc = body();
+    release(c, d);
+    return rc;
+}
+
+/* ---- the lines of the ParSimpleEdges files from the host pass's description and the device's link arrays (disco_partext.h) ---- */
+int64_t disco_format_par_simple(disco_ctx *c, uint32_t n_files, const uint64_t *file_index, const disco_ps_edge *edges, uint64_t n_edges, const disco_ps_piece *pieces,
+                                uint64_t n_pieces, uint64_t *file_offsets)
+{
+    DISCO_TRACE("disco_format_par_simple");
+    if (!c || !file_offsets || n_files == 0 || (n_edges && !edges) || (n_pieces && !pieces)) return DISCO_E_ARG;
+    if (!c->ch_ready) return fail(c, DISCO_E_STATE, "disco_format_par_simple: run disco_contract_chains first");
+    HIPCHK(c, hipSetDevice(c->device));
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
+    c->ptext_bytes = 0;
+    c->ptext_off.assign((size_t)n_files + 1, 0);
+    if (n_edges == 0) return 0;
+    /* the description is small: everything a lane will index with is checked here, before anything is launched */
+    std::vector<disco_chain_edge> comp(c->ch_comp_n);
+    if (c->ch_comp_n) {
+        HIPCHK(c, hipMemcpyAsync(comp.data(), c->d_ch_comp, c->ch_comp_n * sizeof(ChainEdgeOut), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    std::vector<u64> piece_link(n_pieces + 1, 0), edge_item(n_edges + 1, 0), first_item((size_t)n_files + 1, 0);
+    for (u64 p = 0; p < n_pieces; p++) {
+        const disco_ps_piece &x = pieces[p];
+        u64 nl = 1;
+        if (x.kind == 0) {
+            if (x.a >= c->n) return fail(c, DISCO_E_ARG, "disco_format_par_simple: piece %llu names read %u of %llu", (unsigned long long)p, x.a, (unsigned long long)c->n);
+        } else if (x.kind == 1 || x.kind == 2) {
+            if (x.a >= c->ch_comp_n)
+                return fail(c, DISCO_E_ARG, "disco_format_par_simple: piece %llu names composite edge %u of %llu", (unsigned long long)p, x.a, (unsigned long long)c->ch_comp_n);
+            nl = comp[x.a].n_links;
+        } else
+            return fail(c, DISCO_E_ARG, "disco_format_par_simple: piece %llu is of kind %u", (unsigned long long)p, x.kind);
+        piece_link[p + 1] = piece_link[p] + nl;
+    }
+    uint32_t file = 0;
+    for (u64 e = 0; e < n_edges; e++) {
+        const disco_ps_edge &x = edges[e];
+        if (x.n_pieces == 0 || x.first_piece > n_pieces || x.n_pieces > n_pieces - x.first_piece)
+            return fail(c, DISCO_E_ARG, "disco_format_par_simple: the pieces of edge %llu lie outside the %llu given", (unsigned long long)e, (unsigned long long)n_pieces);
+        if (x.src >= c->n || x.dst >= c->n) return fail(c, DISCO_E_ARG, "disco_format_par_simple: edge %llu names a read the context does not hold", (unsigned long long)e);
+        if (x.file >= n_files || x.file < file) return fail(c, DISCO_E_ARG, "disco_format_par_simple: the files of the edges must ascend and lie below %u (edge %llu)", n_files, (unsigned long long)e);
+        edge_item[e + 1] = edge_item[e] + (piece_link[x.first_piece + x.n_pieces] - piece_link[x.first_piece]);
+        for (; file < x.file; file++) first_item[(size_t)file + 1] = edge_item[e];
+    }
+    const u64 n_items = edge_item[n_edges];
+    for (; file < n_files; file++) first_item[(size_t)file + 1] = n_items;
+    DevBuf<disco_ps_edge> d_edges;
+    DevBuf<disco_ps_piece> d_pieces;
+    DevBuf<u64> d_edge_item, d_piece_link, d_first_item, d_findex, place, d_off;
+    DevBuf<u8> bytes;
+    auto body = [&]() -> int {
+        CHK(ensure(c, d_edges, n_edges));
+        CHK(ensure(c, d_pieces, std::max<u64>(n_pieces, 1)));
+        CHK(ensure(c, d_edge_item, n_edges + 1));
+        CHK(ensure(c, d_piece_link, n_pieces + 1));
+        CHK(ensure(c, d_first_item, (u64)n_files + 1));
+        CHK(ensure(c, d_off, (u64)n_files + 1));
+        CHK(ensure(c, bytes, n_items));
+        CHK(ensure(c, place, n_items + 1));
+        HIPCHK(c, hipMemcpyAsync(d_edges, edges, n_edges * sizeof(disco_ps_edge), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_pieces, pieces, n_pieces * sizeof(disco_ps_piece), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_edge_item, edge_item.data(), (n_edges + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_piece_link, piece_link.data(), (n_pieces + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_first_item, first_item.data(), ((size_t)n_files + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if (file_index) {
+            CHK(ensure(c, d_findex, c->n));
+            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        PsView g;
+        g.edges = d_edges;
+        g.pieces = d_pieces;
+        g.edge_item = (const uint64_t *)d_edge_item.p;
+        g.piece_link = (const uint64_t *)d_piece_link.p;
+        g.comp = (const disco_chain_edge *)c->d_ch_comp.p;
+        g.links = (const disco_chain_link *)c->d_ch_links.p;
+        g.len = c->d_len;
+        g.file_index = (const uint64_t *)d_findex.p;
+        g.n_edges = n_edges;
+        g.n_pieces = n_pieces;
+        g.n_items = n_items;
+        hipLaunchKernelGGL(ptext_measure_kernel, dim3(flat_grid(c, n_items)), dim3(256), 0, c->stream, g, bytes.p);
+        u64 total = 0;
+        CHK((scan_exclusive<u8, u64>(c, bytes, n_items, place, true, &total)));
+        hipLaunchKernelGGL(ptext_offsets_kernel, dim3(1), dim3(256), 0, c->stream, (const uint64_t *)d_first_item.p, (const u64 *)place, n_files, (uint64_t *)d_off.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->ptext_off.data(), d_off, ((size_t)n_files + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        CHK(ensure(c, c->d_ptext, std::max<u64>(total, 1)));
+        hipLaunchKernelGGL(ptext_write_kernel, dim3(flat_grid(c, n_items)), dim3(256), 0, c->stream, g, (const u64 *)place, c->d_ptext.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->ptext_bytes = total;
+        return DISCO_OK;
+    };
+    const int rc = body();
+    release(c, d_edges);
+    release(c, d_pieces);
+    release(c, d_edge_item);
+    release(c, d_piece_link);
+    release(c, d_first_item);
+    release(c, d_findex);
+    release(c, place);
+    release(c, d_off);
+    release(c, bytes);
+    if (rc != DISCO_OK) {
+        c->ptext_off.assign((size_t)n_files + 1, 0);
+        return rc;
+    }
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = c->ptext_off[f];
+    if (getenv("DISCO_VERBOSE"))
+        fprintf(stderr, "[disco] par-simple lines: %llu edges, %llu pieces, %llu items, %llu bytes\n", (unsigned long long)n_edges, (unsigned long long)n_pieces,
+                (unsigned long long)n_items, (unsigned long long)c->ptext_bytes);
+    return (int64_t)c->ptext_bytes;
+}
+
+int disco_fetch_par_simple_text(disco_ctx *c, char *out, uint64_t cap)
+{
+    if (!c || (!out && c->ptext_bytes)) return DISCO_E_ARG;
+    if (cap < c->ptext_bytes) return fail(c, DISCO_E_ARG, "disco_fetch_par_simple_text: need room for %llu bytes", (unsigned long long)c->ptext_bytes);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->ptext_bytes) {
+        HIPCHK(c, hipMemcpyAsync(out, c->d_ptext, c->ptext_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return DISCO_OK;
+}
+
+int disco_write_par_simple_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t host_threads)
+{
+    DISCO_TRACE("disco_write_par_simple_text");
+    if (!c || !fds) return DISCO_E_ARG;
+    if (c->ptext_off.size() != (size_t)n_files + 1) return fail(c, DISCO_E_STATE, "disco_write_par_simple_text: run disco_format_par_simple for %u files first", n_files);
+    HIPCHK(c, hipSetDevice(c->device));
+    (void)host_threads;
+    if (c->ptext_bytes == 0) return DISCO_OK;
+    return write_text_through_ring(c, "disco_write_par_simple_text", c->d_ptext, c->ptext_off, fds, n_files);
 }
 
 int disco_set_query_order(disco_ctx *c, const void *d_order_u64)

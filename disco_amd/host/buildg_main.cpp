@@ -17,6 +17,7 @@
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <signal.h>
+#include <fcntl.h>
 #include <unistd.h>
 
 #include <cerrno>
@@ -134,6 +135,14 @@ static bool read_min_overlap(const std::string &path, uint32_t &mo, std::string 
  * pins a 256 MB staging ring for a few MB of text, one rank after the other) and faster at 50 M; the whole process is faster at both. Slower
  * at either size means opt-in; what one GPU and one link per rank gain is a measurement this pool cannot make. */
 static const bool DIST_GPU_TEXT_DEFAULT = false;
+
+/* buildG --par-simple on one GPU: the ParSimpleEdges files written from the device (disco_format_par_simple) instead of from the edges,
+ * links and text fetched to the host. Measured against the commit before it, both in one session on one box, text output, three runs each
+ * (profiles/par_simple_text.txt): from "fetch contained rows" through "partial simplification" 1.53-1.57 s -> 0.22 s at 5*10^7 x 150 bp
+ * (45 M edges, 631 MB of lines) and 0.19-0.23 s -> 0.022 s on the 10 M-read metagenome graph; the process 2.7-3.5 s -> 1.0 s and (page
+ * cache warm) 0.70-1.04 s -> 0.54-0.63 s. Lower at both shapes by more than either range: the default. DISCO_PAR_SIMPLE_GPU_TEXT=0 or
+ * DISCO_PAR_SIMPLE_HOST_TEXT=1 keep the flow through the host. */
+static const bool PAR_SIMPLE_GPU_TEXT_DEFAULT = true;
 
 static int die(const std::string &msg)
 {
@@ -548,6 +557,14 @@ int main(int argc, char **argv)
     }
     /* chains of the reduced graph contracted while it is still on the GPU (the consumer's parsimplify step, --par-simple) */
     const bool gpu_chains = !par_simple.empty() && !mpi_names && !getenv("DISCO_PAR_SIMPLE_HOST");
+    /* ... and, on one GPU, its files written from there too: the host pass gets the residue of the contraction and the composite edges'
+     * headers, describes every final line as pieces, and the device formats the lines from its own link arrays into the open files
+     * (disco_format_par_simple) — the edges, the links and the text never lie on the host. DISCO_PAR_SIMPLE_GPU_TEXT=1 / =0 choose,
+     * DISCO_PAR_SIMPLE_HOST_TEXT=1 forces the flow through the host (PAR_SIMPLE_GPU_TEXT_DEFAULT above says which is the default) */
+    const char *psgt = getenv("DISCO_PAR_SIMPLE_GPU_TEXT");
+    bool par_simple_on_gpu = gpu_chains && gpus == 1 && !max_subs && !getenv("DISCO_PAR_SIMPLE_HOST_TEXT") &&
+                             (psgt ? strcmp(psgt, "0") != 0 : PAR_SIMPLE_GPU_TEXT_DEFAULT);
+    bool par_simple_done = false;
     std::unique_ptr<char[]> edge_text;      /* the edge lines, formatted on the GPU (single GPU, exact overlaps) */
     std::vector<uint64_t> edge_text_off;
     std::vector<disco_chain_edge> ch_comp;
@@ -675,7 +692,7 @@ int main(int argc, char **argv)
             const int64_t nb = disco_format_edges(ctx, (uint32_t)n_edge_files, edge_file.get(), identity ? nullptr : rs.file_index.data(), edge_text_off.data());
             if (nb < 0) return die(disco_last_error(ctx));
             lap("format edge lines on the GPU");
-            if (!binary_out && par_simple.empty() && !getenv("DISCO_TEXT_VIA_HOST")) {
+            if (!binary_out && (par_simple.empty() || par_simple_on_gpu) && !getenv("DISCO_TEXT_VIA_HOST")) {
                 /* straight from the device into the edge files (pieces through a pinned ring, host threads pwrite behind the copies) */
                 const disco::FileTags et = mpi_names ? disco::FileTags::mpi_edges(gpus, threads) : disco::FileTags::plain(threads);
                 std::vector<int> fds((size_t)n_edge_files, -1);
@@ -694,16 +711,99 @@ int main(int argc, char **argv)
             }
         }
         /* the edges as host records: only for what still works on them there (binary side output, partial simplification, host-formatted text) */
-        if (binary_out || !par_simple.empty() || (!edge_text && !edge_text_streamed && !no_text)) {
+        auto fetch_edges = [&]() -> bool {
             edges.reset(new disco_edge[std::max<uint64_t>(e_out, 1)]); /* 1.8 GB at 45 M edges: not zero-filled first */
-            if (e_out && disco_fetch_edges(ctx, edges.get(), e_out) < 0) return die(disco_last_error(ctx));
+            if (e_out && disco_fetch_edges(ctx, edges.get(), e_out) < 0) return false;
             if (max_subs) {
                 edge_subs.reset(new uint16_t[std::max<uint64_t>(e_out, 1)]);
-                if (e_out && disco_fetch_edge_substitutions(ctx, edge_subs.get(), e_out) < 0) return die(disco_last_error(ctx));
+                if (e_out && disco_fetch_edge_substitutions(ctx, edge_subs.get(), e_out) < 0) return false;
             }
             lap("fetch edges");
-        }
-        if (gpu_chains && e_out) {
+            return true;
+        };
+        if (binary_out || (!par_simple.empty() && !par_simple_on_gpu) || (!edge_text && !edge_text_streamed && !no_text))
+            if (!fetch_edges()) return die(disco_last_error(ctx));
+        if (par_simple_on_gpu && e_out) {
+            /* contract -> residue, headers, first edges -> the host rounds on that small graph -> the lines from the device into the files.
+             * A call that has no memory or does not support the case hands the run back to the flow through the host, below */
+            uint64_t nc = 0, nl = 0;
+            DISCO_CALL(ctx, disco_contract_chains(ctx, min_overlap_simplify, &nc, &nl));
+            const int n_ps_files = threads;
+            auto give_up = [&](const char *what) {
+                if (verbose) fprintf(stderr, "[disco host] partial simplification through the host: %s: %s\n", what, disco_last_error(ctx));
+                par_simple_on_gpu = false;
+            };
+            auto soft = [](int64_t rc) { return rc == DISCO_E_NOMEM || rc == DISCO_E_UNSUPPORTED; };
+            const int64_t nres = disco_fetch_chain_residue(ctx, nullptr, nullptr, 0);
+            if (nres < 0) return die(disco_last_error(ctx));
+            std::vector<uint64_t> res_index((size_t)nres), first_edge(nc);
+            std::vector<disco_edge> res_edges((size_t)nres);
+            ch_comp.resize(nc);
+            int64_t rc = disco_fetch_chain_residue(ctx, res_index.data(), res_edges.data(), (uint64_t)nres);
+            if (rc >= 0) rc = disco_fetch_chains(ctx, ch_comp.data(), nullptr, nullptr);
+            if (rc >= 0) rc = disco_fetch_chain_first_edges(ctx, first_edge.data());
+            std::vector<disco_chain_link> comp_first(nc), comp_last_rev(nc);
+            if (rc >= 0) rc = disco_fetch_chain_end_links(ctx, comp_first.data(), comp_last_rev.data());
+            if (soft(rc)) give_up("fetching the residue");
+            else if (rc < 0) return die(disco_last_error(ctx));
+            lap("contract chains on the GPU");
+            if (par_simple_on_gpu) {
+                std::vector<uint16_t> res_file((size_t)nres), comp_file(nc);
+                for (int64_t i = 0; i < nres; i++) res_file[(size_t)i] = edge_file[res_index[(size_t)i]];
+                for (uint64_t k = 0; k < nc; k++) comp_file[k] = edge_file[first_edge[k]];
+                disco::ChainResidue res;
+                res.edges = res_edges.data();
+                res.edge_file = res_file.data();
+                res.n_edges = (uint64_t)nres;
+                res.comp = ch_comp.data();
+                res.comp_file = comp_file.data();
+                res.n_comp = nc;
+                res.comp_first = comp_first.data();
+                res.comp_last_rev = comp_last_rev.data();
+                disco::ParSimpleDescription desc;
+                disco::ParSimpleStats ps;
+                if (!disco::write_par_simple_residue(par_simple, n_ps_files, res, rs, err, &ps, nullptr, nullptr, &desc)) return die(err);
+                lap("partial simplification: host rounds");
+                const bool identity = rs.total_records == rs.size();
+                std::vector<uint64_t> poff((size_t)n_ps_files + 1, 0);
+                const int64_t nb = disco_format_par_simple(ctx, (uint32_t)n_ps_files, identity ? nullptr : rs.file_index.data(), desc.edges.data(), desc.edges.size(),
+                                                           desc.pieces.data(), desc.pieces.size(), poff.data());
+                if (soft(nb)) give_up("formatting the lines");
+                else if (nb < 0) return die(disco_last_error(ctx));
+                else {
+                    if (verbose)
+                        fprintf(stderr, "[disco host] partial simplification on the GPU: residue %lld edges + %llu composite edges -> %zu final edges in %zu pieces (%llu reversed, at most %u in one edge), %lld bytes of text\n",
+                                (long long)nres, (unsigned long long)nc, desc.edges.size(), desc.pieces.size(), (unsigned long long)desc.reversed_pieces, desc.max_pieces, (long long)nb);
+                    const disco::FileTags pt = disco::FileTags::plain(threads);
+                    std::vector<int> fds((size_t)n_ps_files, -1);
+                    bool opened = true;
+                    for (int t = 0; t < n_ps_files && opened; t++) {
+                        const std::string path = par_simple + "_" + pt.tag[(size_t)t] + "_ParSimpleEdges.txt";
+                        fds[(size_t)t] = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+                        if (fds[(size_t)t] < 0) {
+                            opened = false;
+                            err = "Unable to write file: " + path;
+                        }
+                    }
+                    const int wrc = opened ? disco_write_par_simple_text(ctx, fds.data(), (uint32_t)n_ps_files, (uint32_t)threads) : 0;
+                    for (int fd : fds)
+                        if (fd >= 0) close(fd);
+                    if (!opened) return die(err);
+                    if (wrc < 0) return die(disco_last_error(ctx));
+                    std::cout << "Partial simplification (the reference's parsimplify step) on the resident graph: " << ps.edges_in << " edges -> " << ps.edges_out << " ("
+                              << ps.nodes_absorbed << " nodes absorbed into composite edges, " << ps.dead_end_nodes << " dead-end nodes, " << ps.rounds << " rounds); files "
+                              << par_simple << "_<i>_ParSimpleEdges.txt" << std::endl;
+                    lap("partial simplification");
+                    par_simple_done = true;
+                }
+            }
+            if (!par_simple_on_gpu) { /* handed back: what the flow through the host works on */
+                if (!edges && !fetch_edges()) return die(disco_last_error(ctx));
+                ch_links.reset(new disco_chain_link[std::max<uint64_t>(nl, 1)]);
+                ch_absorbed.reset(new uint8_t[e_out]);
+                DISCO_CALL(ctx, disco_fetch_chains(ctx, ch_comp.data(), ch_links.get(), ch_absorbed.get()));
+            }
+        } else if (gpu_chains && e_out) {
             uint64_t nc = 0, nl = 0;
             DISCO_CALL(ctx, disco_contract_chains(ctx, min_overlap_simplify, &nc, &nl));
             ch_comp.resize(nc);
@@ -940,7 +1040,7 @@ int main(int argc, char **argv)
         if (!disco::write_binary(prefix, (int)etags.tag.size(), (int)ctags.tag.size(), edges.get(), e_out, e_out ? edge_file.get() : nullptr, rows, rs, err, edge_subs.get())) return die(err);
         lap("write binary side output");
     }
-    if (!par_simple.empty() && !mpi_names) {
+    if (!par_simple.empty() && !mpi_names && !par_simple_done) {
         disco::ParSimpleStats ps;
         disco::ChainSeed seed;
         if (ch_absorbed) {

@@ -11,7 +11,9 @@
  *     src \t dst \t orient,offset,offset+len(dst),0,0 \t (read,orientation bit,offset)(…)…        source < destination
  * The result is the same SET of lines parsimplify writes for the same edge file (tests/test_host.py compares them sorted; the
  * reference's own line order depends on its container history, and a ring of absorbable nodes ends in a loop whose direction
- * the reference decides by pointer comparison).
+ * the reference decides by pointer comparison). The ORDER of the lines in a file is this project's own and is a function of the
+ * lines alone: by (smaller id, larger id), then — for parallel edges — by offset, number of links and orientation AS PRINTED, then by
+ * the first link the line prints, which no two edges share. So every flow that arrives at the same edges writes the same bytes.
  */
 #ifndef DISCO_PARSIMPLE_H_
 #define DISCO_PARSIMPLE_H_
@@ -47,6 +49,38 @@ bool write_par_simple(const std::string &prefix, int n_files, const disco_edge *
                       const uint8_t *marked = nullptr /* [n reads] nodes all of whose edges are in their file (flags 0 / 1 / 2 of the edge
                                                          lines, SG/OverlapGraphSimple.cpp:591-644); null: every node, as in buildG's files */,
                       const ChainSeed *seed = nullptr /* only with marked == null (the GPU contraction knows no marks) */);
+
+/* ---- the same pass from the RESIDUE of a chain contraction on the GPU ------------------------------------------------------------
+ * What the device hands over after disco_contract_chains is small: the simple edges no composite edge took
+ * (disco_fetch_chain_residue) and one header per composite edge (disco_fetch_chains without links, disco_fetch_chain_first_edges for
+ * their files). The pass — rings, dead ends, the later rounds to the fixpoint, the files' order — works on that graph with the
+ * device's composite edges held as handles: everything the rules ask of an edge follows from its header (number of links, the offset
+ * in either direction, the orientation at either end). No array has one entry per read: nodes are numbered by their place among the
+ * reads the residue touches. The result is a description of every final line as a short list of pieces (disco_ps_edge /
+ * disco_ps_piece, include/disco_hip.h), which disco_format_par_simple turns into text where the links are. Same files, same
+ * ParSimpleStats as write_par_simple with a ChainSeed. */
+struct ChainResidue {
+    const disco_edge *edges = nullptr;      /* [n_edges] the residue                                                        */
+    const uint16_t *edge_file = nullptr;    /* [n_edges] their files (null: file 0)                                         */
+    uint64_t n_edges = 0;
+    const disco_chain_edge *comp = nullptr; /* [n_comp] the composite edges' headers                                        */
+    const uint16_t *comp_file = nullptr;    /* [n_comp] their files (null: file 0)                                          */
+    uint64_t n_comp = 0;
+    const disco_chain_link *comp_first = nullptr, *comp_last_rev = nullptr; /* [n_comp] the first link each prints, forward and turned
+                                               round (disco_fetch_chain_end_links): what orders parallel edges with equal headers; null:
+                                               taken from links                                                              */
+    const disco_chain_link *links = nullptr; /* the composite edges' links: only to format on the host (no sink)            */
+};
+struct ParSimpleDescription {
+    std::vector<disco_ps_edge> edges; /* printing direction, by file, in the files' line order */
+    std::vector<disco_ps_piece> pieces;
+    uint64_t reversed_pieces = 0; /* pieces of kind 2                 */
+    uint32_t max_pieces = 0;      /* the largest piece count of an edge */
+};
+/* sink != null: the description goes there and no file is written (prefix / tags / paths are not used);
+ * sink == null: res.links must be given, and the files are formatted and written here (disco_partext.h's functions, on the host) */
+bool write_par_simple_residue(const std::string &prefix, int n_files, const ChainResidue &res, const ReadSet &rs, std::string &err, ParSimpleStats *stats = nullptr,
+                              const FileTags *tags = nullptr, const std::vector<std::string> *paths = nullptr, ParSimpleDescription *sink = nullptr);
 
 } // namespace disco
 #endif

@@ -478,6 +478,54 @@ int     disco_write_contained_text(disco_ctx *ctx, const int *fds, uint32_t n_fi
 int64_t disco_dist_format_contained(disco_ctx *ctx, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets);
 int64_t disco_dist_format_edges(disco_ctx *ctx, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets);
 
+/* ---- the lines of the ParSimpleEdges files, formatted on the GPU (disco_amd/csrc/disco_partext.h) ------------------------------------ */
+/* After a chain contraction the host needs only the RESIDUE to finish the partial simplification (disco_amd/host/parsimple.h): the edges
+ * that pass the min_overlap_simplify filter and were not absorbed, and one header per composite edge (disco_fetch_chains with links ==
+ * NULL). Links and absorbed edges stay on the device.
+ * disco_fetch_chain_residue: the residue in the order of disco_fetch_edges (or of the array given to disco_contract_chains_of);
+ * edge_index[i] is the edge's position in that order (the index into what disco_fetch_edge_files returned). Returns the count; with
+ * both pointers null the count only, otherwise cap entries must hold it. `edges` receives the records — after disco_contract_chains
+ * only: after disco_contract_chains_of the caller holds them, and a non-null `edges` is DISCO_E_STATE.
+ * disco_fetch_chain_first_edges: one position in the same order per composite edge — the edge that holds its first link (a composite
+ * edge lies in one file: the file of that edge). first_edge[n_composite]. */
+int64_t disco_fetch_chain_residue(disco_ctx *ctx, uint64_t *edge_index, disco_edge *edges, uint64_t cap);
+int disco_fetch_chain_first_edges(disco_ctx *ctx, uint64_t *first_edge);
+/* the first link every composite edge prints, in either direction: first[k] = its link 0, last_reversed[k] = its last link turned round
+ * ({to = the read before the last, offset = len[b] + offset - len[to], orient = twin}). Two parallel edges that agree in everything a
+ * header shows (the two sides of a bubble) are ordered in the files by the first link they print. [n_composite] each. */
+int disco_fetch_chain_end_links(disco_ctx *ctx, disco_chain_link *first, disco_chain_link *last_reversed);
+/* The final edges of the partial simplification, described by the host pass: every line as a short list of pieces. */
+typedef struct disco_ps_edge { /* in printing direction (src <= dst), in the files' line order */
+    uint64_t src, dst;
+    uint64_t offset;
+    uint32_t orient;
+    uint32_t file;
+    uint64_t first_piece; /* its pieces are pieces[first_piece .. first_piece + n_pieces), n_pieces >= 1 */
+    uint32_t n_pieces;
+    uint32_t pad;
+} disco_ps_edge;
+typedef struct disco_ps_piece {
+    uint32_t kind;   /* 0: one inline link into read a, with this offset and orientation
+                        1: all links of the device's composite edge a, forward
+                        2: all links of the device's composite edge a, reversed: for j = n_links-1 .. 0 the link {to = from_j,
+                           offset = len[l_j.to] + l_j.offset - len[from_j], orient = twin(l_j.orient)}, from_j = l_{j-1}.to, from_0 = the edge's a */
+    uint32_t a;
+    uint32_t offset; /* kind 0 only */
+    uint32_t orient; /* kind 0 only */
+} disco_ps_piece;
+/* disco_format_par_simple: the lines "src \t dst \t orient,offset,offset+len(dst),0,0 \t" + "(file_index[to],orient&1,offset)" for every
+ * link of the edge but the last + "\n" (printEdge, SG/OverlapGraphSimple.cpp:658-690), formatted from the device's own link arrays;
+ * file_index as for disco_format_edges (null: read id + 1). The edges' files must ascend; the text of file t is bytes
+ * [file_offsets[t], file_offsets[t + 1]) of what disco_fetch_par_simple_text copies out; returns the total number of bytes. The
+ * description is validated before anything is launched — piece ranges inside `pieces`, composite ids below n_composite, read ids below
+ * disco_num_reads, files ascending and below n_files: DISCO_E_ARG, the context stays usable. DISCO_E_STATE without a finished
+ * contraction, DISCO_E_NOMEM when the text does not fit. Kept apart from the edge text and the contained text. */
+int64_t disco_format_par_simple(disco_ctx *ctx, uint32_t n_files, const uint64_t *file_index, const disco_ps_edge *edges, uint64_t n_edges,
+                                const disco_ps_piece *pieces, uint64_t n_pieces, uint64_t *file_offsets);
+int     disco_fetch_par_simple_text(disco_ctx *ctx, char *out, uint64_t cap);
+/* ... or straight into the caller's open files, through the pinned ring as disco_write_edge_text (empty files are skipped) */
+int     disco_write_par_simple_text(disco_ctx *ctx, const int *fds, uint32_t n_files, uint32_t host_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,12 @@ ABI = [
     ("disco_format_par_simple", C.c_int64, [_P, C.c_uint32, _P, _P, C.c_uint64, _P, C.c_uint64, _P]),
     ("disco_fetch_par_simple_text", C.c_int, [_P, _P, C.c_uint64]),
     ("disco_write_par_simple_text", C.c_int, [_P, _P, C.c_uint32, C.c_uint32]),
+    ("disco_prepare_edge_records", C.c_int64, [_P, C.c_uint32, _P, _P]),
+    ("disco_fetch_edge_records", C.c_int, [_P, _P, C.c_uint64]),
+    ("disco_write_edge_records", C.c_int, [_P, C.c_int, C.c_uint64, C.c_uint32]),
+    ("disco_prepare_contained_records", C.c_int64, [_P, C.c_uint32, _P]),
+    ("disco_fetch_contained_records", C.c_int, [_P, _P, C.c_uint64]),
+    ("disco_write_contained_records", C.c_int, [_P, C.c_int, C.c_uint64, C.c_uint32]),
 ]
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
@@ -185,6 +191,7 @@ PHASES = ("index", "probe_kernel", "verify", "contain", "select", "csr", "twin",
 INSPECT_ABI = [
     ("disco_fetch_order", C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     ("disco_fetch_survivor_layout", C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("disco_set_record_piece", C.c_int, [_P, C.c_uint64]),
 ]
 _inspect_bound = False
 
@@ -534,6 +541,48 @@ class BuildGraph:
         """the text of the last format_par_simple straight from the device into open files: fds[f] receives file f"""
         arr = (C.c_int * len(fds))(*fds)
         self._chk(self.L.disco_write_par_simple_text(self._h, arr, len(fds), threads))
+
+    # -- the records of the binary side output, formed on the GPU (disco_amd/edgefile.py has the dtypes and reads the files) ----
+    def prepare_edge_records(self, n_files: int = 1, edge_file=None, file_index=None) -> int:
+        """after transitive_reduce: the edges' records are ready to leave (disco_prepare_edge_records); edge_file as fetch_edge_files
+        returns it (None: one file), file_index None: read id + 1. Returns the number of records"""
+        ef = None if edge_file is None else np.ascontiguousarray(edge_file, dtype=np.uint16)
+        fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
+        return self._chk(self.L.disco_prepare_edge_records(self._h, n_files, None if ef is None else ef.ctypes.data, None if fi is None else fi.ctypes.data))
+
+    def fetch_edge_records(self, n: int) -> np.ndarray:
+        """the n records of the last prepare_edge_records as an array of edgefile.EDGE, in the order of fetch_edges"""
+        from .edgefile import EDGE
+
+        out = np.zeros(n, dtype=EDGE)
+        self._chk(self.L.disco_fetch_edge_records(self._h, out.ctypes.data if n else None, n))
+        return out
+
+    def write_edge_records(self, fd: int, file_offset: int = 32, threads: int = 8):
+        """... or straight into the open file fd from byte file_offset on (32: behind the header)"""
+        self._chk(self.L.disco_write_edge_records(self._h, fd, file_offset, threads))
+
+    def prepare_contained_records(self, n_files: int = 1, file_index=None) -> int:
+        """from mark_contained on: the contained rows grouped and sorted on the device, ready to leave as records
+        (disco_prepare_contained_records). Returns the number of records"""
+        fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
+        return self._chk(self.L.disco_prepare_contained_records(self._h, n_files, None if fi is None else fi.ctypes.data))
+
+    def fetch_contained_records(self, n: int) -> np.ndarray:
+        """the n records of the last prepare_contained_records as an array of edgefile.CONTAINED: ascending (containing read, j, contained read)"""
+        from .edgefile import CONTAINED
+
+        out = np.zeros(n, dtype=CONTAINED)
+        self._chk(self.L.disco_fetch_contained_records(self._h, out.ctypes.data if n else None, n))
+        return out
+
+    def write_contained_records(self, fd: int, file_offset: int = 32, threads: int = 8):
+        self._chk(self.L.disco_write_contained_records(self._h, fd, file_offset, threads))
+
+    def set_record_piece(self, records: int = 0):
+        """records per piece of the fetch / write calls above (0: the default, a half of the pinned ring). Tests only"""
+        _bind_inspect(self.L)
+        self._chk(self.L.disco_set_record_piece(self._h, records))
 
     def fetch_edge_substitutions(self) -> np.ndarray:
         """substitutions of every edge's overlap, in the order of fetch_edges (all 0 unless max_substitutions > 0)"""

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -43,6 +44,7 @@
 #define DROP_LIST_CAP (1u << 20) /* dropped hits edge selection writes down for the twin search (16 MB); more than that: the bitmap search */
 #include "disco_chains.h"
 #include "disco_text.h"
+#include "disco_binrec.h"
 #include "disco_partext.h"
 #include "disco_ingest.h"
 #include "disco_bgzf.h"
@@ -371,6 +373,18 @@ struct disco_ctx {
     std::vector<u64> ptext_off;
     u64 ptext_bytes = 0;
     DevBuf<char> d_text; /* disco_format_edges: the edge lines of all files, file after file */
+    /* the records of the binary side output (disco_prepare_*_records, disco_binrec.h): what a prepare call uploaded or grouped, kept until
+     * the next pass; the records themselves exist one piece at a time (d_rec_piece: two buffers of rec_piece_cap records) */
+    DevBuf<u16> d_rec_efile, d_rec_subs;
+    DevBuf<u64> d_rec_efindex, d_rec_cfindex;
+    DevBuf<u64> d_rec_cword; /* the contained rows, grouped and sorted (group_contained_rows) */
+    DevBuf<u32> d_rec_csup;
+    bool rec_e_ready = false, rec_e_has_file = false, rec_e_has_findex = false, rec_e_has_subs = false;
+    bool rec_c_ready = false, rec_c_has_findex = false;
+    u32 rec_e_files = 0, rec_c_files = 0;
+    u64 rec_c_n = 0;
+    DevBuf<u64> d_rec_piece[2];
+    u64 rec_piece = 0; /* records per piece; 0: what a ring half holds (disco_set_record_piece: tests) */
     u64 text_bytes = 0;
     DevBuf<u64> d_out_src, d_out_ent; /* (grow together) */
     u64 out_used = 0; /* chunk slots written by the emission (survivors + ~0 tails) */
@@ -723,8 +737,30 @@ static int scan_exclusive(disco_ctx *c, const InT *in, u64 n, OutT *out, bool wr
     return scan_exclusive_on<InT, OutT>(c, c->stream, c->d_tile, c->d_total, in, n, out, write_total, total_host);
 }
 
+/* what disco_prepare_edge_records / disco_prepare_contained_records left belongs to the pass that made the edges / the contained flags:
+ * the phases that make new ones take it away (the piece buffers stay: they are sized by the piece, not by the pass) */
+static void drop_edge_records(disco_ctx *c)
+{
+    c->rec_e_ready = false;
+    release(c, c->d_rec_efile);
+    release(c, c->d_rec_subs);
+    release(c, c->d_rec_efindex);
+}
+static void drop_contained_records(disco_ctx *c)
+{
+    c->rec_c_ready = false;
+    c->rec_c_n = 0;
+    release(c, c->d_rec_cword);
+    release(c, c->d_rec_csup);
+    release(c, c->d_rec_cfindex);
+}
+
 static void free_graph_state(disco_ctx *c)
 {
+    drop_edge_records(c);
+    drop_contained_records(c);
+    release(c, c->d_rec_piece[0]);
+    release(c, c->d_rec_piece[1]);
     /* a key exchange that still runs behind a pass (second communicator, bulk_stream) reads and writes best[]: it is through before the
      * buffer goes back to the arena — a pass that failed after the exchange was issued, or new reads right after a pass, used to free
      * it under the collective */
@@ -3050,6 +3086,8 @@ int disco_probe(disco_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     CHK(settle_contained_rows(c)); /* rows of the previous pass still travelling read best[] */
     CHK(settle_keys(c));           /* ... and so does a key exchange that runs behind a multi-GPU pass */
+    drop_edge_records(c);          /* prepared records are those of the previous pass */
+    drop_contained_records(c);
     settle_hits_prealloc(c);
     const u64 nq = c->q_hi - c->q_lo;
     CHK(ensure(c, c->d_best, c->n_alloc));
@@ -3262,6 +3300,7 @@ int disco_mark_contained(disco_ctx *c, uint64_t *n_contained)
     if (!c) return DISCO_E_ARG;
     if (c->phase < 3) return fail(c, DISCO_E_STATE, "disco_mark_contained: run disco_probe first");
     HIPCHK(c, hipSetDevice(c->device));
+    drop_contained_records(c);
     CHK(ensure(c, c->d_contained, c->n_alloc));
     CHK(ensure(c, c->d_cbits, c->n_alloc / 64 + 1));
     CHK(zero_counter(c, CTR_N_CONTAINED));
@@ -3768,6 +3807,7 @@ int disco_emit_edges(disco_ctx *c, uint64_t *n_out)
     if (!c) return DISCO_E_ARG;
     if (c->phase < 7) return fail(c, DISCO_E_STATE, "disco_emit_edges: run disco_transitive_mark first");
     HIPCHK(c, hipSetDevice(c->device));
+    drop_edge_records(c);
     const u64 nq = c->q_hi - c->q_lo;
     ph_begin(c, DISCO_PH_EMIT);
     const int grid = wq_grid(c, emit_kernel<false>, nq, "DISCO_EMIT_WAVES"); /* (the dense instantiation over the few wide nodes takes it too: 4 KB of LDS more) */
@@ -4355,19 +4395,27 @@ int disco_fetch_edge_text(disco_ctx *c, char *out, uint64_t cap)
  * leaves the device in 128 MB pieces through the context's pinned ring, and while a piece travels host threads pwrite the one before
  * it — the mirror image of disco_ingest_fasta's file reader. (disco_fetch_edge_text into 2.5 GB of fresh pageable memory, then the
  * writer: 0.19 s at config 3; this: the link's 0.05 s.) d_text: the files' text one behind the other, off: n_files + 1 offsets into it */
-static int write_text_through_ring(disco_ctx *c, const char *who, const char *d_text, const std::vector<u64> &off, const int *fds, uint32_t n_files)
+static const size_t OUT_RING_HALF = 128u << 20;
+/* the context's pinned ring for something that leaves the device (first use: allocated, with its two events) */
+static int output_ring(disco_ctx *c, const char *who)
 {
-    const size_t HALF = 128u << 20;
     CHK(ring_back_from_rows(c));
     if (!c->h_ring) {
-        if (hipHostMalloc(&c->h_ring, 2 * HALF, ring_alloc_flags()) != hipSuccess) {
+        if (hipHostMalloc(&c->h_ring, 2 * OUT_RING_HALF, ring_alloc_flags()) != hipSuccess) {
             c->h_ring = nullptr;
             (void)hipGetLastError();
             return fail(c, DISCO_E_NOMEM, "%s: no pinned staging memory", who);
         }
-        c->ring_half = HALF;
+        c->ring_half = OUT_RING_HALF;
         for (int i = 0; i < 2; i++) HIPCHK(c, hipEventCreateWithFlags(&c->ev_ring[i], hipEventDisableTiming));
     }
+    return DISCO_OK;
+}
+
+static int write_text_through_ring(disco_ctx *c, const char *who, const char *d_text, const std::vector<u64> &off, const int *fds, uint32_t n_files)
+{
+    const size_t HALF = OUT_RING_HALF;
+    CHK(output_ring(c, who));
     /* one writer per file and round: writes to ONE file serialise on its inode lock (16 threads on one file: 12 GB/s; one thread on each
      * of 16 files: the link's rate) */
     std::atomic<bool> ok{true};
@@ -4435,46 +4483,80 @@ int disco_write_edge_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32
 /* the body of disco_format_contained and disco_dist_format_contained: the rows of the containing reads [s_lo, s_hi) out of best[0, n).
  * flags != null: the contained reads are the flagged ones and nc of them have a containing read in the range (one GPU: all of them,
  * known since disco_mark_contained); flags == null: read off the keys, counted here (a rank of a multi-GPU job) */
+/* The contained rows of the containing reads [s_lo, s_hi), grouped by containing read and every group sorted — steps 1 and 2 of the text of
+ * the contained-read files, which the records of the binary side output (disco_prepare_contained_records) take too: afterwards row i is
+ * word[i] (CWORD_MAKE: j, contained read, suffix, rev) under the containing read sup[i], ascending (containing read, j, contained read),
+ * gend[s] the end of the group of read s, ctr the figures of the sorts and the count of keys that name no read. The launches are on
+ * c->stream and not waited for; the caller releases the buffers. *nc: in — the number of rows where flags are given; out — the rows of
+ * the range where they are not (0: nothing was placed or sorted) */
+struct ContainedGroups {
+    DevBuf<u32> cnt, gend, sup, list, ctr;
+    DevBuf<u64> word;
+};
+static void release_groups(disco_ctx *c, ContainedGroups &G)
+{
+    release(c, G.cnt);
+    release(c, G.gend);
+    release(c, G.sup);
+    release(c, G.list);
+    release(c, G.ctr);
+    release(c, G.word);
+}
+static int group_contained_rows(disco_ctx *c, const u8 *flags, u64 s_lo, u64 s_hi, u64 *nc_io, ContainedGroups &G)
+{
+    const u64 n = c->n;
+    u64 nc = *nc_io;
+    DevBuf<u32> &cnt = G.cnt, &gend = G.gend, &sup = G.sup, &list = G.list, &ctr = G.ctr;
+    DevBuf<u64> &word = G.word;
+    /* 1. grouped by containing read */
+    CHK(ensure(c, cnt, n + 1));
+    CHK(ensure(c, gend, n + 1));
+    CHK(ensure(c, ctr, CGRP_CTRS));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, (n + 1) * sizeof(u32), c->stream));
+    HIPCHK(c, hipMemsetAsync(ctr, 0, CGRP_CTRS * sizeof(u32), c->stream));
+    if (flags) {
+        hipLaunchKernelGGL(cgrp_count_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, flags, n, cnt.p, ctr.p);
+        CHK((scan_exclusive<u32, u32>(c, cnt, n + 1, gend, false, nullptr)));
+    } else {
+        hipLaunchKernelGGL(cgrp_count_range_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, n, s_lo, s_hi, cnt.p, ctr.p);
+        CHK((scan_exclusive<u32, u32>(c, cnt, n + 1, gend, false, &nc))); /* (the rank's rows: known only now) */
+        *nc_io = nc;
+        if (nc == 0) return DISCO_OK;
+    }
+    CgrpLists L;
+    L.cap = (u32)(nc / (CROW_GROUP_MAX + 1) + 1); /* (a listed group has more than CROW_GROUP_MAX rows) */
+    CHK(ensure(c, word, nc));
+    CHK(ensure(c, sup, nc));
+    CHK(ensure(c, list, 2 * (u64)L.cap));
+    L.lds = list;
+    L.glb = list.p + L.cap;
+    L.ctr = ctr;
+    if (flags) hipLaunchKernelGGL(cgrp_place_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, flags, n, nc, gend.p, word.p, sup.p);
+    else hipLaunchKernelGGL(cgrp_place_range_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, n, s_lo, s_hi, nc, gend.p, word.p, sup.p);
+    /* 2. every group in (j, contained read) order: by its size */
+    hipLaunchKernelGGL(cgrp_sort_small_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u32 *)gend, n, word.p, L);
+    const int big_grid = (int)std::min<u64>(L.cap, (u64)c->n_cu * 4);
+    hipLaunchKernelGGL(cgrp_sort_lds_kernel, dim3(big_grid), dim3(CGRP_BLOCK), 0, c->stream, (const u32 *)gend, word.p, L);
+    hipLaunchKernelGGL(cgrp_sort_global_kernel, dim3(big_grid), dim3(CGRP_BLOCK), 0, c->stream, (const u32 *)gend, word.p, L);
+    HIPCHK(c, hipGetLastError());
+    release(c, cnt);
+    return DISCO_OK;
+}
+
 static int64_t format_contained_rows(disco_ctx *c, const char *who, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets, const u8 *flags, u64 s_lo,
                                      u64 s_hi, u64 nc)
 {
     const u64 n = c->n;
-    DevBuf<u32> cnt, gend, sup, list, ctr;
-    DevBuf<u64> word, place, d_findex, d_off;
+    ContainedGroups G;
+    DevBuf<u32> &gend = G.gend, &sup = G.sup, &ctr = G.ctr;
+    DevBuf<u64> &word = G.word;
+    DevBuf<u64> place, d_findex, d_off;
     DevBuf<u8> bytes;
     u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
     auto body = [&]() -> int {
-        /* 1. grouped by containing read */
-        CHK(ensure(c, cnt, n + 1));
-        CHK(ensure(c, gend, n + 1));
-        CHK(ensure(c, ctr, CGRP_CTRS));
-        HIPCHK(c, hipMemsetAsync(cnt, 0, (n + 1) * sizeof(u32), c->stream));
-        HIPCHK(c, hipMemsetAsync(ctr, 0, CGRP_CTRS * sizeof(u32), c->stream));
-        if (flags) {
-            hipLaunchKernelGGL(cgrp_count_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, flags, n, cnt.p, ctr.p);
-            CHK((scan_exclusive<u32, u32>(c, cnt, n + 1, gend, false, nullptr)));
-        } else {
-            hipLaunchKernelGGL(cgrp_count_range_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, n, s_lo, s_hi, cnt.p, ctr.p);
-            CHK((scan_exclusive<u32, u32>(c, cnt, n + 1, gend, false, &nc))); /* (the rank's rows: known only now) */
-            if (nc == 0) return DISCO_OK;
-        }
-        CgrpLists L;
-        L.cap = (u32)(nc / (CROW_GROUP_MAX + 1) + 1); /* (a listed group has more than CROW_GROUP_MAX rows) */
-        CHK(ensure(c, word, nc));
-        CHK(ensure(c, sup, nc));
-        CHK(ensure(c, list, 2 * (u64)L.cap));
-        L.lds = list;
-        L.glb = list.p + L.cap;
-        L.ctr = ctr;
-        if (flags) hipLaunchKernelGGL(cgrp_place_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, flags, n, nc, gend.p, word.p, sup.p);
-        else hipLaunchKernelGGL(cgrp_place_range_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, n, s_lo, s_hi, nc, gend.p, word.p, sup.p);
-        /* 2. every group in (j, contained read) order: by its size */
-        hipLaunchKernelGGL(cgrp_sort_small_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u32 *)gend, n, word.p, L);
-        const int big_grid = (int)std::min<u64>(L.cap, (u64)c->n_cu * 4);
-        hipLaunchKernelGGL(cgrp_sort_lds_kernel, dim3(big_grid), dim3(CGRP_BLOCK), 0, c->stream, (const u32 *)gend, word.p, L);
-        hipLaunchKernelGGL(cgrp_sort_global_kernel, dim3(big_grid), dim3(CGRP_BLOCK), 0, c->stream, (const u32 *)gend, word.p, L);
-        HIPCHK(c, hipGetLastError());
-        release(c, cnt);
+        /* 1., 2. grouped by containing read, every group in (j, contained read) order */
+        CHK(group_contained_rows(c, flags, s_lo, s_hi, &nc, G));
+        if (nc == 0) return DISCO_OK;
         /* 3. measure -> scan -> write */
         CTextView g;
         g.word = word;
@@ -4507,12 +4589,7 @@ static int64_t format_contained_rows(disco_ctx *c, const char *who, uint32_t n_f
         return DISCO_OK;
     };
     const int rc = body();
-    release(c, cnt);
-    release(c, gend);
-    release(c, sup);
-    release(c, list);
-    release(c, ctr);
-    release(c, word);
+    release_groups(c, G);
     release(c, place);
     release(c, d_findex);
     release(c, d_off);
@@ -4565,6 +4642,251 @@ int disco_write_contained_text(disco_ctx *c, const int *fds, uint32_t n_files, u
     (void)host_threads;
     if (c->ctext_bytes == 0) return DISCO_OK;
     return write_text_through_ring(c, "disco_write_contained_text", c->d_ctext, c->ctext_off, fds, n_files);
+}
+
+/* ---- the records of the binary side output, formed where the edges and the keys are (disco_binrec.h) ------------------------- */
+/* The records [0, total) of one kind leave the device piece by piece: launch(lo, hi, piece) fills a device piece buffer with the records
+ * [lo, hi), the piece travels into a half of the pinned ring, and while it travels the piece before it is delivered — copied to `out`, or
+ * (out == null) written into fd from file_offset on, a piece split among `threads` writers at disjoint offsets: the records of a kind lie in
+ * ONE file, and writes to one file serialise on its inode lock (write_text_through_ring: 16 threads on one file reach 12 GB/s). Kernel
+ * and copy share the stream: 128 MB of records are formed in a fraction of a millisecond and travel for several, so there is nothing a
+ * second stream could hide (profiles/binary_records.txt). No device buffer holds all records. */
+static int records_through_ring(disco_ctx *c, const char *who, u64 total, const std::function<void(u64, u64, u64 *)> &launch, void *out, int fd, u64 file_offset,
+                                uint32_t threads)
+{
+    if (total == 0) return DISCO_OK;
+    CHK(output_ring(c, who));
+    const u64 REC = BINREC_WORDS * sizeof(u64);
+    const u64 fits = c->ring_half / REC;
+    const u64 P = std::min<u64>(c->rec_piece ? std::min<u64>(c->rec_piece, fits) : fits, total);
+    const u64 pieces = (total + P - 1) / P;
+    for (u64 i = 0; i < std::min<u64>(pieces, 2); i++) CHK(ensure(c, c->d_rec_piece[i], P * BINREC_WORDS));
+    const u64 n_thr = std::max<uint32_t>(1, std::min<uint32_t>(threads, 64));
+    std::atomic<bool> ok{true};
+    auto half_of = [&](u64 r) { return (char *)c->h_ring + (r & 1) * c->ring_half; };
+    auto deliver = [&](u64 r) {
+        const char *half = half_of(r);
+        const u64 first = r * P * REC, bytes = (std::min(total, (r + 1) * P) - r * P) * REC;
+        auto part = [&, half, first](u64 b, u64 e) {
+            if (out) {
+                memcpy((char *)out + first + b, half + b, e - b);
+                return;
+            }
+            while (b < e) {
+                const ssize_t w = pwrite(fd, half + b, e - b, (off_t)(file_offset + first + b));
+                if (w <= 0) {
+                    ok.store(false);
+                    return;
+                }
+                b += (u64)w;
+            }
+        };
+        const u64 nt = std::max<u64>(1, std::min<u64>(n_thr, bytes >> 16)); /* (no thread for less than 64 KB) */
+        const u64 slice = ((bytes + nt - 1) / nt + 4095) & ~(u64)4095;
+        if (nt == 1) return part(0, bytes);
+        std::vector<std::thread> th;
+        for (u64 b = 0; b < bytes; b += slice) th.emplace_back(part, b, std::min(bytes, b + slice));
+        for (auto &x : th) x.join();
+    };
+    for (u64 r = 0; r < pieces; r++) {
+        const u64 lo = r * P, hi = std::min(total, lo + P);
+        launch(lo, hi, c->d_rec_piece[r & 1].p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(half_of(r), c->d_rec_piece[r & 1].p, (hi - lo) * REC, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_ring[r & 1], c->stream));
+        if (r >= 1) deliver(r - 1); /* (its copy was waited for below, one piece ago; the half it frees is written again two pieces on) */
+        HIPCHK(c, hipEventSynchronize(c->ev_ring[r & 1]));
+    }
+    deliver(pieces - 1);
+    if (!ok.load()) return fail(c, DISCO_E_ARG, "%s: write error", who);
+    return DISCO_OK;
+}
+
+static int records_common_checks(disco_ctx *c, const char *who, int phase_needed, const char *phase_name)
+{
+    if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "%s: a rank holds its share of the job only (the host writer takes the gathered records)", who);
+    if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "%s: more than 2^31 reads", who);
+    if (c->phase < phase_needed) return fail(c, DISCO_E_STATE, "%s: run %s first", who, phase_name);
+    return DISCO_OK;
+}
+
+/* replaces the edge half of disco::write_binary (disco_amd/host/writer.h; the records of the lines of BG/OverlapGraph.cpp:808-867) */
+int64_t disco_prepare_edge_records(disco_ctx *c, uint32_t n_files, const uint16_t *edge_file, const uint64_t *file_index)
+{
+    DISCO_TRACE("disco_prepare_edge_records");
+    if (!c || n_files == 0) return DISCO_E_ARG;
+    if (n_files > 0xFFFEu) return fail(c, DISCO_E_ARG, "disco_prepare_edge_records: at most 65534 files (%u asked for)", n_files);
+    CHK(records_common_checks(c, "disco_prepare_edge_records", 8, "disco_transitive_reduce"));
+    if (!edge_file && n_files > 1) return fail(c, DISCO_E_ARG, "disco_prepare_edge_records: the file of every edge is needed for more than one file");
+    HIPCHK(c, hipSetDevice(c->device));
+    drop_edge_records(c);
+    const u64 ne = c->n_out;
+    c->rec_e_files = n_files;
+    c->rec_e_has_file = c->rec_e_has_findex = c->rec_e_has_subs = false;
+    auto body = [&]() -> int {
+        if (ne == 0) return DISCO_OK;
+        if (edge_file) {
+            CHK(ensure(c, c->d_rec_efile, ne));
+            HIPCHK(c, hipMemcpyAsync(c->d_rec_efile, edge_file, ne * sizeof(u16), hipMemcpyHostToDevice, c->stream));
+            c->rec_e_has_file = true;
+        }
+        if (file_index) {
+            CHK(ensure(c, c->d_rec_efindex, c->n));
+            HIPCHK(c, hipMemcpyAsync(c->d_rec_efindex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
+            c->rec_e_has_findex = true;
+        }
+        if (c->prm.max_substitutions) { /* by fetch-order rank, as disco_fetch_edge_substitutions has them */
+            CHK(ensure(c, c->d_rec_subs, ne));
+            hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c), c->out_used,
+                               c->d_reads, c->d_len, c->S, c->d_rec_subs.p);
+            HIPCHK(c, hipGetLastError());
+            c->rec_e_has_subs = true;
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream)); /* (the caller's arrays are free again) */
+        return DISCO_OK;
+    };
+    const int rc = body();
+    if (rc != DISCO_OK) {
+        drop_edge_records(c);
+        return rc;
+    }
+    c->rec_e_ready = true;
+    return (int64_t)ne;
+}
+
+static int edge_records_out(disco_ctx *c, const char *who, void *out, int fd, u64 file_offset, uint32_t threads)
+{
+    if (!c->rec_e_ready || c->phase < 8) return fail(c, DISCO_E_STATE, "%s: run disco_prepare_edge_records first", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    const u64 ne = c->n_out;
+    if (ne == 0) return DISCO_OK;
+    BinEdgeView g{};
+    if (c->out_dense) {
+        g.src64 = c->d_out_src;
+        g.ent = c->d_out_ent;
+    } else { /* an emission with unused chunk tails: through disco_fetch_edges's compaction, so that slot i is edge i */
+        CHK(ensure_group(c, ne, ne + ne / 8 + 1024, c->d_fetch_src, c->d_fetch_ent));
+        hipLaunchKernelGGL(emit_compact32_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos, c->out_used,
+                           c->d_fetch_src.p, c->d_fetch_ent.p);
+        HIPCHK(c, hipGetLastError());
+        g.src32 = c->d_fetch_src;
+        g.ent = c->d_fetch_ent;
+    }
+    g.len = c->d_len;
+    g.file_index = c->rec_e_has_findex ? c->d_rec_efindex.p : nullptr;
+    g.edge_file = c->rec_e_has_file ? c->d_rec_efile.p : nullptr;
+    g.subs = c->rec_e_has_subs ? c->d_rec_subs.p : nullptr;
+    g.n_files = c->rec_e_files;
+    return records_through_ring(
+        c, who, ne, [&](u64 lo, u64 hi, u64 *piece) { hipLaunchKernelGGL(binrec_edges_kernel, dim3(flat_grid(c, hi - lo)), dim3(256), 0, c->stream, g, lo, hi, piece); }, out, fd,
+        file_offset, threads);
+}
+
+int disco_fetch_edge_records(disco_ctx *c, disco_bin_edge *out, uint64_t cap)
+{
+    DISCO_TRACE("disco_fetch_edge_records");
+    if (!c) return DISCO_E_ARG;
+    if (c->rec_e_ready && c->phase >= 8 && c->n_out && (!out || cap < c->n_out))
+        return fail(c, DISCO_E_ARG, "disco_fetch_edge_records: need room for %llu records", (unsigned long long)c->n_out);
+    return edge_records_out(c, "disco_fetch_edge_records", out, -1, 0, 16);
+}
+
+int disco_write_edge_records(disco_ctx *c, int fd, uint64_t file_offset, uint32_t host_threads)
+{
+    DISCO_TRACE("disco_write_edge_records");
+    if (!c || fd < 0) return DISCO_E_ARG;
+    return edge_records_out(c, "disco_write_edge_records", nullptr, fd, file_offset, host_threads);
+}
+
+/* replaces the contained half of disco::write_binary (disco_amd/host/writer.h; the records of the lines of BG/OverlapGraph.cpp:438-447) */
+int64_t disco_prepare_contained_records(disco_ctx *c, uint32_t n_files, const uint64_t *file_index)
+{
+    DISCO_TRACE("disco_prepare_contained_records");
+    if (!c || n_files == 0) return DISCO_E_ARG;
+    if (n_files > 0xFFFEu) return fail(c, DISCO_E_ARG, "disco_prepare_contained_records: at most 65534 files (%u asked for)", n_files);
+    CHK(records_common_checks(c, "disco_prepare_contained_records", 4, "disco_mark_contained"));
+    HIPCHK(c, hipSetDevice(c->device));
+    drop_contained_records(c);
+    c->rec_c_files = n_files;
+    c->rec_c_has_findex = false;
+    u64 nc = c->n_contained;
+    if (nc == 0) {
+        c->rec_c_ready = true;
+        return 0;
+    }
+    CHK(settle_keys(c));
+    ContainedGroups G;
+    u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
+    auto body = [&]() -> int {
+        CHK(group_contained_rows(c, (const u8 *)c->d_contained, 0, c->n, &nc, G));
+        if (file_index) {
+            CHK(ensure(c, c->d_rec_cfindex, c->n));
+            HIPCHK(c, hipMemcpyAsync(c->d_rec_cfindex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
+            c->rec_c_has_findex = true;
+        }
+        HIPCHK(c, hipMemcpyAsync(h_ctr, G.ctr, sizeof h_ctr, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "disco_prepare_contained_records: %u contained reads have a key that names no containing read", h_ctr[CGRP_BAD_KEYS]);
+        return DISCO_OK;
+    };
+    const int rc = body();
+    if (rc == DISCO_OK) { /* the grouped rows stay with the context; the rest of the grouping goes */
+        c->d_rec_cword = G.word; /* (empty since drop_contained_records; the bytes stay counted) */
+        c->d_rec_csup = G.sup;
+        G.word = DevBuf<u64>();
+        G.sup = DevBuf<u32>();
+    }
+    release_groups(c, G);
+    if (rc != DISCO_OK) {
+        drop_contained_records(c);
+        return rc;
+    }
+    c->rec_c_n = nc;
+    c->rec_c_ready = true;
+    return (int64_t)nc;
+}
+
+static int contained_records_out(disco_ctx *c, const char *who, void *out, int fd, u64 file_offset, uint32_t threads)
+{
+    if (!c->rec_c_ready || c->phase < 4) return fail(c, DISCO_E_STATE, "%s: run disco_prepare_contained_records first", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->rec_c_n == 0) return DISCO_OK;
+    CTextView g;
+    g.word = c->d_rec_cword;
+    g.sup = c->d_rec_csup;
+    g.len = c->d_len;
+    g.file_index = c->rec_c_has_findex ? c->d_rec_cfindex.p : nullptr;
+    g.nc = c->rec_c_n;
+    g.k = (u32)c->k;
+    const u64 n = c->n;
+    const u32 nf = c->rec_c_files;
+    return records_through_ring(
+        c, who, c->rec_c_n,
+        [&](u64 lo, u64 hi, u64 *piece) { hipLaunchKernelGGL(binrec_contained_kernel, dim3(flat_grid(c, hi - lo)), dim3(256), 0, c->stream, g, n, nf, lo, hi, piece); }, out, fd,
+        file_offset, threads);
+}
+
+int disco_fetch_contained_records(disco_ctx *c, disco_bin_contained *out, uint64_t cap)
+{
+    DISCO_TRACE("disco_fetch_contained_records");
+    if (!c) return DISCO_E_ARG;
+    if (c->rec_c_ready && c->rec_c_n && (!out || cap < c->rec_c_n))
+        return fail(c, DISCO_E_ARG, "disco_fetch_contained_records: need room for %llu records", (unsigned long long)c->rec_c_n);
+    return contained_records_out(c, "disco_fetch_contained_records", out, -1, 0, 16);
+}
+
+int disco_write_contained_records(disco_ctx *c, int fd, uint64_t file_offset, uint32_t host_threads)
+{
+    DISCO_TRACE("disco_write_contained_records");
+    if (!c || fd < 0) return DISCO_E_ARG;
+    return contained_records_out(c, "disco_write_contained_records", nullptr, fd, file_offset, host_threads);
+}
+
+int disco_set_record_piece(disco_ctx *c, uint64_t records)
+{
+    if (!c) return DISCO_E_ARG;
+    c->rec_piece = records;
+    return DISCO_OK;
 }
 
 /* the contained rows of the current flags start their way to the host now, on a side stream (grouped: also in the order of the

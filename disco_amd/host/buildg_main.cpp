@@ -144,6 +144,16 @@ static const bool DIST_GPU_TEXT_DEFAULT = false;
  * DISCO_PAR_SIMPLE_HOST_TEXT=1 keep the flow through the host. */
 static const bool PAR_SIMPLE_GPU_TEXT_DEFAULT = true;
 
+/* buildG --binary-out / --no-text on one GPU: DISCO_GPU_BINARY=1 has <prefix>_edges.bin and <prefix>_contained.bin written from the device
+ * (disco_write_edge_records / disco_write_contained_records: no edge record and no contained row reaches the host, and with --binary-out the
+ * text files keep their device path); 0 keeps the host writer (disco::write_binary). With --binary-out it is off unless asked for. With
+ * --no-text the default is this constant, decided by the rule of profiles/par_simple_text.txt: on only when the device path's median is
+ * lower at both measured shapes by more than the larger run-to-run range. Measured against the commit before and against this one with the
+ * knob off, interleaved in one session on one box, three runs each (profiles/binary_records.txt): the laps from `wait for lengths + file
+ * indices` to the end 0.963 -> 0.246 s at 5*10^7 x 150 bp (1.81 GB of edge records; larger range 0.033) and 0.343 -> 0.062 s on the 10 M-read
+ * metagenome shape (0.052); the process 1.82 -> 1.00 s (0.32) and 0.79 -> 0.46 s (0.10). Lower at both by more than either range: the default. */
+static const bool GPU_BINARY_NO_TEXT_DEFAULT = true;
+
 static int die(const std::string &msg)
 {
     std::cout << "\nError: " << msg << std::endl; /* the reference prints and exits 0 (BG/Common.h:64); we exit non-zero */
@@ -565,7 +575,11 @@ int main(int argc, char **argv)
     bool par_simple_on_gpu = gpu_chains && gpus == 1 && !max_subs && !getenv("DISCO_PAR_SIMPLE_HOST_TEXT") &&
                              (psgt ? strcmp(psgt, "0") != 0 : PAR_SIMPLE_GPU_TEXT_DEFAULT);
     bool par_simple_done = false;
-    std::unique_ptr<char[]> edge_text;      /* the edge lines, formatted on the GPU (single GPU, exact overlaps) */
+    /* ... and the binary side output (GPU_BINARY_NO_TEXT_DEFAULT above): parsed as DISCO_DIST_GPU_TEXT is — 0 is off, anything else on */
+    const char *gbin = getenv("DISCO_GPU_BINARY");
+    const bool gpu_binary = binary_out && gpus == 1 && (gbin ? strcmp(gbin, "0") != 0 : (no_text && GPU_BINARY_NO_TEXT_DEFAULT));
+    bool bin_contained_on_gpu = false, bin_edges_on_gpu = false; /* that file has been written from the device */
+    std::unique_ptr<char[]> edge_text;     /* the edge lines, formatted on the GPU (single GPU, exact overlaps) */
     std::vector<uint64_t> edge_text_off;
     std::vector<disco_chain_edge> ch_comp;
     std::unique_ptr<disco_chain_link[]> ch_links;
@@ -617,8 +631,11 @@ int main(int argc, char **argv)
         /* the contained-read files from the GPU (disco_format_contained: rows grouped, sorted and formatted where the keys are, the lines
          * through the pinned ring into the files) — or, where the rows are wanted on the host (binary side output, no text, DISCO_HOST_TEXT
          * / DISCO_HOST_CONTAINED_TEXT=1), the rows leave now, grouped for their files, while the edges are selected and reduced */
-        bool gpu_contained = !no_text && !binary_out && !getenv("DISCO_HOST_TEXT") && !getenv("DISCO_HOST_CONTAINED_TEXT");
-        if (!gpu_contained && n_cont && !getenv("DISCO_HOST_ROW_SORT") && !getenv("DISCO_LATE_ROWS")) (void)disco_start_contained_rows(ctx, 1);
+        /* with the binary files written from the device (gpu_binary) the rows are wanted on the host for host-formatted text only, and a
+         * --binary-out run keeps the text path of a run without the flag */
+        bool gpu_contained = !no_text && (!binary_out || gpu_binary) && !getenv("DISCO_HOST_TEXT") && !getenv("DISCO_HOST_CONTAINED_TEXT");
+        const bool rows_wanted = !gpu_contained && !(gpu_binary && no_text);
+        if (rows_wanted && n_cont && !getenv("DISCO_HOST_ROW_SORT") && !getenv("DISCO_LATE_ROWS")) (void)disco_start_contained_rows(ctx, 1);
         DISCO_CALL(ctx, disco_build_edges(ctx, &e_pre));
         DISCO_CALL(ctx, disco_transitive_reduce(ctx, &e_out));
         t_graph = secs(t0);
@@ -662,8 +679,33 @@ int main(int argc, char **argv)
             }
             contained_on_gpu = gpu_contained;
         }
-        if (!gpu_contained) rows.resize(n_cont);
-        if (n_cont && !gpu_contained) { /* in the files' order where the device grouped them during the pass; by id (sorted by the writer) otherwise */
+        auto soft = [](int64_t rc) { return rc == DISCO_E_NOMEM || rc == DISCO_E_UNSUPPORTED; };
+        const bool identity_ids = rs.total_records == rs.size(); /* no record was filtered: file index = read id + 1 */
+        if (gpu_binary) {
+            /* <prefix>_contained.bin: the header from here, the records from the device (grouped and sorted there) into the open file */
+            const int ncf = (int)ctags_early.tag.size();
+            const int64_t nr = disco_prepare_contained_records(ctx, (uint32_t)ncf, identity_ids ? nullptr : rs.file_index.data());
+            if (nr < 0 && !soft(nr)) return die(disco_last_error(ctx));
+            int wrc = (int)std::min<int64_t>(nr, 0);
+            if (nr >= 0) {
+                std::string ferr;
+                const int fd = disco::open_binary_records(prefix, true, (uint64_t)nr, ncf, ferr);
+                if (fd < 0) return die(ferr);
+                wrc = disco_write_contained_records(ctx, fd, 32, (uint32_t)threads);
+                close(fd);
+                if (wrc < 0 && !soft(wrc)) return die(disco_last_error(ctx));
+            }
+            if (wrc < 0) {
+                if (verbose) fprintf(stderr, "[disco host] binary contained records by the host writer: %s\n", disco_last_error(ctx));
+            } else {
+                bin_contained_on_gpu = true;
+                lap("binary contained records on the GPU");
+            }
+        }
+        /* the rows as host records: for host-formatted text and for the host writer of the binary file */
+        const bool rows_needed = (!no_text && !gpu_contained) || (binary_out && !bin_contained_on_gpu);
+        if (rows_needed) rows.resize(n_cont);
+        if (n_cont && rows_needed) { /* in the files' order where the device grouped them during the pass; by id (sorted by the writer) otherwise */
             const int64_t grc = getenv("DISCO_HOST_ROW_SORT") ? (int64_t)DISCO_E_UNSUPPORTED : disco_fetch_contained_grouped(ctx, rows.data(), n_cont);
             rows_grouped = grc >= 0;
             if (grc < 0 && grc != DISCO_E_UNSUPPORTED) return die(disco_last_error(ctx));
@@ -672,7 +714,8 @@ int main(int argc, char **argv)
         lap("fetch contained rows");
         /* the contained-read files are written by a thread of their own while the device partitions and formats the edges (their rows
          * have been final since the contained flags were fixed); joined before the checkpoint is written */
-        if (!no_text && !binary_out && !gpu_contained) {
+        /* (not beside the host writer of the binary file: write_binary_contained sorts the rows in place) */
+        if (!no_text && (!binary_out || bin_contained_on_gpu) && !gpu_contained) {
             contained_early = true;
             contained_writer = std::thread([&]() {
                 std::string e2;
@@ -692,7 +735,7 @@ int main(int argc, char **argv)
             const int64_t nb = disco_format_edges(ctx, (uint32_t)n_edge_files, edge_file.get(), identity ? nullptr : rs.file_index.data(), edge_text_off.data());
             if (nb < 0) return die(disco_last_error(ctx));
             lap("format edge lines on the GPU");
-            if (!binary_out && (par_simple.empty() || par_simple_on_gpu) && !getenv("DISCO_TEXT_VIA_HOST")) {
+            if ((!binary_out || gpu_binary) && (par_simple.empty() || par_simple_on_gpu) && !getenv("DISCO_TEXT_VIA_HOST")) {
                 /* straight from the device into the edge files (pieces through a pinned ring, host threads pwrite behind the copies) */
                 const disco::FileTags et = mpi_names ? disco::FileTags::mpi_edges(gpus, threads) : disco::FileTags::plain(threads);
                 std::vector<int> fds((size_t)n_edge_files, -1);
@@ -721,7 +764,27 @@ int main(int argc, char **argv)
             lap("fetch edges");
             return true;
         };
-        if (binary_out || (!par_simple.empty() && !par_simple_on_gpu) || (!edge_text && !edge_text_streamed && !no_text))
+        if (gpu_binary) {
+            /* <prefix>_edges.bin the same way: any number of files, substitutions included (the edge TEXT of such runs stays with the host writer) */
+            const int64_t nr = disco_prepare_edge_records(ctx, (uint32_t)n_edge_files, edge_file.get(), identity_ids ? nullptr : rs.file_index.data());
+            if (nr < 0 && !soft(nr)) return die(disco_last_error(ctx));
+            int wrc = (int)std::min<int64_t>(nr, 0);
+            if (nr >= 0) {
+                std::string ferr;
+                const int fd = disco::open_binary_records(prefix, false, (uint64_t)nr, n_edge_files, ferr);
+                if (fd < 0) return die(ferr);
+                wrc = disco_write_edge_records(ctx, fd, 32, (uint32_t)threads);
+                close(fd);
+                if (wrc < 0 && !soft(wrc)) return die(disco_last_error(ctx));
+            }
+            if (wrc < 0) {
+                if (verbose) fprintf(stderr, "[disco host] binary edge records by the host writer: %s\n", disco_last_error(ctx));
+            } else {
+                bin_edges_on_gpu = true;
+                lap("binary edge records on the GPU");
+            }
+        }
+        if ((binary_out && !bin_edges_on_gpu) || (!par_simple.empty() && !par_simple_on_gpu) || (!edge_text && !edge_text_streamed && !no_text))
             if (!fetch_edges()) return die(disco_last_error(ctx));
         if (par_simple_on_gpu && e_out) {
             /* contract -> residue, headers, first edges -> the host rounds on that small graph -> the lines from the device into the files.
@@ -1036,8 +1099,10 @@ int main(int argc, char **argv)
     /* ---- outputs -------------------------------------------------------------------------------------------------- */
     disco::FileTags etags = mpi_names ? disco::FileTags::mpi_edges(gpus, threads) : disco::FileTags::plain(threads);
     disco::FileTags ctags = mpi_names ? disco::FileTags::mpi_contained(gpus, threads) : disco::FileTags::plain(threads);
-    if (binary_out) {
-        if (!disco::write_binary(prefix, (int)etags.tag.size(), (int)ctags.tag.size(), edges.get(), e_out, e_out ? edge_file.get() : nullptr, rows, rs, err, edge_subs.get())) return die(err);
+    if (binary_out && !(bin_edges_on_gpu && bin_contained_on_gpu)) { /* (a file the device has written is left alone) */
+        if (!bin_edges_on_gpu && !disco::write_binary_edges(prefix, (int)etags.tag.size(), edges.get(), e_out, e_out ? edge_file.get() : nullptr, rs, err, edge_subs.get()))
+            return die(err);
+        if (!bin_contained_on_gpu && !disco::write_binary_contained(prefix, (int)ctags.tag.size(), rows, rs, err)) return die(err);
         lap("write binary side output");
     }
     if (!par_simple.empty() && !mpi_names && !par_simple_done) {

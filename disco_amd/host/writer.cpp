@@ -440,19 +440,21 @@ struct BinHeader {
     uint64_t n_records;
     uint32_t n_files, reserved;
 };
-struct BinEdge {
-    uint64_t src, dst;
-    uint32_t orient, offset, len_src, len_dst;
-    uint16_t file, flag;
-    uint32_t subs;
-};
-struct BinContained {
-    uint64_t contained, super;
-    uint32_t orient, len2, len1, start;
-    uint16_t file, pad0;
-    uint32_t pad1;
-};
+using BinEdge = disco_bin_edge; /* the records: include/disco_hip.h */
+using BinContained = disco_bin_contained;
 static_assert(sizeof(BinHeader) == 32 && sizeof(BinEdge) == 40 && sizeof(BinContained) == 40, "binary side-output layout");
+
+BinHeader make_header(const char *magic, uint64_t n_records, int n_files)
+{
+    BinHeader h;
+    memcpy(h.magic, magic, 8);
+    h.version = 1;
+    h.record_bytes = 40;
+    h.n_records = n_records;
+    h.n_files = (uint32_t)n_files;
+    h.reserved = 0;
+    return h;
+}
 
 template <typename R>
 bool write_records(const std::string &path, const char *magic, const std::vector<R> &rec, int n_files, std::string &err)
@@ -462,13 +464,7 @@ bool write_records(const std::string &path, const char *magic, const std::vector
         err = "Unable to open file: " + path;
         return false;
     }
-    BinHeader h;
-    memcpy(h.magic, magic, 8);
-    h.version = 1;
-    h.record_bytes = (uint32_t)sizeof(R);
-    h.n_records = rec.size();
-    h.n_files = (uint32_t)n_files;
-    h.reserved = 0;
+    const BinHeader h = make_header(magic, rec.size(), n_files);
     bool ok = fwrite(&h, sizeof h, 1, f) == 1 && (rec.empty() || fwrite(rec.data(), sizeof(R), rec.size(), f) == rec.size());
     fclose(f);
     if (!ok) err = "Short write: " + path;
@@ -476,8 +472,31 @@ bool write_records(const std::string &path, const char *magic, const std::vector
 }
 } // namespace
 
+int open_binary_records(const std::string &prefix, bool contained, uint64_t n_records, int n_files, std::string &err)
+{
+    const std::string path = prefix + (contained ? "_contained.bin" : "_edges.bin");
+    const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) {
+        err = "Unable to open file: " + path;
+        return -1;
+    }
+    const BinHeader h = make_header(contained ? "DISCOCON" : "DISCOEDG", n_records, n_files);
+    if (pwrite(fd, &h, sizeof h, 0) != (ssize_t)sizeof h) {
+        err = "Short write: " + path;
+        close(fd);
+        return -1;
+    }
+    return fd;
+}
+
 bool write_binary(const std::string &prefix, int n_edge_files, int n_contained_files, const disco_edge *edges, size_t n_edges, const uint16_t *edge_file,
                   std::vector<disco_contained_row> &rows, const ReadSet &rs, std::string &err, const uint16_t *edge_subs)
+{
+    return write_binary_edges(prefix, n_edge_files, edges, n_edges, edge_file, rs, err, edge_subs) && write_binary_contained(prefix, n_contained_files, rows, rs, err);
+}
+
+bool write_binary_edges(const std::string &prefix, int n_edge_files, const disco_edge *edges, size_t n_edges, const uint16_t *edge_file, const ReadSet &rs, std::string &err,
+                        const uint16_t *edge_subs)
 {
     const uint64_t n = rs.size();
     std::vector<BinEdge> be(n_edges);
@@ -493,10 +512,14 @@ bool write_binary(const std::string &prefix, int n_edge_files, int n_contained_f
         o.len_dst = e.len_dst;
         o.file = edge_file ? (uint16_t)std::min<int>(edge_file[i], n_edge_files - 1) : (uint16_t)owner_of(e.src, n, n_edge_files);
         o.flag = 2; /* the files are cut along connected components: both ends have all their edges in this file */
-        o.subs = edge_subs ? edge_subs[i] : 0;
+        o.substitutions = edge_subs ? edge_subs[i] : 0;
     }
-    if (!write_records(prefix + "_edges.bin", "DISCOEDG", be, n_edge_files, err)) return false;
-    std::vector<BinEdge>().swap(be);
+    return write_records(prefix + "_edges.bin", "DISCOEDG", be, n_edge_files, err);
+}
+
+bool write_binary_contained(const std::string &prefix, int n_contained_files, std::vector<disco_contained_row> &rows, const ReadSet &rs, std::string &err)
+{
+    const uint64_t n = rs.size();
     /* same order as the text files: by containing read, then (j, contained id) */
     sort_contained(rows, n);
     std::vector<BinContained> bc(rows.size());

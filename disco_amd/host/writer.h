@@ -56,9 +56,21 @@ bool write_edge_text(const std::string &prefix, int n_files, const char *text, c
  *             — the line "src\tdst\torient,len_src-offset,substitutions,0,len_src,offset,len_src-1,len_dst,0,len_src-offset-1,NA,flag" of file `file`
  *   contained: n x { u64 contained, super (file indices); u32 orient, len2, len1, start; u16 file; u16 pad; u32 pad }                  40 B
  *             — the line "contained\tsuper\torient,len2,0,0,len2,0,len2,len1,start,start+len2" of file `file`; rows of one super read adjacent
- * disco_amd/edgefile.py reads them and re-creates the text files byte for byte (tests/test_host.py). */
+ * disco_amd/edgefile.py reads them and re-creates the text files byte for byte (tests/test_host.py).
+ * The two record types are disco_bin_edge / disco_bin_contained of include/disco_hip.h. Two ways to the same files:
+ *   write_binary (= write_binary_edges + write_binary_contained): from disco_edge / disco_contained_row records fetched to the host —
+ *     the records are converted and the contained rows sorted here, each file written in one piece;
+ *   open_binary_records + disco_write_edge_records / disco_write_contained_records (one GPU, buildG with DISCO_GPU_BINARY=1): this side
+ *     writes the 32-byte header only; the records are formed on the device and come through the pinned ring into the open file from
+ *     byte 32 on. A kind whose device calls decline (DISCO_E_NOMEM, DISCO_E_UNSUPPORTED) is written by its write_binary_* half. */
 bool write_binary(const std::string &prefix, int n_edge_files, int n_contained_files, const disco_edge *edges, size_t n_edges, const uint16_t *edge_file,
                   std::vector<disco_contained_row> &rows, const ReadSet &rs, std::string &err, const uint16_t *edge_subs = nullptr);
+bool write_binary_edges(const std::string &prefix, int n_edge_files, const disco_edge *edges, size_t n_edges, const uint16_t *edge_file, const ReadSet &rs, std::string &err,
+                        const uint16_t *edge_subs = nullptr);
+bool write_binary_contained(const std::string &prefix, int n_contained_files, std::vector<disco_contained_row> &rows, const ReadSet &rs, std::string &err);
+/* <prefix>_edges.bin (contained: <prefix>_contained.bin) created with its header for n_records records; returns the descriptor, open for
+ * the records at byte 32, or -1 */
+int open_binary_records(const std::string &prefix, bool contained, uint64_t n_records, int n_files, std::string &err);
 bool write_checkpoint(const std::string &prefix, bool ccr, bool gc, bool append, std::string &err);
 void read_checkpoint(const std::string &prefix, bool &ccr, bool &gc);
 

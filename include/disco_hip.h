@@ -526,6 +526,52 @@ int     disco_fetch_par_simple_text(disco_ctx *ctx, char *out, uint64_t cap);
 /* ... or straight into the caller's open files, through the pinned ring as disco_write_edge_text (empty files are skipped) */
 int     disco_write_par_simple_text(disco_ctx *ctx, const int *fds, uint32_t n_files, uint32_t host_threads);
 
+/* ---- the records of the binary side output, formed on the GPU (disco_amd/csrc/disco_binrec.h) -------------------------------------- */
+/* <prefix>_edges.bin / <prefix>_contained.bin (disco_amd/host/writer.h has the file layout, disco_amd/edgefile.py
+ * reads it): a 32-byte header, then fixed records of 40 bytes, little endian — record i lies at byte 32 + 40 i. The two record types: */
+typedef struct disco_bin_edge { /* one line of <prefix>_<file>_parGraph.txt (BG/OverlapGraph.cpp:808-867) */
+    uint64_t src, dst;          /* 1-based file indices, src < dst by read id */
+    uint32_t orient, offset, len_src, len_dst;
+    uint16_t file, flag;        /* flag 2: the files are cut along connected components */
+    uint32_t substitutions;
+} disco_bin_edge;
+typedef struct disco_bin_contained { /* one line of <prefix>_<file>_containedReads.txt (BG/OverlapGraph.cpp:438-447) */
+    uint64_t contained, super;       /* 1-based file indices */
+    uint32_t orient, len2, len1, start;
+    uint16_t file, pad0;
+    uint32_t pad1;
+} disco_bin_contained;
+#if defined(__cplusplus)
+static_assert(sizeof(disco_bin_edge) == 40 && sizeof(disco_bin_contained) == 40, "binary side-output records are 40 bytes");
+#else /* (C99 has no static assertion: an array type of negative size does not compile) */
+typedef char disco_bin_edge_is_40_bytes[sizeof(disco_bin_edge) == 40 ? 1 : -1];
+typedef char disco_bin_contained_is_40_bytes[sizeof(disco_bin_contained) == 40 ? 1 : -1];
+#endif
+/* The records are formed where their edges and containment keys lie and leave the device piece by piece: a kernel fills one of two device
+ * piece buffers (one lane per record, every byte of a record written), the piece travels into a half of the context's pinned ring, and
+ * host threads deliver it behind the copy — there is no device buffer of all records, and neither disco_edge nor disco_contained_row
+ * records are made. Single GPU: DISCO_E_UNSUPPORTED on a context with a communicator or with 2^31 or more reads; DISCO_E_NOMEM when
+ * the piece buffers or the ring cannot be had (a caller then takes disco_fetch_edges / disco_fetch_contained and the host writer:
+ * disco_amd/host/writer.h write_binary). What a prepare call left is valid until the next pass on the context (disco_run_graph or any of
+ * its phases); the write / fetch calls may be repeated.
+ * disco_prepare_edge_records (the records of saveParGraphToFile's lines, BG/OverlapGraph.cpp:808-867, in the order of disco_fetch_edges):
+ * after disco_transitive_reduce. edge_file = the file of every edge (disco_fetch_edge_files; may be null for one file: DISCO_E_ARG for
+ * more), a record's file = min(edge_file[i], n_files - 1) as the host writer has it; file_index as for disco_format_edges (null: read id
+ * + 1); flag 2; substitutions 0 for exact overlaps, otherwise what disco_fetch_edge_substitutions returns. Up to 65534 files — nothing
+ * runs once per file — and inexact overlaps are covered. Returns the number of records.
+ * disco_prepare_contained_records (the records of the contained-read lines, BG/OverlapGraph.cpp:438-447): from disco_mark_contained
+ * on. The rows are grouped and sorted on the device as for disco_format_contained: ascending (containing read, j, contained read),
+ * whatever the size of a group; a record's file = floor(super * n_files / disco_num_reads), pad0 = pad1 = 0. Returns the number of
+ * records, 0 when nothing is contained.
+ * disco_fetch_*_records copy the records to host memory (cap: room in records); disco_write_*_records pwrite them into the open
+ * descriptor fd from byte file_offset on (32 behind the header), every piece split among host_threads writers at disjoint offsets. */
+int64_t disco_prepare_edge_records(disco_ctx *ctx, uint32_t n_files, const uint16_t *edge_file, const uint64_t *file_index);
+int     disco_fetch_edge_records(disco_ctx *ctx, disco_bin_edge *out, uint64_t cap);
+int     disco_write_edge_records(disco_ctx *ctx, int fd, uint64_t file_offset, uint32_t host_threads);
+int64_t disco_prepare_contained_records(disco_ctx *ctx, uint32_t n_files, const uint64_t *file_index);
+int     disco_fetch_contained_records(disco_ctx *ctx, disco_bin_contained *out, uint64_t cap);
+int     disco_write_contained_records(disco_ctx *ctx, int fd, uint64_t file_offset, uint32_t host_threads);
+
 #ifdef __cplusplus
 }
 #endif

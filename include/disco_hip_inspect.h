@@ -27,6 +27,11 @@ int disco_fetch_order(disco_ctx *ctx, uint64_t *order_words, uint32_t *keys, uin
  * row's flags, or a communicator). Tests only. */
 int disco_fetch_survivor_layout(disco_ctx *ctx, uint8_t *list_len, uint64_t cap, uint64_t *n, int *dense, uint64_t *out_used);
 
+/* records per piece of disco_fetch_*_records / disco_write_*_records (results do not depend on it): 0 = the default, as many as a half of
+ * the pinned ring holds (3 355 443) — with which a small test would never cross a piece boundary; larger values are cut to the default.
+ * Tests only. */
+int disco_set_record_piece(disco_ctx *ctx, uint64_t records);
+
 #ifdef __cplusplus
 }
 #endif

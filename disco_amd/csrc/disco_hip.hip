@@ -33,6 +33,7 @@
 #include <thread>
 #include <map>
 #include <mutex>
+#include <queue>
 #include <vector>
 
 #include "../../include/disco_hip.h"
@@ -4182,8 +4183,10 @@ int64_t disco_fetch_edge_substitutions(disco_ctx *c, uint16_t *out, uint64_t cap
 /* connected components of the edges in the slots [0, n_slots) (valid[i] != 0; pos[i] = rank of the edge among the valid ones)
  * dealt out to n_files files: out[pos[i]] = file of edge i — on the host, or, with d_out (room for ne entries), left on the device.
  * The assignment depends on the SET of edges only, not on their order or on who computes it: a component's root is its smallest read
- * (uf_hook_kernel), its size a count, the large ones are dealt out in (size, root) order, the others by a hash of the root — which is
- * what lets every rank of a multi-GPU job run it on the gathered edges and arrive at the same files (disco_dist_format_edges) */
+ * (uf_hook_kernel), its size its number of edges, those of at least max(ne / (64 n_files), 1) edges are dealt out in (size descending,
+ * root ascending) order to the lightest file (the lowest index among equals), the others by a hash of the root (tests/partition_model.py
+ * is this rule in numpy, and tests/test_gpu_edge_partition.py holds the kernels to it) — which is what lets every rank of a multi-GPU
+ * job run it on the gathered edges and arrive at the same files (disco_dist_format_edges) */
 static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent, const u8 *d_valid, const u64 *d_pos, u64 n_slots, u64 ne, u64 n,
                                uint32_t n_files, uint16_t *out, u16 *d_out = nullptr)
 {
@@ -4191,7 +4194,11 @@ static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent,
     DevBuf<u32> parent, cnt, d_nlist;
     DevBuf<u16> cfile, efile;
     DevBuf<u64> list;
-    const u32 list_cap = n_files * 64 + 64;
+    /* components of at least 1/(64 files) of the edges are dealt out by size, largest first to the lightest file; the rest
+     * (there can be millions of small ones) go by hash. ALL of the former: the list holds as many as there can be — min(n, ne / thr),
+     * and ne / thr < 128 files — so that which of them are dealt out by size is never a matter of who arrived first */
+    const u32 thr = (u32)std::max<u64>(ne / ((u64)n_files * 64), 1);
+    const u32 list_cap = (u32)std::max<u64>(std::min<u64>(n, ne / thr), 1);
     int rc = DISCO_OK;
     auto cleanup = [&]() {
         release(c, parent);
@@ -4222,26 +4229,32 @@ static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent,
     (void)hipMemsetAsync(cfile, 0xFF, n * sizeof(u16), c->stream);
     (void)hipMemsetAsync(d_nlist, 0, sizeof(u32), c->stream);
     hipLaunchKernelGGL(uf_count_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, d_src, d_valid, n_slots, parent, cnt);
-    /* components of at least 1/(64 files) of the edges are dealt out by size, largest first to the lightest file; the rest
-     * (there can be millions of small ones) go by hash */
-    const u32 thr = (u32)std::max<u64>(ne / ((u64)n_files * 64), 1);
     hipLaunchKernelGGL(uf_big_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, cnt, n, thr, list, d_nlist, list_cap);
     u32 n_list = 0;
-    std::vector<u64> hl(list_cap);
-    if (hipMemcpyAsync(&n_list, d_nlist, sizeof(u32), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipMemcpyAsync(hl.data(), list, list_cap * sizeof(u64), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (hipMemcpyAsync(&n_list, d_nlist, sizeof(u32), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
         cleanup();
         return fail(c, DISCO_E_HIP, "edge partition: %s", hipGetErrorString(hipGetLastError()));
     }
-    n_list = std::min(n_list, list_cap);
-    hl.resize(n_list);
+    if (n_list > list_cap) { /* cannot happen (see list_cap); a clipped list would cut files that depend on the order of arrival */
+        cleanup();
+        return fail(c, DISCO_E_CAPACITY, "edge partition: %u components of at least %u edges, room for %u", n_list, thr, list_cap);
+    }
+    std::vector<u64> hl(n_list);
+    if (n_list && (hipMemcpyAsync(hl.data(), list, n_list * sizeof(u64), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                   hipStreamSynchronize(c->stream) != hipSuccess)) {
+        cleanup();
+        return fail(c, DISCO_E_HIP, "edge partition: %s", hipGetErrorString(hipGetLastError()));
+    }
     std::sort(hl.begin(), hl.end(), [](u64 a, u64 b) { return (u32)a != (u32)b ? (u32)a > (u32)b : a < b; }); /* by size, then root: deterministic */
-    std::vector<u64> load(n_files, 0);
+    /* the lightest file, the lowest index among equals: a heap of (load, file) — the list can hold 128 entries per file */
+    typedef std::pair<u64, u32> LoadOfFile;
+    std::priority_queue<LoadOfFile, std::vector<LoadOfFile>, std::greater<LoadOfFile>> lightest;
+    for (u32 f = 0; f < n_files; f++) lightest.push(LoadOfFile(0, f));
     for (u64 &e : hl) {
-        const u32 f = (u32)(std::min_element(load.begin(), load.end()) - load.begin());
-        load[f] += (u32)e;
-        e = (e & 0xFFFFFFFF00000000ull) | f;
+        const LoadOfFile t = lightest.top();
+        lightest.pop();
+        lightest.push(LoadOfFile(t.first + (u32)e, t.second));
+        e = (e & 0xFFFFFFFF00000000ull) | t.second;
     }
     if (n_list) {
         if (hipMemcpyAsync(list, hl.data(), n_list * sizeof(u64), hipMemcpyHostToDevice, c->stream) != hipSuccess) {

@@ -368,7 +368,8 @@ int64_t disco_fetch_edge_substitutions(disco_ctx *ctx, uint16_t *out, uint64_t c
  * gets it from the locality of its BFS batches, BG/OverlapGraph.cpp:100-325) */
 int64_t disco_fetch_edge_files(disco_ctx *ctx, uint32_t n_files, uint16_t *out, uint64_t cap);
 /* the same partition for edges the HOST holds (buildG --gpus N: the edges all ranks emitted, concatenated; n_nodes = reads of
- * the whole job): out[i] = file of edges[i]. Any context will do; its graph state is not touched. */
+ * the whole job): out[i] = file of edges[i]. Any context will do; its graph state is not touched. Every src and dst must be below
+ * n_nodes: the ids are NOT checked, and a larger one makes the device read and write outside its arrays. */
 int64_t disco_partition_edges(disco_ctx *ctx, const disco_edge *edges, uint64_t n_edges, uint64_t n_nodes, uint32_t n_files, uint16_t *out);
 int disco_get_counters(disco_ctx *ctx, disco_counters *out);
 /* milliseconds of the last run of each phase, measured with HIP events on the stream the kernels were launched on

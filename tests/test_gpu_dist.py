@@ -229,6 +229,9 @@ def test_partition_of_host_edges_keeps_components_together():
     with buildgraph.BuildGraph(min_overlap=40) as g:
         f = g.partition_edges(e, n, 7)
     assert f.max() < 7 and len(np.unique(f)) == 7
+    from tests.partition_model import partition_model
+
+    assert np.array_equal(f, partition_model(e["src"], e["dst"], n, 7)[0])   # exactly the rule's files
     file_of_comp = {}
     for s, fi in zip(e["src"], f):
         assert file_of_comp.setdefault(int(comp[s]), int(fi)) == int(fi)

@@ -251,6 +251,33 @@ def test_containers_and_their_substrings_on_different_ranks():
     assert len(per_rank[0][0]) > 0 and len(per_rank[2][0]) == 0   # the containers' files: ranks 0 and 1 (files 0-1 and 2-3); none in the last range
 
 
+@pytest.mark.parametrize("G", [2, 3])
+def test_more_components_by_size_than_64_per_file_under_ranks(G):
+    """300 disjoint pairs of reads that overlap by 60 bases into 3 files: 300 components of one edge, thr = 1, all of them dealt out by
+    size — more than 64 * 3 + 64. Every rank cuts the gathered edges on its own device and writes its files only: the ranks must agree, with
+    each other, with a single context, and with the rule (tests/partition_model.py)"""
+    from tests.partition_model import SHARE, partition_model
+
+    rng = np.random.default_rng(300)
+    reads = []
+    for _ in range(300):
+        x = "".join("ACGT"[b] for b in rng.integers(0, 4, 140))
+        reads += [x[0:100], x[40:140]]
+    n_files = 3
+    want_c, want_e = _single_files(reads, 40, n_files)
+    got_c, got_e, _, _, _ = _dist_files(reads, 40, G, n_files)
+    assert all(len(f) == 0 for f in want_c)                  # nothing contained
+    every = [l for f in got_e for l in f]
+    assert len(every) == 300 == len(set(every))              # every edge line exactly once
+    assert got_e == want_e and got_c == want_c
+    ends = [np.array([[int(x) - 1 for x in l.split(b"\t")[:2]] for l in f], dtype=np.int64).reshape(-1, 2) for f in want_e]
+    src, dst = np.concatenate([a[:, 0] for a in ends]), np.concatenate([a[:, 1] for a in ends])
+    assert sorted(zip(np.minimum(src, dst).tolist(), np.maximum(src, dst).tolist())) == [(2 * k, 2 * k + 1) for k in range(300)]
+    model, info = partition_model(src, dst, len(reads), n_files)
+    assert info["thr"] == 1 and SHARE * n_files + SHARE < info["n_big"] == 300 < 2 * SHARE * n_files
+    assert np.array_equal(model, np.repeat(np.arange(n_files), [len(a) for a in ends]))   # the single-context files are the model's
+
+
 # ---- 4. streaming, 5. a second pass ----------------------------------------------------------------------------------------------------
 def test_texts_streamed_into_files_and_a_second_pass(single, cov_ranks, tmp_path):
     """every rank writes its files through the pinned ring: rank after rank they are the fetched texts, and the single-context files. The

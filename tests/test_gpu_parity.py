@@ -200,15 +200,18 @@ def test_edge_files_follow_connected_components():
     """disco_fetch_edge_files: all edges of a node in ONE file (what the consumer's per-file pre-simplification needs), large
     components dealt out by size"""
     from disco_amd import buildgraph
+    from tests.partition_model import components, partition_model
 
     spec = readgen.GenSpec.coverage(41, 30000, 150, 30.0, n_contigs=12)
     with buildgraph.BuildGraph(min_overlap=40) as g:
         g.generate_reads(spec)
         g.run_graph()
         e = g.fetch_edges()
+        root = components(e["src"], e["dst"], spec.n_reads)
         for nf in (1, 4, 7):
             f = g.fetch_edge_files(nf)
             assert len(f) == len(e) and f.max() < nf
+            assert np.array_equal(f, partition_model(e["src"], e["dst"], spec.n_reads, nf, root)[0])   # exactly the rule's files
             node_file = {}
             for a, b, t in zip(e["src"].tolist(), e["dst"].tolist(), f.tolist()):
                 assert node_file.setdefault(a, t) == t and node_file.setdefault(b, t) == t

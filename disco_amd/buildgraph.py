@@ -135,6 +135,7 @@ ABI = [
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
 FLAG_TWO_PASS_VERIFY = 1  # DISCO_FLAG_TWO_PASS_VERIFY
+FLAG_SEEDED_KMER = 2  # DISCO_FLAG_SEEDED_KMER: any min_overlap >= 2 (the index holds a seed of at most 94 bases, verify the true k-mer)
 XCHG = ("reads", "index_records", "index_shards", "contain", "row_requests", "row_data", "push", "adjacency", "twins", "queries", "hits", "keys", "reads_dealt", "contain_keys")
 UNIQUE_ID_BYTES = 128
 DIST_GATHER_READS = 1

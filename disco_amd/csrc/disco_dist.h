@@ -857,6 +857,9 @@ __global__ void __launch_bounds__(64) emit_push_recv_kernel(EmitRecvArgs a)
  * run), so the set of (window, record) candidates is the replicated flow's.
  *   query : x = bucket << 32 | read index inside the requester's range ; y = PQ_Y(requester rank, fingerprint, strand, occ - first, end, first)
  *   hit   : x = requester rank << 32 | read index inside its range      ; y = HIT_MAKE(window, id, suffix, strand relation, length)
+ * A seed shorter than the reference's k-mer (DiscoView::ks): the windows are the seed's, and the owner — who does not know the
+ * requester's read — maps a hit to the reference's window and drops it where the reference does not look: a suffix-aligned record
+ * below window k - ks, a prefix-aligned one in the run's last `cut` windows (PQ_CUT: those at or beyond L - k; 0 without a seed).
  * ======================================================================================================================= */
 #define PQ_Y(rank, fp, rev, delta, wend, wstart) \
     (((u64)(rank) << 47) | ((u64)(fp) << 37) | ((u64)(rev) << 36) | ((u64)(delta) << 30) | ((u64)(wend) << 15) | (u64)(wstart))
@@ -866,6 +869,10 @@ __global__ void __launch_bounds__(64) emit_push_recv_kernel(EmitRecvArgs a)
 #define PQ_REV(y) ((u32)(((y) >> 36) & 1u))
 #define PQ_FP(y) ((u32)(((y) >> 37) & 0x3FFu))
 #define PQ_RANK(y) ((u32)(((y) >> 47) & 0x3Fu))
+#define PQ_CUT_SHIFT 53 /* a run has at most 64 windows (they share one m-mer): 7 bits */
+#define PQ_CUT(y) ((int)(((y) >> PQ_CUT_SHIFT) & 0x7Fu))
+/* windows at the end of the seed run [wstart, wend) of a read of L bases that lie at or beyond the reference's last looked-up one */
+__device__ __forceinline__ u64 pq_cut(int wstart, int wend, int L, int k) { return (u64)(wend - min(wend, max(wstart, L - k))) << PQ_CUT_SHIFT; }
 
 struct RouteByHitRank { /* {rank << 32 | read index, hit} */
     __device__ __forceinline__ u32 operator()(const ulonglong2 &h) const { return (u32)(h.x >> 32); }
@@ -873,7 +880,7 @@ struct RouteByHitRank { /* {rank << 32 | read index, hit} */
 
 /* runs of the reads [lo, hi) -> queries; reads whose run list is unusable (ties, too many runs) -> slow list (pq_slow_kernel).
  * LPR u32 words of run entries per read (index_runs_kernel); one thread per word = two entries. out == nullptr: count only. */
-template <int LPR>
+template <int LPR, bool SEEDED = false>
 __global__ void __launch_bounds__(256) pq_make_kernel(DiscoView v, const u32 *__restrict__ runs, u64 lo, u64 hi, u32 my_rank, ulonglong2 *__restrict__ out,
                                                       u64 *__restrict__ n_out, u32 *__restrict__ slow, u32 slow_cap, u32 *__restrict__ n_slow)
 {
@@ -892,7 +899,7 @@ __global__ void __launch_bounds__(256) pq_make_kernel(DiscoView v, const u32 *__
         const u32 nx = (u32)__shfl_down((int)e0, 1);
         const u64 A = lo + ri;
         const int L = in ? (int)v.len[A] : 0;
-        const u32 npos = (u32)(L - v.k);
+        const u32 npos = (u32)(L - (SEEDED ? v.ks : v.k));
         const bool v0 = in && !slowread && e0 < 0xFFFEu, v1 = in && !slowread && e1 < 0xFFFEu;
         if (in && slowread && e == 0 && slow) { /* (first pass only) */
             const u32 si = atomicAdd(n_slow, 1u);
@@ -913,7 +920,7 @@ __global__ void __launch_bounds__(256) pq_make_kernel(DiscoView v, const u32 *__
         auto emit = [&](u64 where, u32 en, u32 wend) {
             const u32 wstart = RUN_W(en), delta = RUN_DELTA(en), rev = RUN_STRAND(en);
             const u64 key = mmer_key(row, v.S, (int)(wstart + delta), v.m);
-            out[where] = make_ulonglong2(((key >> v.bshift) << 32) | (u64)(u32)ri, PQ_Y(my_rank, KEY_FP(key), rev, delta, wend, wstart));
+            out[where] = make_ulonglong2(((key >> v.bshift) << 32) | (u64)(u32)ri, PQ_Y(my_rank, KEY_FP(key), rev, delta, wend, wstart) | (SEEDED ? pq_cut((int)wstart, (int)wend, L, v.k) : 0ull));
         };
         if (v0) emit(pos, e0, wend0);
         if (v1) emit(pos + 1, e1, wend1);
@@ -926,7 +933,7 @@ __global__ void __launch_bounds__(256) pq_make_kernel(DiscoView v, const u32 *__
  * occurrence can own several such ranges; their windows are disjoint, so the owner's test still yields every (window, record) pair
  * once. One thread per read. out == nullptr: queries per read -> cnt; else the queries at out + start[i]. list == nullptr: read i of
  * the range itself. */
-template <bool LONGK>
+template <bool LONGK, bool SEEDED = false>
 __global__ void pq_slow_kernel(DiscoView v, const u32 *__restrict__ list, u64 n_list, u64 lo, u32 my_rank, u32 *__restrict__ cnt, const u64 *__restrict__ start,
                                ulonglong2 *__restrict__ out)
 {
@@ -934,7 +941,7 @@ __global__ void pq_slow_kernel(DiscoView v, const u32 *__restrict__ list, u64 n_
     for (; i < n_list; i += (u64)gridDim.x * blockDim.x) {
         const u64 ri = list ? (u64)list[i] : i, A = lo + ri;
         const u64 *row = v.reads + A * v.S;
-        const int L = v.len[A], k = v.k, m = v.m, nf = k - m + 1, npos = L - k;
+        const int L = v.len[A], k = SEEDED ? v.ks : v.k, m = v.m, nf = k - m + 1, npos = L - k;
         ulonglong2 *o = out ? out + start[i] : nullptr;
         u32 n = 0;
         int run_w = 0, run_p = -1;
@@ -943,7 +950,7 @@ __global__ void pq_slow_kernel(DiscoView v, const u32 *__restrict__ list, u64 n_
             if (run_p < 0) return;
             if (o) {
                 const u64 key = mmer_key(row, v.S, run_p, m);
-                o[n] = make_ulonglong2(((key >> v.bshift) << 32) | (u64)(u32)ri, PQ_Y(my_rank, KEY_FP(key), run_rev, run_p - run_w, wend, run_w));
+                o[n] = make_ulonglong2(((key >> v.bshift) << 32) | (u64)(u32)ri, PQ_Y(my_rank, KEY_FP(key), run_rev, run_p - run_w, wend, run_w) | (SEEDED ? pq_cut(run_w, wend, L, v.k) : 0ull));
             }
             n++;
         };
@@ -982,9 +989,9 @@ __global__ void pq_slow_kernel(DiscoView v, const u32 *__restrict__ list, u64 n_
 
 /* the owner's side: one thread per query walks its bucket (bkt / ent: this rank's slices, bucket indices relative to blo, record
  * positions relative to the slice). FILL = false: hits per query -> cnt; FILL = true: the hits at out + start[query]. */
-template <bool FILL>
+template <bool FILL, bool SEEDED = false>
 __global__ void __launch_bounds__(256) pq_answer_kernel(const ulonglong2 *__restrict__ q, u64 nq, const u32 *__restrict__ bkt, const u64 *__restrict__ ent, u64 blo,
-                                                        u64 per, int nf, u32 *__restrict__ cnt, const u64 *__restrict__ start, ulonglong2 *__restrict__ out)
+                                                        u64 per, int nf, int dl, u32 *__restrict__ cnt, const u64 *__restrict__ start, ulonglong2 *__restrict__ out)
 {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; i < nq; i += (u64)gridDim.x * blockDim.x) {
@@ -992,6 +999,7 @@ __global__ void __launch_bounds__(256) pq_answer_kernel(const ulonglong2 *__rest
         const u64 b = (qq.x >> 32) - blo;
         const u32 idx = (u32)qq.x, rank = PQ_RANK(qq.y), fp = PQ_FP(qq.y), rev = PQ_REV(qq.y);
         const int wstart = PQ_WSTART(qq.y), wend = PQ_WEND(qq.y), prel = wstart + PQ_DELTA(qq.y);
+        const int wpre = SEEDED ? wend - PQ_CUT(qq.y) : wend, wsuf = SEEDED ? max(wstart, dl) : wstart; /* dl = k - ks: where a prefix- / suffix-aligned record's window must lie */
         const u64 self = (u64)rank * per + idx; /* BG/OverlapGraph.cpp:421,655: a read is no candidate of its own */
         const u32 s = bkt[b], e = bkt[b + 1];
         u32 n = 0;
@@ -1000,8 +1008,9 @@ __global__ void __launch_bounds__(256) pq_answer_kernel(const ulonglong2 *__rest
             const u64 pay = ent[r];
             const int t = (int)PAY_T(pay);
             const int w = rev ? prel - (nf - 1 - t) : prel - t;
-            if (PAY_FP(pay) == fp && PAY_ID(pay) != self && w >= wstart && w < wend) {
-                if (FILL) out[at + n] = make_ulonglong2(((u64)rank << 32) | idx, HIT_MAKE(w, PAY_ID(pay), PAY_SUFFIX(pay), PAY_REV(pay) ^ rev, PAY_LEN(pay)));
+            const bool pal = !SEEDED || PAY_SUFFIX(pay) == (PAY_REV(pay) ^ rev);
+            if (PAY_FP(pay) == fp && PAY_ID(pay) != self && w >= (pal ? wstart : wsuf) && w < (pal ? wpre : wend)) {
+                if (FILL) out[at + n] = make_ulonglong2(((u64)rank << 32) | idx, HIT_MAKE(pal ? w : w - dl, PAY_ID(pay), PAY_SUFFIX(pay), PAY_REV(pay) ^ rev, PAY_LEN(pay)));
                 n++;
             }
         }

@@ -176,7 +176,8 @@ struct disco_ctx {
     int device = 0;
     disco_params prm{};
     DevArena arena;
-    int k = 0;
+    int k = 0;  /* the reference's k = min_overlap - 1 */
+    int ks = 0; /* the seed the index holds: min(k, DISCO_MAX_K) (DISCO_FLAG_SEEDED_KMER; DiscoView::ks) */
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     int n_cu = 256;
@@ -609,10 +610,11 @@ static DiscoView view(const disco_ctx *c)
     v.n = c->n;
     v.S = c->S;
     v.k = c->k;
-    v.m = disco_minimizer_len(c->k);
+    v.ks = c->ks;
+    v.m = disco_minimizer_len(c->ks);
     if (const char *e = getenv("DISCO_MINIMIZER_LEN")) { /* tuning knob: odd, <= min(k, 23), k - m <= 63 */
         const int m = atoi(e);
-        if (m >= 1 && (m & 1) && m <= v.m && c->k - m <= 63) v.m = m;
+        if (m >= 1 && (m & 1) && m <= v.m && c->ks - m <= 63) v.m = m;
     }
     v.bkt = c->d_bkt;
     v.ent = c->d_ent;
@@ -943,8 +945,8 @@ static int runs_lpr_for(const disco_ctx *c, int nf, u32 max_len, u64 nloc)
     const int m = view(c).m;
     const bool nf_built = runs_nf_built(nf, m);
     const bool nf_generic = nf >= 2 && nf <= 64 && m > 16 && m <= 31 && !getenv("DISCO_NO_GENERIC_RUNS");
-    if ((nf_built || nf_generic) && max_len > (u32)c->k && !getenv("DISCO_NO_RUNS")) {
-        const u32 maxwin = max_len - (u32)c->k;
+    if ((nf_built || nf_generic) && max_len > (u32)c->ks && !getenv("DISCO_NO_RUNS")) {
+        const u32 maxwin = max_len - (u32)c->ks; /* (the seed's windows) */
         /* a read of W windows has about 2 W / (NF + 1) runs: 32 entries where that stays below 20 (room for the spread), else 64 */
         const u32 expect = 2u * maxwin / (u32)(nf + 1);
         lpr = maxwin <= 256 ? (maxwin <= 128 && expect <= 20 ? 16 : (expect <= 44 ? 32 : 0)) : 0;
@@ -963,7 +965,7 @@ static bool two_class_ok(const disco_ctx *c, int S, u64 n, u64 n_long, u32 short
     if (((c->comm || c->dist_reads) && !c->dist_two_class) || !(c->reads_owned || will_own) || c->prm.max_substitutions || getenv("DISCO_NO_TWO_CLASS")) return false;
     if (S <= VERIFY_SW || n_long == 0 || n_long * (u64)env_int("DISCO_TWO_CLASS_ONE_IN", 5) > n || n + n_long >= (1ull << 31)) return false;
     /* the short class takes the paths of a pure short set (minimizer runs, flat verify); the long one the lists those paths keep */
-    return runs_lpr_for(c, c->k - view(c).m + 1, short_max, n) != 0;
+    return runs_lpr_for(c, c->ks - view(c).m + 1, short_max, n) != 0;
 }
 
 /* the long class's buffers for a table of n_long long reads of stride Sx whose short class has reads of up to short_max bases; the rows
@@ -1052,7 +1054,7 @@ static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, In
     c->runs_lpr = 0;
     c->runs_n = 0;
     c->runs_by_pos = false;
-    const int nf = v.k - v.m + 1;
+    const int nf = v.ks - v.m + 1;
     const int lpr = c->S == VERIFY_SW ? runs_lpr_for(c, nf, c->max_len, nloc) : 0;
     if (lpr && nloc) {
         CHK(ensure(c, c->d_runs, nloc * (u64)lpr));
@@ -1125,7 +1127,7 @@ static int index_count_chunk(disco_ctx *c, const DiscoView &v, const IndexCountP
     u32 *oslot = pl.oslot ? pl.oslot + (a - pl.lo) : nullptr;
     u64 *oitem = pl.oitem ? pl.oitem + (a - pl.lo) : nullptr; /* (at the read's global position, whichever chunk brings it) */
     u32 *okey = pl.list ? nullptr : c->d_okey.p; /* (a list: the keys were made when the reads were dealt, by read id) */
-    const IndexCountKernel k = index_count_pick(count, pl.nf, v.m, pl.lpr, c->k > 64, false);
+    const IndexCountKernel k = index_count_pick(count, pl.nf, v.m, pl.lpr, c->ks > 64, false);
     if (k.runs) hipLaunchKernelGGL(k.runs, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, c->d_runs + (a - pl.lo) * (u64)pl.lpr, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.list);
     else hipLaunchKernelGGL(k.plain, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.list);
     HIPCHK(c, hipGetLastError());
@@ -1137,7 +1139,7 @@ static int index_count_chunk(disco_ctx *c, const DiscoView &v, const IndexCountP
 static int index_count_long(disco_ctx *c, const DiscoView &v, const IndexCountPlan &pl, bool count, ulonglong2 *rec, u32 *oslot, u64 x_lo, u64 x_hi)
 {
     const dim3 g((unsigned)((x_hi - x_lo + 255) / 256));
-    hipLaunchKernelGGL(index_count_pick(count, 0, v.m, 0, c->k > 64, true).plain, g, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, x_lo, x_hi, pl.ocnt, oslot, (u64 *)nullptr, 0u, pl.oshift,
+    hipLaunchKernelGGL(index_count_pick(count, 0, v.m, 0, c->ks > 64, true).plain, g, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, x_lo, x_hi, pl.ocnt, oslot, (u64 *)nullptr, 0u, pl.oshift,
                        (const u64 *)nullptr);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
@@ -1435,11 +1437,11 @@ static ProbeFn probe_mode_pick(bool ldsrow, bool row17, bool longk, bool long_cl
 static ProbeKernel probe_pick(const disco_ctx *c, int mode, bool use_runs)
 {
     const bool ldsrow = c->S <= PROBE_ACAP; /* (two classes of rows: c->S = 8; the lists' kernels take the long class's stride into account) */
-    const bool row17 = c->k - view(c).m == 16 && !getenv("DISCO_NO_ROW17"); /* window = 17 m-mers: DPP row-scan variant */
-    const bool longk = c->k > 64;                                            /* three-word k-mers: variants of their own (kmer_is_rev) */
+    const bool row17 = c->ks - view(c).m == 16 && !getenv("DISCO_NO_ROW17"); /* window = 17 m-mers: DPP row-scan variant */
+    const bool longk = c->ks > 64;                                           /* three-word k-mers: variants of their own (kmer_is_rev) */
     const bool long_class = c->two_class && c->S_ext > PROBE_ACAP;
     ProbeKernel k;
-    if (mode == 0 && use_runs) k.runs = c->runs_lpr == 16 ? probe_runs_kernel<16> : probe_runs_kernel<32>;
+    if (mode == 0 && use_runs) k.runs = c->k != c->ks ? (c->runs_lpr == 16 ? probe_runs_kernel<16, true> : probe_runs_kernel<32, true>) : (c->runs_lpr == 16 ? probe_runs_kernel<16> : probe_runs_kernel<32>);
     else if (mode == 0) k.plain = probe_mode_pick<0>(ldsrow, row17, longk, long_class);
     else if (mode == 1) k.plain = probe_mode_pick<1>(ldsrow, row17, longk, long_class);
     else k.plain = probe_mode_pick<2>(ldsrow, row17, longk, long_class);
@@ -1598,7 +1600,9 @@ int disco_abi_version(void) { return DISCO_ABI_VERSION; }
 int disco_create(int device, const disco_params *p, disco_ctx **out)
 {
     if (!p || !out) return fail(nullptr, DISCO_E_ARG, "disco_create: null argument");
-    if (p->min_overlap < 2 || p->min_overlap - 1 > DISCO_MAX_K)
+    /* (a longer k-mer: only for a caller who asks for the seeded index — every length a read can have is then accepted, and the reads'
+     * own validation, min_overlap < length <= 32767, is the bound) */
+    if (p->min_overlap < 2 || (p->min_overlap - 1 > DISCO_MAX_K && !(p->flags & DISCO_FLAG_SEEDED_KMER)))
         return fail(nullptr, DISCO_E_UNSUPPORTED, "disco_create: min_overlap %u unsupported (k = min_overlap-1 must be in [1,%d])", p->min_overlap, DISCO_MAX_K);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -1611,6 +1615,7 @@ int disco_create(int device, const disco_params *p, disco_ctx **out)
     if (c->prm.max_edges_per_kmer == 0) c->prm.max_edges_per_kmer = 4;
     if (c->prm.max_substitutions > 32767) c->prm.max_substitutions = 32767; /* no read is longer (15-bit length field) */
     c->k = (int)p->min_overlap - 1;
+    c->ks = std::min(c->k, DISCO_MAX_K);
 #define CREATE_CHK(call)                                                                              \
     do {                                                                                              \
         hipError_t e2 = (call);                                                                       \
@@ -5765,7 +5770,8 @@ static int dist_partitioned_probe(disco_ctx *c)
     const u32 G = (u32)c->comm->world, r = (u32)c->comm->rank;
     const u64 lo = c->q_lo, nloc = c->q_hi - c->q_lo;
     DiscoView v = view(c);
-    const int nf = v.k - v.m + 1;
+    const int nf = v.ks - v.m + 1;
+    const bool seeded = c->k != c->ks; /* (instantiations of their own: without a seed the kernels are what they were) */
     const bool have_runs = c->runs_lpr != 0 && c->runs_lo == lo && c->runs_n == nloc; /* (every rank decides alike: the shape of the JOB) */
     int logT = 0;
     while ((1ull << logT) < c->T) ++logT;
@@ -5777,8 +5783,8 @@ static int dist_partitioned_probe(disco_ctx *c)
         const int grid = flat_grid(c, nloc * (u64)c->runs_lpr);
         u32 *slow = collect_slow ? (u32 *)c->d_slow_list.p : nullptr;
         const u32 cap = c->d_slow_list.cap * 2; /* (the list's u64 slots hold two read indices each) */
-        if (c->runs_lpr == 16) hipLaunchKernelGGL(pq_make_kernel<16>, dim3(grid), dim3(256), 0, c->stream, v, (const u32 *)c->d_runs, lo, c->q_hi, r, out, c->d_list_n, slow, cap, d_nslow);
-        else hipLaunchKernelGGL(pq_make_kernel<32>, dim3(grid), dim3(256), 0, c->stream, v, (const u32 *)c->d_runs, lo, c->q_hi, r, out, c->d_list_n, slow, cap, d_nslow);
+        auto fn = seeded ? (c->runs_lpr == 16 ? pq_make_kernel<16, true> : pq_make_kernel<32, true>) : (c->runs_lpr == 16 ? pq_make_kernel<16> : pq_make_kernel<32>);
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, c->stream, v, (const u32 *)c->d_runs, lo, c->q_hi, r, out, c->d_list_n, slow, cap, d_nslow);
     };
     u64 nq_fast = 0, n_slow = 0;
     const u32 *slow = nullptr; /* null: every read of the range */
@@ -5810,7 +5816,8 @@ static int dist_partitioned_probe(disco_ctx *c)
         if (!n_slow) return DISCO_OK;
         CHK(ensure(c, slow_cnt, n_slow));
         CHK(ensure(c, slow_start, n_slow + 1));
-        if (c->k > 64) hipLaunchKernelGGL(pq_slow_kernel<true>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)nullptr, (ulonglong2 *)nullptr);
+        if (seeded) hipLaunchKernelGGL((pq_slow_kernel<true, true>), dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)nullptr, (ulonglong2 *)nullptr);
+        else if (c->ks > 64) hipLaunchKernelGGL(pq_slow_kernel<true>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)nullptr, (ulonglong2 *)nullptr);
         else hipLaunchKernelGGL(pq_slow_kernel<false>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)nullptr, (ulonglong2 *)nullptr);
         CHK((scan_exclusive<u32, u64>(c, slow_cnt, n_slow, slow_start, false, &nq_slow)));
         return DISCO_OK;
@@ -5822,7 +5829,8 @@ static int dist_partitioned_probe(disco_ctx *c)
         HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
         if (have_runs && nloc) make(c->d_x16a, false);
         if (n_slow) {
-            if (c->k > 64) hipLaunchKernelGGL(pq_slow_kernel<true>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
+            if (seeded) hipLaunchKernelGGL((pq_slow_kernel<true, true>), dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
+            else if (c->ks > 64) hipLaunchKernelGGL(pq_slow_kernel<true>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
             else hipLaunchKernelGGL(pq_slow_kernel<false>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
         }
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, DISCO_E_HIP, "dist_partitioned_probe: query kernels failed");
@@ -5845,13 +5853,15 @@ static int dist_partitioned_probe(disco_ctx *c)
     CHK(ensure(c, c->d_pq_start, nq_in + 1));
     const u32 *bkt = c->d_bkt;
     u64 n_hits_out = 0;
-    if (nq_in) hipLaunchKernelGGL(pq_answer_kernel<false>, dim3(flat_grid(c, nq_in)), dim3(256), 0, c->stream, (const ulonglong2 *)c->d_x16b, nq_in, bkt, (const u64 *)c->d_ent, c->part_blo, c->per,
-                                  nf, c->d_deg_tmp, (const u64 *)nullptr, (ulonglong2 *)nullptr);
+    auto answer_count = seeded ? pq_answer_kernel<false, true> : pq_answer_kernel<false, false>;
+    auto answer_fill = seeded ? pq_answer_kernel<true, true> : pq_answer_kernel<true, false>;
+    if (nq_in) hipLaunchKernelGGL(answer_count, dim3(flat_grid(c, nq_in)), dim3(256), 0, c->stream, (const ulonglong2 *)c->d_x16b, nq_in, bkt, (const u64 *)c->d_ent, c->part_blo, c->per,
+                                  nf, c->k - c->ks, c->d_deg_tmp, (const u64 *)nullptr, (ulonglong2 *)nullptr);
     CHK((scan_exclusive<u32, u64>(c, c->d_deg_tmp, nq_in, c->d_pq_start, false, &n_hits_out)));
     /* hits: flat list | partitioned by requester — in the send buffer (the queries it held have been answered into counts) */
     CHK(ensure_keep(c, c->d_x16a, std::max<u64>(2 * n_hits_out, 1), 0));
-    if (nq_in) hipLaunchKernelGGL(pq_answer_kernel<true>, dim3(flat_grid(c, nq_in)), dim3(256), 0, c->stream, (const ulonglong2 *)c->d_x16b, nq_in, bkt, (const u64 *)c->d_ent, c->part_blo, c->per,
-                                  nf, c->d_deg_tmp, (const u64 *)c->d_pq_start, c->d_x16a);
+    if (nq_in) hipLaunchKernelGGL(answer_fill, dim3(flat_grid(c, nq_in)), dim3(256), 0, c->stream, (const ulonglong2 *)c->d_x16b, nq_in, bkt, (const u64 *)c->d_ent, c->part_blo, c->per,
+                                  nf, c->k - c->ks, c->d_deg_tmp, (const u64 *)c->d_pq_start, c->d_x16a);
     HIPCHK(c, hipGetLastError());
     /* 4. hits -> the reads' owners */
     ulonglong2 *h_sorted = c->d_x16a + n_hits_out;

@@ -178,8 +178,10 @@ struct DiscoView {
     const u16 *len;   /* [n]    */
     u64 n;
     int S;
-    int k;
-    int m; /* minimizer length, disco_minimizer_len(k) */
+    int k;  /* the reference's k = min-overlap - 1: verify, containment, edge selection, emission */
+    int ks; /* seed length min(k, DISCO_MAX_K): what the index keys and the probe looks up (ks == k up to min-overlap 95). A seed hit at
+               window w stands for the reference's window j = w (prefix-aligned record) or w - (k - ks) (suffix-aligned); HIT_J holds j */
+    int m;  /* minimizer length, disco_minimizer_len(ks) */
     /* index */
     const u32 *bkt;         /* [T+1] bucket b = entries [bkt[b], bkt[b+1]) */
     const u64 *ent;         /* [2n] 8-byte records (PAY_MAKE)               */
@@ -332,7 +334,7 @@ __global__ void __launch_bounds__(256) index_count_kernel(DiscoView v, u32 *__re
     const int S = LONGCLASS ? v.SL : v.S;
     const u64 *__restrict__ p = LONGCLASS ? v.full + x * (u64)S : v.reads + rid * (u64)S;
     if (!LONGCLASS && v.full && v.len[rid] > DISCO_SHORT_MAX) return; /* (a long read's turn comes with the LONGCLASS launch) */
-    const int L = (!LONGCLASS && list) ? ORDER_LEN(lw) : (int)v.len[rid], k = v.k, m = v.m, nf = k - m + 1;
+    const int L = (!LONGCLASS && list) ? ORDER_LEN(lw) : (int)v.len[rid], k = v.ks, m = v.m, nf = k - m + 1;
     const int nmm = L - m + 1; /* m-mer positions (L >= k: validate_len_kernel) */
     const int sfx0 = nmm - nf; /* = L - k: first m-mer of the suffix k-mer */
     const u64 mask = (1ull << (2 * m)) - 1ull;
@@ -508,12 +510,12 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
      * every one of them walks in full need none of the per-lane tests against the read's end — see the two loops over the blocks below */
     const bool mine = i < hi && !other_class;
     const int L = mine ? (list ? ORDER_LEN(lw) : (int)v.len[rid]) : 0;
-    int npos_lo = mine ? L - v.k : 0x7FFFFFFF;
+    int npos_lo = mine ? L - v.ks : 0x7FFFFFFF;
     for (int o = 32; o; o >>= 1) npos_lo = min(npos_lo, __shfl_xor(npos_lo, o));
     npos_lo = __builtin_amdgcn_readfirstlane(npos_lo);
     if (mine) {
         const u64 *__restrict__ p = v.reads + rid * v.S;
-        const int k = v.k;
+        const int k = v.ks;
         const int m = NF ? RUNS_M : v.m; /* (the host takes a specialised instantiation for m = RUNS_M only: runs_lpr_for) */
         const int nf = NF ? NF : k - m + 1; /* (wave uniform) */
         const int nmm = L - m + 1; /* m-mer positions */
@@ -1036,8 +1038,9 @@ __global__ void __launch_bounds__(64, (LONGK || LONGCLASS) ? PROBE_WAVES_PER_SIM
     __shared__ u8 s_mark[64];           /* starts of the non-empty buckets in the concatenated record list             */
     __shared__ u64 s_a[PROBE_ACAP + 2]; /* the query read's own packed row + zero padding for the branch-free extracts */
     const u32 lane = threadIdx.x;
-    const int S = a.v.S, k = a.v.k;
+    const int S = a.v.S, k = a.v.ks; /* the seed: what the index holds */
     const int m = a.v.m, nf = k - m + 1;
+    const int dl = LONGK ? a.v.k - k : 0; /* bases of the reference's k-mer beyond the seed (only seeds of DISCO_MAX_K > 64 bases have any) */
     u64 chunk_base = 0;
     u32 chunk_used = PROBE_CHUNK;
     u32 my_maxrow = 0;
@@ -1092,6 +1095,7 @@ __global__ void __launch_bounds__(64, (LONGK || LONGCLASS) ? PROBE_WAVES_PER_SIM
             if (LDSROW && (int)lane < PROBE_ACAP + 2) s_a[lane] = ((int)lane < Sx) ? ga[lane] : 0ull;
         }
         const int npos = LA - k; /* windows j in [0, npos) : BG/OverlapGraph.cpp:401 (containment), :638 (edges, j >= 1) */
+        const u32 nref = (u32)(npos - dl); /* the reference's windows: [0, LA - a.v.k) */
         const u64 *pa = LDSROW ? (const u64 *)s_a : ga;
         u32 nrow = 0;
         u64 *grow = nullptr;
@@ -1134,6 +1138,10 @@ __global__ void __launch_bounds__(64, (LONGK || LONGCLASS) ? PROBE_WAVES_PER_SIM
 
         /* append the candidates flagged by `take` to the row */
         auto push = [&](bool take, u64 pay, u32 rev, int jj) {
+            if (LONGK) { /* seed window -> the reference's window (DiscoView::ks): a suffix-aligned record's k-mer ENDS where its seed ends */
+                if (PAY_SUFFIX(pay) != rev) jj -= dl;
+                take = take && (u32)jj < nref;
+            }
             const u64 mm = __ballot(take);
             if (take) {
                 const u32 pos = nrow + rank_below(mm);
@@ -1396,13 +1404,16 @@ __device__ __forceinline__ u64 shfl_u64(u64 x, u32 l)
 #endif
 /* runs_lo == ~0: the run lists are stored by POSITION in the processing order (multi-GPU flow, ranks own loci: index_runs_kernel ran
  * over the order itself), not by read id */
-template <int LPR>
+/* SEEDED: the reference's k-mer is longer than the seed (min-overlap above DISCO_MAX_K + 1) — a candidate carries the reference's window,
+ * and only where that window is one the reference looks up (DiscoView::ks) */
+template <int LPR, bool SEEDED = false>
 __global__ void __launch_bounds__(64, PR_WAVES_PER_SIMD) probe_runs_kernel(ProbeArgs a, const u32 *__restrict__ runs, u64 runs_lo)
 {
     constexpr int G = 64 / LPR;      /* reads per group                                            */
     constexpr int RS = VERIFY_SW + 1; /* words of a staged row (+ one readable word for the branch-free extract) */
     __shared__ u64 s_rows[G * RS];
     __shared__ u32 s_id[G];
+    __shared__ u32 s_nref[SEEDED ? G : 1]; /* SEEDED: the reference's windows of the slot's read, LA - a.v.k */
     __shared__ u32 s_occ[128]; /* the group's runs, compacted: OCC_MAKE */
     __shared__ u32 s_o_fp[64], s_o_start[64], s_o_excl[64], s_o_desc[64]; /* current batch of lookups with records */
     __shared__ u8 s_mark[PR_MARKCAP];
@@ -1410,7 +1421,8 @@ __global__ void __launch_bounds__(64, PR_WAVES_PER_SIMD) probe_runs_kernel(Probe
     __shared__ u32 s_len_exp[G];
 #endif
     const u32 lane = threadIdx.x;
-    const int k = a.v.k, m = a.v.m, nf = k - m + 1;
+    const int k = a.v.ks, m = a.v.m, nf = k - m + 1; /* the seed: what the index holds */
+    const int dl = SEEDED ? a.v.k - k : 0;
     const u32 slot = lane / LPR, e = lane % LPR;
     const u64 le = lane_mask_lt() | (1ull << lane);
     const u64 nq = a.v.q_hi - a.v.q_lo;
@@ -1466,6 +1478,7 @@ __global__ void __launch_bounds__(64, PR_WAVES_PER_SIMD) probe_runs_kernel(Probe
             __syncthreads();
             if (lane < (u32)(G * 8)) s_rows[(lane >> 3) * RS + (lane & 7)] = pre_row;
             if (e == 0) s_id[slot] = sv ? A : 0xFFFFFFFFu;
+            if (SEEDED && e == 0) s_nref[slot] = sv ? npos - (u32)dl : 0u;
 #if defined(VERIFY_EXP_HALF)
             if (e == 0) s_len_exp[slot] = (u32)LA;
 #endif
@@ -1580,9 +1593,13 @@ __global__ void __launch_bounds__(64, PR_WAVES_PER_SIMD) probe_runs_kernel(Probe
                     const int wst = (int)OCC_FIRST(dd), wen = (int)OCC_END(dd), prel = wst + (int)OCC_DELTA(dd);
                     const int t = (int)PAY_T(pay);
                     /* a window in canonical-forward orientation starts t before the occurrence, a reversed one k - m - t before */
-                    const int w = rv ? prel - (nf - 1 - t) : prel - t;
+                    int w = rv ? prel - (nf - 1 - t) : prel - t;
                     bool take = in && PAY_FP(pay) == s_o_fp[lo] && (u32)PAY_ID(pay) != s_id[dslot] /* self: BG/OverlapGraph.cpp:421,655 */
                                 && w >= wst && w < wen;
+                    if (SEEDED) { /* seed window -> the reference's window: a suffix-aligned record's k-mer ENDS where its seed ends */
+                        if (PAY_SUFFIX(pay) != (PAY_REV(pay) ^ rv)) w -= dl;
+                        take = take && (u32)w < s_nref[dslot];
+                    }
 #if defined(VERIFY_EXP_HALF) /* timing experiment (results are wrong): the reference compares a pair once and inserts the twin (BG/OverlapGraph.cpp:614-626,
                                 652-653); here every overlap is compared from both sides. What half the overlap-type candidates would leave of probe
                                 + verify: those into a read of smaller id are dropped (containment-type candidates stay: verify's MODE 1 rule) */

@@ -340,7 +340,7 @@ int main(int argc, char **argv)
         return ingest_fetch_rc.load() >= 0;
     };
     if (gpus == 1 && !getenv("DISCO_HOST_INPUT")) {
-        const disco_params prm0{min_overlap, 4, getenv("DISCO_EXACT_COUNTERS") ? 0u : DISCO_FLAG_TWO_PASS_VERIFY, max_subs};
+        const disco_params prm0{min_overlap, 4, DISCO_FLAG_SEEDED_KMER | (getenv("DISCO_EXACT_COUNTERS") ? 0u : DISCO_FLAG_TWO_PASS_VERIFY), max_subs};
         if (disco_create(gpu, &prm0, &ctx1) < 0) return die(std::string("disco_create: ") + disco_last_error(nullptr));
         if (getenv("DISCO_VERBOSE")) fprintf(stderr, "[disco host] process start to context ready   %.3f s\n", secs(t_main));
         std::vector<const char *> paths;
@@ -420,7 +420,7 @@ int main(int argc, char **argv)
     } watchdog_join{ranks_done, watchdog};
     /* the ranks' contexts, the communicator (in-process: joined here; RCCL: its id) and the watchdog; "" or what went wrong */
     auto make_ranks = [&]() -> std::string {
-        const disco_params prm0{min_overlap, 4, getenv("DISCO_EXACT_COUNTERS") ? 0u : DISCO_FLAG_TWO_PASS_VERIFY, max_subs};
+        const disco_params prm0{min_overlap, 4, DISCO_FLAG_SEEDED_KMER | (getenv("DISCO_EXACT_COUNTERS") ? 0u : DISCO_FLAG_TWO_PASS_VERIFY), max_subs};
         ctx.assign((size_t)gpus, nullptr);
         for (int r = 0; r < gpus; r++)
             if (disco_create(same_device ? gpu : gpu + r, &prm0, &ctx[(size_t)r]) < 0)
@@ -588,7 +588,7 @@ int main(int argc, char **argv)
     const bool verbose = getenv("DISCO_VERBOSE") != nullptr;
     /* two-pass verify for read sets of mixed lengths (metagenomes: most reads contained): same files, fewer candidate-row fetches;
      * only the diagnostic k-mer-hit count in the log then counts the compared candidates */
-    disco_params prm{min_overlap, 4, getenv("DISCO_EXACT_COUNTERS") ? 0u : DISCO_FLAG_TWO_PASS_VERIFY, max_subs};
+    disco_params prm{min_overlap, 4, DISCO_FLAG_SEEDED_KMER | (getenv("DISCO_EXACT_COUNTERS") ? 0u : DISCO_FLAG_TWO_PASS_VERIFY), max_subs};
     std::unique_ptr<uint16_t[]> edge_subs; /* substitutions per edge (third number of an edge line); stays null with exact overlaps */
     uint64_t n_cont = 0, e_pre = 0, e_out = 0;
     std::vector<disco_contained_row> rows;

@@ -55,6 +55,10 @@ enum {
                                          the faster form on the shapes measured (50 M reads of 100-250 bases: 31 against 39 ms of
                                          verify); the flag stays for read sets it still helps and is ignored on a table with two
                                          classes of rows (disco_long_rows) */
+#define DISCO_FLAG_SEEDED_KMER 2u     /* accept any min_overlap >= 2 (without it: at most 95, as before; no effect up to 95). The index
+                                         holds a SEED of ks = min(k, 94) bases at each read end; a seed hit at window w of read A stands
+                                         for the reference's window j = w (prefix-aligned record; kept if w < len(A) - k) or
+                                         j = w - (k - ks) (suffix-aligned; kept if w >= k - ks), and verify compares with the true k */
 
 typedef struct disco_ctx disco_ctx;
 

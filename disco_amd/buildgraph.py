@@ -193,6 +193,7 @@ INSPECT_ABI = [
     ("disco_fetch_order", C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     ("disco_fetch_survivor_layout", C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     ("disco_set_record_piece", C.c_int, [_P, C.c_uint64]),
+    ("disco_set_order_sub_bits", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
 ]
 _inspect_bound = False
 
@@ -637,6 +638,14 @@ class BuildGraph:
         order, keys = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros(max(n.value, 1), dtype=np.uint32)
         self._chk(self.L.disco_fetch_order(self._h, order.ctypes.data, keys.ctypes.data, len(order), C.byref(n), C.byref(bits)))
         return order[:n.value], keys[:n.value], bits.value
+
+    def order_sub_bits(self, limit: int = -1) -> int:
+        """bits of the grouping's sub-key (start order inside a bucket) the last build_index used; limit >= 0: later index builds take at
+        most that many (0: none). Tests only"""
+        _bind_inspect(self.L)
+        used = C.c_int(0)
+        self._chk(self.L.disco_set_order_sub_bits(self._h, limit, C.byref(used)))
+        return used.value
 
     def fetch_survivor_layout(self, lengths: bool = True):
         """(list lengths or None, dense, out_used) of the last transitive_reduce: the decoded length of every node's self-delimiting

@@ -262,6 +262,9 @@ struct disco_ctx {
     bool order_counted = false;
     bool order_items = false; /* ... as items for the partition levels (d_rec2; the binned grouping): only disco_build_index can finish it */
     int order_id_bits = 0;    /* (bits of the read id in an item) */
+    int order_spare_bits = 0; /* (bits of an item that bucket, length and read id leave) */
+    int order_sub_bits = 0;   /* (... and how many of them hold the sub-key, directly below the bucket: ORDER_SUBKEY; 0 = none) */
+    int order_sub_limit = ORDER_SUB_MAX; /* (disco_set_order_sub_bits: tests take the sub-key away) */
     /* the big-item lists are sized from counts the producing kernels leave behind (verify: rows beyond ES_CAP; edge selection: nodes
      * beyond TR_CAP) — valid until something else changes the rows: then the counting pass (ensure_big_cap) runs as before */
     bool es_big_counted = false, tr_big_counted = false;
@@ -914,7 +917,7 @@ static bool own_order_wanted(const disco_ctx *c, u64 nq, int *bits)
     const u64 order_min = getenv("DISCO_ORDER_MIN_READS") ? (u64)atoll(getenv("DISCO_ORDER_MIN_READS")) : 4096; /* tests: 1 */
     int b = 16;
     while (b < 27 && (1ull << b) < nq) ++b;
-    if (const char *e = getenv("DISCO_ORDER_BITS")) b = std::min(std::max(atoi(e), 16), 26); /* tests: two partition levels on a small set */
+    if (const char *e = getenv("DISCO_ORDER_BITS")) b = std::min(std::max(atoi(e), 12), 26); /* tests: two partition levels on a small set; dozens of reads per bucket */
     *bits = b;
     return !c->order_external && !getenv("DISCO_NO_ORDER") && nq >= order_min && nq > 0;
 }
@@ -929,6 +932,7 @@ struct IndexCountPlan {
     u64 *oitem = nullptr; /* the binned grouping: an item per read instead of a count and a slot */
     u32 oidbits = 0;
     u32 oshift = 0;
+    u32 osub = 0; /* the sub-key of an item (ORDER_SUBKEY): its bits << 24 | its multiplier; 0 = none */
     const u64 *list = nullptr; /* ranks own loci: position x of [lo, hi) stands for read ORDER_ID(list[x]) (records, runs, slots by position) */
 };
 
@@ -1019,6 +1023,7 @@ static bool binned_order_wanted(disco_ctx *c, u64 n, int obits, int *id_bits)
         return false;
     }
     *id_bits = idb;
+    c->order_spare_bits = 64 - (obits + lenb + idb);
     return true;
 }
 
@@ -1065,13 +1070,23 @@ static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, In
         pl->lpr = lpr;
         pl->nf = nf;
     }
+    /* the binned grouping's sub-key: index_runs_kernel knows where the read-level minimizer lies in the read, so the spare bits of the
+     * item (four at 5 x 10^7 reads of 150 bases, ORDER_SUB_MAX of them taken) order the reads of a bucket by their start;
+     * index_count_kernel and a full word: none */
+    c->order_sub_bits = 0;
+    if (pl->oitem && pl->lpr) {
+        const int qbits = std::max(0, std::min(c->order_spare_bits, std::min(c->order_sub_limit, ORDER_SUB_MAX)));
+        const u32 nmm_max = c->max_len - (u32)v.m + 1u; /* (lpr != 0: the longest read has a k-mer) */
+        if (qbits) pl->osub = ((u32)qbits << 24) | ((1u << (qbits + 16)) / nmm_max);
+        c->order_sub_bits = qbits;
+    }
     return DISCO_OK;
 }
 
 /* which instantiation counts this shape — the ONLY place that names the template arguments of index_runs_kernel / index_count_kernel.
  * lpr != 0: with the minimizer runs (16 / 32 words per read: NL 1 / 2), a window of nf m-mers; long_class: the long reads of two row
  * classes, from their full rows (never with runs) */
-typedef void (*IndexRunsFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u32 *, u64 *, u32, u32, const u64 *);
+typedef void (*IndexRunsFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u32 *, u64 *, u32, u32, u32, const u64 *);
 typedef void (*IndexCountFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u64 *, u32, u32, const u64 *);
 struct IndexCountKernel {
     IndexRunsFn runs = nullptr; /* one of the two */
@@ -1128,7 +1143,7 @@ static int index_count_chunk(disco_ctx *c, const DiscoView &v, const IndexCountP
     u64 *oitem = pl.oitem ? pl.oitem + (a - pl.lo) : nullptr; /* (at the read's global position, whichever chunk brings it) */
     u32 *okey = pl.list ? nullptr : c->d_okey.p; /* (a list: the keys were made when the reads were dealt, by read id) */
     const IndexCountKernel k = index_count_pick(count, pl.nf, v.m, pl.lpr, c->ks > 64, false);
-    if (k.runs) hipLaunchKernelGGL(k.runs, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, c->d_runs + (a - pl.lo) * (u64)pl.lpr, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.list);
+    if (k.runs) hipLaunchKernelGGL(k.runs, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, c->d_runs + (a - pl.lo) * (u64)pl.lpr, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.osub, pl.list);
     else hipLaunchKernelGGL(k.plain, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.list);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
@@ -1275,7 +1290,7 @@ static int binned_build_index(disco_ctx *c)
  * behind the items are the other side of the ping-pong. Runs before the record build takes d_rec2. */
 static int binned_build_order(disco_ctx *c)
 {
-    const int bits = c->order_counted_bits;
+    const int bits = c->order_counted_bits + c->order_sub_bits; /* (bucket and sub-key: one key) */
     const u32 total = (u32)c->n, kshift = 64u - (u32)bits;
     u64 *items = (u64 *)c->d_rec2.p;
     const u64 *rec;
@@ -6481,6 +6496,13 @@ int disco_fetch_survivor_layout(disco_ctx *c, uint8_t *list_len, uint64_t cap, u
     }
     for (u64 v = 0; v < c->n; v++) /* (a node without a row has no list this pass: whatever an earlier pass left) */
         list_len[v] = REF_DEG(ref[v]) ? (uint8_t)surv_len(half[4 * v], half[4 * v + 1], half[4 * v + 2], half[4 * v + 3]) : 0xFFu;
+    return DISCO_OK;
+}
+int disco_set_order_sub_bits(disco_ctx *c, int bits, int *in_use)
+{
+    if (!c) return DISCO_E_ARG;
+    if (in_use) *in_use = c->order_sub_bits;
+    if (bits >= 0) c->order_sub_limit = std::min(bits, ORDER_SUB_MAX);
     return DISCO_OK;
 }
 int disco_comm_rank(const disco_ctx *c) { return (c && c->comm) ? c->comm->rank : 0; }

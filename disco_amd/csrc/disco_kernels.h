@@ -92,6 +92,28 @@ enum {
 /* a read's item of the binned grouping, one word: order bucket (its 32 - shift bits on top) | length << idbits | read id — the host
  * takes this form only where the three fit (binned_order_wanted) */
 #define ORDER_ITEM(key, shift, id, l, idbits) (((u64)ORDER_BUCKET(key, shift) << (32u + (shift))) | ((u64)(l) << (idbits)) | (u64)(id))
+/* the sub-key of an item, directly below its bucket (qbits = ORDER_SUB_BITS(sub) of the bits the three fields leave, at most ORDER_SUB_MAX; the
+ * host packs sub = qbits << 24 | floor(2^(qbits + 16) / m-mer positions of the table's longest read), 0: no sub-key): how far the read
+ * starts in front of the m-mer its group shares, in the m-mer's canonical orientation — its position in the read if it stands forward there,
+ * counted from the read's end otherwise — in 2^qbits steps over the longest read's positions. Bucket and sub-key are ONE key to the partition
+ * levels and the build kernel, so the reads of a bucket lie in the order of their starts on the genome (descending): neighbours in the
+ * processing order overlap most. A heuristic, no result depends on it: sk = hash | position << 1 | strand of the run occurrence with the
+ * smallest hash bits; whatever it holds, the sub-key stays inside its bits. -DORDER_EXP_NO_START_KEY: 0 (A/B against the free order) */
+#ifndef ORDER_SUB_MAX
+#define ORDER_SUB_MAX 3 /* (four bits, steps of 8 bases at 150: the same gain in the four long kernels, 0.4 ms more in the grouping's 2^16 partitions) */
+#endif
+#define ORDER_SUB_BITS(sub) ((u32)(sub) >> 24)
+#define ORDER_SUB_MUL(sub) ((u32)(sub)&0xFFFFFFu)
+__device__ __forceinline__ u32 ORDER_SUBKEY(u32 sk, int nmm, u32 sub)
+{
+#ifdef ORDER_EXP_NO_START_KEY
+    return 0u;
+#else
+    const u32 pos = (sk >> 1) & 0xFFu;
+    const u32 rel = (sk & 1u) ? (u32)(nmm - 1) - pos : pos;
+    return min((rel * ORDER_SUB_MUL(sub)) >> 16, (1u << ORDER_SUB_BITS(sub)) - 1u);
+#endif
+}
 /* the first active lane's value as a SCALAR: a value broadcast by a cross-lane shuffle is divergent to the compiler, and with it every
  * loop bound, branch and address derived from it (counters in vector registers, exec-mask loops, saveexec around uniform branches) */
 __device__ __forceinline__ u32 uniform_u32(u32 x) { return (u32)__builtin_amdgcn_readfirstlane((int)x); }
@@ -490,7 +512,7 @@ struct MmerRoll {
 template <bool COUNT, int NF, int NL, int NFMAX = NF, bool LONGK = false>
 __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__restrict__ bkt, ulonglong2 *__restrict__ rec, u32 *__restrict__ okey, u64 lo, u64 hi,
                                                          u32 *__restrict__ runs, u32 *__restrict__ ocnt, u32 *__restrict__ oslot, u64 *__restrict__ oitem, u32 oidbits,
-                                                         u32 oshift,
+                                                         u32 oshift, u32 osub,
                                                          const u64 *__restrict__ list = nullptr)
 {
     static_assert(NF == 0 || NF == NFMAX, "a specialised instantiation holds exactly its window");
@@ -534,6 +556,10 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
         u16 *my = s_runs + tid * CAP;
         u32 cnt = 0, lastm = 0xFFFFFFFFu, tie = 0;
         u32 P1 = 0, P2 = 0;
+        /* the run with the smallest 23 hash bits, the first of equal ones, as hash | its slot in the list (below 512): its occurrence is the
+         * read-level minimizer, and where that lies in the read is where the read starts against the m-mer its group shares (ORDER_SUBKEY,
+         * behind the loop). Two instructions where a run opens — a branch some lane of the wavefront takes at nearly every window */
+        u32 sk = 0xFFFFFFFFu;
         u32 *sx = s_x + tid;
         /* window w (wave uniform: every thread walks the same positions) with minima m1 / m2 over positions relative to `base`; tw = w - base */
         /* inner (a constant): the block lies in front of every read's last windows — w < npos and q < nmm hold for the whole wavefront */
@@ -555,6 +581,7 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
                          * (bit 8 is never set), the rest is the same for every thread. A list that overflows is marked unusable below: its
                          * last slot may take whatever comes */
                         my[cnt < (u32)CAP ? cnt : (u32)CAP - 1u] = (u16)((m1 & 0xFFu) + (((u32)w << 7) - 2u * (u32)tw)); /* (RUN_W / RUN_DELTA / RUN_STRAND) */
+                        sk = min(sk, (m1 & ~0x1FFu) | cnt);
                         ++cnt;
                     }
                 }
@@ -605,7 +632,15 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
         for (; b < nblk; ++b) block(FlagConst<false>(), b);
         if (okey) okey[i] = best;
         /* the grouping: the read's item for the partition levels (binned grouping: no atomic, no slot), or the counting pass, fused */
-        if (oitem) oitem[i - lo] = ORDER_ITEM(best, oshift, rid, L, oidbits);
+        if (oitem) {
+            u32 sub = 0;
+            if (osub) { /* (scalar) hash | position << 1 | strand of that run's occurrence, from its entry, or of the suffix window's minimum: the read's last m-mer lies in that window alone */
+                const u32 e = my[min(sk & 0x1FFu, (u32)CAP - 1u)];
+                const u32 xm = sx[0];
+                sub = ORDER_SUBKEY(min((sk & ~0x1FFu) | ((RUN_W(e) + RUN_DELTA(e)) << 1) | RUN_STRAND(e), (xm & ~0x1FFu) | ((xm & 0xFFu) + (sx[512] << 1))), nmm, osub);
+            }
+            oitem[i - lo] = ORDER_ITEM(best, oshift, rid, L, oidbits) | ((u64)sub << (32u + oshift - ORDER_SUB_BITS(osub)));
+        }
         else if (ocnt) oslot[i - lo] = atomicAdd(&ocnt[ORDER_BUCKET(best, oshift)], 1u);
         if ((tie & ~1u) != 0 || cnt > (u32)CAP) my[0] = 0xFFFEu; /* (bit 0 of m1 ^ m2: the two strands of a tie may differ) */
         /* the two end k-mers' records: window_minimizer's rule on the minima of windows 0 and npos */
@@ -850,16 +885,41 @@ __global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const R *_
                                                                       u32 *__restrict__ bkt, u64 *__restrict__ ent)
 {
     constexpr bool TABLE = sizeof(R) == sizeof(ulonglong2);
-    __shared__ u32 s_c[1u << BINX_SPAN_BITS];
+    __shared__ __attribute__((aligned(16))) u32 s_c[1u << BINX_SPAN_BITS];
     __shared__ u32 s_w[16];
     const u32 tid = threadIdx.x, p = blockIdx.x;
     const u32 nbk = 1u << span, mask = nbk - 1u;
     const u32 beg = part[p], end = part[p + 1];
-    for (u32 x = tid; x < nbk; x += BINX_BUILD_BLOCK) s_c[x] = 0;
+    for (u32 x = tid; x < nbk / 4u; x += BINX_BUILD_BLOCK) ((uint4 *)s_c)[x] = make_uint4(0u, 0u, 0u, 0u); /* (nbk is a multiple of the block) */
     __syncthreads();
     for (u32 i = beg + tid; i < end; i += BINX_BUILD_BLOCK) atomicAdd(&s_c[(u32)(binx_key(rec[i]) >> kshift) & mask], 1u);
     __syncthreads();
     u32 carry = beg;
+    if constexpr (!TABLE) {
+        /* no bucket table to write: ONE block scan — a thread sums its nbk / 1024 consecutive counters (a multiple of four: 16-byte LDS
+         * accesses), the sums are scanned, the thread lays the starts over its counters. With the sub-key in the key a partition holds a
+         * fraction of the items it held (a sixteenth with four bits: 760 at 5 x 10^7 reads, in 2^16 partitions): with sixteen block scans
+         * each the order phase then took 3.3 ms against the parent's 1.2 (profiles/group_start_order_ab.txt) */
+        const u32 per4 = nbk / BINX_BUILD_BLOCK / 4u;
+        uint4 *own = (uint4 *)(s_c + tid * per4 * 4u);
+        u32 sum = 0;
+        for (u32 j = 0; j < per4; j++) {
+            const uint4 x = own[j];
+            sum += x.x + x.y + x.z + x.w;
+        }
+        u32 all;
+        u32 run = carry + binx_block_scan1024(sum, s_w, &all);
+        for (u32 j = 0; j < per4; j++) {
+            const uint4 x = own[j];
+            uint4 y;
+            y.x = run;
+            y.y = y.x + x.x;
+            y.z = y.y + x.y;
+            y.w = y.z + x.z;
+            run = y.w + x.w;
+            own[j] = y;
+        }
+    } else
     for (u32 base = 0; base < nbk; base += BINX_BUILD_BLOCK) { /* (nbk is a multiple of the block) */
         const u32 x = s_c[base + tid];
         u32 sum;

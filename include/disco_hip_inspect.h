@@ -19,6 +19,15 @@ extern "C" {
  * takes, two classes of rows, a caller's order, DISCO_NO_ORDER). Tests only. */
 int disco_fetch_order(disco_ctx *ctx, uint64_t *order_words, uint32_t *keys, uint64_t cap, uint64_t *n, int *order_bits);
 
+/* the sub-key of the binned grouping (results do not depend on it): inside an order bucket the reads lie in the order of
+ * sub = min((start_rel * floor(2^(b + 16) / P)) >> 16, 2^b - 1), b = *in_use, not decreasing — start_rel = the position of the read's
+ * minimizer occurrence (among its m-mers the one with the smallest order hash >> 9, the leftmost of equal ones) if the m-mer is the
+ * canonical one as it stands in the read, the read's m-mer positions - 1 - that position otherwise; P = the m-mer positions of the table's
+ * longest read. *in_use (may be null): the bits the last disco_build_index gave it — what bucket, length and
+ * read id leave of an item's 64, at most 3; 0: no binned grouping, no minimizer runs, or no bit left. bits >= 0: later index builds use at
+ * most that many (0: the item as it was before the sub-key); bits < 0: only the look. Tests only. */
+int disco_set_order_sub_bits(disco_ctx *ctx, int bits, int *in_use);
+
 /* how the last disco_transitive_reduce laid its survivors out (results do not depend on it): *dense = 1 if the emission wrote its edges
  * back to back (no unused chunk tails: *out_used, the slots it wrote, is then the number of edges), list_len[v] = the decoded length of
  * node v's self-delimiting survivor list (disco_amd/csrc/disco_survivor.h): 0..4, 5 = wide (more than four survivors, judged by its row),

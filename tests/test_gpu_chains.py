@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from disco_amd import buildgraph, readgen
+from tests.chain_model import chain_model
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +65,12 @@ def test_composite_edges_are_made_of_the_absorbed_edges(shape):
         # the same records from the edge list handed back by the host (what buildG --gpus N does)
         comp2, links2, absorbed2 = g.contract_chains(min_ovl, edges=edges)
         assert np.array_equal(comp, comp2) and np.array_equal(links, links2) and np.array_equal(absorbed, absorbed2)
+        # ... and every record is the one tests/chain_model.py walks to: all chains, maximal, complete, in order
+        want = chain_model(edges, length, min_ovl)
+        assert np.array_equal(comp, want.comp) and np.array_equal(links, want.links) and np.array_equal(absorbed, want.absorbed)
+        end_first, end_last_rev = g.chain_end_links(len(comp))
+        assert np.array_equal(g.chain_residue(records=False)[0], want.residue) and np.array_equal(g.chain_first_edges(len(comp)), want.first_edges)
+        assert np.array_equal(end_first, want.end_first) and np.array_equal(end_last_rev, want.end_last_rev)
     finally:
         g.close()
 

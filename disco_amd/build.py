@@ -128,6 +128,14 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+    # buildG's output plan on the host: every combination of options, knobs and demotions
+    pl = os.path.join(HERE, "bin", "plan_check")
+    plsrc = [os.path.join(HERE, "host", "plan_check.cpp"), os.path.join(HERE, "host", "output_plan.h")]
+    if force or _stale(pl, plsrc):
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", pl, plsrc[0]]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
     return BUILDG
 
 

@@ -43,7 +43,7 @@ def test_test_only_entry_points_live_in_their_own_header():
     product, test_only = declared_functions(("disco_hip.h",)), declared_functions(("disco_hip_test.h",))
     assert set(test_only) == {"disco_generate_reads", "disco_substitute_bases", "disco_dist_generate_reads", "disco_measure_hbm", "disco_measure_gather", "disco_probe_run_words"}
     assert not set(product) & set(test_only)
-    for host in ("buildg_main.cpp", "writer.cpp", "parsimple.cpp", "fastx.cpp"):  # the drop-in executable binds the product header only
+    for host in ("buildg_main.cpp", "output_plan.h", "plan_check.cpp", "writer.cpp", "parsimple.cpp", "fastx.cpp"):  # the drop-in executable binds the product header only
         txt = open(os.path.join(ROOT, "disco_amd", "host", host)).read()
         assert "disco_hip_test.h" not in txt and not any(n + "(" in txt for n in test_only), host
 

@@ -128,6 +128,14 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+    # the line and item functions behind <prefix>.gfa on the host: the header the kernels include, as plain C++
+    gc = os.path.join(HERE, "bin", "gfa_check")
+    gcsrc = [os.path.join(HERE, "host", "gfa_check.cpp"), os.path.join(HERE, "csrc", "disco_gfa.h"), os.path.join(ROOT, "include", "disco_hip.h")]
+    if force or _stale(gc, gcsrc):
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", gc, gcsrc[0]]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
     # buildG's output plan on the host: every combination of options, knobs and demotions
     pl = os.path.join(HERE, "bin", "plan_check")
     plsrc = [os.path.join(HERE, "host", "plan_check.cpp"), os.path.join(HERE, "host", "output_plan.h")]

@@ -131,7 +131,10 @@ ABI = [
     ("disco_prepare_contained_records", C.c_int64, [_P, C.c_uint32, _P]),
     ("disco_fetch_contained_records", C.c_int, [_P, _P, C.c_uint64]),
     ("disco_write_contained_records", C.c_int, [_P, C.c_int, C.c_uint64, C.c_uint32]),
+    ("disco_write_gfa", C.c_int64, [_P, C.c_int, _P, C.c_uint32, C.c_uint64, C.c_uint32]),
 ]
+
+GFA_NO_SEQ = 1  # DISCO_GFA_NO_SEQ: S lines carry * instead of the bases
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
 FLAG_TWO_PASS_VERIFY = 1  # DISCO_FLAG_TWO_PASS_VERIFY
@@ -585,6 +588,13 @@ class BuildGraph:
         """records per piece of the fetch / write calls above (0: the default, a half of the pinned ring). Tests only"""
         _bind_inspect(self.L)
         self._chk(self.L.disco_set_record_piece(self._h, records))
+
+    def write_gfa(self, fd: int, file_index=None, no_seq: bool = False, piece_bytes: int = 0, threads: int = 8) -> int:
+        """after transitive_reduce: the graph as GFA 1.0 into the open file fd, from its byte 0 on (disco_write_gfa) — S lines of all
+        reads (no_seq: * for the bases), L lines in the order of fetch_edges, C lines in the order of format_contained; formatted on
+        the GPU in pieces of at most piece_bytes (0: a half of the pinned ring). Returns the bytes written"""
+        fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
+        return self._chk(self.L.disco_write_gfa(self._h, fd, None if fi is None else fi.ctypes.data, GFA_NO_SEQ if no_seq else 0, piece_bytes, threads))
 
     def fetch_edge_substitutions(self) -> np.ndarray:
         """substitutions of every edge's overlap, in the order of fetch_edges (all 0 unless max_substitutions > 0)"""

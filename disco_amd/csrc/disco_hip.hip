@@ -46,6 +46,7 @@
 #include "disco_chains.h"
 #include "disco_text.h"
 #include "disco_binrec.h"
+#include "disco_gfa.h"
 #include "disco_partext.h"
 #include "disco_ingest.h"
 #include "disco_bgzf.h"
@@ -4920,6 +4921,210 @@ int disco_set_record_piece(disco_ctx *c, uint64_t records)
     if (!c) return DISCO_E_ARG;
     c->rec_piece = records;
     return DISCO_OK;
+}
+
+/* ---- the overlap graph as GFA 1.0, formatted where the reads, the edges and the keys are (disco_gfa.h) ------------------------------- */
+static_assert(GFA_SHORT_MAX == DISCO_SHORT_MAX, "disco_gfa.h reads the long class as the table lays it out");
+/* where the pieces of the text go: two device piece buffers, the two halves of the pinned ring, the file. A piece is formatted, copied
+ * into its half and, while the next one is formatted and travels, written into the file (records_through_ring's scheme, with pieces of
+ * the sizes the lines give them) */
+struct GfaSink {
+    int fd = -1;
+    u32 threads = 1;
+    u64 cap = 0, unit = 0; /* bytes a piece may hold; a piece takes the lines that start in one stretch of `unit` bytes (cap - GFA_MAX_LINE) */
+    u64 file_off = 0;      /* where the next section begins in the file */
+    u64 issued = 0;        /* pieces so far: piece k uses buffer and half k & 1 */
+    DevBuf<u8> piece[2];
+    DevBuf<u64> d_cut;
+    bool pending = false; /* the piece before the current one lies in its half, not yet written */
+    u64 p_half = 0, p_bytes = 0, p_off = 0;
+    bool write_ok = true;
+};
+static void gfa_deliver(disco_ctx *c, GfaSink &o)
+{
+    if (!o.pending) return;
+    o.pending = false;
+    const char *half = (const char *)c->h_ring + o.p_half * c->ring_half;
+    const u64 bytes = o.p_bytes, first = o.p_off;
+    std::atomic<bool> ok{true};
+    auto part = [&](u64 b, u64 e) {
+        while (b < e) {
+            const ssize_t w = pwrite(o.fd, half + b, e - b, (off_t)(first + b));
+            if (w <= 0) {
+                ok.store(false);
+                return;
+            }
+            b += (u64)w;
+        }
+    };
+    const u64 nt = std::max<u64>(1, std::min<u64>(std::min<u32>(o.threads, 64), bytes >> 16)); /* (no thread for less than 64 KB) */
+    if (nt == 1) part(0, bytes);
+    else {
+        const u64 slice = ((bytes + nt - 1) / nt + 4095) & ~(u64)4095;
+        std::vector<std::thread> th;
+        for (u64 b = 0; b < bytes; b += slice) th.emplace_back(part, b, std::min(bytes, b + slice));
+        for (auto &x : th) x.join();
+    }
+    if (!ok.load()) o.write_ok = false;
+}
+/* one section of the file — n_lines lines whose starts are place[0 .. n_lines], place[n_lines] = total — piece by piece: launch(a, b,
+ * piece) formats the lines [a[0], b[0]) into a piece that begins at byte a[1] of the section (a, b: two entries of gfa_cuts_kernel) */
+static int gfa_section(disco_ctx *c, const char *who, GfaSink &o, const u64 *place, u64 n_lines, u64 total, const u32 *ovf, u32 n_long,
+                       const std::function<void(const u64 *, const u64 *, char *)> &launch)
+{
+    if (total == 0) return DISCO_OK;
+    const u64 np = (total + o.unit - 1) / o.unit;
+    std::vector<u64> cut(3 * (np + 1));
+    CHK(ensure(c, o.d_cut, 3 * (np + 1)));
+    for (int i = 0; i < 2; i++) CHK(ensure(c, o.piece[i], std::min(o.cap, total))); /* (grow-only; nothing of the section before is in flight) */
+    hipLaunchKernelGGL(gfa_cuts_kernel, dim3(flat_grid(c, np + 1)), dim3(256), 0, c->stream, place, n_lines, o.unit, np, ovf, n_long, o.d_cut.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(cut.data(), o.d_cut, cut.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (u64 r = 0; r < np; r++) {
+        const u64 *a = &cut[3 * r], *b = &cut[3 * (r + 1)];
+        const u64 bytes = b[1] - a[1];
+        if (bytes == 0) continue; /* (a line longer than the stretch: the one behind it has no line of its own) */
+        if (b[0] < a[0] || b[0] > n_lines || bytes > o.cap) return fail(c, DISCO_E_CAPACITY, "%s: a piece of %llu bytes, room for %llu", who, (unsigned long long)bytes, (unsigned long long)o.cap);
+        const u64 h = o.issued & 1;
+        launch(a, b, (char *)o.piece[h].p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync((char *)c->h_ring + h * c->ring_half, o.piece[h].p, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_ring[h], c->stream));
+        gfa_deliver(c, o); /* the piece before: its copy was waited for below, one piece ago; the half it frees is written again two pieces on */
+        HIPCHK(c, hipEventSynchronize(c->ev_ring[h]));
+        o.pending = true;
+        o.p_half = h;
+        o.p_bytes = bytes;
+        o.p_off = o.file_off + a[1];
+        o.issued++;
+    }
+    o.file_off += total;
+    return DISCO_OK;
+}
+
+int64_t disco_write_gfa(disco_ctx *c, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads)
+{
+    DISCO_TRACE("disco_write_gfa");
+    static const char who[] = "disco_write_gfa";
+    if (!c || fd < 0) return DISCO_E_ARG;
+    if (flags & ~(uint32_t)DISCO_GFA_NO_SEQ) return fail(c, DISCO_E_ARG, "%s: unknown flags %#x", who, flags);
+    if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "%s: a rank holds its share of the graph only", who);
+    if (c->phase < 8) return fail(c, DISCO_E_STATE, "%s: run disco_transitive_reduce first", who);
+    if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "%s: more than 2^31 reads", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(output_ring(c, who));
+    const bool no_seq = (flags & DISCO_GFA_NO_SEQ) != 0;
+    const u64 n = c->n, ne = c->n_out;
+    GfaSink o;
+    o.fd = fd;
+    o.threads = std::max<uint32_t>(host_threads, 1);
+    o.cap = piece_bytes ? std::min<u64>(std::max<u64>(piece_bytes, 65536), c->ring_half) : c->ring_half;
+    o.unit = o.cap - GFA_MAX_LINE;
+    DevBuf<u64> d_findex, place;
+    DevBuf<u16> sbytes, subs;
+    DevBuf<u8> bytes;
+    ContainedGroups G;
+    auto body = [&]() -> int {
+        if (file_index) {
+            CHK(ensure(c, d_findex, n));
+            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, n * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        static const char header[] = GFA_HEADER;
+        if (pwrite(fd, header, sizeof header - 1, 0) != (ssize_t)(sizeof header - 1)) return fail(c, DISCO_E_ARG, "%s: write error", who);
+        o.file_off = sizeof header - 1;
+        /* S lines: a lane per word of a read */
+        GfaReads R;
+        R.rows = (const uint64_t *)c->d_reads;
+        R.S = (u32)c->S;
+        R.full = c->two_class ? (const uint64_t *)c->d_full.p : nullptr;
+        R.ovf = c->two_class ? c->d_ovf.p : nullptr;
+        R.long_ids = c->two_class ? c->d_long_ids.p : nullptr;
+        R.SL = c->two_class ? (u32)c->S_ext : 0u;
+        R.len = c->d_len;
+        R.file_index = (const uint64_t *)d_findex.p;
+        R.n = n;
+        u64 total = 0;
+        if (n) {
+            CHK(ensure(c, sbytes, n));
+            CHK(ensure(c, place, n + 1));
+            hipLaunchKernelGGL(gfa_s_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, no_seq ? 1u : 0u, sbytes.p);
+            CHK((scan_exclusive<u16, u64>(c, sbytes, n, place, true, &total)));
+            const u32 W = no_seq ? 1u : R.S;
+            const bool long_pass = c->two_class && !no_seq && R.SL > GFA_HEAD_WORDS;
+            CHK(gfa_section(c, who, o, place, n, total, R.ovf, (u32)c->n_long, [&](const u64 *a, const u64 *b, char *piece) {
+                hipLaunchKernelGGL(gfa_s_write_kernel, dim3(flat_grid(c, (b[0] - a[0]) * W)), dim3(256), 0, c->stream, R, (const u64 *)place, a[0], b[0], a[1], no_seq ? 1u : 0u, W, piece);
+                if (long_pass && b[2] > a[2])
+                    hipLaunchKernelGGL(gfa_s_write_long_kernel, dim3(flat_grid(c, (b[2] - a[2]) * (R.SL - GFA_HEAD_WORDS))), dim3(256), 0, c->stream, R, (const u64 *)place, a[2], b[2],
+                                       a[1], piece);
+            }));
+        }
+        /* L lines: a lane per edge, in the order of disco_fetch_edges */
+        if (ne) {
+            TextView g;
+            g.src = c->d_out_src;
+            g.ent = c->d_out_ent;
+            g.valid = out_valid(c);
+            g.pos = out_pos(c);
+            g.len = c->d_len;
+            g.file_index = d_findex;
+            g.n_slots = c->out_used;
+            if (c->prm.max_substitutions) { /* by fetch-order rank, as disco_fetch_edge_substitutions has them */
+                CHK(ensure(c, subs, ne));
+                hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c), c->out_used,
+                                   c->d_reads, c->d_len, c->S, subs.p);
+            }
+            const u16 *d_subs = c->prm.max_substitutions ? subs.p : nullptr;
+            CHK(ensure(c, bytes, ne));
+            CHK(ensure(c, place, ne + 1));
+            hipLaunchKernelGGL(gfa_l_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, d_subs, bytes.p);
+            CHK((scan_exclusive<u8, u64>(c, bytes, ne, place, true, &total)));
+            const bool dense = c->out_dense;
+            CHK(gfa_section(c, who, o, place, ne, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+                const u64 s_lo = dense ? a[0] : 0, s_hi = dense ? b[0] : g.n_slots;
+                hipLaunchKernelGGL(gfa_l_write_kernel, dim3(flat_grid(c, s_hi - s_lo)), dim3(256), 0, c->stream, g, d_subs, (const u64 *)place, s_lo, s_hi, a[0], b[0], a[1], piece);
+            }));
+        }
+        /* C lines: a lane per contained row, grouped and sorted as for the contained-read files */
+        u64 nc = c->n_contained;
+        if (nc) {
+            CHK(settle_keys(c));
+            CHK(group_contained_rows(c, (const u8 *)c->d_contained, 0, n, &nc, G));
+            u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
+            HIPCHK(c, hipMemcpyAsync(h_ctr, G.ctr, sizeof h_ctr, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "%s: %u contained reads have a key that names no containing read", who, h_ctr[CGRP_BAD_KEYS]);
+            CTextView g;
+            g.word = G.word;
+            g.sup = G.sup;
+            g.len = c->d_len;
+            g.file_index = d_findex;
+            g.nc = nc;
+            g.k = (u32)c->k;
+            CHK(ensure(c, bytes, nc));
+            CHK(ensure(c, place, nc + 1));
+            hipLaunchKernelGGL(gfa_c_measure_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, g, bytes.p);
+            CHK((scan_exclusive<u8, u64>(c, bytes, nc, place, true, &total)));
+            CHK(gfa_section(c, who, o, place, nc, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+                hipLaunchKernelGGL(gfa_c_write_kernel, dim3(flat_grid(c, b[0] - a[0])), dim3(256), 0, c->stream, g, (const u64 *)place, a[0], b[0], a[1], piece);
+            }));
+        }
+        gfa_deliver(c, o);
+        if (!o.write_ok) return fail(c, DISCO_E_ARG, "%s: write error", who);
+        return DISCO_OK;
+    };
+    const int rc = body();
+    if (rc != DISCO_OK) (void)hipStreamSynchronize(c->stream); /* (nothing in flight reads what is released below) */
+    release(c, o.piece[0]);
+    release(c, o.piece[1]);
+    release(c, o.d_cut);
+    release(c, d_findex);
+    release(c, place);
+    release(c, sbytes);
+    release(c, subs);
+    release(c, bytes);
+    release_groups(c, G);
+    return rc != DISCO_OK ? rc : (int64_t)o.file_off;
 }
 
 /* the contained rows of the current flags start their way to the host now, on a side stream (grouped: also in the order of the

@@ -64,7 +64,10 @@ static void usage()
               << "  --max-substitutions N\textension: accept overlaps / containments with up to N differing bases around an exact end-k-mer seed and\n"
               << "\t\twrite the count into the substitutions column (default 0 = the reference; parameter file key MaxSubstitutions4BuildGraph)\n"
               << "  --binary-out\talso write <prefix>_edges.bin / <prefix>_contained.bin (fixed 40-byte records, disco_amd/host/writer.h)\n"
-              << "  --no-text\tbinary output only: leave the text edge / contained files empty (a consumer with the loader patch)\n";
+              << "  --no-text\tbinary output only: leave the text edge / contained files empty (a consumer with the loader patch)\n"
+              << "  --gfa\talso write <prefix>.gfa: the reduced graph as GFA 1.0 (S lines of all reads, L lines of the edges, C lines of the\n"
+              << "\t\tcontained reads; names = the file indices of <prefix>_ReadIDMap.txt), formatted on the GPU; single GPU\n"
+              << "  --gfa-no-seq\t--gfa with * in place of the bases\n";
 }
 
 static std::vector<std::string> split(const std::string &s, char d)
@@ -149,6 +152,7 @@ struct Args {
     std::string prefix, cfg;
     int threads = omp_get_max_threads(), gpu = 0, gpus = 1;
     bool same_device = false, mpi_names = false, binary_out = false, no_text = false, partitioned_index = false;
+    bool gfa = false, gfa_no_seq = false; /* <prefix>.gfa, with or without the bases */
     std::string par_simple; /* prefix of the <prefix>_<i>_ParSimpleEdges.txt files, or empty */
     uint32_t min_overlap = 30, min_overlap_simplify = 0, max_subs = 0;
     std::vector<const char *> paths() const
@@ -204,6 +208,8 @@ static int parse_args(int argc, char **argv, Args &a)
         else if (o == "--max-substitutions") max_subs_cli = (long long)num(0, 32767);
         else if (o == "--binary-out") a.binary_out = true;
         else if (o == "--no-text") a.binary_out = a.no_text = true;
+        else if (o == "--gfa") a.gfa = true;
+        else if (o == "--gfa-no-seq") a.gfa = a.gfa_no_seq = true;
         else {
             usage();
             if (o == "-h" || o == "--help") return 0;
@@ -214,6 +220,10 @@ static int parse_args(int argc, char **argv, Args &a)
             usage();
             return 1;
         }
+    }
+    if (a.gfa && a.gpus > 1) {
+        std::cerr << "--gfa writes the graph of one GPU: with --gpus " << a.gpus << " every rank holds its share only, run it without --gpus." << std::endl;
+        return 1;
     }
     std::string cfg_err;
     if (!read_min_overlap(a.cfg, a.min_overlap, cfg_err, &a.min_overlap_simplify, &a.max_subs)) {
@@ -729,6 +739,23 @@ static int par_simple_on_device(Job &J, disco_ctx *ctx, const Lap &lap, const Fa
     return GO_ON;
 }
 
+/* <prefix>.gfa (--gfa, --gfa-no-seq): the reduced graph as GFA 1.0, formatted on the GPU and sent through the pinned ring into the file
+ * (disco_write_gfa). No product of the plan: the host has no maker for it, so every failure is an error of the run */
+static int write_gfa_file(Job &J, disco_ctx *ctx)
+{
+    const std::string path = J.a.prefix + ".gfa";
+    Fds fds;
+    fds.fd.assign(1, open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666));
+    if (fds.fd[0] < 0) return die("Unable to open file: " + path);
+    const auto t = Clock::now();
+    const int64_t nb = disco_write_gfa(ctx, fds.fd[0], J.ids(), J.a.gfa_no_seq ? DISCO_GFA_NO_SEQ : 0u, 0, (uint32_t)J.a.threads);
+    if (nb < 0) return die(std::string("disco_write_gfa : ") + disco_last_error(ctx));
+    const double s = secs(t);
+    if (J.verbose) fprintf(stderr, "[disco host] GFA: %lld bytes in %.3f s (%.2f GB/s)\n", (long long)nb, s, s > 0 ? (double)nb / s * 1e-9 : 0.0);
+    J.lap("GFA from the GPU into the file");
+    return GO_ON;
+}
+
 /* ---- the graph on one GPU, and every file the device writes ------------------------------------------------------------------------- */
 static int graph_single_gpu(Job &J)
 {
@@ -870,6 +897,7 @@ static int graph_single_gpu(Job &J)
         if (rc == GO_ON) J.lap("contract chains on the GPU");
     }
     if (rc != GO_ON) return rc;
+    if (a.gfa && (rc = write_gfa_file(J, ctx)) != GO_ON) return rc;
     /* the context is released by a thread of its own while the files are written (0.07 s of hipFree at config 3) */
     J.ctx_releaser.t = std::thread([ctx]() { disco_destroy(ctx); });
     J.lap("release GPU context (in the background)");

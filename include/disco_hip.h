@@ -577,6 +577,25 @@ int64_t disco_prepare_contained_records(disco_ctx *ctx, uint32_t n_files, const 
 int     disco_fetch_contained_records(disco_ctx *ctx, disco_bin_contained *out, uint64_t cap);
 int     disco_write_contained_records(disco_ctx *ctx, int fd, uint64_t file_offset, uint32_t host_threads);
 
+/* ---- the overlap graph as GFA 1.0, formatted on the GPU (disco_amd/csrc/disco_gfa.h) ------------------------------------------------ */
+/* <prefix>.gfa, for everything that is not DISCO's own consumer (Bandage, gfatools, vg, a script): one file, LF line ends,
+ *     H \t VN:Z:1.0
+ *     S \t name \t bases \t LN:i:len                          every read, contained ones included, in read-id order
+ *     L \t src \t so \t dst \t do \t ovl M                      every reduced edge, in the order of disco_fetch_edges
+ *     C \t container \t + \t contained \t o \t pos \t len2 M    every contained-read row, in the order disco_format_contained writes one file
+ * name = the read's 1-based file index (file_index as for disco_format_edges; null: read id + 1). An edge (BG/Edge.h:30-34) has
+ * ovl = len_src - offset, so = '+' when orient & 2, do = '+' when orient & 1: the last ovl bases of oriented src are the first ovl bases of
+ * oriented dst; with max_substitutions > 0 the line ends in \t NM:i:n, n as disco_fetch_edge_substitutions counts it. A contained row
+ * (disco_contained_row) has o = '+' for orientation 0 or 3, '-' for 1 or 2, and pos = start for orientation 3 or 2, len1 - start - len2 for
+ * 0 or 1: the oriented contained read is container[pos, pos + len2). DISCO_GFA_NO_SEQ writes * for the bases.
+ * After disco_transitive_reduce. The text is formatted piece by piece — pieces end at line ends — into a device buffer and every piece
+ * travels through the context's pinned ring into fd, from the file's byte 0 on, split among host_threads writers; the whole text is
+ * never resident anywhere. piece_bytes: the most a piece may hold; 0 = one half of the ring, less than 64 KiB counts as 64 KiB (a line can
+ * be 32 767 bases long), more than a half of the ring as that. Returns the bytes written (the file's size; the caller truncates an older,
+ * longer file). DISCO_E_STATE before disco_transitive_reduce, DISCO_E_UNSUPPORTED on a context with a communicator or with 2^31 or more reads. */
+#define DISCO_GFA_NO_SEQ 1u
+int64_t disco_write_gfa(disco_ctx *ctx, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads);
+
 #ifdef __cplusplus
 }
 #endif

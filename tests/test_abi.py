@@ -2,6 +2,7 @@
 import ctypes
 import os
 import re
+import subprocess
 
 from disco_amd import build, buildgraph
 
@@ -35,6 +36,15 @@ def test_library_builds_and_exports_every_declared_symbol():
     # round 6: version 2 — disco_dist_info grew in the middle in round 5; library, header and the Python mirror carry ONE number, and the
     # mirror / buildG refuse a library that answers another
     assert L.disco_abi_version() == header_abi_version() == buildgraph.ABI_VERSION == 2
+
+
+def test_library_exports_exactly_the_declared_functions():
+    """the functions the library exports under the name disco_* are exactly the ones the three public headers declare: nothing of its
+    inside is part of the ABI, however its source is divided into files"""
+    nm = subprocess.run(["nm", "-D", "--defined-only", build.build_lib()], check=True, stdout=subprocess.PIPE, text=True).stdout
+    rows = [l.split() for l in nm.splitlines()]
+    exported = sorted(r[2] for r in rows if len(r) == 3 and r[1] == "T" and r[2].startswith("disco_"))
+    assert exported == declared_functions(HEADERS + ("disco_hip_inspect.h",))
 
 
 def test_test_only_entry_points_live_in_their_own_header():

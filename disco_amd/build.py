@@ -136,6 +136,14 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+    # the item functions behind <prefix>.unitigs.gfa on the host: the header the kernels include, as plain C++
+    uc = os.path.join(HERE, "bin", "gfa_chains_check")
+    ucsrc = [os.path.join(HERE, "host", "gfa_chains_check.cpp"), os.path.join(HERE, "csrc", "disco_gfa_chains.h")] + gcsrc[1:]
+    if force or _stale(uc, ucsrc):
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", uc, ucsrc[0]]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
     # buildG's output plan on the host: every combination of options, knobs and demotions
     pl = os.path.join(HERE, "bin", "plan_check")
     plsrc = [os.path.join(HERE, "host", "plan_check.cpp"), os.path.join(HERE, "host", "output_plan.h")]

@@ -132,6 +132,7 @@ ABI = [
     ("disco_fetch_contained_records", C.c_int, [_P, _P, C.c_uint64]),
     ("disco_write_contained_records", C.c_int, [_P, C.c_int, C.c_uint64, C.c_uint32]),
     ("disco_write_gfa", C.c_int64, [_P, C.c_int, _P, C.c_uint32, C.c_uint64, C.c_uint32]),
+    ("disco_write_gfa_chains", C.c_int64, [_P, C.c_int, _P, C.c_uint32, C.c_uint64, C.c_uint32]),
 ]
 
 GFA_NO_SEQ = 1  # DISCO_GFA_NO_SEQ: S lines carry * instead of the bases
@@ -595,6 +596,14 @@ class BuildGraph:
         the GPU in pieces of at most piece_bytes (0: a half of the pinned ring). Returns the bytes written"""
         fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
         return self._chk(self.L.disco_write_gfa(self._h, fd, None if fi is None else fi.ctypes.data, GFA_NO_SEQ if no_seq else 0, piece_bytes, threads))
+
+    def write_gfa_chains(self, fd: int, file_index=None, no_seq: bool = False, piece_bytes: int = 0, threads: int = 8) -> int:
+        """after contract_chains (without `edges`): the compacted graph as GFA 1.0 into the open file fd, from its byte 0 on
+        (disco_write_gfa_chains) — every composite edge one segment c<k> with its merged bases, S lines of the reads that are neither
+        contained nor inside a chain, L lines of the edges that were not absorbed and of every composite edge's two ends. Returns the
+        bytes written"""
+        fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
+        return self._chk(self.L.disco_write_gfa_chains(self._h, fd, None if fi is None else fi.ctypes.data, GFA_NO_SEQ if no_seq else 0, piece_bytes, threads))
 
     def fetch_edge_substitutions(self) -> np.ndarray:
         """substitutions of every edge's overlap, in the order of fetch_edges (all 0 unless max_substitutions > 0)"""

@@ -21,6 +21,9 @@
  * of one stride, narrow or wide, and two classes of rows, where the words of a read of more than 256 bases come from its full row.
  *
  * The line and item functions are plain functions (host and device): disco_amd/host/gfa_check.cpp runs them without a GPU.
+ *
+ * The S and L kernels take an optional skip flag per read / per edge: <prefix>.unitigs.gfa (disco_gfa_chains.h) writes the reads and
+ * edges that the chain contraction left outside its composite edges with them; disco_write_gfa passes none.
  */
 #ifndef DISCO_GFA_H_
 #define DISCO_GFA_H_
@@ -248,33 +251,34 @@ __global__ void gfa_cuts_kernel(const u64 *__restrict__ place, u64 n_lines, u64 
     }
 }
 
-__global__ void gfa_s_measure_kernel(GfaReads g, u32 no_seq, u16 *__restrict__ bytes)
+/* skip (here and in the writers below): null, or a flag per read / per edge in fetch order — a flagged one has no line (0 bytes) */
+__global__ void gfa_s_measure_kernel(GfaReads g, const u8 *__restrict__ skip, u32 no_seq, u16 *__restrict__ bytes)
 {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; i < g.n; i += (u64)gridDim.x * blockDim.x) bytes[i] = (u16)gfa_s_bytes(gfa_name(g, i), g.len[i], no_seq != 0);
+    for (; i < g.n; i += (u64)gridDim.x * blockDim.x) bytes[i] = (skip && skip[i]) ? (u16)0 : (u16)gfa_s_bytes(gfa_name(g, i), g.len[i], no_seq != 0);
 }
 /* the S lines of the reads [lo, hi) into the piece that begins at byte `base` of the section: W lanes per read, lane w its word w (W =
  * the stride of the table; 8 with two classes, where the words from 8 on are gfa_s_write_long_kernel's; 1 without sequences) */
-__global__ void gfa_s_write_kernel(GfaReads g, const u64 *__restrict__ place, u64 lo, u64 hi, u64 base, u32 no_seq, u32 W, char *__restrict__ piece)
+__global__ void gfa_s_write_kernel(GfaReads g, const u8 *__restrict__ skip, const u64 *__restrict__ place, u64 lo, u64 hi, u64 base, u32 no_seq, u32 W, char *__restrict__ piece)
 {
     u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u64 total = (hi - lo) * W;
     for (; t < total; t += (u64)gridDim.x * blockDim.x) {
         const u64 i = lo + t / W;
         const u32 w = (u32)(t % W), len = g.len[i];
-        if (w >= gfa_s_items(len, no_seq != 0)) continue;
+        if (w >= gfa_s_items(len, no_seq != 0) || (skip && skip[i])) continue;
         gfa_s_put(piece + (place[i] - base), gfa_name(g, i), len, w, no_seq ? 0ull : gfa_word(g, i, w), no_seq != 0);
     }
 }
 /* two classes: the words from 8 on of the long reads [jlo, jhi), SL - 8 lanes per read */
-__global__ void gfa_s_write_long_kernel(GfaReads g, const u64 *__restrict__ place, u64 jlo, u64 jhi, u64 base, char *__restrict__ piece)
+__global__ void gfa_s_write_long_kernel(GfaReads g, const u8 *__restrict__ skip, const u64 *__restrict__ place, u64 jlo, u64 jhi, u64 base, char *__restrict__ piece)
 {
     u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u64 per = g.SL - GFA_HEAD_WORDS, total = (jhi - jlo) * per;
     for (; t < total; t += (u64)gridDim.x * blockDim.x) {
         const u64 j = jlo + t / per, i = g.long_ids[j];
         const u32 w = GFA_HEAD_WORDS + (u32)(t % per), len = g.len[i];
-        if (w >= gfa_s_items(len, false)) continue;
+        if (w >= gfa_s_items(len, false) || (skip && skip[i])) continue;
         gfa_s_put(piece + (place[i] - base), gfa_name(g, i), len, w, g.full[j * g.SL + w], false);
     }
 }
@@ -292,23 +296,23 @@ __device__ __forceinline__ GfaL gfa_l_of(const TextView &g, const u16 *__restric
     t.nm = subs ? subs[e] : 0u;
     return t;
 }
-__global__ void gfa_l_measure_kernel(TextView g, const u16 *__restrict__ subs, u8 *__restrict__ bytes)
+__global__ void gfa_l_measure_kernel(TextView g, const u16 *__restrict__ subs, const u8 *__restrict__ skip, u8 *__restrict__ bytes)
 {
     u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; s < g.n_slots; s += (u64)gridDim.x * blockDim.x) {
         if (g.valid && !g.valid[s]) continue;
         const u64 e = g.pos ? g.pos[s] : s;
-        bytes[e] = (u8)gfa_l_bytes(gfa_l_of(g, subs, s, e));
+        bytes[e] = (skip && skip[e]) ? (u8)0 : (u8)gfa_l_bytes(gfa_l_of(g, subs, s, e));
     }
 }
 /* the lines of the edges of rank [lo, hi), looked for in the slots [s_lo, s_hi) (a dense emission: the same range) */
-__global__ void gfa_l_write_kernel(TextView g, const u16 *__restrict__ subs, const u64 *__restrict__ place, u64 s_lo, u64 s_hi, u64 lo, u64 hi, u64 base, char *__restrict__ piece)
+__global__ void gfa_l_write_kernel(TextView g, const u16 *__restrict__ subs, const u8 *__restrict__ skip, const u64 *__restrict__ place, u64 s_lo, u64 s_hi, u64 lo, u64 hi, u64 base, char *__restrict__ piece)
 {
     u64 s = s_lo + (u64)blockIdx.x * blockDim.x + threadIdx.x;
     for (; s < s_hi; s += (u64)gridDim.x * blockDim.x) {
         if (g.valid && !g.valid[s]) continue;
         const u64 e = g.pos ? g.pos[s] : s;
-        if (e < lo || e >= hi) continue;
+        if (e < lo || e >= hi || (skip && skip[e])) continue;
         gfa_l_put(piece + (place[e] - base), gfa_l_of(g, subs, s, e));
     }
 }

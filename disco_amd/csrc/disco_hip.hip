@@ -47,6 +47,7 @@
 #include "disco_text.h"
 #include "disco_binrec.h"
 #include "disco_gfa.h"
+#include "disco_gfa_chains.h"
 #include "disco_partext.h"
 #include "disco_ingest.h"
 #include "disco_bgzf.h"
@@ -4967,6 +4968,23 @@ static void gfa_deliver(disco_ctx *c, GfaSink &o)
     }
     if (!ok.load()) o.write_ok = false;
 }
+/* the piece just launched into buffer issued & 1, `bytes` long, belongs at byte file_pos of the file: it travels into its half of the
+ * ring while the host writes the piece before it */
+static int gfa_ship(disco_ctx *c, GfaSink &o, u64 bytes, u64 file_pos)
+{
+    const u64 h = o.issued & 1;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync((char *)c->h_ring + h * c->ring_half, o.piece[h].p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_ring[h], c->stream));
+    gfa_deliver(c, o); /* the piece before: its copy was waited for below, one piece ago; the half it frees is written again two pieces on */
+    HIPCHK(c, hipEventSynchronize(c->ev_ring[h]));
+    o.pending = true;
+    o.p_half = h;
+    o.p_bytes = bytes;
+    o.p_off = file_pos;
+    o.issued++;
+    return DISCO_OK;
+}
 /* one section of the file — n_lines lines whose starts are place[0 .. n_lines], place[n_lines] = total — piece by piece: launch(a, b,
  * piece) formats the lines [a[0], b[0]) into a piece that begins at byte a[1] of the section (a, b: two entries of gfa_cuts_kernel) */
 static int gfa_section(disco_ctx *c, const char *who, GfaSink &o, const u64 *place, u64 n_lines, u64 total, const u32 *ovf, u32 n_long,
@@ -4986,21 +5004,43 @@ static int gfa_section(disco_ctx *c, const char *who, GfaSink &o, const u64 *pla
         const u64 bytes = b[1] - a[1];
         if (bytes == 0) continue; /* (a line longer than the stretch: the one behind it has no line of its own) */
         if (b[0] < a[0] || b[0] > n_lines || bytes > o.cap) return fail(c, DISCO_E_CAPACITY, "%s: a piece of %llu bytes, room for %llu", who, (unsigned long long)bytes, (unsigned long long)o.cap);
-        const u64 h = o.issued & 1;
-        launch(a, b, (char *)o.piece[h].p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync((char *)c->h_ring + h * c->ring_half, o.piece[h].p, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_ring[h], c->stream));
-        gfa_deliver(c, o); /* the piece before: its copy was waited for below, one piece ago; the half it frees is written again two pieces on */
-        HIPCHK(c, hipEventSynchronize(c->ev_ring[h]));
-        o.pending = true;
-        o.p_half = h;
-        o.p_bytes = bytes;
-        o.p_off = o.file_off + a[1];
-        o.issued++;
+        launch(a, b, (char *)o.piece[o.issued & 1].p);
+        CHK(gfa_ship(c, o, bytes, o.file_off + a[1]));
     }
     o.file_off += total;
     return DISCO_OK;
+}
+/* a section that is one stream of bytes with no line a piece could end at (the chain S lines of disco_write_gfa_chains: a line can be a
+ * genome): piece r is the bytes [r step, (r + 1) step) of it, step = the piece's room rounded down to 16 so that every piece begins
+ * 16-byte aligned in the stream as in its buffer; launch(lo, hi, piece) fills the piece with the bytes [lo, hi) */
+static int gfa_byte_section(disco_ctx *c, GfaSink &o, u64 total, const std::function<void(u64, u64, char *)> &launch)
+{
+    if (total == 0) return DISCO_OK;
+    const u64 step = o.cap & ~(u64)15;
+    for (int i = 0; i < 2; i++) CHK(ensure(c, o.piece[i], std::min(o.cap, total)));
+    for (u64 lo = 0; lo < total; lo += step) {
+        const u64 hi = std::min(total, lo + step);
+        launch(lo, hi, (char *)o.piece[o.issued & 1].p);
+        CHK(gfa_ship(c, o, hi - lo, o.file_off + lo));
+    }
+    o.file_off += total;
+    return DISCO_OK;
+}
+
+/* the read table as disco_gfa.h looks at it, whichever of its three layouts it has */
+static GfaReads gfa_reads(const disco_ctx *c, const u64 *d_findex)
+{
+    GfaReads R;
+    R.rows = (const uint64_t *)c->d_reads;
+    R.S = (u32)c->S;
+    R.full = c->two_class ? (const uint64_t *)c->d_full.p : nullptr;
+    R.ovf = c->two_class ? c->d_ovf.p : nullptr;
+    R.long_ids = c->two_class ? c->d_long_ids.p : nullptr;
+    R.SL = c->two_class ? (u32)c->S_ext : 0u;
+    R.len = c->d_len;
+    R.file_index = (const uint64_t *)d_findex;
+    R.n = c->n;
+    return R;
 }
 
 int64_t disco_write_gfa(disco_ctx *c, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads)
@@ -5034,28 +5074,19 @@ int64_t disco_write_gfa(disco_ctx *c, int fd, const uint64_t *file_index, uint32
         if (pwrite(fd, header, sizeof header - 1, 0) != (ssize_t)(sizeof header - 1)) return fail(c, DISCO_E_ARG, "%s: write error", who);
         o.file_off = sizeof header - 1;
         /* S lines: a lane per word of a read */
-        GfaReads R;
-        R.rows = (const uint64_t *)c->d_reads;
-        R.S = (u32)c->S;
-        R.full = c->two_class ? (const uint64_t *)c->d_full.p : nullptr;
-        R.ovf = c->two_class ? c->d_ovf.p : nullptr;
-        R.long_ids = c->two_class ? c->d_long_ids.p : nullptr;
-        R.SL = c->two_class ? (u32)c->S_ext : 0u;
-        R.len = c->d_len;
-        R.file_index = (const uint64_t *)d_findex.p;
-        R.n = n;
+        const GfaReads R = gfa_reads(c, d_findex);
         u64 total = 0;
         if (n) {
             CHK(ensure(c, sbytes, n));
             CHK(ensure(c, place, n + 1));
-            hipLaunchKernelGGL(gfa_s_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, no_seq ? 1u : 0u, sbytes.p);
+            hipLaunchKernelGGL(gfa_s_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, (const u8 *)nullptr, no_seq ? 1u : 0u, sbytes.p);
             CHK((scan_exclusive<u16, u64>(c, sbytes, n, place, true, &total)));
             const u32 W = no_seq ? 1u : R.S;
             const bool long_pass = c->two_class && !no_seq && R.SL > GFA_HEAD_WORDS;
             CHK(gfa_section(c, who, o, place, n, total, R.ovf, (u32)c->n_long, [&](const u64 *a, const u64 *b, char *piece) {
-                hipLaunchKernelGGL(gfa_s_write_kernel, dim3(flat_grid(c, (b[0] - a[0]) * W)), dim3(256), 0, c->stream, R, (const u64 *)place, a[0], b[0], a[1], no_seq ? 1u : 0u, W, piece);
+                hipLaunchKernelGGL(gfa_s_write_kernel, dim3(flat_grid(c, (b[0] - a[0]) * W)), dim3(256), 0, c->stream, R, (const u8 *)nullptr, (const u64 *)place, a[0], b[0], a[1], no_seq ? 1u : 0u, W, piece);
                 if (long_pass && b[2] > a[2])
-                    hipLaunchKernelGGL(gfa_s_write_long_kernel, dim3(flat_grid(c, (b[2] - a[2]) * (R.SL - GFA_HEAD_WORDS))), dim3(256), 0, c->stream, R, (const u64 *)place, a[2], b[2],
+                    hipLaunchKernelGGL(gfa_s_write_long_kernel, dim3(flat_grid(c, (b[2] - a[2]) * (R.SL - GFA_HEAD_WORDS))), dim3(256), 0, c->stream, R, (const u8 *)nullptr, (const u64 *)place, a[2], b[2],
                                        a[1], piece);
             }));
         }
@@ -5077,12 +5108,12 @@ int64_t disco_write_gfa(disco_ctx *c, int fd, const uint64_t *file_index, uint32
             const u16 *d_subs = c->prm.max_substitutions ? subs.p : nullptr;
             CHK(ensure(c, bytes, ne));
             CHK(ensure(c, place, ne + 1));
-            hipLaunchKernelGGL(gfa_l_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, d_subs, bytes.p);
+            hipLaunchKernelGGL(gfa_l_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, d_subs, (const u8 *)nullptr, bytes.p);
             CHK((scan_exclusive<u8, u64>(c, bytes, ne, place, true, &total)));
             const bool dense = c->out_dense;
             CHK(gfa_section(c, who, o, place, ne, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
                 const u64 s_lo = dense ? a[0] : 0, s_hi = dense ? b[0] : g.n_slots;
-                hipLaunchKernelGGL(gfa_l_write_kernel, dim3(flat_grid(c, s_hi - s_lo)), dim3(256), 0, c->stream, g, d_subs, (const u64 *)place, s_lo, s_hi, a[0], b[0], a[1], piece);
+                hipLaunchKernelGGL(gfa_l_write_kernel, dim3(flat_grid(c, s_hi - s_lo)), dim3(256), 0, c->stream, g, d_subs, (const u8 *)nullptr, (const u64 *)place, s_lo, s_hi, a[0], b[0], a[1], piece);
             }));
         }
         /* C lines: a lane per contained row, grouped and sorted as for the contained-read files */
@@ -5124,6 +5155,139 @@ int64_t disco_write_gfa(disco_ctx *c, int fd, const uint64_t *file_index, uint32
     release(c, subs);
     release(c, bytes);
     release_groups(c, G);
+    return rc != DISCO_OK ? rc : (int64_t)o.file_off;
+}
+
+/* ---- the compacted graph as GFA 1.0: the composite edges of the contraction as segments with their merged bases (disco_gfa_chains.h) ---- */
+int64_t disco_write_gfa_chains(disco_ctx *c, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads)
+{
+    DISCO_TRACE("disco_write_gfa_chains");
+    static const char who[] = "disco_write_gfa_chains";
+    if (!c || fd < 0) return DISCO_E_ARG;
+    if (flags & ~(uint32_t)DISCO_GFA_NO_SEQ) return fail(c, DISCO_E_ARG, "%s: unknown flags %#x", who, flags);
+    if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "%s: a rank holds its share of the graph only", who);
+    if (c->prm.max_substitutions) return fail(c, DISCO_E_UNSUPPORTED, "%s: with max_substitutions > 0 the reads of a chain disagree about its bases", who);
+    if (c->phase < 8) return fail(c, DISCO_E_STATE, "%s: run disco_transitive_reduce first", who);
+    if (!c->ch_ready || !c->ch_resident || c->ch_edges_n != c->n_out)
+        return fail(c, DISCO_E_STATE, "%s: run disco_contract_chains on the resident edges first (after disco_contract_chains_of the host holds them)", who);
+    if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "%s: more than 2^31 reads", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(output_ring(c, who));
+    const bool no_seq = (flags & DISCO_GFA_NO_SEQ) != 0;
+    const u64 n = c->n, ne = c->n_out, nk = c->ch_comp_n, nl = c->ch_links_n;
+    GfaSink o;
+    o.fd = fd;
+    o.threads = std::max<uint32_t>(host_threads, 1);
+    o.cap = piece_bytes ? std::min<u64>(std::max<u64>(piece_bytes, 65536), c->ring_half) : c->ring_half;
+    o.unit = o.cap - GFA_MAX_LINE;
+    DevBuf<u64> d_findex, place, lsum, cbytes, cplace;
+    DevBuf<u32> loff;
+    DevBuf<u16> sbytes;
+    DevBuf<u8> bytes, skip;
+    auto body = [&]() -> int {
+        if (file_index) {
+            CHK(ensure(c, d_findex, n));
+            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, n * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        static const char header[] = GFA_HEADER;
+        if (pwrite(fd, header, sizeof header - 1, 0) != (ssize_t)(sizeof header - 1)) return fail(c, DISCO_E_ARG, "%s: write error", who);
+        o.file_off = sizeof header - 1;
+        const GfaReads R = gfa_reads(c, d_findex);
+        GfuChains H;
+        H.comp = (const disco_chain_edge *)c->d_ch_comp.p;
+        H.links = (const disco_chain_link *)c->d_ch_links.p;
+        H.lsum = H.cplace = nullptr;
+        H.n_comp = nk;
+        H.no_seq = no_seq;
+        u64 total = 0;
+        /* S lines of the reads that are neither contained nor inside a chain: disco_write_gfa's writers behind the skip flags */
+        if (n) {
+            CHK(ensure(c, skip, n));
+            HIPCHK(c, hipMemcpyAsync(skip, c->d_contained, n, hipMemcpyDeviceToDevice, c->stream));
+            if (nk) {
+                hipLaunchKernelGGL(gfu_mark_links_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, skip.p);
+                hipLaunchKernelGGL(gfu_unmark_ends_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, H.comp, nk, (const u8 *)c->d_contained, skip.p);
+            }
+            CHK(ensure(c, sbytes, n));
+            CHK(ensure(c, place, n + 1));
+            hipLaunchKernelGGL(gfa_s_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, (const u8 *)skip, no_seq ? 1u : 0u, sbytes.p);
+            CHK((scan_exclusive<u16, u64>(c, sbytes, n, place, true, &total)));
+            const u32 W = no_seq ? 1u : R.S;
+            const bool long_pass = c->two_class && !no_seq && R.SL > GFA_HEAD_WORDS;
+            CHK(gfa_section(c, who, o, place, n, total, R.ovf, (u32)c->n_long, [&](const u64 *a, const u64 *b, char *piece) {
+                hipLaunchKernelGGL(gfa_s_write_kernel, dim3(flat_grid(c, (b[0] - a[0]) * W)), dim3(256), 0, c->stream, R, (const u8 *)skip, (const u64 *)place, a[0], b[0], a[1],
+                                   no_seq ? 1u : 0u, W, piece);
+                if (long_pass && b[2] > a[2])
+                    hipLaunchKernelGGL(gfa_s_write_long_kernel, dim3(flat_grid(c, (b[2] - a[2]) * (R.SL - GFA_HEAD_WORDS))), dim3(256), 0, c->stream, R, (const u8 *)skip,
+                                       (const u64 *)place, a[2], b[2], a[1], piece);
+            }));
+        }
+        /* S lines of the composite edges: one stream of bytes, a lane per 16 of them */
+        if (nk) {
+            CHK(ensure(c, loff, nl));
+            CHK(ensure(c, lsum, nl + 1));
+            CHK(ensure(c, cbytes, nk));
+            CHK(ensure(c, cplace, nk + 1));
+            hipLaunchKernelGGL(gfu_link_offsets_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, loff.p);
+            CHK((scan_exclusive<u32, u64>(c, loff, nl, lsum, true, nullptr)));
+            H.lsum = (const uint64_t *)lsum.p;
+            hipLaunchKernelGGL(gfu_s_measure_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, H, (const u16 *)c->d_len, cbytes.p);
+            CHK((scan_exclusive<u64, u64>(c, cbytes, nk, cplace, true, &total)));
+            H.cplace = (const uint64_t *)cplace.p;
+            CHK(gfa_byte_section(c, o, total, [&](u64 lo, u64 hi, char *piece) {
+                hipLaunchKernelGGL(gfu_spell_kernel, dim3(flat_grid(c, gfu_items(lo, hi))), dim3(256), 0, c->stream, R, H, lo, hi, piece);
+            }));
+        }
+        /* L lines of the edges that went into no composite edge, in the order of disco_fetch_edges */
+        if (ne) {
+            TextView g;
+            g.src = c->d_out_src;
+            g.ent = c->d_out_ent;
+            g.valid = out_valid(c);
+            g.pos = out_pos(c);
+            g.len = c->d_len;
+            g.file_index = d_findex;
+            g.n_slots = c->out_used;
+            const u8 *dead = c->d_ch_dead;
+            CHK(ensure(c, bytes, ne));
+            CHK(ensure(c, place, ne + 1));
+            hipLaunchKernelGGL(gfa_l_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, (const u16 *)nullptr, dead, bytes.p);
+            CHK((scan_exclusive<u8, u64>(c, bytes, ne, place, true, &total)));
+            const bool dense = c->out_dense;
+            CHK(gfa_section(c, who, o, place, ne, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+                const u64 s_lo = dense ? a[0] : 0, s_hi = dense ? b[0] : g.n_slots;
+                hipLaunchKernelGGL(gfa_l_write_kernel, dim3(flat_grid(c, s_hi - s_lo)), dim3(256), 0, c->stream, g, (const u16 *)nullptr, dead, (const u64 *)place, s_lo, s_hi, a[0], b[0],
+                                   a[1], piece);
+            }));
+        }
+        /* ... and the head and the tail link of every composite edge, a lane per composite edge */
+        if (nk) {
+            CHK(ensure(c, bytes, nk));
+            CHK(ensure(c, place, nk + 1));
+            hipLaunchKernelGGL(gfu_l_measure_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, R, H, bytes.p);
+            CHK((scan_exclusive<u8, u64>(c, bytes, nk, place, true, &total)));
+            CHK(gfa_section(c, who, o, place, nk, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+                hipLaunchKernelGGL(gfu_l_write_kernel, dim3(flat_grid(c, b[0] - a[0])), dim3(256), 0, c->stream, R, H, (const u64 *)place, a[0], b[0], a[1], piece);
+            }));
+        }
+        gfa_deliver(c, o);
+        if (!o.write_ok) return fail(c, DISCO_E_ARG, "%s: write error", who);
+        return DISCO_OK;
+    };
+    const int rc = body();
+    if (rc != DISCO_OK) (void)hipStreamSynchronize(c->stream); /* (nothing in flight reads what is released below) */
+    release(c, o.piece[0]);
+    release(c, o.piece[1]);
+    release(c, o.d_cut);
+    release(c, d_findex);
+    release(c, place);
+    release(c, lsum);
+    release(c, cbytes);
+    release(c, cplace);
+    release(c, loff);
+    release(c, sbytes);
+    release(c, bytes);
+    release(c, skip);
     return rc != DISCO_OK ? rc : (int64_t)o.file_off;
 }
 

@@ -67,7 +67,10 @@ static void usage()
               << "  --no-text\tbinary output only: leave the text edge / contained files empty (a consumer with the loader patch)\n"
               << "  --gfa\talso write <prefix>.gfa: the reduced graph as GFA 1.0 (S lines of all reads, L lines of the edges, C lines of the\n"
               << "\t\tcontained reads; names = the file indices of <prefix>_ReadIDMap.txt), formatted on the GPU; single GPU\n"
-              << "  --gfa-no-seq\t--gfa with * in place of the bases\n";
+              << "  --gfa-no-seq\t--gfa with * in place of the bases\n"
+              << "  --gfa-unitigs\talso write <prefix>.unitigs.gfa: the compacted graph as GFA 1.0 — every unbranched chain of reads one segment c<k>\n"
+              << "\t\twith its merged bases, spelled on the GPU; no contained reads (--gfa has them); exact overlaps, single GPU;\n"
+              << "\t\twith --gfa-no-seq beside it: * in place of the bases, and no <prefix>.gfa unless --gfa asks for it\n";
 }
 
 static std::vector<std::string> split(const std::string &s, char d)
@@ -153,6 +156,7 @@ struct Args {
     int threads = omp_get_max_threads(), gpu = 0, gpus = 1;
     bool same_device = false, mpi_names = false, binary_out = false, no_text = false, partitioned_index = false;
     bool gfa = false, gfa_no_seq = false; /* <prefix>.gfa, with or without the bases */
+    bool gfa_unitigs = false;             /* <prefix>.unitigs.gfa */
     std::string par_simple; /* prefix of the <prefix>_<i>_ParSimpleEdges.txt files, or empty */
     uint32_t min_overlap = 30, min_overlap_simplify = 0, max_subs = 0;
     std::vector<const char *> paths() const
@@ -168,6 +172,7 @@ struct Args {
 static int parse_args(int argc, char **argv, Args &a)
 {
     long long max_subs_cli = -1; /* --max-substitutions (overrides MaxSubstitutions4BuildGraph of the parameter file) */
+    bool gfa_cli = false;        /* --gfa itself */
     std::cout << "PRINTING ARGUMENTS\n";
     for (int i = 0; i < argc; i++) std::cout << argv[i] << ' ';
     std::cout << std::endl;
@@ -208,8 +213,9 @@ static int parse_args(int argc, char **argv, Args &a)
         else if (o == "--max-substitutions") max_subs_cli = (long long)num(0, 32767);
         else if (o == "--binary-out") a.binary_out = true;
         else if (o == "--no-text") a.binary_out = a.no_text = true;
-        else if (o == "--gfa") a.gfa = true;
-        else if (o == "--gfa-no-seq") a.gfa = a.gfa_no_seq = true;
+        else if (o == "--gfa") gfa_cli = true;
+        else if (o == "--gfa-no-seq") a.gfa_no_seq = true;
+        else if (o == "--gfa-unitigs") a.gfa_unitigs = true;
         else {
             usage();
             if (o == "-h" || o == "--help") return 0;
@@ -220,6 +226,11 @@ static int parse_args(int argc, char **argv, Args &a)
             usage();
             return 1;
         }
+    }
+    a.gfa = gfa_cli || (a.gfa_no_seq && !a.gfa_unitigs); /* alone, --gfa-no-seq means --gfa; beside --gfa-unitigs it is that file's */
+    if (a.gfa_unitigs && a.gpus > 1) {
+        std::cerr << "--gfa-unitigs writes the graph of one GPU: with --gpus " << a.gpus << " every rank holds its share only, run it without --gpus." << std::endl;
+        return 1;
     }
     if (a.gfa && a.gpus > 1) {
         std::cerr << "--gfa writes the graph of one GPU: with --gpus " << a.gpus << " every rank holds its share only, run it without --gpus." << std::endl;
@@ -237,6 +248,11 @@ static int parse_args(int argc, char **argv, Args &a)
     std::cout << "MinOverlap4BuildGraph = " << a.min_overlap << std::endl;
     disco::set_writer_threads(a.threads);
     if (max_subs_cli >= 0) a.max_subs = (uint32_t)max_subs_cli;
+    if (a.gfa_unitigs && a.max_subs) {
+        std::cerr << "--gfa-unitigs spells every chain from reads that overlap exactly: with " << a.max_subs << " substitutions allowed (--max-substitutions, "
+                  << "MaxSubstitutions4BuildGraph) the reads of a chain disagree about its bases. Use --gfa." << std::endl;
+        return 1;
+    }
     if (a.max_subs)
         std::cout << "MaxSubstitutions4BuildGraph = " << a.max_subs << " (extension: overlaps and containments may differ in that many bases around an exact "
                   << "end-k-mer seed; the reference compares exactly)" << std::endl;
@@ -756,6 +772,30 @@ static int write_gfa_file(Job &J, disco_ctx *ctx)
     return GO_ON;
 }
 
+/* <prefix>.unitigs.gfa (--gfa-unitigs): the compacted graph — every chain one segment with its merged bases (disco_write_gfa_chains). A
+ * stage of its own behind every planned product and --gfa: it contracts for itself, every overlap counted (filter 0), whatever
+ * --par-simple contracted before (its files are written, and what the host needs of that contraction it holds). No product of the plan */
+static int write_gfa_unitigs_file(Job &J, disco_ctx *ctx)
+{
+    const std::string path = J.a.prefix + ".unitigs.gfa";
+    uint64_t nc = 0, nl = 0;
+    auto t = Clock::now();
+    DISCO_CALL(ctx, disco_contract_chains(ctx, 0, &nc, &nl));
+    const double s_contract = secs(t);
+    Fds fds;
+    fds.fd.assign(1, open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666));
+    if (fds.fd[0] < 0) return die("Unable to open file: " + path);
+    t = Clock::now();
+    const int64_t nb = disco_write_gfa_chains(ctx, fds.fd[0], J.ids(), J.a.gfa_no_seq ? DISCO_GFA_NO_SEQ : 0u, 0, (uint32_t)J.a.threads);
+    if (nb < 0) return die(std::string("disco_write_gfa_chains : ") + disco_last_error(ctx));
+    const double s = secs(t);
+    if (J.verbose)
+        fprintf(stderr, "[disco host] GFA of unitigs: %llu chains of %llu links contracted in %.3f s; %lld bytes in %.3f s (%.2f GB/s)\n", (unsigned long long)nc, (unsigned long long)nl,
+                s_contract, (long long)nb, s, s > 0 ? (double)nb / s * 1e-9 : 0.0);
+    J.lap("GFA of unitigs from the GPU into the file");
+    return GO_ON;
+}
+
 /* ---- the graph on one GPU, and every file the device writes ------------------------------------------------------------------------- */
 static int graph_single_gpu(Job &J)
 {
@@ -898,6 +938,7 @@ static int graph_single_gpu(Job &J)
     }
     if (rc != GO_ON) return rc;
     if (a.gfa && (rc = write_gfa_file(J, ctx)) != GO_ON) return rc;
+    if (a.gfa_unitigs && (rc = write_gfa_unitigs_file(J, ctx)) != GO_ON) return rc;
     /* the context is released by a thread of its own while the files are written (0.07 s of hipFree at config 3) */
     J.ctx_releaser.t = std::thread([ctx]() { disco_destroy(ctx); });
     J.lap("release GPU context (in the background)");

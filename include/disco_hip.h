@@ -596,6 +596,28 @@ int     disco_write_contained_records(disco_ctx *ctx, int fd, uint64_t file_offs
 #define DISCO_GFA_NO_SEQ 1u
 int64_t disco_write_gfa(disco_ctx *ctx, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads);
 
+/* <prefix>.unitigs.gfa, the COMPACTED graph (disco_amd/csrc/disco_gfa_chains.h): every composite edge of the chain contraction is one
+ * segment with the merged bases of the reads inside it, and the reads inside chains have no line of their own:
+ *     H \t VN:Z:1.0
+ *     S \t name \t bases \t LN:i:len                every read that is neither contained nor inside a chain, in read-id order
+ *     S \t c<k> \t bases \t LN:i:LN \t RC:i:m       every composite edge k (0-based, the order of disco_fetch_chains)
+ *     L \t src \t so \t dst \t do \t ovl M          every edge whose absorbed flag is 0, in the order of disco_fetch_edges, as disco_write_gfa writes it
+ *     L \t a \t sa \t c<k> \t + \t ovl_a M          then per composite edge k its head link ...
+ *     L \t c<k> \t + \t b \t sb \t ovl_b M          ... and its tail link
+ * No C lines and no contained reads: disco_write_gfa or the contained-read files have them. With the links l_0 .. l_{n-1} of composite
+ * edge k and m = n - 1: its interior reads are r_j = l_j.to for j < m, read forward iff l_j.orient & 1 (otherwise as the reverse
+ * complement), r_j begins at base s_j of the segment, s_0 = 0, s_j = s_{j-1} + l_j.offset; LN = s_{m-1} + len[r_{m-1}] (64 bits), RC = m;
+ * base p of the segment is base p - s_j of oriented r_j for the largest j with s_j <= p. sa = '+' iff l_0.orient & 2, ovl_a = len[a] -
+ * l_0.offset; sb = '+' iff l_{n-1}.orient & 1, ovl_b = len[r_{m-1}] - l_{n-1}.offset. A chain with a == b, and two chains between the
+ * same ends, are segments like any other; a ring of absorbable nodes is left alone by the contraction: its reads and edges stay S and
+ * L lines. DISCO_GFA_NO_SEQ writes * for every segment's bases; LN stays.
+ * Arguments, pieces and the return value as for disco_write_gfa; the S lines of the composite edges are cut into pieces at any byte (a
+ * line can be as long as a genome), everything else at line ends. Needs a finished disco_contract_chains on the resident edges, and
+ * writes whatever filter it was given (an edge below the filter is not absorbed: an L line): DISCO_E_STATE otherwise, also after
+ * disco_contract_chains_of, whose edges the host holds. DISCO_E_UNSUPPORTED on a context with a communicator, with 2^31 or more reads,
+ * and with max_substitutions > 0 (the reads of a chain would disagree about its bases). */
+int64_t disco_write_gfa_chains(disco_ctx *ctx, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,40 @@ HIP_DEPS = HIP_SOURCES + [os.path.join(HERE, "csrc", f) for f in sorted(f for f 
 HOST_SOURCES = [os.path.join(HERE, "host", f) for f in ("buildg_main.cpp", "fastx.cpp", "writer.cpp", "parsimple.cpp")]
 
 
+def _host(*names):
+    return [os.path.join(HERE, "host", n) for n in names]
+
+
+def _csrc(*names):
+    return [os.path.join(HERE, "csrc", n) for n in names]
+
+
+_PRODUCT_H = os.path.join(ROOT, "include", "disco_hip.h")
+_W, _OMP, _INC, _Z = ["-Wall"], ["-fopenmp"], ["-I", os.path.join(ROOT, "include")], ["-lz"]
+# The stand-alone host programs under disco_amd/bin: (name, sources, headers that make it stale too, flags in front of -o, libraries).
+# A *_check program is a header the kernels or the library include, built as plain C++ and held to its rules by a CPU test.
+STANDALONE = [
+    ("fastx_dump", _host("fastx_dump.cpp", "fastx.cpp"), _host("fastx.h"), _OMP + _W, _Z),
+    # (parsimple.cpp formats with the kernels' item functions when it has no device)
+    ("parsimplify", _host("parsimplify_main.cpp", "parsimple.cpp", "fastx.cpp", "writer.cpp"), _host("parsimple.h", "writer.h", "fastx.h") + _csrc("disco_partext.h"),
+     _OMP + _W + _INC, _Z),
+    ("readgen", _host("readgen_main.cpp"), _csrc("readgen.h"), _W, []),
+    # the device input stage's BGZF decode core: the same header, a serial byte sink
+    ("inflate_check", _host("inflate_check.cpp"), _csrc("disco_inflate.h"), _W, []),
+    # the self-delimiting survivor lists of the marking
+    ("survivor_check", _host("survivor_check.cpp"), _csrc("disco_survivor.h"), _W, []),
+    # the item functions behind the ParSimpleEdges lines
+    ("partext_check", _host("partext_check.cpp"), _csrc("disco_partext.h") + [_PRODUCT_H], _W, []),
+    # the line and item functions behind <prefix>.gfa, and the item functions behind <prefix>.unitigs.gfa
+    ("gfa_check", _host("gfa_check.cpp"), _csrc("disco_gfa.h") + [_PRODUCT_H], _W, []),
+    ("gfa_chains_check", _host("gfa_chains_check.cpp"), _csrc("disco_gfa_chains.h", "disco_gfa.h") + [_PRODUCT_H], _W, []),
+    # buildG's output plan: every combination of options, knobs and demotions
+    ("plan_check", _host("plan_check.cpp"), _host("output_plan.h"), _W, []),
+    # the host's end of the output ring: split writers, pieces of several segments, files that take no bytes
+    ("ringio_check", _host("ringio_check.cpp"), _csrc("disco_ringio.h"), _W + ["-pthread"], []),
+]
+
+
 def _hipcc() -> str:
     for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
         if cand and os.path.exists(cand):
@@ -70,6 +104,16 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
     return LIB
 
 
+def _build_standalone(name, sources, headers, flags, libs, force, verbose):
+    out = os.path.join(HERE, "bin", name)
+    if force or _stale(out, sources + headers):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        cmd = ["g++", "-O2", "-std=c++17"] + flags + ["-o", out] + sources + libs
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+
+
 def build_host(force: bool = False, verbose: bool = False) -> str:
     srcs = [s for s in HOST_SOURCES if os.path.exists(s)]
     if not srcs:
@@ -83,75 +127,8 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
-    dump = os.path.join(HERE, "bin", "fastx_dump")
-    dsrc = [os.path.join(HERE, "host", "fastx_dump.cpp"), os.path.join(HERE, "host", "fastx.cpp")]
-    if force or _stale(dump, dsrc + [os.path.join(HERE, "host", "fastx.h")]):
-        cmd = ["g++", "-O2", "-std=c++17", "-fopenmp", "-Wall", "-o", dump] + dsrc + ["-lz"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    ps = os.path.join(HERE, "bin", "parsimplify")
-    psrc = [os.path.join(HERE, "host", f) for f in ("parsimplify_main.cpp", "parsimple.cpp", "fastx.cpp", "writer.cpp")]
-    if force or _stale(ps, psrc + [os.path.join(HERE, "host", f) for f in ("parsimple.h", "writer.h", "fastx.h")] + [partext]):
-        cmd = ["g++", "-O2", "-std=c++17", "-fopenmp", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", ps] + psrc + ["-lz"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    gen = os.path.join(HERE, "bin", "readgen")
-    gsrc = [os.path.join(HERE, "host", "readgen_main.cpp"), os.path.join(HERE, "csrc", "readgen.h")]
-    if force or _stale(gen, gsrc):
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", gen, gsrc[0]]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    # the device input stage's BGZF decode core on the host: the same header, a serial byte sink
-    chk = os.path.join(HERE, "bin", "inflate_check")
-    csrc = [os.path.join(HERE, "host", "inflate_check.cpp"), os.path.join(HERE, "csrc", "disco_inflate.h")]
-    if force or _stale(chk, csrc):
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", chk, csrc[0]]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    # the self-delimiting survivor lists of the marking on the host: the header the kernels include, as plain C++
-    sv = os.path.join(HERE, "bin", "survivor_check")
-    ssrc = [os.path.join(HERE, "host", "survivor_check.cpp"), os.path.join(HERE, "csrc", "disco_survivor.h")]
-    if force or _stale(sv, ssrc):
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", sv, ssrc[0]]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    # the item functions behind the ParSimpleEdges lines on the host: the header the kernels include, as plain C++
-    pc = os.path.join(HERE, "bin", "partext_check")
-    pcsrc = [os.path.join(HERE, "host", "partext_check.cpp"), partext, os.path.join(ROOT, "include", "disco_hip.h")]
-    if force or _stale(pc, pcsrc):
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", pc, pcsrc[0]]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    # the line and item functions behind <prefix>.gfa on the host: the header the kernels include, as plain C++
-    gc = os.path.join(HERE, "bin", "gfa_check")
-    gcsrc = [os.path.join(HERE, "host", "gfa_check.cpp"), os.path.join(HERE, "csrc", "disco_gfa.h"), os.path.join(ROOT, "include", "disco_hip.h")]
-    if force or _stale(gc, gcsrc):
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", gc, gcsrc[0]]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    # the item functions behind <prefix>.unitigs.gfa on the host: the header the kernels include, as plain C++
-    uc = os.path.join(HERE, "bin", "gfa_chains_check")
-    ucsrc = [os.path.join(HERE, "host", "gfa_chains_check.cpp"), os.path.join(HERE, "csrc", "disco_gfa_chains.h")] + gcsrc[1:]
-    if force or _stale(uc, ucsrc):
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", uc, ucsrc[0]]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    # buildG's output plan on the host: every combination of options, knobs and demotions
-    pl = os.path.join(HERE, "bin", "plan_check")
-    plsrc = [os.path.join(HERE, "host", "plan_check.cpp"), os.path.join(HERE, "host", "output_plan.h")]
-    if force or _stale(pl, plsrc):
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", pl, plsrc[0]]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
+    for name, sources, headers, flags, libs in STANDALONE:
+        _build_standalone(name, sources, headers, flags, libs, force, verbose)
     return BUILDG
 
 

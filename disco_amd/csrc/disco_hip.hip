@@ -49,6 +49,7 @@
 #include "disco_gfa.h"
 #include "disco_gfa_chains.h"
 #include "disco_partext.h"
+#include "disco_ringio.h"
 #include "disco_ingest.h"
 #include "disco_bgzf.h"
 #include "read_filter_tables.h"
@@ -165,13 +166,50 @@ struct DevArena {
 };
 
 /* A device buffer the context owns: the pointer and the elements it was allocated with, which is what release gives back to hbm_bytes.
- * It reads as a plain pointer. Only ensure / ensure_keep / release / adopt / disown (below) change it: frees stay ordered with the
- * streams and the arena, so there is no destructor. */
+ * It reads as a plain pointer. Only ensure / ensure_keep / release / adopt / disown (below) change it. The context's members live as
+ * long as the context and are released by name (free_graph_state and its like), so DevBuf has no destructor; a function's own buffers
+ * are LocalBufs. */
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     u64 cap = 0;
     operator T *() const { return p; }
+};
+
+struct disco_ctx;
+template <typename T>
+static void release(disco_ctx *c, DevBuf<T> &b);
+
+/* A device buffer a function (or a short-lived struct) owns: a DevBuf wherever one is taken, released when it leaves its scope, so that
+ * CHK / HIPCHK may return from anywhere. release(c, b) before that gives the memory back early (peak memory, the arena's first fit);
+ * give / take hand the memory to a member of the context, or borrow a member's for a while, without touching hbm_bytes. */
+template <typename T>
+struct LocalBuf : DevBuf<T> {
+    disco_ctx *const c;
+    explicit LocalBuf(disco_ctx *ctx) : c(ctx) {}
+    LocalBuf(const LocalBuf &) = delete;
+    LocalBuf &operator=(const LocalBuf &) = delete;
+    ~LocalBuf() { release(c, *this); }
+    void give(DevBuf<T> &to) /* to's own memory is released first */
+    {
+        release(c, to);
+        to = *this;
+        DevBuf<T>::operator=(DevBuf<T>());
+    }
+    void take(DevBuf<T> &from)
+    {
+        release(c, *this);
+        DevBuf<T>::operator=(from);
+        from = DevBuf<T>();
+    }
+};
+
+/* formatted lines that wait on the device to be fetched or written: the files' text one behind the other, the byte range of every file
+ * inside it (n_files + 1 offsets), and the bytes in all (0: nothing formatted, whatever d still holds) */
+struct TextProduct {
+    DevBuf<char> d;
+    std::vector<u64> off;
+    u64 bytes = 0;
 };
 
 struct disco_ctx {
@@ -298,12 +336,9 @@ struct disco_ctx {
     std::vector<u64> ingest_id_base, ingest_rec_base; /* per file: first read id, records before the file */
     u64 ingest_n = 0;
     void *h_ring = nullptr; /* pinned: two halves of the text staging ring */
-    std::vector<u64> text_off; /* disco_format_edges: byte range of every file inside d_text */
-    /* disco_format_contained: the lines of the contained-read files, their byte range per file — state of its own, so that either text
-     * may be formatted first */
-    DevBuf<char> d_ctext;
-    std::vector<u64> ctext_off;
-    u64 ctext_bytes = 0;
+    /* the three texts, each state of its own, so that any may be formatted first: the edge lines of all files, file after file
+     * (disco_format_edges), the lines of the contained-read files (disco_format_contained) ... */
+    TextProduct text, ctext;
     DevBuf<u8> d_ingest; /* the input stage's own arena (text, record arrays) when the hit buffer is allocated NEXT to it ... */
     std::thread hits_prealloc; /* ... by this thread, while the files travel and the filter runs (settle_hits_prealloc) */
     DevBuf<u64> prealloc; /* (hipMalloc of that thread; settle_hits_prealloc adopts or frees it) */
@@ -375,11 +410,7 @@ struct disco_ctx {
     DevBuf<u64> d_ch_first, d_ch_res_pos, d_ch_res_slot;
     u64 ch_res_n = 0;
     bool ch_resident = false; /* contracted from the emission's slots (disco_contract_chains), which still hold the records */
-    /* disco_format_par_simple: the lines of the ParSimpleEdges files, kept apart from the two other texts */
-    DevBuf<char> d_ptext;
-    std::vector<u64> ptext_off;
-    u64 ptext_bytes = 0;
-    DevBuf<char> d_text; /* disco_format_edges: the edge lines of all files, file after file */
+    TextProduct ptext; /* ... and the lines of the ParSimpleEdges files (disco_format_par_simple) */
     /* the records of the binary side output (disco_prepare_*_records, disco_binrec.h): what a prepare call uploaded or grouped, kept until
      * the next pass; the records themselves exist one piece at a time (d_rec_piece: two buffers of rec_piece_cap records) */
     DevBuf<u16> d_rec_efile, d_rec_subs;
@@ -390,9 +421,8 @@ struct disco_ctx {
     bool rec_c_ready = false, rec_c_has_findex = false;
     u32 rec_e_files = 0, rec_c_files = 0;
     u64 rec_c_n = 0;
-    DevBuf<u64> d_rec_piece[2];
+    DevBuf<u8> d_rec_piece[2];
     u64 rec_piece = 0; /* records per piece; 0: what a ring half holds (disco_set_record_piece: tests) */
-    u64 text_bytes = 0;
     DevBuf<u64> d_out_src, d_out_ent; /* (grow together) */
     u64 out_used = 0; /* chunk slots written by the emission (survivors + ~0 tails) */
     bool out_dense = false; /* the last emission wrote no tails: slot i is edge i, out_used == n_out, d_out_valid / d_out_pos are not there */
@@ -573,12 +603,11 @@ static int ensure_group(disco_ctx *c, u64 need, u64 size, DevBuf<T> &...b)
 template <typename T>
 static int move_keep(disco_ctx *c, DevBuf<T> &b, u64 ncap, u64 used)
 {
-    DevBuf<T> q;
+    LocalBuf<T> q(c);
     CHK(ensure(c, q, ncap));
     if (b.p && used) HIPCHK(c, hipMemcpyAsync(q.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    release(c, b);
-    b = q;
+    q.give(b);
     return DISCO_OK;
 }
 
@@ -824,14 +853,14 @@ static void free_graph_state(disco_ctx *c)
     release(c, c->d_ch_res_pos);
     release(c, c->d_ch_res_slot);
     c->ch_res_n = 0;
-    release(c, c->d_ptext);
-    c->ptext_bytes = 0;
-    c->ptext_off.clear();
-    release(c, c->d_text);
-    c->text_bytes = 0;
-    release(c, c->d_ctext);
-    c->ctext_bytes = 0;
-    c->ctext_off.clear();
+    release(c, c->ptext.d);
+    c->ptext.bytes = 0;
+    c->ptext.off.clear();
+    release(c, c->text.d);
+    c->text.bytes = 0;
+    release(c, c->ctext.d);
+    c->ctext.bytes = 0;
+    c->ctext.off.clear();
     c->ch_ready = false;
     release(c, c->d_out_pos);
     release(c, c->d_out_src);
@@ -1592,7 +1621,7 @@ static int tr_big_nodes(disco_ctx *c, TrArgs *a, u32 n_big, bool defer, const ch
     while (hcap < 2 * maxd) hcap <<= 1;
     const int g2 = (int)std::min<u64>(n_big, (u64)c->n_cu * 8);
     const u64 per = hcap * 8 + hcap * 4 + hcap;
-    DevBuf<u8> scratch;
+    LocalBuf<u8> scratch(c);
     CHK(ensure(c, scratch, (u64)g2 * per));
     a->scratch = (u64 *)scratch.p;
     a->hcap = hcap;
@@ -1600,8 +1629,7 @@ static int tr_big_nodes(disco_ctx *c, TrArgs *a, u32 n_big, bool defer, const ch
     HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
     hipLaunchKernelGGL(tr_pick(true, defer, false, false), dim3(g2), dim3(64), 0, c->stream, *a);
     const hipError_t e = hipGetLastError();
-    const int rc = read_counters(c); /* synchronises; the scratch goes back before anything is reported */
-    release(c, scratch);
+    const int rc = read_counters(c); /* synchronises before the scratch goes back */
     if (e != hipSuccess) return fail(c, DISCO_E_HIP, "transitive_mark_kernel (%s): %s", what, hipGetErrorString(e));
     return rc;
 }
@@ -1890,11 +1918,11 @@ static void drop_reads(disco_ctx *c) { (void)set_reads_common(c, 0, VERIFY_SW, n
  * survives the release of the graph state of a read set of another shape */
 static int begin_rows(disco_ctx *c, u64 n, u64 n_alloc, u64 extra_rows, uint32_t stride, bool may_keep, bool spare_hits = false)
 {
-    DevBuf<u64> hits;
+    LocalBuf<u64> hits(c);
     bool kept = false;
-    if (spare_hits) std::swap(hits, c->d_hits);
+    if (spare_hits) hits.take(c->d_hits);
     const int rc = set_reads_common(c, n, stride, may_keep ? &kept : nullptr);
-    if (spare_hits) std::swap(hits, c->d_hits);
+    if (spare_hits) hits.give(c->d_hits);
     CHK(rc);
     c->reads_owned = true; /* whatever is allocated from here on is released by free_reads */
     c->n_alloc = n_alloc;
@@ -1996,8 +2024,8 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
         for (u64 k = 0; k < n_chunks; k++)
             ring_words = std::max<u64>(ring_words, ragged ? chunk_words[k + 1] - chunk_words[k] : (std::min<u64>(n, (k + 1) * CH) - k * CH) * (u64)stride_words);
         if (!direct) CHK(ensure(c, c->d_dense, 3 * ring_words));
-        DevBuf<u64> woff;
-        DevBuf<u32> nw;
+        LocalBuf<u64> woff(c);
+        LocalBuf<u32> nw(c);
         if (ragged) { /* word offset of every read: scan of ceil(len / 32) */
             CHK(ensure(c, woff, n));
             CHK(ensure(c, nw, n));
@@ -2048,11 +2076,7 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
         if (getenv("DISCO_VERBOSE"))
             fprintf(stderr, "[disco] %s: lengths checked %.1f ms, buffers %.1f, chunks issued %.1f, lengths mirrored %.1f, copies done %.1f (%s%s)\n", who, t_scan, t_alloc, t_issued,
                     t_mirror, lapms(), classes ? "two classes of rows" : "one stride", eager ? ", index counted behind the copies" : "");
-        if (woff) { /* (read by the unpack kernels on the context's stream) */
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            release(c, woff);
-            release(c, nw);
-        }
+        if (woff) HIPCHK(c, hipStreamSynchronize(c->stream)); /* (read by the unpack kernels on the context's stream; it goes with this block) */
         c->index_counted = eager;
     } else
         c->h_len.clear();
@@ -2144,23 +2168,29 @@ static unsigned ring_alloc_flags()
     return mode == 1 ? hipHostMallocNonCoherent : (mode == 2 ? hipHostMallocCoherent : hipHostMallocDefault);
 }
 
-/* the pinned ring, its events and the copy stream (first use). Measured, round 5: calls into the runtime from this thread — this
+/* the context's pinned ring and its two events (first use), for what enters the device (ingest_ring: with the copy stream) and for
+ * what leaves it (RingSink). Measured, round 5: calls into the runtime from this thread — this
  * allocation, every hipMemcpyAsync of the reader — can wait behind the helper thread's hipMalloc of the 28 GB hit buffer; that is the
  * stage's "slow mode" (files into HBM 0.2 s or, in bursts, 0.6-1.8 s with the reader's own waits unchanged). Making the ring first moves
  * the overlap onto the filter kernels instead (0.12 -> 0.18 s): no gain, not kept. */
-static int ingest_ring(disco_ctx *c)
+static const size_t RING_HALF = 128u << 20;
+static int pinned_ring(disco_ctx *c, const char *who)
 {
-    const size_t HALF = 128u << 20;
     CHK(ring_back_from_rows(c));
     if (!c->h_ring) {
-        if (hipHostMalloc(&c->h_ring, 2 * HALF, ring_alloc_flags()) != hipSuccess) {
+        if (hipHostMalloc(&c->h_ring, 2 * RING_HALF, ring_alloc_flags()) != hipSuccess) {
             c->h_ring = nullptr;
             (void)hipGetLastError();
-            return fail(c, DISCO_E_NOMEM, "disco_ingest_fasta: no pinned staging memory");
+            return fail(c, DISCO_E_NOMEM, "%s: no pinned staging memory", who);
         }
-        c->ring_half = HALF;
+        c->ring_half = RING_HALF;
         for (int i = 0; i < 2; i++) HIPCHK(c, hipEventCreateWithFlags(&c->ev_ring[i], hipEventDisableTiming));
     }
+    return DISCO_OK;
+}
+static int ingest_ring(disco_ctx *c)
+{
+    CHK(pinned_ring(c, "disco_ingest_fasta"));
     return ensure_copy_stream(c);
 }
 
@@ -2309,26 +2339,17 @@ extern "C" int64_t disco_inflate_bgzf(disco_ctx *c, const void *bgzf, uint64_t n
     if (!out) return (int64_t)total;
     if (cap < total) return fail(c, DISCO_E_CAPACITY, "disco_inflate_bgzf: %llu bytes of text, room for %llu", (unsigned long long)total, (unsigned long long)cap);
     HIPCHK(c, hipSetDevice(c->device));
-    DevBuf<u8> d_comp, d_text;
-    DevBuf<infl::BgzfBlock> d_blk;
-    DevBuf<u32> d_status;
+    LocalBuf<u8> d_comp(c), d_text(c);
+    LocalBuf<infl::BgzfBlock> d_blk(c);
+    LocalBuf<u32> d_status(c);
     int e = infl::INFL_OK;
-    auto body = [&]() -> int {
-        CHK(ensure(c, d_comp, n_bytes));
-        CHK(ensure(c, d_text, total));
-        CHK(ensure(c, d_blk, blocks.size()));
-        CHK(ensure(c, d_status, blocks.size() + 1));
-        HIPCHK(c, hipMemcpyAsync(d_comp.p, bgzf, n_bytes, hipMemcpyHostToDevice, c->stream));
-        CHK(bgzf_inflate_run(c, d_comp, blocks.data(), blocks.size(), d_blk, d_status, d_text, 0, total, &bad, &e));
-        if (e == infl::INFL_OK && total) HIPCHK(c, hipMemcpy(out, d_text.p, total, hipMemcpyDeviceToHost));
-        return DISCO_OK;
-    };
-    const int rc = body();
-    release(c, d_comp);
-    release(c, d_text);
-    release(c, d_blk);
-    release(c, d_status);
-    CHK(rc);
+    CHK(ensure(c, d_comp, n_bytes));
+    CHK(ensure(c, d_text, total));
+    CHK(ensure(c, d_blk, blocks.size()));
+    CHK(ensure(c, d_status, blocks.size() + 1));
+    HIPCHK(c, hipMemcpyAsync(d_comp.p, bgzf, n_bytes, hipMemcpyHostToDevice, c->stream));
+    CHK(bgzf_inflate_run(c, d_comp, blocks.data(), blocks.size(), d_blk, d_status, d_text, 0, total, &bad, &e));
+    if (e == infl::INFL_OK && total) HIPCHK(c, hipMemcpy(out, d_text.p, total, hipMemcpyDeviceToHost));
     if (e != infl::INFL_OK) return fail(c, DISCO_E_UNSUPPORTED, "disco_inflate_bgzf: member %llu: %s", (unsigned long long)bad, infl::reason(e));
     return (int64_t)total;
 }
@@ -2346,26 +2367,17 @@ extern "C" int64_t disco_inflate_bgzf_window(disco_ctx *c, const void *bgzf, uin
     infl::bgzf_window_members(blocks, text_lo, n, &first, &count);
     infl::bgzf_rebase(blocks, first, count, sub, &comp_lo, &comp_n);
     HIPCHK(c, hipSetDevice(c->device));
-    DevBuf<u8> d_comp, d_text;
-    DevBuf<infl::BgzfBlock> d_blk;
-    DevBuf<u32> d_status;
+    LocalBuf<u8> d_comp(c), d_text(c);
+    LocalBuf<infl::BgzfBlock> d_blk(c);
+    LocalBuf<u32> d_status(c);
     int e = infl::INFL_OK;
-    auto body = [&]() -> int {
-        CHK(ensure(c, d_comp, comp_n));
-        CHK(ensure(c, d_text, n));
-        CHK(ensure(c, d_blk, sub.size()));
-        CHK(ensure(c, d_status, sub.size() + 1));
-        HIPCHK(c, hipMemcpyAsync(d_comp.p, (const u8 *)bgzf + comp_lo, comp_n, hipMemcpyHostToDevice, c->stream));
-        CHK(bgzf_inflate_run(c, d_comp, sub.data(), sub.size(), d_blk, d_status, d_text, text_lo, n, &bad, &e));
-        if (e == infl::INFL_OK) HIPCHK(c, hipMemcpy(out, d_text.p, n, hipMemcpyDeviceToHost));
-        return DISCO_OK;
-    };
-    const int rc = body();
-    release(c, d_comp);
-    release(c, d_text);
-    release(c, d_blk);
-    release(c, d_status);
-    CHK(rc);
+    CHK(ensure(c, d_comp, comp_n));
+    CHK(ensure(c, d_text, n));
+    CHK(ensure(c, d_blk, sub.size()));
+    CHK(ensure(c, d_status, sub.size() + 1));
+    HIPCHK(c, hipMemcpyAsync(d_comp.p, (const u8 *)bgzf + comp_lo, comp_n, hipMemcpyHostToDevice, c->stream));
+    CHK(bgzf_inflate_run(c, d_comp, sub.data(), sub.size(), d_blk, d_status, d_text, text_lo, n, &bad, &e));
+    if (e == infl::INFL_OK) HIPCHK(c, hipMemcpy(out, d_text.p, n, hipMemcpyDeviceToHost));
     if (e != infl::INFL_OK) return fail(c, DISCO_E_UNSUPPORTED, "disco_inflate_bgzf_window: member %llu: %s", (unsigned long long)(first + bad), infl::reason(e));
     return (int64_t)n;
 }
@@ -2981,7 +2993,7 @@ int disco_download_reads(disco_ctx *c, uint64_t *packed, uint16_t *len)
 {
     if (!c || c->phase < 1) return c ? fail(c, DISCO_E_STATE, "no reads") : DISCO_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    DevBuf<u64> joined;
+    LocalBuf<u64> joined(c);
     if (packed && c->n && c->two_class) { /* the table as the caller knows it: one stride */
         CHK(ensure(c, joined, c->n * (u64)c->S_ext));
         hipLaunchKernelGGL(class_join_kernel, dim3(flat_grid(c, c->n * (u64)c->S_ext)), dim3(256), 0, c->stream, (const u64 *)c->d_reads, (const u64 *)c->d_full, c->S_ext,
@@ -2991,7 +3003,6 @@ int disco_download_reads(disco_ctx *c, uint64_t *packed, uint16_t *len)
         HIPCHK(c, hipMemcpyAsync(packed, c->d_reads, c->n * (u64)c->S * 8, hipMemcpyDeviceToHost, c->stream));
     if (len && c->n) (void)hipMemcpyAsync(len, c->d_len, c->n * 2, hipMemcpyDeviceToHost, c->stream);
     const hipError_t e = hipStreamSynchronize(c->stream);
-    release(c, joined);
     if (e != hipSuccess) return fail(c, DISCO_E_HIP, "disco_download_reads: %s", hipGetErrorString(e));
     return DISCO_OK;
 }
@@ -3018,32 +3029,27 @@ static int two_class_convert(disco_ctx *c)
 {
     if (c->two_class || !c->n || c->max_len <= (u32)DISCO_SHORT_MAX || !two_class_ok(c, c->S, c->n, 1, (u32)c->k + 1)) return DISCO_OK; /* (cheap part first) */
     const int Sx = c->S;
-    DevBuf<u32> ovf;
+    LocalBuf<u32> ovf(c);
     CHK(ensure(c, ovf, c->n_alloc));
     CHK(zero_counter(c, CTR_SHORT_MAX));
     u64 n_long = 0;
     CHK(number_long_reads(c, ovf, nullptr, &n_long)); /* (class_split_kernel writes the ids) */
     CHK(read_counters(c));
     const u32 short_max = (u32)c->h_ctr[CTR_SHORT_MAX];
-    if (!two_class_ok(c, Sx, c->n, n_long, short_max)) {
-        release(c, ovf);
-        return DISCO_OK;
-    }
-    DevBuf<u64> rows8;
-    c->d_ovf = ovf; /* (the context's from here on: released with the long class, also when something below fails) */
+    if (!two_class_ok(c, Sx, c->n, n_long, short_max)) return DISCO_OK;
+    LocalBuf<u64> rows8(c);
+    ovf.give(c->d_ovf); /* (the context's from here on: released with the long class, also when something below fails) */
     int rca = ensure(c, rows8, (c->n + n_long) * 8);
     if (rca == DISCO_OK) rca = two_class_alloc(c, n_long, Sx, short_max);
     if (rca != DISCO_OK) { /* the table keeps its one stride */
-        release(c, rows8);
         free_long_class(c);
         return rca;
     }
-    hipLaunchKernelGGL(class_split_kernel, dim3(flat_grid(c, c->n * 8)), dim3(256), 0, c->stream, (const u64 *)c->reads_own, Sx, (const u16 *)c->d_len, (const u32 *)ovf, c->n, c->tailb,
+    hipLaunchKernelGGL(class_split_kernel, dim3(flat_grid(c, c->n * 8)), dim3(256), 0, c->stream, (const u64 *)c->reads_own, Sx, (const u16 *)c->d_len, (const u32 *)c->d_ovf, c->n, c->tailb,
                        rows8.p, c->d_full, c->d_long_ids);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream)); /* (the old table goes back: nothing of it may still be in flight) */
-    release(c, c->reads_own);
-    c->reads_own = rows8;
+    rows8.give(c->reads_own);
     c->d_reads = c->reads_own;
     set_read_lengths(c, c->max_len, short_max, c->min_len);
     return DISCO_OK;
@@ -3439,15 +3445,14 @@ static int select_edges(disco_ctx *c)
     if (n_big && c->h_ctr[CTR_MAX_ROW] > ES_MID) {
         int g2 = (int)std::min<u64>(n_big, (u64)c->n_cu * 8); /* work queue, one big row per grab */
         u64 cap = c->h_ctr[CTR_MAX_ROW] + 64;
-        DevBuf<u64> scratch;
+        LocalBuf<u64> scratch(c);
         CHK(ensure(c, scratch, (u64)g2 * 2 * cap));
         a.scratch = scratch;
         a.scratch_cap = cap;
         HIPCHK(c, hipMemsetAsync(c->d_wq, 0, sizeof(u64) * WQ_WORDS, c->stream));
         hipLaunchKernelGGL(edge_select_pick(true, false, false), dim3(g2), dim3(64), 0, c->stream, a);
         hipError_t e = hipGetLastError();
-        int rc = read_counters(c);
-        release(c, scratch);
+        int rc = read_counters(c); /* synchronises before the scratch goes back */
         if (e != hipSuccess) return fail(c, DISCO_E_HIP, "edge_select_kernel (big rows): %s", hipGetErrorString(e));
         CHK(rc);
     }
@@ -3621,46 +3626,35 @@ static int merge_extras(disco_ctx *c)
             return DISCO_OK;
         }
     }
-    DevBuf<u32> new_deg;
-    DevBuf<u64> new_start, new_adj, scratch;
+    LocalBuf<u32> new_deg(c);
+    LocalBuf<u64> new_start(c), new_adj(c), scratch(c);
     u64 total = 0;
-    auto body = [&]() -> int {
-        CHK(ensure(c, new_deg, c->n));
-        CHK(ensure(c, new_start, c->n + 1));
-        hipLaunchKernelGGL(merge_deg_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_adj_ref, c->d_extra_cnt, c->n, new_deg);
-        CHK((scan_exclusive<u32, u64>(c, new_deg, c->n, new_start, true, &total)));
-        if (c->d_adj_spare.cap >= total && c->d_adj_spare) { /* the buffer the previous pass's merge left behind */
-            new_adj = c->d_adj_spare;
-            c->d_adj_spare = DevBuf<u64>();
-        } else
-            CHK(ensure(c, new_adj, total + total / 16));
-        hipLaunchKernelGGL(merge_scatter_kernel, dim3(flat_grid(c, c->n_extra)), dim3(256), 0, c->stream, c->d_extra_node, c->d_extra_key, c->n_extra, c->d_adj_ref, new_start, new_adj);
-        /* row scratch: the longest merged row (reduced on the device) */
-        CHK(zero_counter(c, CTR_MAX_DEG));
-        hipLaunchKernelGGL(max_u32_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, new_deg, c->n, c->d_ctr + CTR_MAX_DEG);
-        HIPCHK(c, hipGetLastError());
-        CHK(read_counters(c));
-        const u64 maxdeg = c->h_ctr[CTR_MAX_DEG];
-        const int g = (int)std::min<u64>(c->n, (u64)c->n_cu * 32); /* one wavefront per row at a time */
-        CHK(ensure(c, scratch, (u64)g * (maxdeg + 1)));
-        hipLaunchKernelGGL(merge_rows_kernel, dim3(g), dim3(64), 0, c->stream, c->d_adj_ref, c->d_adj, c->d_extra_cnt, new_start, new_adj, c->n, scratch, maxdeg + 1);
-        hipLaunchKernelGGL(ref_from_start_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, new_start, new_deg, c->n, c->d_adj_ref);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return DISCO_OK;
-    };
-    const int rc = body();
-    release(c, scratch);
-    release(c, new_deg);
-    release(c, new_start);
-    if (rc != DISCO_OK) {
-        release(c, new_adj);
-        return rc;
-    }
+    CHK(ensure(c, new_deg, c->n));
+    CHK(ensure(c, new_start, c->n + 1));
+    hipLaunchKernelGGL(merge_deg_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_adj_ref, c->d_extra_cnt, c->n, new_deg);
+    CHK((scan_exclusive<u32, u64>(c, new_deg, c->n, new_start, true, &total)));
+    if (c->d_adj_spare.cap >= total && c->d_adj_spare) /* the buffer the previous pass's merge left behind */
+        new_adj.take(c->d_adj_spare);
+    else
+        CHK(ensure(c, new_adj, total + total / 16));
+    hipLaunchKernelGGL(merge_scatter_kernel, dim3(flat_grid(c, c->n_extra)), dim3(256), 0, c->stream, c->d_extra_node, c->d_extra_key, c->n_extra, c->d_adj_ref, new_start, new_adj);
+    /* row scratch: the longest merged row (reduced on the device) */
+    CHK(zero_counter(c, CTR_MAX_DEG));
+    hipLaunchKernelGGL(max_u32_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, new_deg, c->n, c->d_ctr + CTR_MAX_DEG);
+    HIPCHK(c, hipGetLastError());
+    CHK(read_counters(c));
+    const u64 maxdeg = c->h_ctr[CTR_MAX_DEG];
+    const int g = (int)std::min<u64>(c->n, (u64)c->n_cu * 32); /* one wavefront per row at a time */
+    CHK(ensure(c, scratch, (u64)g * (maxdeg + 1)));
+    hipLaunchKernelGGL(merge_rows_kernel, dim3(g), dim3(64), 0, c->stream, c->d_adj_ref, c->d_adj, c->d_extra_cnt, new_start, new_adj, c->n, scratch, maxdeg + 1);
+    hipLaunchKernelGGL(ref_from_start_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, new_start, new_deg, c->n, c->d_adj_ref);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     /* the rows move to new_adj; what held the imported / merged rows so far waits for the next pass's merge */
     release(c, c->d_adj_spare);
     c->d_adj_spare = c->d_adj_own;
-    c->d_adj_own = new_adj;
+    c->d_adj_own = DevBuf<u64>();
+    new_adj.give(c->d_adj_own);
     c->d_adj = c->d_adj_own;
     c->adj_total = total;
     c->adj_span = total; /* compact, node ordered */
@@ -4036,24 +4030,16 @@ int64_t disco_fetch_contained(disco_ctx *c, disco_contained_row *out, uint64_t c
     }
     CHK(ensure_host_len(c));
     CHK(settle_keys(c));
-    DevBuf<u64> pos, ids, keys;
+    LocalBuf<u64> pos(c), ids(c), keys(c);
     std::vector<u64> hid(nc), hkey(nc);
-    auto gather = [&]() -> int {
-        CHK(ensure(c, pos, c->n + 1));
-        CHK(ensure(c, ids, nc));
-        CHK(ensure(c, keys, nc));
-        CHK((scan_exclusive<u8, u64>(c, c->d_contained, c->n, pos, false, nullptr)));
-        hipLaunchKernelGGL(contain_rows_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_best, c->d_contained, pos, c->n, ids, keys);
-        HIPCHK(c, hipMemcpyAsync(hid.data(), ids, nc * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(hkey.data(), keys, nc * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return DISCO_OK;
-    };
-    const int grc = gather();
-    release(c, pos);
-    release(c, ids);
-    release(c, keys);
-    CHK(grc);
+    CHK(ensure(c, pos, c->n + 1));
+    CHK(ensure(c, ids, nc));
+    CHK(ensure(c, keys, nc));
+    CHK((scan_exclusive<u8, u64>(c, c->d_contained, c->n, pos, false, nullptr)));
+    hipLaunchKernelGGL(contain_rows_kernel, dim3(flat_grid(c, c->n)), dim3(256), 0, c->stream, c->d_best, c->d_contained, pos, c->n, ids, keys);
+    HIPCHK(c, hipMemcpyAsync(hid.data(), ids, nc * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hkey.data(), keys, nc * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     for (u64 i = 0; i < nc; i++) /* (a key that names no read must not index the length table: fail loudly) */
         if (CKEY_SUPER(hkey[i]) >= c->n || hid[i] >= c->n)
             return fail(c, DISCO_E_STATE, "disco_fetch_contained: row %llu of %llu: read %llu has the key %llx (no containing read)", (unsigned long long)i, (unsigned long long)nc,
@@ -4191,14 +4177,12 @@ int64_t disco_fetch_edge_substitutions(disco_ctx *c, uint16_t *out, uint64_t cap
         memset(out, 0, ne * sizeof(uint16_t));
         return (int64_t)ne;
     }
-    DevBuf<u16> subs;
+    LocalBuf<u16> subs(c);
     CHK(ensure(c, subs, ne));
     hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c),
                        c->out_used, c->d_reads, c->d_len, c->S, subs);
-    hipError_t e1 = hipMemcpyAsync(out, subs, ne * sizeof(u16), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e2 = hipStreamSynchronize(c->stream);
-    release(c, subs);
-    if (e1 != hipSuccess || e2 != hipSuccess) return fail(c, DISCO_E_HIP, "disco_fetch_edge_substitutions: copy failed");
+    if (hipMemcpyAsync(out, subs, ne * sizeof(u16), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(c, DISCO_E_HIP, "disco_fetch_edge_substitutions: copy failed");
     return (int64_t)ne;
 }
 
@@ -4213,37 +4197,20 @@ static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent,
                                uint32_t n_files, uint16_t *out, u16 *d_out = nullptr)
 {
     DISCO_TRACE("partition_edges");
-    DevBuf<u32> parent, cnt, d_nlist;
-    DevBuf<u16> cfile, efile;
-    DevBuf<u64> list;
+    LocalBuf<u32> parent(c), cnt(c), d_nlist(c);
+    LocalBuf<u16> cfile(c), efile(c);
+    LocalBuf<u64> list(c);
     /* components of at least 1/(64 files) of the edges are dealt out by size, largest first to the lightest file; the rest
      * (there can be millions of small ones) go by hash. ALL of the former: the list holds as many as there can be — min(n, ne / thr),
      * and ne / thr < 128 files — so that which of them are dealt out by size is never a matter of who arrived first */
     const u32 thr = (u32)std::max<u64>(ne / ((u64)n_files * 64), 1);
     const u32 list_cap = (u32)std::max<u64>(std::min<u64>(n, ne / thr), 1);
-    int rc = DISCO_OK;
-    auto cleanup = [&]() {
-        release(c, parent);
-        release(c, cnt);
-        release(c, cfile);
-        release(c, efile);
-        release(c, list);
-        release(c, d_nlist);
-    };
-#define PART_CHK(x)            \
-    do {                       \
-        rc = (x);              \
-        if (rc != DISCO_OK) {  \
-            cleanup();         \
-            return rc;         \
-        }                      \
-    } while (0)
-    PART_CHK(ensure(c, parent, n));
-    PART_CHK(ensure(c, cnt, n));
-    PART_CHK(ensure(c, cfile, n));
-    if (!d_out) PART_CHK(ensure(c, efile, ne));
-    PART_CHK(ensure(c, list, list_cap));
-    PART_CHK(ensure(c, d_nlist, 1));
+    CHK(ensure(c, parent, n));
+    CHK(ensure(c, cnt, n));
+    CHK(ensure(c, cfile, n));
+    if (!d_out) CHK(ensure(c, efile, ne));
+    CHK(ensure(c, list, list_cap));
+    CHK(ensure(c, d_nlist, 1));
     hipLaunchKernelGGL(uf_init_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, parent, n);
     hipLaunchKernelGGL(uf_hook_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, d_src, d_ent, d_valid, n_slots, parent);
     hipLaunchKernelGGL(uf_compress_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, parent, n);
@@ -4253,20 +4220,14 @@ static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent,
     hipLaunchKernelGGL(uf_count_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, d_src, d_valid, n_slots, parent, cnt);
     hipLaunchKernelGGL(uf_big_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, cnt, n, thr, list, d_nlist, list_cap);
     u32 n_list = 0;
-    if (hipMemcpyAsync(&n_list, d_nlist, sizeof(u32), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-        cleanup();
+    if (hipMemcpyAsync(&n_list, d_nlist, sizeof(u32), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
         return fail(c, DISCO_E_HIP, "edge partition: %s", hipGetErrorString(hipGetLastError()));
-    }
-    if (n_list > list_cap) { /* cannot happen (see list_cap); a clipped list would cut files that depend on the order of arrival */
-        cleanup();
+    if (n_list > list_cap) /* cannot happen (see list_cap); a clipped list would cut files that depend on the order of arrival */
         return fail(c, DISCO_E_CAPACITY, "edge partition: %u components of at least %u edges, room for %u", n_list, thr, list_cap);
-    }
     std::vector<u64> hl(n_list);
     if (n_list && (hipMemcpyAsync(hl.data(), list, n_list * sizeof(u64), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                   hipStreamSynchronize(c->stream) != hipSuccess)) {
-        cleanup();
+                   hipStreamSynchronize(c->stream) != hipSuccess))
         return fail(c, DISCO_E_HIP, "edge partition: %s", hipGetErrorString(hipGetLastError()));
-    }
     std::sort(hl.begin(), hl.end(), [](u64 a, u64 b) { return (u32)a != (u32)b ? (u32)a > (u32)b : a < b; }); /* by size, then root: deterministic */
     /* the lightest file, the lowest index among equals: a heap of (load, file) — the list can hold 128 entries per file */
     typedef std::pair<u64, u32> LoadOfFile;
@@ -4279,18 +4240,12 @@ static int64_t partition_edges(disco_ctx *c, const u64 *d_src, const u64 *d_ent,
         e = (e & 0xFFFFFFFF00000000ull) | t.second;
     }
     if (n_list) {
-        if (hipMemcpyAsync(list, hl.data(), n_list * sizeof(u64), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-            cleanup();
-            return fail(c, DISCO_E_HIP, "edge partition: upload failed");
-        }
+        if (hipMemcpyAsync(list, hl.data(), n_list * sizeof(u64), hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(c, DISCO_E_HIP, "edge partition: upload failed");
         hipLaunchKernelGGL(uf_assign_kernel, dim3((n_list + 255) / 256), dim3(256), 0, c->stream, list, n_list, cfile);
     }
     hipLaunchKernelGGL(uf_edge_file_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, d_src, d_valid, d_pos, n_slots, parent, cfile, n_files, d_out ? d_out : efile.p);
-    hipError_t e1 = d_out ? hipGetLastError() : hipMemcpyAsync(out, efile, ne * sizeof(u16), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e2 = hipStreamSynchronize(c->stream);
-    cleanup();
-#undef PART_CHK
-    if (e1 != hipSuccess || e2 != hipSuccess) return fail(c, DISCO_E_HIP, "edge partition: copy failed");
+    if ((d_out ? hipGetLastError() : hipMemcpyAsync(out, efile, ne * sizeof(u16), hipMemcpyDeviceToHost, c->stream)) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(c, DISCO_E_HIP, "edge partition: copy failed");
     return (int64_t)ne;
 }
 
@@ -4316,8 +4271,8 @@ int64_t disco_partition_edges(disco_ctx *c, const disco_edge *edges, uint64_t n_
     if (n_nodes >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_partition_edges: more than 2^31 nodes");
     HIPCHK(c, hipSetDevice(c->device));
     if (n_edges == 0) return 0;
-    DevBuf<u64> d_src, d_ent, d_pos;
-    DevBuf<u8> d_valid;
+    LocalBuf<u64> d_src(c), d_ent(c), d_pos(c);
+    LocalBuf<u8> d_valid(c);
     std::unique_ptr<u64[]> hs(new u64[n_edges]), he(new u64[n_edges]);
     parallel_for(n_edges, [&](u64 b, u64 e_) {
         for (u64 i = b; i < e_; i++) {
@@ -4325,30 +4280,39 @@ int64_t disco_partition_edges(disco_ctx *c, const disco_edge *edges, uint64_t n_
             he[i] = ADJ_MAKE(0u, edges[i].dst, 0u, 0u);
         }
     });
-    int rc = DISCO_OK;
-    int64_t res = 0;
-    do {
-        if ((rc = ensure(c, d_src, n_edges)) != DISCO_OK) break;
-        if ((rc = ensure(c, d_ent, n_edges)) != DISCO_OK) break;
-        if ((rc = ensure(c, d_pos, n_edges)) != DISCO_OK) break;
-        if ((rc = ensure(c, d_valid, n_edges)) != DISCO_OK) break;
-        if (hipMemcpyAsync(d_src, hs.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(d_ent, he.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemsetAsync(d_valid, 1, n_edges, c->stream) != hipSuccess) {
-            rc = fail(c, DISCO_E_HIP, "disco_partition_edges: upload failed");
-            break;
-        }
-        hipLaunchKernelGGL(iota_u64_kernel, dim3(flat_grid(c, n_edges)), dim3(256), 0, c->stream, d_pos, n_edges);
-        res = partition_edges(c, d_src, d_ent, d_valid, d_pos, n_edges, n_edges, n_nodes, n_files, out);
-    } while (0);
-    release(c, d_src);
-    release(c, d_ent);
-    release(c, d_pos);
-    release(c, d_valid);
-    return rc != DISCO_OK ? rc : res;
+    CHK(ensure(c, d_src, n_edges));
+    CHK(ensure(c, d_ent, n_edges));
+    CHK(ensure(c, d_pos, n_edges));
+    CHK(ensure(c, d_valid, n_edges));
+    if (hipMemcpyAsync(d_src, hs.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(d_ent, he.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipMemsetAsync(d_valid, 1, n_edges, c->stream) != hipSuccess)
+        return fail(c, DISCO_E_HIP, "disco_partition_edges: upload failed");
+    hipLaunchKernelGGL(iota_u64_kernel, dim3(flat_grid(c, n_edges)), dim3(256), 0, c->stream, d_pos, n_edges);
+    return partition_edges(c, d_src, d_ent, d_valid, d_pos, n_edges, n_edges, n_nodes, n_files, out);
 }
 
 /* ---- the edge lines of the text files, formatted where the edges are (disco_text.h) ------------------------------------------ */
+/* every line measured (bytes[ne]), then the lines of the files [f_lo, f_hi) placed, file behind file: place[i] = where the line of edge i
+ * begins in the text, off[f] = where file f does (a file outside the range is empty), off[n_files] = all bytes. One GPU: every file; a
+ * rank of a multi-GPU job: its own. sel / within: scratch of ne and ne + 1 elements (not touched when the range is empty) */
+static int place_edge_lines(disco_ctx *c, const TextView &g, u64 ne, const u16 *efile, uint32_t n_files, uint32_t f_lo, uint32_t f_hi, u8 *bytes, u8 *sel, u64 *within, u64 *place,
+                            uint64_t *off)
+{
+    hipLaunchKernelGGL(text_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, bytes);
+    u64 base = 0;
+    for (uint32_t f = 0; f < n_files; f++) {
+        off[f] = base;
+        if (f < f_lo || f >= f_hi) continue;
+        u64 total = 0;
+        hipLaunchKernelGGL(text_select_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, (const u8 *)bytes, efile, ne, f, sel);
+        CHK((scan_exclusive<u8, u64>(c, sel, ne, within, false, &total)));
+        hipLaunchKernelGGL(text_place_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, (const u64 *)within, efile, ne, f, base, place);
+        base += total;
+    }
+    off[n_files] = base;
+    return DISCO_OK;
+}
+
 int64_t disco_format_edges(disco_ctx *c, uint32_t n_files, const uint16_t *edge_file, const uint64_t *file_index, uint64_t *file_offsets)
 {
     DISCO_TRACE("disco_format_edges");
@@ -4359,7 +4323,7 @@ int64_t disco_format_edges(disco_ctx *c, uint32_t n_files, const uint16_t *edge_
     HIPCHK(c, hipSetDevice(c->device));
     const u64 ne = c->n_out;
     for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
-    c->text_bytes = 0;
+    c->text.bytes = 0;
     if (ne == 0) return 0;
     if (!edge_file && n_files > 1) return fail(c, DISCO_E_ARG, "disco_format_edges: the file of every edge is needed for more than one file");
     TextView g;
@@ -4369,149 +4333,162 @@ int64_t disco_format_edges(disco_ctx *c, uint32_t n_files, const uint16_t *edge_
     g.pos = out_pos(c);
     g.len = c->d_len;
     g.n_slots = c->out_used;
-    DevBuf<u64> d_findex, within, place;
-    DevBuf<u8> bytes, sel;
-    DevBuf<u16> efile;
-    auto body = [&]() -> int {
-        if (file_index) {
-            CHK(ensure(c, d_findex, c->n));
-            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
-        }
-        g.file_index = d_findex;
-        CHK(ensure(c, bytes, ne));
-        CHK(ensure(c, sel, ne));
-        CHK(ensure(c, efile, ne));
-        CHK(ensure(c, within, ne + 1));
-        CHK(ensure(c, place, ne));
-        if (edge_file) HIPCHK(c, hipMemcpyAsync(efile, edge_file, ne * sizeof(u16), hipMemcpyHostToDevice, c->stream));
-        else HIPCHK(c, hipMemsetAsync(efile, 0, ne * sizeof(u16), c->stream));
-        hipLaunchKernelGGL(text_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, bytes);
-        u64 base = 0;
-        for (uint32_t f = 0; f < n_files; f++) {
-            u64 total = 0;
-            hipLaunchKernelGGL(text_select_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, bytes, efile, ne, f, sel);
-            CHK((scan_exclusive<u8, u64>(c, sel, ne, within, false, &total)));
-            hipLaunchKernelGGL(text_place_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, within, efile, ne, f, base, place);
-            file_offsets[f] = base;
-            base += total;
-        }
-        file_offsets[n_files] = base;
-        c->text_off.assign(file_offsets, file_offsets + n_files + 1);
-        CHK(ensure(c, c->d_text, std::max<u64>(base, 1)));
-        hipLaunchKernelGGL(text_write_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, place, c->d_text);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->text_bytes = base;
-        return DISCO_OK;
-    };
-    const int rc = body();
-    release(c, d_findex);
-    release(c, bytes);
-    release(c, sel);
-    release(c, efile);
-    release(c, within);
-    release(c, place);
-    return rc != DISCO_OK ? rc : (int64_t)c->text_bytes;
+    LocalBuf<u64> d_findex(c), within(c), place(c);
+    LocalBuf<u8> bytes(c), sel(c);
+    LocalBuf<u16> efile(c);
+    if (file_index) {
+        CHK(ensure(c, d_findex, c->n));
+        HIPCHK(c, hipMemcpyAsync(d_findex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    g.file_index = d_findex;
+    CHK(ensure(c, bytes, ne));
+    CHK(ensure(c, sel, ne));
+    CHK(ensure(c, efile, ne));
+    CHK(ensure(c, within, ne + 1));
+    CHK(ensure(c, place, ne));
+    if (edge_file) HIPCHK(c, hipMemcpyAsync(efile, edge_file, ne * sizeof(u16), hipMemcpyHostToDevice, c->stream));
+    else HIPCHK(c, hipMemsetAsync(efile, 0, ne * sizeof(u16), c->stream));
+    CHK(place_edge_lines(c, g, ne, efile, n_files, 0, n_files, bytes, sel, within, place, file_offsets));
+    const u64 base = file_offsets[n_files];
+    c->text.off.assign(file_offsets, file_offsets + n_files + 1);
+    CHK(ensure(c, c->text.d, std::max<u64>(base, 1)));
+    hipLaunchKernelGGL(text_write_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, place, c->text.d);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->text.bytes = base;
+    return (int64_t)c->text.bytes;
 }
 
-int disco_fetch_edge_text(disco_ctx *c, char *out, uint64_t cap)
+/* a text into the caller's memory */
+static int fetch_text(disco_ctx *c, const char *who, const TextProduct &t, char *out, uint64_t cap)
 {
-    if (!c || (!out && c->text_bytes)) return DISCO_E_ARG;
-    if (cap < c->text_bytes) return fail(c, DISCO_E_ARG, "disco_fetch_edge_text: need room for %llu bytes", (unsigned long long)c->text_bytes);
+    if (!out && t.bytes) return DISCO_E_ARG;
+    if (cap < t.bytes) return fail(c, DISCO_E_ARG, "%s: need room for %llu bytes", who, (unsigned long long)t.bytes);
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->text_bytes) {
-        HIPCHK(c, hipMemcpyAsync(out, c->d_text, c->text_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (t.bytes) {
+        HIPCHK(c, hipMemcpyAsync(out, t.d, t.bytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return DISCO_OK;
 }
 
-/* formatted lines straight into the caller's open files (fds[f] receives the bytes of file f, from its offset 0): the text
- * leaves the device in 128 MB pieces through the context's pinned ring, and while a piece travels host threads pwrite the one before
- * it — the mirror image of disco_ingest_fasta's file reader. (disco_fetch_edge_text into 2.5 GB of fresh pageable memory, then the
- * writer: 0.19 s at config 3; this: the link's 0.05 s.) d_text: the files' text one behind the other, off: n_files + 1 offsets into it */
-static const size_t OUT_RING_HALF = 128u << 20;
-/* the context's pinned ring for something that leaves the device (first use: allocated, with its two events) */
-static int output_ring(disco_ctx *c, const char *who)
-{
-    CHK(ring_back_from_rows(c));
-    if (!c->h_ring) {
-        if (hipHostMalloc(&c->h_ring, 2 * OUT_RING_HALF, ring_alloc_flags()) != hipSuccess) {
-            c->h_ring = nullptr;
-            (void)hipGetLastError();
-            return fail(c, DISCO_E_NOMEM, "%s: no pinned staging memory", who);
-        }
-        c->ring_half = OUT_RING_HALF;
-        for (int i = 0; i < 2; i++) HIPCHK(c, hipEventCreateWithFlags(&c->ev_ring[i], hipEventDisableTiming));
-    }
-    return DISCO_OK;
-}
+int disco_fetch_edge_text(disco_ctx *c, char *out, uint64_t cap) { return c ? fetch_text(c, "disco_fetch_edge_text", c->text, out, cap) : DISCO_E_ARG; }
 
-static int write_text_through_ring(disco_ctx *c, const char *who, const char *d_text, const std::vector<u64> &off, const int *fds, uint32_t n_files)
+/* Everything that leaves the device through the pinned ring: piece k is copied into half k & 1 of the ring and, while it travels, the
+ * host delivers piece k - 1 to where it belongs (disco_ringio.h) — the mirror image of disco_ingest_fasta's file reader. A piece is
+ * one or more parts, each with a place in the half and a destination; the two device buffers pieces are formed in are the sink's
+ * (home: the context keeps them between calls). Kernel and copy share the stream: 128 MB are formed in a fraction of a millisecond and
+ * travel for several, so there is nothing a second stream could hide (profiles/binary_records.txt). */
+struct RingPart {
+    const void *d_src; /* on the device */
+    size_t at, len;    /* [at, at + len) of the half */
+    int fd;            /* the file ... */
+    char *host;        /* ... or, not null, the caller's memory */
+    u64 off;           /* where the bytes belong there */
+};
+struct RingSink {
+    disco_ctx *const c;
+    const char *const who;
+    DevBuf<u8> *const home;
+    LocalBuf<u8> piece[2];
+    u64 issued = 0; /* pieces so far */
+    std::vector<ringio::Segment> pending; /* the piece before the current one lies in its half, not yet delivered */
+    unsigned pending_split = 0;
+    bool write_ok = true;
+
+    RingSink(disco_ctx *ctx, const char *w, DevBuf<u8> *keep = nullptr) : c(ctx), who(w), home(keep), piece{LocalBuf<u8>(ctx), LocalBuf<u8>(ctx)}
+    {
+        for (int i = 0; home && i < 2; i++) piece[i].take(home[i]);
+    }
+    ~RingSink()
+    {
+        for (int i = 0; home && i < 2; i++) piece[i].give(home[i]);
+    }
+    u8 *next() const { return piece[issued & 1].p; } /* where the next piece is formed */
+    void deliver()
+    {
+        bool ok = true;
+        if (pending_split) {
+            for (const ringio::Segment &s : pending) ok = ringio::deliver_split(s, pending_split) && ok;
+        } else
+            ok = ringio::deliver_each(pending.data(), pending.size());
+        pending.clear();
+        if (!ok) write_ok = false;
+    }
+    /* the next piece: its parts travel into their half while the host delivers the piece before — split: every part among that many
+     * writers (the bytes of ONE file); 0: one writer per part (writes to one file serialise on its inode lock — 16 threads on one
+     * file: 12 GB/s; one thread on each of 16 files: the link's rate) */
+    int ship(const RingPart *parts, size_t n, unsigned split)
+    {
+        const u64 k = issued & 1;
+        char *half = (char *)c->h_ring + k * c->ring_half;
+        for (size_t i = 0; i < n; i++)
+            if (parts[i].len) HIPCHK(c, hipMemcpyAsync(half + parts[i].at, parts[i].d_src, parts[i].len, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_ring[k], c->stream));
+        deliver(); /* (its copies were waited for below, one piece ago; the half it frees is written again two pieces on) */
+        HIPCHK(c, hipEventSynchronize(c->ev_ring[k]));
+        for (size_t i = 0; i < n; i++) {
+            ringio::Segment s;
+            s.src = half + parts[i].at;
+            s.len = parts[i].len;
+            s.fd = parts[i].fd;
+            s.host = parts[i].host;
+            s.off = parts[i].off;
+            pending.push_back(s);
+        }
+        pending_split = split;
+        issued++;
+        return DISCO_OK;
+    }
+    /* ... the piece of `bytes` bytes just launched into next() */
+    int ship_piece(u64 bytes, int fd, void *host, u64 off, unsigned split)
+    {
+        HIPCHK(c, hipGetLastError());
+        const RingPart p = {next(), 0, (size_t)bytes, fd, (char *)host, off};
+        return ship(&p, 1, split);
+    }
+    int flush()
+    {
+        deliver();
+        if (!write_ok) return fail(c, DISCO_E_ARG, "%s: write error", who);
+        return DISCO_OK;
+    }
+};
+
+/* formatted lines straight into the caller's open files (fds[f] receives the bytes of file f, from its offset 0), in rounds of up to
+ * 128 MB. (disco_fetch_edge_text into 2.5 GB of fresh pageable memory, then the writer: 0.19 s at config 3; this: the link's 0.05 s.)
+ * d_text: the files' text one behind the other, off: n_files + 1 offsets into it */
+static int write_text(disco_ctx *c, const char *who, const char *formatter, const TextProduct &t, const int *fds, uint32_t n_files)
 {
-    const size_t HALF = OUT_RING_HALF;
-    CHK(output_ring(c, who));
-    /* one writer per file and round: writes to ONE file serialise on its inode lock (16 threads on one file: 12 GB/s; one thread on each
-     * of 16 files: the link's rate) */
-    std::atomic<bool> ok{true};
+    if (!fds) return DISCO_E_ARG;
+    if (t.off.size() != (size_t)n_files + 1) return fail(c, DISCO_E_STATE, "%s: run %s for %u files first", who, formatter, n_files);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (t.bytes == 0) return DISCO_OK;
+    const char *d_text = t.d;
+    const std::vector<u64> &off = t.off;
+    CHK(pinned_ring(c, who));
     /* a round moves one slice of every file: slice r of file f = bytes [r S, (r + 1) S) of it, S = the ring half divided among the files */
-    const size_t S = (HALF / n_files) & ~(size_t)4095;
+    const size_t S = (RING_HALF / n_files) & ~(size_t)4095;
     if (S == 0) return fail(c, DISCO_E_UNSUPPORTED, "%s: too many files for the staging ring", who);
     u64 longest = 0;
     for (uint32_t f = 0; f < n_files; f++) longest = std::max(longest, off[f + 1] - off[f]);
     const u64 rounds = (longest + S - 1) / S;
-    auto slice = [&](uint32_t f, u64 r, u64 &lo, size_t &len) { /* file-local byte range of the slice */
-        const u64 fl = off[f + 1] - off[f];
-        lo = std::min<u64>(r * S, fl);
-        len = (size_t)(std::min<u64>((r + 1) * S, fl) - lo);
-    };
-    auto drain = [&](u64 r, const char *half) {
-        std::vector<std::thread> th;
-        for (uint32_t f = 0; f < n_files; f++) {
-            u64 lo;
-            size_t len;
-            slice(f, r, lo, len);
-            if (!len) continue;
-            th.emplace_back([&, f, lo, len]() {
-                size_t done = 0;
-                while (done < len) {
-                    const ssize_t w = pwrite(fds[f], half + (size_t)f * S + done, len - done, (off_t)(lo + done));
-                    if (w <= 0) {
-                        ok.store(false);
-                        return;
-                    }
-                    done += (size_t)w;
-                }
-            });
-        }
-        for (auto &x : th) x.join();
-    };
+    RingSink o(c, who);
+    std::vector<RingPart> parts(n_files);
     for (u64 r = 0; r < rounds; r++) {
-        char *half = (char *)c->h_ring + (r & 1) * HALF;
         for (uint32_t f = 0; f < n_files; f++) {
-            u64 lo;
-            size_t len;
-            slice(f, r, lo, len);
-            if (len) HIPCHK(c, hipMemcpyAsync(half + (size_t)f * S, d_text + off[f] + lo, len, hipMemcpyDeviceToHost, c->stream));
+            const u64 fl = off[f + 1] - off[f], lo = std::min<u64>(r * S, fl); /* file-local byte range of the slice */
+            parts[f] = {d_text + off[f] + lo, (size_t)f * S, (size_t)(std::min<u64>((r + 1) * S, fl) - lo), fds[f], nullptr, lo};
         }
-        HIPCHK(c, hipEventRecord(c->ev_ring[r & 1], c->stream));
-        if (r >= 1) drain(r - 1, (const char *)c->h_ring + ((r - 1) & 1) * HALF); /* (its copies were waited for below, one round ago) */
-        HIPCHK(c, hipEventSynchronize(c->ev_ring[r & 1]));
+        CHK(o.ship(parts.data(), n_files, 0));
     }
-    if (rounds) drain(rounds - 1, (const char *)c->h_ring + ((rounds - 1) & 1) * HALF);
-    if (!ok.load()) return fail(c, DISCO_E_ARG, "%s: write error", who);
-    return DISCO_OK;
+    return o.flush();
 }
 
-int disco_write_edge_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t host_threads)
+int disco_write_edge_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t)
 {
     DISCO_TRACE("disco_write_edge_text");
-    if (!c || !fds) return DISCO_E_ARG;
-    if (c->text_off.size() != (size_t)n_files + 1) return fail(c, DISCO_E_STATE, "disco_write_edge_text: run disco_format_edges for %u files first", n_files);
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)host_threads;
-    if (c->text_bytes == 0) return DISCO_OK;
-    return write_text_through_ring(c, "disco_write_edge_text", c->d_text, c->text_off, fds, n_files);
+    return c ? write_text(c, "disco_write_edge_text", "disco_format_edges", c->text, fds, n_files) : DISCO_E_ARG;
 }
 
 /* ---- the lines of the contained-read files, grouped, sorted and formatted where the keys are (disco_text.h) ------------------ */
@@ -4522,21 +4499,13 @@ int disco_write_edge_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32
  * the contained-read files, which the records of the binary side output (disco_prepare_contained_records) take too: afterwards row i is
  * word[i] (CWORD_MAKE: j, contained read, suffix, rev) under the containing read sup[i], ascending (containing read, j, contained read),
  * gend[s] the end of the group of read s, ctr the figures of the sorts and the count of keys that name no read. The launches are on
- * c->stream and not waited for; the caller releases the buffers. *nc: in — the number of rows where flags are given; out — the rows of
+ * c->stream and not waited for; the buffers go with G. *nc: in — the number of rows where flags are given; out — the rows of
  * the range where they are not (0: nothing was placed or sorted) */
 struct ContainedGroups {
-    DevBuf<u32> cnt, gend, sup, list, ctr;
-    DevBuf<u64> word;
+    LocalBuf<u32> cnt, gend, sup, list, ctr;
+    LocalBuf<u64> word;
+    explicit ContainedGroups(disco_ctx *c) : cnt(c), gend(c), sup(c), list(c), ctr(c), word(c) {}
 };
-static void release_groups(disco_ctx *c, ContainedGroups &G)
-{
-    release(c, G.cnt);
-    release(c, G.gend);
-    release(c, G.sup);
-    release(c, G.list);
-    release(c, G.ctr);
-    release(c, G.word);
-}
 static int group_contained_rows(disco_ctx *c, const u8 *flags, u64 s_lo, u64 s_hi, u64 *nc_io, ContainedGroups &G)
 {
     const u64 n = c->n;
@@ -4574,7 +4543,7 @@ static int group_contained_rows(disco_ctx *c, const u8 *flags, u64 s_lo, u64 s_h
     hipLaunchKernelGGL(cgrp_sort_lds_kernel, dim3(big_grid), dim3(CGRP_BLOCK), 0, c->stream, (const u32 *)gend, word.p, L);
     hipLaunchKernelGGL(cgrp_sort_global_kernel, dim3(big_grid), dim3(CGRP_BLOCK), 0, c->stream, (const u32 *)gend, word.p, L);
     HIPCHK(c, hipGetLastError());
-    release(c, cnt);
+    release(c, cnt); /* (only the grouping needed it: not held while the caller formats) */
     return DISCO_OK;
 }
 
@@ -4582,17 +4551,17 @@ static int64_t format_contained_rows(disco_ctx *c, const char *who, uint32_t n_f
                                      u64 s_hi, u64 nc)
 {
     const u64 n = c->n;
-    ContainedGroups G;
+    ContainedGroups G(c);
     DevBuf<u32> &gend = G.gend, &sup = G.sup, &ctr = G.ctr;
     DevBuf<u64> &word = G.word;
-    DevBuf<u64> place, d_findex, d_off;
-    DevBuf<u8> bytes;
+    LocalBuf<u64> place(c), d_findex(c), d_off(c);
+    LocalBuf<u8> bytes(c);
     u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
-    auto body = [&]() -> int {
-        /* 1., 2. grouped by containing read, every group in (j, contained read) order */
-        CHK(group_contained_rows(c, flags, s_lo, s_hi, &nc, G));
-        if (nc == 0) return DISCO_OK;
-        /* 3. measure -> scan -> write */
+    /* 1., 2. grouped by containing read, every group in (j, contained read) order */
+    CHK(group_contained_rows(c, flags, s_lo, s_hi, &nc, G));
+    if (nc) {
+        /* 3. measure -> scan -> write; the context's offsets (all 0 since the caller began) change only once the text is there */
+        std::vector<u64> off((size_t)n_files + 1, 0);
         CTextView g;
         g.word = word;
         g.sup = sup;
@@ -4612,32 +4581,22 @@ static int64_t format_contained_rows(disco_ctx *c, const char *who, uint32_t n_f
         CHK((scan_exclusive<u8, u64>(c, bytes, nc, place, true, &total)));
         hipLaunchKernelGGL(ctext_offsets_kernel, dim3(flat_grid(c, (u64)n_files + 1)), dim3(256), 0, c->stream, (const u32 *)gend, n, nc, (const u64 *)place, n_files, d_off.p);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->ctext_off.data(), d_off, ((size_t)n_files + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(off.data(), d_off, ((size_t)n_files + 1) * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "%s: %u contained reads have a key that names no containing read", who, h_ctr[CGRP_BAD_KEYS]);
-        CHK(ensure(c, c->d_ctext, std::max<u64>(total, 1)));
-        hipLaunchKernelGGL(ctext_write_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, g, (const u64 *)place, c->d_ctext.p);
+        CHK(ensure(c, c->ctext.d, std::max<u64>(total, 1)));
+        hipLaunchKernelGGL(ctext_write_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, g, (const u64 *)place, c->ctext.d.p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->ctext_bytes = total;
-        return DISCO_OK;
-    };
-    const int rc = body();
-    release_groups(c, G);
-    release(c, place);
-    release(c, d_findex);
-    release(c, d_off);
-    release(c, bytes);
-    if (rc != DISCO_OK) {
-        c->ctext_off.assign((size_t)n_files + 1, 0);
-        return rc;
+        c->ctext.off.swap(off);
+        c->ctext.bytes = total;
     }
-    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = c->ctext_off[f];
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = c->ctext.off[f];
     if (getenv("DISCO_VERBOSE"))
         fprintf(stderr, "[disco] contained lines: %llu rows, %llu bytes; groups of more than %d rows: %u sorted in LDS, %u through global memory, the largest of %u rows\n",
-                (unsigned long long)nc, (unsigned long long)c->ctext_bytes, CROW_GROUP_MAX, h_ctr[CGRP_N_LDS], h_ctr[CGRP_N_GLOBAL], h_ctr[CGRP_LARGEST]);
-    return (int64_t)c->ctext_bytes;
+                (unsigned long long)nc, (unsigned long long)c->ctext.bytes, CROW_GROUP_MAX, h_ctr[CGRP_N_LDS], h_ctr[CGRP_N_GLOBAL], h_ctr[CGRP_LARGEST]);
+    return (int64_t)c->ctext.bytes;
 }
 
 int64_t disco_format_contained(disco_ctx *c, uint32_t n_files, const uint64_t *file_index, uint64_t *file_offsets)
@@ -4649,92 +4608,42 @@ int64_t disco_format_contained(disco_ctx *c, uint32_t n_files, const uint64_t *f
     if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_format_contained: more than 2^31 reads");
     HIPCHK(c, hipSetDevice(c->device));
     for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
-    c->ctext_bytes = 0;
-    c->ctext_off.assign((size_t)n_files + 1, 0);
+    c->ctext.bytes = 0;
+    c->ctext.off.assign((size_t)n_files + 1, 0);
     if (c->n_contained == 0) return 0;
     CHK(settle_keys(c));
     return format_contained_rows(c, "disco_format_contained", n_files, file_index, file_offsets, (const u8 *)c->d_contained, 0, c->n, c->n_contained);
 }
 
-int disco_fetch_contained_text(disco_ctx *c, char *out, uint64_t cap)
-{
-    if (!c || (!out && c->ctext_bytes)) return DISCO_E_ARG;
-    if (cap < c->ctext_bytes) return fail(c, DISCO_E_ARG, "disco_fetch_contained_text: need room for %llu bytes", (unsigned long long)c->ctext_bytes);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->ctext_bytes) {
-        HIPCHK(c, hipMemcpyAsync(out, c->d_ctext, c->ctext_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return DISCO_OK;
-}
+int disco_fetch_contained_text(disco_ctx *c, char *out, uint64_t cap) { return c ? fetch_text(c, "disco_fetch_contained_text", c->ctext, out, cap) : DISCO_E_ARG; }
 
-int disco_write_contained_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t host_threads)
+int disco_write_contained_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t)
 {
     DISCO_TRACE("disco_write_contained_text");
-    if (!c || !fds) return DISCO_E_ARG;
-    if (c->ctext_off.size() != (size_t)n_files + 1) return fail(c, DISCO_E_STATE, "disco_write_contained_text: run disco_format_contained for %u files first", n_files);
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)host_threads;
-    if (c->ctext_bytes == 0) return DISCO_OK;
-    return write_text_through_ring(c, "disco_write_contained_text", c->d_ctext, c->ctext_off, fds, n_files);
+    return c ? write_text(c, "disco_write_contained_text", "disco_format_contained", c->ctext, fds, n_files) : DISCO_E_ARG;
 }
 
 /* ---- the records of the binary side output, formed where the edges and the keys are (disco_binrec.h) ------------------------- */
 /* The records [0, total) of one kind leave the device piece by piece: launch(lo, hi, piece) fills a device piece buffer with the records
- * [lo, hi), the piece travels into a half of the pinned ring, and while it travels the piece before it is delivered — copied to `out`, or
- * (out == null) written into fd from file_offset on, a piece split among `threads` writers at disjoint offsets: the records of a kind lie in
- * ONE file, and writes to one file serialise on its inode lock (write_text_through_ring: 16 threads on one file reach 12 GB/s). Kernel
- * and copy share the stream: 128 MB of records are formed in a fraction of a millisecond and travel for several, so there is nothing a
- * second stream could hide (profiles/binary_records.txt). No device buffer holds all records. */
+ * [lo, hi), and the pieces go through a RingSink to `out` or (out == null) into fd from file_offset on, a piece split among `threads`
+ * writers: the records of a kind lie in ONE file. No device buffer holds all records. */
 static int records_through_ring(disco_ctx *c, const char *who, u64 total, const std::function<void(u64, u64, u64 *)> &launch, void *out, int fd, u64 file_offset,
                                 uint32_t threads)
 {
     if (total == 0) return DISCO_OK;
-    CHK(output_ring(c, who));
+    CHK(pinned_ring(c, who));
     const u64 REC = BINREC_WORDS * sizeof(u64);
     const u64 fits = c->ring_half / REC;
     const u64 P = std::min<u64>(c->rec_piece ? std::min<u64>(c->rec_piece, fits) : fits, total);
     const u64 pieces = (total + P - 1) / P;
-    for (u64 i = 0; i < std::min<u64>(pieces, 2); i++) CHK(ensure(c, c->d_rec_piece[i], P * BINREC_WORDS));
-    const u64 n_thr = std::max<uint32_t>(1, std::min<uint32_t>(threads, 64));
-    std::atomic<bool> ok{true};
-    auto half_of = [&](u64 r) { return (char *)c->h_ring + (r & 1) * c->ring_half; };
-    auto deliver = [&](u64 r) {
-        const char *half = half_of(r);
-        const u64 first = r * P * REC, bytes = (std::min(total, (r + 1) * P) - r * P) * REC;
-        auto part = [&, half, first](u64 b, u64 e) {
-            if (out) {
-                memcpy((char *)out + first + b, half + b, e - b);
-                return;
-            }
-            while (b < e) {
-                const ssize_t w = pwrite(fd, half + b, e - b, (off_t)(file_offset + first + b));
-                if (w <= 0) {
-                    ok.store(false);
-                    return;
-                }
-                b += (u64)w;
-            }
-        };
-        const u64 nt = std::max<u64>(1, std::min<u64>(n_thr, bytes >> 16)); /* (no thread for less than 64 KB) */
-        const u64 slice = ((bytes + nt - 1) / nt + 4095) & ~(u64)4095;
-        if (nt == 1) return part(0, bytes);
-        std::vector<std::thread> th;
-        for (u64 b = 0; b < bytes; b += slice) th.emplace_back(part, b, std::min(bytes, b + slice));
-        for (auto &x : th) x.join();
-    };
-    for (u64 r = 0; r < pieces; r++) {
-        const u64 lo = r * P, hi = std::min(total, lo + P);
-        launch(lo, hi, c->d_rec_piece[r & 1].p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(half_of(r), c->d_rec_piece[r & 1].p, (hi - lo) * REC, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_ring[r & 1], c->stream));
-        if (r >= 1) deliver(r - 1); /* (its copy was waited for below, one piece ago; the half it frees is written again two pieces on) */
-        HIPCHK(c, hipEventSynchronize(c->ev_ring[r & 1]));
+    RingSink o(c, who, c->d_rec_piece);
+    for (u64 i = 0; i < std::min<u64>(pieces, 2); i++) CHK(ensure(c, o.piece[i], P * REC));
+    for (u64 lo = 0; lo < total; lo += P) {
+        const u64 hi = std::min(total, lo + P);
+        launch(lo, hi, (u64 *)o.next());
+        CHK(o.ship_piece((hi - lo) * REC, fd, out, (out ? 0 : file_offset) + lo * REC, std::max<uint32_t>(threads, 1)));
     }
-    deliver(pieces - 1);
-    if (!ok.load()) return fail(c, DISCO_E_ARG, "%s: write error", who);
-    return DISCO_OK;
+    return o.flush();
 }
 
 static int records_common_checks(disco_ctx *c, const char *who, int phase_needed, const char *phase_name)
@@ -4742,6 +4651,31 @@ static int records_common_checks(disco_ctx *c, const char *who, int phase_needed
     if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "%s: a rank holds its share of the job only (the host writer takes the gathered records)", who);
     if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "%s: more than 2^31 reads", who);
     if (c->phase < phase_needed) return fail(c, DISCO_E_STATE, "%s: run %s first", who, phase_name);
+    return DISCO_OK;
+}
+
+/* what the edge records need next to the edges: the caller's arrays and the substitution counts, kept in the context */
+static int edge_record_inputs(disco_ctx *c, const uint16_t *edge_file, const uint64_t *file_index)
+{
+    const u64 ne = c->n_out;
+    if (edge_file) {
+        CHK(ensure(c, c->d_rec_efile, ne));
+        HIPCHK(c, hipMemcpyAsync(c->d_rec_efile, edge_file, ne * sizeof(u16), hipMemcpyHostToDevice, c->stream));
+        c->rec_e_has_file = true;
+    }
+    if (file_index) {
+        CHK(ensure(c, c->d_rec_efindex, c->n));
+        HIPCHK(c, hipMemcpyAsync(c->d_rec_efindex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
+        c->rec_e_has_findex = true;
+    }
+    if (c->prm.max_substitutions) { /* by fetch-order rank, as disco_fetch_edge_substitutions has them */
+        CHK(ensure(c, c->d_rec_subs, ne));
+        hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c), c->out_used,
+                           c->d_reads, c->d_len, c->S, c->d_rec_subs.p);
+        HIPCHK(c, hipGetLastError());
+        c->rec_e_has_subs = true;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* (the caller's arrays are free again) */
     return DISCO_OK;
 }
 
@@ -4755,38 +4689,15 @@ int64_t disco_prepare_edge_records(disco_ctx *c, uint32_t n_files, const uint16_
     if (!edge_file && n_files > 1) return fail(c, DISCO_E_ARG, "disco_prepare_edge_records: the file of every edge is needed for more than one file");
     HIPCHK(c, hipSetDevice(c->device));
     drop_edge_records(c);
-    const u64 ne = c->n_out;
     c->rec_e_files = n_files;
     c->rec_e_has_file = c->rec_e_has_findex = c->rec_e_has_subs = false;
-    auto body = [&]() -> int {
-        if (ne == 0) return DISCO_OK;
-        if (edge_file) {
-            CHK(ensure(c, c->d_rec_efile, ne));
-            HIPCHK(c, hipMemcpyAsync(c->d_rec_efile, edge_file, ne * sizeof(u16), hipMemcpyHostToDevice, c->stream));
-            c->rec_e_has_file = true;
-        }
-        if (file_index) {
-            CHK(ensure(c, c->d_rec_efindex, c->n));
-            HIPCHK(c, hipMemcpyAsync(c->d_rec_efindex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
-            c->rec_e_has_findex = true;
-        }
-        if (c->prm.max_substitutions) { /* by fetch-order rank, as disco_fetch_edge_substitutions has them */
-            CHK(ensure(c, c->d_rec_subs, ne));
-            hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c), c->out_used,
-                               c->d_reads, c->d_len, c->S, c->d_rec_subs.p);
-            HIPCHK(c, hipGetLastError());
-            c->rec_e_has_subs = true;
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream)); /* (the caller's arrays are free again) */
-        return DISCO_OK;
-    };
-    const int rc = body();
+    const int rc = c->n_out ? edge_record_inputs(c, edge_file, file_index) : DISCO_OK;
     if (rc != DISCO_OK) {
         drop_edge_records(c);
         return rc;
     }
     c->rec_e_ready = true;
-    return (int64_t)ne;
+    return (int64_t)c->n_out;
 }
 
 static int edge_records_out(disco_ctx *c, const char *who, void *out, int fd, u64 file_offset, uint32_t threads)
@@ -4833,6 +4744,25 @@ int disco_write_edge_records(disco_ctx *c, int fd, uint64_t file_offset, uint32_
     return edge_records_out(c, "disco_write_edge_records", nullptr, fd, file_offset, host_threads);
 }
 
+/* the contained rows grouped and sorted, and the caller's array: the rows stay with the context, the rest of the grouping goes */
+static int contained_record_inputs(disco_ctx *c, const uint64_t *file_index, u64 *nc)
+{
+    ContainedGroups G(c);
+    u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
+    CHK(group_contained_rows(c, (const u8 *)c->d_contained, 0, c->n, nc, G));
+    if (file_index) {
+        CHK(ensure(c, c->d_rec_cfindex, c->n));
+        HIPCHK(c, hipMemcpyAsync(c->d_rec_cfindex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
+        c->rec_c_has_findex = true;
+    }
+    HIPCHK(c, hipMemcpyAsync(h_ctr, G.ctr, sizeof h_ctr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "disco_prepare_contained_records: %u contained reads have a key that names no containing read", h_ctr[CGRP_BAD_KEYS]);
+    G.word.give(c->d_rec_cword); /* (empty since drop_contained_records; the bytes stay counted) */
+    G.sup.give(c->d_rec_csup);
+    return DISCO_OK;
+}
+
 /* replaces the contained half of disco::write_binary (disco_amd/host/writer.h; the records of the lines of BG/OverlapGraph.cpp:438-447) */
 int64_t disco_prepare_contained_records(disco_ctx *c, uint32_t n_files, const uint64_t *file_index)
 {
@@ -4850,28 +4780,7 @@ int64_t disco_prepare_contained_records(disco_ctx *c, uint32_t n_files, const ui
         return 0;
     }
     CHK(settle_keys(c));
-    ContainedGroups G;
-    u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
-    auto body = [&]() -> int {
-        CHK(group_contained_rows(c, (const u8 *)c->d_contained, 0, c->n, &nc, G));
-        if (file_index) {
-            CHK(ensure(c, c->d_rec_cfindex, c->n));
-            HIPCHK(c, hipMemcpyAsync(c->d_rec_cfindex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
-            c->rec_c_has_findex = true;
-        }
-        HIPCHK(c, hipMemcpyAsync(h_ctr, G.ctr, sizeof h_ctr, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "disco_prepare_contained_records: %u contained reads have a key that names no containing read", h_ctr[CGRP_BAD_KEYS]);
-        return DISCO_OK;
-    };
-    const int rc = body();
-    if (rc == DISCO_OK) { /* the grouped rows stay with the context; the rest of the grouping goes */
-        c->d_rec_cword = G.word; /* (empty since drop_contained_records; the bytes stay counted) */
-        c->d_rec_csup = G.sup;
-        G.word = DevBuf<u64>();
-        G.sup = DevBuf<u32>();
-    }
-    release_groups(c, G);
+    const int rc = contained_record_inputs(c, file_index, &nc);
     if (rc != DISCO_OK) {
         drop_contained_records(c);
         return rc;
@@ -4926,65 +4835,32 @@ int disco_set_record_piece(disco_ctx *c, uint64_t records)
 
 /* ---- the overlap graph as GFA 1.0, formatted where the reads, the edges and the keys are (disco_gfa.h) ------------------------------- */
 static_assert(GFA_SHORT_MAX == DISCO_SHORT_MAX, "disco_gfa.h reads the long class as the table lays it out");
-/* where the pieces of the text go: two device piece buffers, the two halves of the pinned ring, the file. A piece is formatted, copied
- * into its half and, while the next one is formatted and travels, written into the file (records_through_ring's scheme, with pieces of
- * the sizes the lines give them) */
+/* where the pieces of the text go: a RingSink and the file behind it, with pieces of the sizes the lines give them */
 struct GfaSink {
-    int fd = -1;
-    u32 threads = 1;
-    u64 cap = 0, unit = 0; /* bytes a piece may hold; a piece takes the lines that start in one stretch of `unit` bytes (cap - GFA_MAX_LINE) */
-    u64 file_off = 0;      /* where the next section begins in the file */
-    u64 issued = 0;        /* pieces so far: piece k uses buffer and half k & 1 */
-    DevBuf<u8> piece[2];
-    DevBuf<u64> d_cut;
-    bool pending = false; /* the piece before the current one lies in its half, not yet written */
-    u64 p_half = 0, p_bytes = 0, p_off = 0;
-    bool write_ok = true;
-};
-static void gfa_deliver(disco_ctx *c, GfaSink &o)
-{
-    if (!o.pending) return;
-    o.pending = false;
-    const char *half = (const char *)c->h_ring + o.p_half * c->ring_half;
-    const u64 bytes = o.p_bytes, first = o.p_off;
-    std::atomic<bool> ok{true};
-    auto part = [&](u64 b, u64 e) {
-        while (b < e) {
-            const ssize_t w = pwrite(o.fd, half + b, e - b, (off_t)(first + b));
-            if (w <= 0) {
-                ok.store(false);
-                return;
-            }
-            b += (u64)w;
-        }
-    };
-    const u64 nt = std::max<u64>(1, std::min<u64>(std::min<u32>(o.threads, 64), bytes >> 16)); /* (no thread for less than 64 KB) */
-    if (nt == 1) part(0, bytes);
-    else {
-        const u64 slice = ((bytes + nt - 1) / nt + 4095) & ~(u64)4095;
-        std::vector<std::thread> th;
-        for (u64 b = 0; b < bytes; b += slice) th.emplace_back(part, b, std::min(bytes, b + slice));
-        for (auto &x : th) x.join();
+    RingSink ring;
+    int fd;
+    u32 threads;
+    u64 cap, unit;    /* bytes a piece may hold; a piece takes the lines that start in one stretch of `unit` bytes (cap - GFA_MAX_LINE) */
+    u64 file_off = 0; /* where the next section begins in the file */
+    LocalBuf<u64> d_cut;
+    GfaSink(disco_ctx *c, const char *who, int fd_, uint64_t piece_bytes, uint32_t host_threads)
+        : ring(c, who), fd(fd_), threads(std::max<uint32_t>(host_threads, 1)),
+          cap(piece_bytes ? std::min<u64>(std::max<u64>(piece_bytes, 65536), c->ring_half) : c->ring_half), unit(cap - GFA_MAX_LINE), d_cut(c)
+    {
     }
-    if (!ok.load()) o.write_ok = false;
-}
-/* the piece just launched into buffer issued & 1, `bytes` long, belongs at byte file_pos of the file: it travels into its half of the
- * ring while the host writes the piece before it */
-static int gfa_ship(disco_ctx *c, GfaSink &o, u64 bytes, u64 file_pos)
-{
-    const u64 h = o.issued & 1;
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync((char *)c->h_ring + h * c->ring_half, o.piece[h].p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_ring[h], c->stream));
-    gfa_deliver(c, o); /* the piece before: its copy was waited for below, one piece ago; the half it frees is written again two pieces on */
-    HIPCHK(c, hipEventSynchronize(c->ev_ring[h]));
-    o.pending = true;
-    o.p_half = h;
-    o.p_bytes = bytes;
-    o.p_off = file_pos;
-    o.issued++;
-    return DISCO_OK;
-}
+    /* the piece just launched into ring.next(), `bytes` long, belongs at byte file_pos of the file */
+    int ship(u64 bytes, u64 file_pos) { return ring.ship_piece(bytes, fd, nullptr, file_pos, threads); }
+};
+/* declared behind a function's LocalBufs, so that it goes before they do: unless the function got to its end (done), it waits for the
+ * stream — nothing in flight reads what they release */
+struct WaitUnlessDone {
+    disco_ctx *c;
+    bool done = false;
+    ~WaitUnlessDone()
+    {
+        if (!done) (void)hipStreamSynchronize(c->stream);
+    }
+};
 /* one section of the file — n_lines lines whose starts are place[0 .. n_lines], place[n_lines] = total — piece by piece: launch(a, b,
  * piece) formats the lines [a[0], b[0]) into a piece that begins at byte a[1] of the section (a, b: two entries of gfa_cuts_kernel) */
 static int gfa_section(disco_ctx *c, const char *who, GfaSink &o, const u64 *place, u64 n_lines, u64 total, const u32 *ovf, u32 n_long,
@@ -4994,7 +4870,7 @@ static int gfa_section(disco_ctx *c, const char *who, GfaSink &o, const u64 *pla
     const u64 np = (total + o.unit - 1) / o.unit;
     std::vector<u64> cut(3 * (np + 1));
     CHK(ensure(c, o.d_cut, 3 * (np + 1)));
-    for (int i = 0; i < 2; i++) CHK(ensure(c, o.piece[i], std::min(o.cap, total))); /* (grow-only; nothing of the section before is in flight) */
+    for (int i = 0; i < 2; i++) CHK(ensure(c, o.ring.piece[i], std::min(o.cap, total))); /* (grow-only; nothing of the section before is in flight) */
     hipLaunchKernelGGL(gfa_cuts_kernel, dim3(flat_grid(c, np + 1)), dim3(256), 0, c->stream, place, n_lines, o.unit, np, ovf, n_long, o.d_cut.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(cut.data(), o.d_cut, cut.size() * 8, hipMemcpyDeviceToHost, c->stream));
@@ -5004,8 +4880,8 @@ static int gfa_section(disco_ctx *c, const char *who, GfaSink &o, const u64 *pla
         const u64 bytes = b[1] - a[1];
         if (bytes == 0) continue; /* (a line longer than the stretch: the one behind it has no line of its own) */
         if (b[0] < a[0] || b[0] > n_lines || bytes > o.cap) return fail(c, DISCO_E_CAPACITY, "%s: a piece of %llu bytes, room for %llu", who, (unsigned long long)bytes, (unsigned long long)o.cap);
-        launch(a, b, (char *)o.piece[o.issued & 1].p);
-        CHK(gfa_ship(c, o, bytes, o.file_off + a[1]));
+        launch(a, b, (char *)o.ring.next());
+        CHK(o.ship(bytes, o.file_off + a[1]));
     }
     o.file_off += total;
     return DISCO_OK;
@@ -5017,11 +4893,11 @@ static int gfa_byte_section(disco_ctx *c, GfaSink &o, u64 total, const std::func
 {
     if (total == 0) return DISCO_OK;
     const u64 step = o.cap & ~(u64)15;
-    for (int i = 0; i < 2; i++) CHK(ensure(c, o.piece[i], std::min(o.cap, total)));
+    for (int i = 0; i < 2; i++) CHK(ensure(c, o.ring.piece[i], std::min(o.cap, total)));
     for (u64 lo = 0; lo < total; lo += step) {
         const u64 hi = std::min(total, lo + step);
-        launch(lo, hi, (char *)o.piece[o.issued & 1].p);
-        CHK(gfa_ship(c, o, hi - lo, o.file_off + lo));
+        launch(lo, hi, (char *)o.ring.next());
+        CHK(o.ship(hi - lo, o.file_off + lo));
     }
     o.file_off += total;
     return DISCO_OK;
@@ -5053,109 +4929,92 @@ int64_t disco_write_gfa(disco_ctx *c, int fd, const uint64_t *file_index, uint32
     if (c->phase < 8) return fail(c, DISCO_E_STATE, "%s: run disco_transitive_reduce first", who);
     if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "%s: more than 2^31 reads", who);
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(output_ring(c, who));
+    CHK(pinned_ring(c, who));
     const bool no_seq = (flags & DISCO_GFA_NO_SEQ) != 0;
     const u64 n = c->n, ne = c->n_out;
-    GfaSink o;
-    o.fd = fd;
-    o.threads = std::max<uint32_t>(host_threads, 1);
-    o.cap = piece_bytes ? std::min<u64>(std::max<u64>(piece_bytes, 65536), c->ring_half) : c->ring_half;
-    o.unit = o.cap - GFA_MAX_LINE;
-    DevBuf<u64> d_findex, place;
-    DevBuf<u16> sbytes, subs;
-    DevBuf<u8> bytes;
-    ContainedGroups G;
-    auto body = [&]() -> int {
-        if (file_index) {
-            CHK(ensure(c, d_findex, n));
-            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, n * 8, hipMemcpyHostToDevice, c->stream));
+    GfaSink o(c, who, fd, piece_bytes, host_threads);
+    LocalBuf<u64> d_findex(c), place(c);
+    LocalBuf<u16> sbytes(c), subs(c);
+    LocalBuf<u8> bytes(c);
+    ContainedGroups G(c);
+    WaitUnlessDone settled{c};
+    if (file_index) {
+        CHK(ensure(c, d_findex, n));
+        HIPCHK(c, hipMemcpyAsync(d_findex, file_index, n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    static const char header[] = GFA_HEADER;
+    if (pwrite(fd, header, sizeof header - 1, 0) != (ssize_t)(sizeof header - 1)) return fail(c, DISCO_E_ARG, "%s: write error", who);
+    o.file_off = sizeof header - 1;
+    /* S lines: a lane per word of a read */
+    const GfaReads R = gfa_reads(c, d_findex);
+    u64 total = 0;
+    if (n) {
+        CHK(ensure(c, sbytes, n));
+        CHK(ensure(c, place, n + 1));
+        hipLaunchKernelGGL(gfa_s_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, (const u8 *)nullptr, no_seq ? 1u : 0u, sbytes.p);
+        CHK((scan_exclusive<u16, u64>(c, sbytes, n, place, true, &total)));
+        const u32 W = no_seq ? 1u : R.S;
+        const bool long_pass = c->two_class && !no_seq && R.SL > GFA_HEAD_WORDS;
+        CHK(gfa_section(c, who, o, place, n, total, R.ovf, (u32)c->n_long, [&](const u64 *a, const u64 *b, char *piece) {
+            hipLaunchKernelGGL(gfa_s_write_kernel, dim3(flat_grid(c, (b[0] - a[0]) * W)), dim3(256), 0, c->stream, R, (const u8 *)nullptr, (const u64 *)place, a[0], b[0], a[1], no_seq ? 1u : 0u, W, piece);
+            if (long_pass && b[2] > a[2])
+                hipLaunchKernelGGL(gfa_s_write_long_kernel, dim3(flat_grid(c, (b[2] - a[2]) * (R.SL - GFA_HEAD_WORDS))), dim3(256), 0, c->stream, R, (const u8 *)nullptr, (const u64 *)place, a[2], b[2],
+                                   a[1], piece);
+        }));
+    }
+    /* L lines: a lane per edge, in the order of disco_fetch_edges */
+    if (ne) {
+        TextView g;
+        g.src = c->d_out_src;
+        g.ent = c->d_out_ent;
+        g.valid = out_valid(c);
+        g.pos = out_pos(c);
+        g.len = c->d_len;
+        g.file_index = d_findex;
+        g.n_slots = c->out_used;
+        if (c->prm.max_substitutions) { /* by fetch-order rank, as disco_fetch_edge_substitutions has them */
+            CHK(ensure(c, subs, ne));
+            hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c), c->out_used,
+                               c->d_reads, c->d_len, c->S, subs.p);
         }
-        static const char header[] = GFA_HEADER;
-        if (pwrite(fd, header, sizeof header - 1, 0) != (ssize_t)(sizeof header - 1)) return fail(c, DISCO_E_ARG, "%s: write error", who);
-        o.file_off = sizeof header - 1;
-        /* S lines: a lane per word of a read */
-        const GfaReads R = gfa_reads(c, d_findex);
-        u64 total = 0;
-        if (n) {
-            CHK(ensure(c, sbytes, n));
-            CHK(ensure(c, place, n + 1));
-            hipLaunchKernelGGL(gfa_s_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, (const u8 *)nullptr, no_seq ? 1u : 0u, sbytes.p);
-            CHK((scan_exclusive<u16, u64>(c, sbytes, n, place, true, &total)));
-            const u32 W = no_seq ? 1u : R.S;
-            const bool long_pass = c->two_class && !no_seq && R.SL > GFA_HEAD_WORDS;
-            CHK(gfa_section(c, who, o, place, n, total, R.ovf, (u32)c->n_long, [&](const u64 *a, const u64 *b, char *piece) {
-                hipLaunchKernelGGL(gfa_s_write_kernel, dim3(flat_grid(c, (b[0] - a[0]) * W)), dim3(256), 0, c->stream, R, (const u8 *)nullptr, (const u64 *)place, a[0], b[0], a[1], no_seq ? 1u : 0u, W, piece);
-                if (long_pass && b[2] > a[2])
-                    hipLaunchKernelGGL(gfa_s_write_long_kernel, dim3(flat_grid(c, (b[2] - a[2]) * (R.SL - GFA_HEAD_WORDS))), dim3(256), 0, c->stream, R, (const u8 *)nullptr, (const u64 *)place, a[2], b[2],
-                                       a[1], piece);
-            }));
-        }
-        /* L lines: a lane per edge, in the order of disco_fetch_edges */
-        if (ne) {
-            TextView g;
-            g.src = c->d_out_src;
-            g.ent = c->d_out_ent;
-            g.valid = out_valid(c);
-            g.pos = out_pos(c);
-            g.len = c->d_len;
-            g.file_index = d_findex;
-            g.n_slots = c->out_used;
-            if (c->prm.max_substitutions) { /* by fetch-order rank, as disco_fetch_edge_substitutions has them */
-                CHK(ensure(c, subs, ne));
-                hipLaunchKernelGGL(edge_subs_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, out_valid(c), out_pos(c), c->out_used,
-                                   c->d_reads, c->d_len, c->S, subs.p);
-            }
-            const u16 *d_subs = c->prm.max_substitutions ? subs.p : nullptr;
-            CHK(ensure(c, bytes, ne));
-            CHK(ensure(c, place, ne + 1));
-            hipLaunchKernelGGL(gfa_l_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, d_subs, (const u8 *)nullptr, bytes.p);
-            CHK((scan_exclusive<u8, u64>(c, bytes, ne, place, true, &total)));
-            const bool dense = c->out_dense;
-            CHK(gfa_section(c, who, o, place, ne, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
-                const u64 s_lo = dense ? a[0] : 0, s_hi = dense ? b[0] : g.n_slots;
-                hipLaunchKernelGGL(gfa_l_write_kernel, dim3(flat_grid(c, s_hi - s_lo)), dim3(256), 0, c->stream, g, d_subs, (const u8 *)nullptr, (const u64 *)place, s_lo, s_hi, a[0], b[0], a[1], piece);
-            }));
-        }
-        /* C lines: a lane per contained row, grouped and sorted as for the contained-read files */
-        u64 nc = c->n_contained;
-        if (nc) {
-            CHK(settle_keys(c));
-            CHK(group_contained_rows(c, (const u8 *)c->d_contained, 0, n, &nc, G));
-            u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
-            HIPCHK(c, hipMemcpyAsync(h_ctr, G.ctr, sizeof h_ctr, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "%s: %u contained reads have a key that names no containing read", who, h_ctr[CGRP_BAD_KEYS]);
-            CTextView g;
-            g.word = G.word;
-            g.sup = G.sup;
-            g.len = c->d_len;
-            g.file_index = d_findex;
-            g.nc = nc;
-            g.k = (u32)c->k;
-            CHK(ensure(c, bytes, nc));
-            CHK(ensure(c, place, nc + 1));
-            hipLaunchKernelGGL(gfa_c_measure_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, g, bytes.p);
-            CHK((scan_exclusive<u8, u64>(c, bytes, nc, place, true, &total)));
-            CHK(gfa_section(c, who, o, place, nc, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
-                hipLaunchKernelGGL(gfa_c_write_kernel, dim3(flat_grid(c, b[0] - a[0])), dim3(256), 0, c->stream, g, (const u64 *)place, a[0], b[0], a[1], piece);
-            }));
-        }
-        gfa_deliver(c, o);
-        if (!o.write_ok) return fail(c, DISCO_E_ARG, "%s: write error", who);
-        return DISCO_OK;
-    };
-    const int rc = body();
-    if (rc != DISCO_OK) (void)hipStreamSynchronize(c->stream); /* (nothing in flight reads what is released below) */
-    release(c, o.piece[0]);
-    release(c, o.piece[1]);
-    release(c, o.d_cut);
-    release(c, d_findex);
-    release(c, place);
-    release(c, sbytes);
-    release(c, subs);
-    release(c, bytes);
-    release_groups(c, G);
-    return rc != DISCO_OK ? rc : (int64_t)o.file_off;
+        const u16 *d_subs = c->prm.max_substitutions ? subs.p : nullptr;
+        CHK(ensure(c, bytes, ne));
+        CHK(ensure(c, place, ne + 1));
+        hipLaunchKernelGGL(gfa_l_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, d_subs, (const u8 *)nullptr, bytes.p);
+        CHK((scan_exclusive<u8, u64>(c, bytes, ne, place, true, &total)));
+        const bool dense = c->out_dense;
+        CHK(gfa_section(c, who, o, place, ne, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+            const u64 s_lo = dense ? a[0] : 0, s_hi = dense ? b[0] : g.n_slots;
+            hipLaunchKernelGGL(gfa_l_write_kernel, dim3(flat_grid(c, s_hi - s_lo)), dim3(256), 0, c->stream, g, d_subs, (const u8 *)nullptr, (const u64 *)place, s_lo, s_hi, a[0], b[0], a[1], piece);
+        }));
+    }
+    /* C lines: a lane per contained row, grouped and sorted as for the contained-read files */
+    u64 nc = c->n_contained;
+    if (nc) {
+        CHK(settle_keys(c));
+        CHK(group_contained_rows(c, (const u8 *)c->d_contained, 0, n, &nc, G));
+        u32 h_ctr[CGRP_CTRS] = {0, 0, 0, 0};
+        HIPCHK(c, hipMemcpyAsync(h_ctr, G.ctr, sizeof h_ctr, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h_ctr[CGRP_BAD_KEYS]) return fail(c, DISCO_E_STATE, "%s: %u contained reads have a key that names no containing read", who, h_ctr[CGRP_BAD_KEYS]);
+        CTextView g;
+        g.word = G.word;
+        g.sup = G.sup;
+        g.len = c->d_len;
+        g.file_index = d_findex;
+        g.nc = nc;
+        g.k = (u32)c->k;
+        CHK(ensure(c, bytes, nc));
+        CHK(ensure(c, place, nc + 1));
+        hipLaunchKernelGGL(gfa_c_measure_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, g, bytes.p);
+        CHK((scan_exclusive<u8, u64>(c, bytes, nc, place, true, &total)));
+        CHK(gfa_section(c, who, o, place, nc, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+            hipLaunchKernelGGL(gfa_c_write_kernel, dim3(flat_grid(c, b[0] - a[0])), dim3(256), 0, c->stream, g, (const u64 *)place, a[0], b[0], a[1], piece);
+        }));
+    }
+    CHK(o.ring.flush());
+    settled.done = true;
+    return (int64_t)o.file_off;
 }
 
 /* ---- the compacted graph as GFA 1.0: the composite edges of the contraction as segments with their merged bases (disco_gfa_chains.h) ---- */
@@ -5172,123 +5031,103 @@ int64_t disco_write_gfa_chains(disco_ctx *c, int fd, const uint64_t *file_index,
         return fail(c, DISCO_E_STATE, "%s: run disco_contract_chains on the resident edges first (after disco_contract_chains_of the host holds them)", who);
     if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "%s: more than 2^31 reads", who);
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(output_ring(c, who));
+    CHK(pinned_ring(c, who));
     const bool no_seq = (flags & DISCO_GFA_NO_SEQ) != 0;
     const u64 n = c->n, ne = c->n_out, nk = c->ch_comp_n, nl = c->ch_links_n;
-    GfaSink o;
-    o.fd = fd;
-    o.threads = std::max<uint32_t>(host_threads, 1);
-    o.cap = piece_bytes ? std::min<u64>(std::max<u64>(piece_bytes, 65536), c->ring_half) : c->ring_half;
-    o.unit = o.cap - GFA_MAX_LINE;
-    DevBuf<u64> d_findex, place, lsum, cbytes, cplace;
-    DevBuf<u32> loff;
-    DevBuf<u16> sbytes;
-    DevBuf<u8> bytes, skip;
-    auto body = [&]() -> int {
-        if (file_index) {
-            CHK(ensure(c, d_findex, n));
-            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, n * 8, hipMemcpyHostToDevice, c->stream));
-        }
-        static const char header[] = GFA_HEADER;
-        if (pwrite(fd, header, sizeof header - 1, 0) != (ssize_t)(sizeof header - 1)) return fail(c, DISCO_E_ARG, "%s: write error", who);
-        o.file_off = sizeof header - 1;
-        const GfaReads R = gfa_reads(c, d_findex);
-        GfuChains H;
-        H.comp = (const disco_chain_edge *)c->d_ch_comp.p;
-        H.links = (const disco_chain_link *)c->d_ch_links.p;
-        H.lsum = H.cplace = nullptr;
-        H.n_comp = nk;
-        H.no_seq = no_seq;
-        u64 total = 0;
-        /* S lines of the reads that are neither contained nor inside a chain: disco_write_gfa's writers behind the skip flags */
-        if (n) {
-            CHK(ensure(c, skip, n));
-            HIPCHK(c, hipMemcpyAsync(skip, c->d_contained, n, hipMemcpyDeviceToDevice, c->stream));
-            if (nk) {
-                hipLaunchKernelGGL(gfu_mark_links_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, skip.p);
-                hipLaunchKernelGGL(gfu_unmark_ends_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, H.comp, nk, (const u8 *)c->d_contained, skip.p);
-            }
-            CHK(ensure(c, sbytes, n));
-            CHK(ensure(c, place, n + 1));
-            hipLaunchKernelGGL(gfa_s_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, (const u8 *)skip, no_seq ? 1u : 0u, sbytes.p);
-            CHK((scan_exclusive<u16, u64>(c, sbytes, n, place, true, &total)));
-            const u32 W = no_seq ? 1u : R.S;
-            const bool long_pass = c->two_class && !no_seq && R.SL > GFA_HEAD_WORDS;
-            CHK(gfa_section(c, who, o, place, n, total, R.ovf, (u32)c->n_long, [&](const u64 *a, const u64 *b, char *piece) {
-                hipLaunchKernelGGL(gfa_s_write_kernel, dim3(flat_grid(c, (b[0] - a[0]) * W)), dim3(256), 0, c->stream, R, (const u8 *)skip, (const u64 *)place, a[0], b[0], a[1],
-                                   no_seq ? 1u : 0u, W, piece);
-                if (long_pass && b[2] > a[2])
-                    hipLaunchKernelGGL(gfa_s_write_long_kernel, dim3(flat_grid(c, (b[2] - a[2]) * (R.SL - GFA_HEAD_WORDS))), dim3(256), 0, c->stream, R, (const u8 *)skip,
-                                       (const u64 *)place, a[2], b[2], a[1], piece);
-            }));
-        }
-        /* S lines of the composite edges: one stream of bytes, a lane per 16 of them */
+    GfaSink o(c, who, fd, piece_bytes, host_threads);
+    LocalBuf<u64> d_findex(c), place(c), lsum(c), cbytes(c), cplace(c);
+    LocalBuf<u32> loff(c);
+    LocalBuf<u16> sbytes(c);
+    LocalBuf<u8> bytes(c), skip(c);
+    WaitUnlessDone settled{c};
+    if (file_index) {
+        CHK(ensure(c, d_findex, n));
+        HIPCHK(c, hipMemcpyAsync(d_findex, file_index, n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    static const char header[] = GFA_HEADER;
+    if (pwrite(fd, header, sizeof header - 1, 0) != (ssize_t)(sizeof header - 1)) return fail(c, DISCO_E_ARG, "%s: write error", who);
+    o.file_off = sizeof header - 1;
+    const GfaReads R = gfa_reads(c, d_findex);
+    GfuChains H;
+    H.comp = (const disco_chain_edge *)c->d_ch_comp.p;
+    H.links = (const disco_chain_link *)c->d_ch_links.p;
+    H.lsum = H.cplace = nullptr;
+    H.n_comp = nk;
+    H.no_seq = no_seq;
+    u64 total = 0;
+    /* S lines of the reads that are neither contained nor inside a chain: disco_write_gfa's writers behind the skip flags */
+    if (n) {
+        CHK(ensure(c, skip, n));
+        HIPCHK(c, hipMemcpyAsync(skip, c->d_contained, n, hipMemcpyDeviceToDevice, c->stream));
         if (nk) {
-            CHK(ensure(c, loff, nl));
-            CHK(ensure(c, lsum, nl + 1));
-            CHK(ensure(c, cbytes, nk));
-            CHK(ensure(c, cplace, nk + 1));
-            hipLaunchKernelGGL(gfu_link_offsets_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, loff.p);
-            CHK((scan_exclusive<u32, u64>(c, loff, nl, lsum, true, nullptr)));
-            H.lsum = (const uint64_t *)lsum.p;
-            hipLaunchKernelGGL(gfu_s_measure_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, H, (const u16 *)c->d_len, cbytes.p);
-            CHK((scan_exclusive<u64, u64>(c, cbytes, nk, cplace, true, &total)));
-            H.cplace = (const uint64_t *)cplace.p;
-            CHK(gfa_byte_section(c, o, total, [&](u64 lo, u64 hi, char *piece) {
-                hipLaunchKernelGGL(gfu_spell_kernel, dim3(flat_grid(c, gfu_items(lo, hi))), dim3(256), 0, c->stream, R, H, lo, hi, piece);
-            }));
+            hipLaunchKernelGGL(gfu_mark_links_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, skip.p);
+            hipLaunchKernelGGL(gfu_unmark_ends_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, H.comp, nk, (const u8 *)c->d_contained, skip.p);
         }
-        /* L lines of the edges that went into no composite edge, in the order of disco_fetch_edges */
-        if (ne) {
-            TextView g;
-            g.src = c->d_out_src;
-            g.ent = c->d_out_ent;
-            g.valid = out_valid(c);
-            g.pos = out_pos(c);
-            g.len = c->d_len;
-            g.file_index = d_findex;
-            g.n_slots = c->out_used;
-            const u8 *dead = c->d_ch_dead;
-            CHK(ensure(c, bytes, ne));
-            CHK(ensure(c, place, ne + 1));
-            hipLaunchKernelGGL(gfa_l_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, (const u16 *)nullptr, dead, bytes.p);
-            CHK((scan_exclusive<u8, u64>(c, bytes, ne, place, true, &total)));
-            const bool dense = c->out_dense;
-            CHK(gfa_section(c, who, o, place, ne, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
-                const u64 s_lo = dense ? a[0] : 0, s_hi = dense ? b[0] : g.n_slots;
-                hipLaunchKernelGGL(gfa_l_write_kernel, dim3(flat_grid(c, s_hi - s_lo)), dim3(256), 0, c->stream, g, (const u16 *)nullptr, dead, (const u64 *)place, s_lo, s_hi, a[0], b[0],
-                                   a[1], piece);
-            }));
-        }
-        /* ... and the head and the tail link of every composite edge, a lane per composite edge */
-        if (nk) {
-            CHK(ensure(c, bytes, nk));
-            CHK(ensure(c, place, nk + 1));
-            hipLaunchKernelGGL(gfu_l_measure_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, R, H, bytes.p);
-            CHK((scan_exclusive<u8, u64>(c, bytes, nk, place, true, &total)));
-            CHK(gfa_section(c, who, o, place, nk, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
-                hipLaunchKernelGGL(gfu_l_write_kernel, dim3(flat_grid(c, b[0] - a[0])), dim3(256), 0, c->stream, R, H, (const u64 *)place, a[0], b[0], a[1], piece);
-            }));
-        }
-        gfa_deliver(c, o);
-        if (!o.write_ok) return fail(c, DISCO_E_ARG, "%s: write error", who);
-        return DISCO_OK;
-    };
-    const int rc = body();
-    if (rc != DISCO_OK) (void)hipStreamSynchronize(c->stream); /* (nothing in flight reads what is released below) */
-    release(c, o.piece[0]);
-    release(c, o.piece[1]);
-    release(c, o.d_cut);
-    release(c, d_findex);
-    release(c, place);
-    release(c, lsum);
-    release(c, cbytes);
-    release(c, cplace);
-    release(c, loff);
-    release(c, sbytes);
-    release(c, bytes);
-    release(c, skip);
-    return rc != DISCO_OK ? rc : (int64_t)o.file_off;
+        CHK(ensure(c, sbytes, n));
+        CHK(ensure(c, place, n + 1));
+        hipLaunchKernelGGL(gfa_s_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, (const u8 *)skip, no_seq ? 1u : 0u, sbytes.p);
+        CHK((scan_exclusive<u16, u64>(c, sbytes, n, place, true, &total)));
+        const u32 W = no_seq ? 1u : R.S;
+        const bool long_pass = c->two_class && !no_seq && R.SL > GFA_HEAD_WORDS;
+        CHK(gfa_section(c, who, o, place, n, total, R.ovf, (u32)c->n_long, [&](const u64 *a, const u64 *b, char *piece) {
+            hipLaunchKernelGGL(gfa_s_write_kernel, dim3(flat_grid(c, (b[0] - a[0]) * W)), dim3(256), 0, c->stream, R, (const u8 *)skip, (const u64 *)place, a[0], b[0], a[1],
+                               no_seq ? 1u : 0u, W, piece);
+            if (long_pass && b[2] > a[2])
+                hipLaunchKernelGGL(gfa_s_write_long_kernel, dim3(flat_grid(c, (b[2] - a[2]) * (R.SL - GFA_HEAD_WORDS))), dim3(256), 0, c->stream, R, (const u8 *)skip,
+                                   (const u64 *)place, a[2], b[2], a[1], piece);
+        }));
+    }
+    /* S lines of the composite edges: one stream of bytes, a lane per 16 of them */
+    if (nk) {
+        CHK(ensure(c, loff, nl));
+        CHK(ensure(c, lsum, nl + 1));
+        CHK(ensure(c, cbytes, nk));
+        CHK(ensure(c, cplace, nk + 1));
+        hipLaunchKernelGGL(gfu_link_offsets_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, loff.p);
+        CHK((scan_exclusive<u32, u64>(c, loff, nl, lsum, true, nullptr)));
+        H.lsum = (const uint64_t *)lsum.p;
+        hipLaunchKernelGGL(gfu_s_measure_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, H, (const u16 *)c->d_len, cbytes.p);
+        CHK((scan_exclusive<u64, u64>(c, cbytes, nk, cplace, true, &total)));
+        H.cplace = (const uint64_t *)cplace.p;
+        CHK(gfa_byte_section(c, o, total, [&](u64 lo, u64 hi, char *piece) {
+            hipLaunchKernelGGL(gfu_spell_kernel, dim3(flat_grid(c, gfu_items(lo, hi))), dim3(256), 0, c->stream, R, H, lo, hi, piece);
+        }));
+    }
+    /* L lines of the edges that went into no composite edge, in the order of disco_fetch_edges */
+    if (ne) {
+        TextView g;
+        g.src = c->d_out_src;
+        g.ent = c->d_out_ent;
+        g.valid = out_valid(c);
+        g.pos = out_pos(c);
+        g.len = c->d_len;
+        g.file_index = d_findex;
+        g.n_slots = c->out_used;
+        const u8 *dead = c->d_ch_dead;
+        CHK(ensure(c, bytes, ne));
+        CHK(ensure(c, place, ne + 1));
+        hipLaunchKernelGGL(gfa_l_measure_kernel, dim3(flat_grid(c, g.n_slots)), dim3(256), 0, c->stream, g, (const u16 *)nullptr, dead, bytes.p);
+        CHK((scan_exclusive<u8, u64>(c, bytes, ne, place, true, &total)));
+        const bool dense = c->out_dense;
+        CHK(gfa_section(c, who, o, place, ne, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+            const u64 s_lo = dense ? a[0] : 0, s_hi = dense ? b[0] : g.n_slots;
+            hipLaunchKernelGGL(gfa_l_write_kernel, dim3(flat_grid(c, s_hi - s_lo)), dim3(256), 0, c->stream, g, (const u16 *)nullptr, dead, (const u64 *)place, s_lo, s_hi, a[0], b[0],
+                               a[1], piece);
+        }));
+    }
+    /* ... and the head and the tail link of every composite edge, a lane per composite edge */
+    if (nk) {
+        CHK(ensure(c, bytes, nk));
+        CHK(ensure(c, place, nk + 1));
+        hipLaunchKernelGGL(gfu_l_measure_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, R, H, bytes.p);
+        CHK((scan_exclusive<u8, u64>(c, bytes, nk, place, true, &total)));
+        CHK(gfa_section(c, who, o, place, nk, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+            hipLaunchKernelGGL(gfu_l_write_kernel, dim3(flat_grid(c, b[0] - a[0])), dim3(256), 0, c->stream, R, H, (const u64 *)place, a[0], b[0], a[1], piece);
+        }));
+    }
+    CHK(o.ring.flush());
+    settled.done = true;
+    return (int64_t)o.file_off;
 }
 
 /* the contained rows of the current flags start their way to the host now, on a side stream (grouped: also in the order of the
@@ -5309,8 +5148,8 @@ static int contract_chains(disco_ctx *c, const u64 *d_src, const u64 *d_ent, con
 {
     DISCO_TRACE("contract_chains");
     c->ch_ready = false;
-    c->ptext_bytes = 0; /* (a text formatted from the contraction before this one names composite edges that are gone) */
-    c->ptext_off.clear();
+    c->ptext.bytes = 0; /* (a text formatted from the contraction before this one names composite edges that are gone) */
+    c->ptext.off.clear();
     if (n_slots >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "chain contraction: more than 2^31 edge slots");
     ChainView g;
     g.src = d_src;
@@ -5320,85 +5159,70 @@ static int contract_chains(disco_ctx *c, const u64 *d_src, const u64 *d_ent, con
     g.len = c->d_len;
     g.n_slots = n_slots;
     g.min_ovl = min_ovl;
-    DevBuf<u32> deg, he, links_of, live;
-    DevBuf<u8> internal, is_head;
-    DevBuf<ChRank> ra, rb;
-    DevBuf<u64> comp_id, link_start;
+    LocalBuf<u32> deg(c), he(c), links_of(c), live(c);
+    LocalBuf<u8> internal(c), is_head(c);
+    LocalBuf<ChRank> ra(c), rb(c);
+    LocalBuf<u64> comp_id(c), link_start(c);
     const u64 n_half = 2 * n_slots;
-    int rc = DISCO_OK;
-    auto body = [&]() -> int {
-        CHK(ensure(c, deg, n));
-        CHK(ensure(c, he, 2 * n));
-        CHK(ensure(c, internal, n));
-        CHK(ensure(c, ra, n_half));
-        CHK(ensure(c, rb, n_half));
-        CHK(ensure(c, live, 1));
-        HIPCHK(c, hipMemsetAsync(deg, 0, n * sizeof(u32), c->stream));
-        hipLaunchKernelGGL(ch_degree_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, deg, he);
-        hipLaunchKernelGGL(ch_internal_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, g, deg, he, n, internal);
-        hipLaunchKernelGGL(ch_init_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, he, ra);
-        HIPCHK(c, hipGetLastError());
-        /* a chain of L half-edges is ranked after ceil(log2 L) rounds and no chain has more than n_half elements; a ring of
-         * absorbable nodes never finishes (its elements are discarded by ch_heads_kernel and left to the host pass), so the
-         * rounds stop at that bound instead of running while anything is live */
-        int max_rounds = 1;
-        while (max_rounds < 32 && (1ull << max_rounds) < n_half) ++max_rounds;
-        for (int round = 0; round < max_rounds; round++) {
-            u32 h_live = 0;
-            HIPCHK(c, hipMemsetAsync(live, 0, sizeof(u32), c->stream));
-            hipLaunchKernelGGL(ch_jump_kernel, dim3(flat_grid(c, n_half)), dim3(256), 0, c->stream, ra, rb, n_half, live);
-            HIPCHK(c, hipMemcpyAsync(&h_live, live, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            std::swap(ra, rb);
-            if (!h_live) break;
-        }
-        release(c, rb);
-        release(c, deg);
-        CHK(ensure(c, is_head, n_slots));
-        CHK(ensure(c, links_of, n_slots));
-        CHK(ensure(c, c->d_ch_dead, std::max<u64>(ne, 1)));
-        HIPCHK(c, hipMemsetAsync(c->d_ch_dead, 0, std::max<u64>(ne, 1), c->stream));
-        hipLaunchKernelGGL(ch_heads_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, ra, is_head, links_of, c->d_ch_dead);
-        CHK(ensure(c, comp_id, n_slots + 1));
-        CHK(ensure(c, link_start, n_slots + 1));
-        u64 n_comp = 0, n_links = 0;
-        CHK((scan_exclusive<u8, u64>(c, is_head, n_slots, comp_id, false, &n_comp)));
-        CHK((scan_exclusive<u32, u64>(c, links_of, n_slots, link_start, false, &n_links)));
-        CHK(ensure(c, c->d_ch_comp, std::max<u64>(n_comp, 1)));
-        CHK(ensure(c, c->d_ch_links, std::max<u64>(n_links, 1)));
-        CHK(ensure(c, c->d_ch_first, std::max<u64>(n_comp, 1)));
-        hipLaunchKernelGGL(ch_emit_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, ra, comp_id, link_start, c->d_ch_comp, c->d_ch_links,
-                           c->d_ch_first);
-        HIPCHK(c, hipGetLastError());
-        /* the residue, compacted in fetch order (the flags and the scan reuse the buffers of the heads, which the emission is through with) */
-        u64 n_res = 0;
-        hipLaunchKernelGGL(ch_residue_flag_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, (const u8 *)c->d_ch_dead, is_head.p);
-        CHK((scan_exclusive<u8, u64>(c, is_head, n_slots, comp_id, false, &n_res)));
-        CHK(ensure(c, c->d_ch_res_pos, std::max<u64>(n_res, 1)));
-        CHK(ensure(c, c->d_ch_res_slot, std::max<u64>(n_res, 1)));
-        hipLaunchKernelGGL(ch_residue_scatter_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, (const u8 *)is_head, (const u64 *)comp_id, c->d_ch_res_pos.p,
-                           c->d_ch_res_slot.p);
-        HIPCHK(c, hipGetLastError());
+    CHK(ensure(c, deg, n));
+    CHK(ensure(c, he, 2 * n));
+    CHK(ensure(c, internal, n));
+    CHK(ensure(c, ra, n_half));
+    CHK(ensure(c, rb, n_half));
+    CHK(ensure(c, live, 1));
+    HIPCHK(c, hipMemsetAsync(deg, 0, n * sizeof(u32), c->stream));
+    hipLaunchKernelGGL(ch_degree_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, deg, he);
+    hipLaunchKernelGGL(ch_internal_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, g, deg, he, n, internal);
+    hipLaunchKernelGGL(ch_init_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, he, ra);
+    HIPCHK(c, hipGetLastError());
+    /* a chain of L half-edges is ranked after ceil(log2 L) rounds and no chain has more than n_half elements; a ring of
+     * absorbable nodes never finishes (its elements are discarded by ch_heads_kernel and left to the host pass), so the
+     * rounds stop at that bound instead of running while anything is live */
+    int max_rounds = 1;
+    while (max_rounds < 32 && (1ull << max_rounds) < n_half) ++max_rounds;
+    for (int round = 0; round < max_rounds; round++) {
+        u32 h_live = 0;
+        HIPCHK(c, hipMemsetAsync(live, 0, sizeof(u32), c->stream));
+        hipLaunchKernelGGL(ch_jump_kernel, dim3(flat_grid(c, n_half)), dim3(256), 0, c->stream, ra, rb, n_half, live);
+        HIPCHK(c, hipMemcpyAsync(&h_live, live, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->ch_res_n = n_res;
-        c->ch_comp_n = n_comp;
-        c->ch_links_n = n_links;
-        c->ch_edges_n = ne;
-        c->ch_ready = true;
-        return DISCO_OK;
-    };
-    rc = body();
+        std::swap<DevBuf<ChRank>>(ra, rb); /* (the memory changes hands; both stay the function's) */
+        if (!h_live) break;
+    }
+    release(c, rb); /* (the ranking is done: not held while the composite edges are emitted) */
     release(c, deg);
-    release(c, he);
-    release(c, internal);
-    release(c, ra);
-    release(c, rb);
-    release(c, live);
-    release(c, is_head);
-    release(c, links_of);
-    release(c, comp_id);
-    release(c, link_start);
-    return rc;
+    CHK(ensure(c, is_head, n_slots));
+    CHK(ensure(c, links_of, n_slots));
+    CHK(ensure(c, c->d_ch_dead, std::max<u64>(ne, 1)));
+    HIPCHK(c, hipMemsetAsync(c->d_ch_dead, 0, std::max<u64>(ne, 1), c->stream));
+    hipLaunchKernelGGL(ch_heads_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, ra, is_head, links_of, c->d_ch_dead);
+    CHK(ensure(c, comp_id, n_slots + 1));
+    CHK(ensure(c, link_start, n_slots + 1));
+    u64 n_comp = 0, n_links = 0;
+    CHK((scan_exclusive<u8, u64>(c, is_head, n_slots, comp_id, false, &n_comp)));
+    CHK((scan_exclusive<u32, u64>(c, links_of, n_slots, link_start, false, &n_links)));
+    CHK(ensure(c, c->d_ch_comp, std::max<u64>(n_comp, 1)));
+    CHK(ensure(c, c->d_ch_links, std::max<u64>(n_links, 1)));
+    CHK(ensure(c, c->d_ch_first, std::max<u64>(n_comp, 1)));
+    hipLaunchKernelGGL(ch_emit_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, internal, ra, comp_id, link_start, c->d_ch_comp, c->d_ch_links,
+                       c->d_ch_first);
+    HIPCHK(c, hipGetLastError());
+    /* the residue, compacted in fetch order (the flags and the scan reuse the buffers of the heads, which the emission is through with) */
+    u64 n_res = 0;
+    hipLaunchKernelGGL(ch_residue_flag_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, (const u8 *)c->d_ch_dead, is_head.p);
+    CHK((scan_exclusive<u8, u64>(c, is_head, n_slots, comp_id, false, &n_res)));
+    CHK(ensure(c, c->d_ch_res_pos, std::max<u64>(n_res, 1)));
+    CHK(ensure(c, c->d_ch_res_slot, std::max<u64>(n_res, 1)));
+    hipLaunchKernelGGL(ch_residue_scatter_kernel, dim3(flat_grid(c, n_slots)), dim3(256), 0, c->stream, g, (const u8 *)is_head, (const u64 *)comp_id, c->d_ch_res_pos.p,
+                       c->d_ch_res_slot.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ch_res_n = n_res;
+    c->ch_comp_n = n_comp;
+    c->ch_links_n = n_links;
+    c->ch_edges_n = ne;
+    c->ch_ready = true;
+    return DISCO_OK;
 }
 
 int disco_contract_chains(disco_ctx *c, uint32_t min_overlap_simplify, uint64_t *n_composite, uint64_t *n_links)
@@ -5428,8 +5252,8 @@ int disco_contract_chains_of(disco_ctx *c, const disco_edge *edges, uint64_t n_e
         c->ch_comp_n = c->ch_links_n = c->ch_edges_n = c->ch_res_n = 0;
         c->ch_ready = true;
     } else {
-        DevBuf<u64> d_src, d_ent, d_pos;
-        DevBuf<u8> d_valid;
+        LocalBuf<u64> d_src(c), d_ent(c), d_pos(c);
+        LocalBuf<u8> d_valid(c);
         std::unique_ptr<u64[]> hs(new u64[n_edges]), he(new u64[n_edges]);
         std::atomic<bool> bad{false};
         parallel_for(n_edges, [&](u64 b, u64 e_) {
@@ -5440,26 +5264,15 @@ int disco_contract_chains_of(disco_ctx *c, const disco_edge *edges, uint64_t n_e
             }
         });
         if (bad) return fail(c, DISCO_E_ARG, "disco_contract_chains_of: an edge names a read the context does not hold");
-        int rc = DISCO_OK;
-        do {
-            if ((rc = ensure(c, d_src, n_edges)) != DISCO_OK) break;
-            if ((rc = ensure(c, d_ent, n_edges)) != DISCO_OK) break;
-            if ((rc = ensure(c, d_pos, n_edges)) != DISCO_OK) break;
-            if ((rc = ensure(c, d_valid, n_edges)) != DISCO_OK) break;
-            if (hipMemcpyAsync(d_src, hs.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                hipMemcpyAsync(d_ent, he.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                hipMemsetAsync(d_valid, 1, n_edges, c->stream) != hipSuccess) {
-                rc = fail(c, DISCO_E_HIP, "disco_contract_chains_of: upload failed");
-                break;
-            }
-            hipLaunchKernelGGL(iota_u64_kernel, dim3(flat_grid(c, n_edges)), dim3(256), 0, c->stream, d_pos, n_edges);
-            rc = contract_chains(c, d_src, d_ent, d_valid, d_pos, n_edges, n_edges, c->n, min_overlap_simplify);
-        } while (0);
-        release(c, d_src);
-        release(c, d_ent);
-        release(c, d_pos);
-        release(c, d_valid);
-        if (rc != DISCO_OK) return rc;
+        CHK(ensure(c, d_src, n_edges));
+        CHK(ensure(c, d_ent, n_edges));
+        CHK(ensure(c, d_pos, n_edges));
+        CHK(ensure(c, d_valid, n_edges));
+        if (hipMemcpyAsync(d_src, hs.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(d_ent, he.get(), n_edges * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipMemsetAsync(d_valid, 1, n_edges, c->stream) != hipSuccess)
+            return fail(c, DISCO_E_HIP, "disco_contract_chains_of: upload failed");
+        hipLaunchKernelGGL(iota_u64_kernel, dim3(flat_grid(c, n_edges)), dim3(256), 0, c->stream, d_pos, n_edges);
+        CHK(contract_chains(c, d_src, d_ent, d_valid, d_pos, n_edges, n_edges, c->n, min_overlap_simplify));
     }
     if (n_composite) *n_composite = c->ch_comp_n;
     if (n_links) *n_links = c->ch_links_n;
@@ -5490,22 +5303,17 @@ int64_t disco_fetch_chain_residue(disco_ctx *c, uint64_t *edge_index, disco_edge
     if (nr == 0) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     static_assert(sizeof(disco_edge) == sizeof(ChEdgeOut) && sizeof(uint64_t) == sizeof(u64), "residue records");
-    DevBuf<ChEdgeOut> rec;
-    auto body = [&]() -> int {
-        if (edge_index) HIPCHK(c, hipMemcpyAsync(edge_index, c->d_ch_res_pos, nr * 8, hipMemcpyDeviceToHost, c->stream));
-        if (edges) {
-            CHK(ensure(c, rec, nr));
-            hipLaunchKernelGGL(ch_residue_records_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const u64 *)c->d_out_src, (const u64 *)c->d_out_ent, (const u16 *)c->d_len,
-                               (const u64 *)c->d_ch_res_slot, nr, rec.p);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(edges, rec, nr * sizeof(ChEdgeOut), hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return DISCO_OK;
-    };
-    const int rc = body();
-    release(c, rec);
-    return rc != DISCO_OK ? rc : (int64_t)nr;
+    LocalBuf<ChEdgeOut> rec(c);
+    if (edge_index) HIPCHK(c, hipMemcpyAsync(edge_index, c->d_ch_res_pos, nr * 8, hipMemcpyDeviceToHost, c->stream));
+    if (edges) {
+        CHK(ensure(c, rec, nr));
+        hipLaunchKernelGGL(ch_residue_records_kernel, dim3(flat_grid(c, nr)), dim3(256), 0, c->stream, (const u64 *)c->d_out_src, (const u64 *)c->d_out_ent, (const u16 *)c->d_len,
+                           (const u64 *)c->d_ch_res_slot, nr, rec.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(edges, rec, nr * sizeof(ChEdgeOut), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return (int64_t)nr;
 }
 
 int disco_fetch_chain_first_edges(disco_ctx *c, uint64_t *first_edge)
@@ -5526,20 +5334,15 @@ int disco_fetch_chain_end_links(disco_ctx *c, disco_chain_link *first, disco_cha
     const u64 nc = c->ch_comp_n;
     if (nc == 0) return DISCO_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    DevBuf<ChainLinkOut> d;
-    auto body = [&]() -> int {
-        CHK(ensure(c, d, 2 * nc));
-        hipLaunchKernelGGL(ch_end_links_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, (const ChainEdgeOut *)c->d_ch_comp, (const ChainLinkOut *)c->d_ch_links,
-                           (const u16 *)c->d_len, nc, d.p, d.p + nc);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(first, d.p, nc * sizeof(ChainLinkOut), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(last_reversed, d.p + nc, nc * sizeof(ChainLinkOut), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return DISCO_OK;
-    };
-    const int rc = body();
-    release(c, d);
-    return rc;
+    LocalBuf<ChainLinkOut> d(c);
+    CHK(ensure(c, d, 2 * nc));
+    hipLaunchKernelGGL(ch_end_links_kernel, dim3(flat_grid(c, nc)), dim3(256), 0, c->stream, (const ChainEdgeOut *)c->d_ch_comp, (const ChainLinkOut *)c->d_ch_links,
+                       (const u16 *)c->d_len, nc, d.p, d.p + nc);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(first, d.p, nc * sizeof(ChainLinkOut), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(last_reversed, d.p + nc, nc * sizeof(ChainLinkOut), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DISCO_OK;
 }
 
 /* ---- the lines of the ParSimpleEdges files from the host pass's description and the device's link arrays (disco_partext.h) ---- */
@@ -5551,8 +5354,8 @@ int64_t disco_format_par_simple(disco_ctx *c, uint32_t n_files, const uint64_t *
     if (!c->ch_ready) return fail(c, DISCO_E_STATE, "disco_format_par_simple: run disco_contract_chains first");
     HIPCHK(c, hipSetDevice(c->device));
     for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
-    c->ptext_bytes = 0;
-    c->ptext_off.assign((size_t)n_files + 1, 0);
+    c->ptext.bytes = 0;
+    c->ptext.off.assign((size_t)n_files + 1, 0);
     if (n_edges == 0) return 0;
     /* the description is small: everything a lane will index with is checked here, before anything is launched */
     std::vector<disco_chain_edge> comp(c->ch_comp_n);
@@ -5586,95 +5389,65 @@ int64_t disco_format_par_simple(disco_ctx *c, uint32_t n_files, const uint64_t *
     }
     const u64 n_items = edge_item[n_edges];
     for (; file < n_files; file++) first_item[(size_t)file + 1] = n_items;
-    DevBuf<disco_ps_edge> d_edges;
-    DevBuf<disco_ps_piece> d_pieces;
-    DevBuf<u64> d_edge_item, d_piece_link, d_first_item, d_findex, place, d_off;
-    DevBuf<u8> bytes;
-    auto body = [&]() -> int {
-        CHK(ensure(c, d_edges, n_edges));
-        CHK(ensure(c, d_pieces, std::max<u64>(n_pieces, 1)));
-        CHK(ensure(c, d_edge_item, n_edges + 1));
-        CHK(ensure(c, d_piece_link, n_pieces + 1));
-        CHK(ensure(c, d_first_item, (u64)n_files + 1));
-        CHK(ensure(c, d_off, (u64)n_files + 1));
-        CHK(ensure(c, bytes, n_items));
-        CHK(ensure(c, place, n_items + 1));
-        HIPCHK(c, hipMemcpyAsync(d_edges, edges, n_edges * sizeof(disco_ps_edge), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_pieces, pieces, n_pieces * sizeof(disco_ps_piece), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_edge_item, edge_item.data(), (n_edges + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_piece_link, piece_link.data(), (n_pieces + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_first_item, first_item.data(), ((size_t)n_files + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        if (file_index) {
-            CHK(ensure(c, d_findex, c->n));
-            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
-        }
-        PsView g;
-        g.edges = d_edges;
-        g.pieces = d_pieces;
-        g.edge_item = (const uint64_t *)d_edge_item.p;
-        g.piece_link = (const uint64_t *)d_piece_link.p;
-        g.comp = (const disco_chain_edge *)c->d_ch_comp.p;
-        g.links = (const disco_chain_link *)c->d_ch_links.p;
-        g.len = c->d_len;
-        g.file_index = (const uint64_t *)d_findex.p;
-        g.n_edges = n_edges;
-        g.n_pieces = n_pieces;
-        g.n_items = n_items;
-        hipLaunchKernelGGL(ptext_measure_kernel, dim3(flat_grid(c, n_items)), dim3(256), 0, c->stream, g, bytes.p);
-        u64 total = 0;
-        CHK((scan_exclusive<u8, u64>(c, bytes, n_items, place, true, &total)));
-        hipLaunchKernelGGL(ptext_offsets_kernel, dim3(1), dim3(256), 0, c->stream, (const uint64_t *)d_first_item.p, (const u64 *)place, n_files, (uint64_t *)d_off.p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->ptext_off.data(), d_off, ((size_t)n_files + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        CHK(ensure(c, c->d_ptext, std::max<u64>(total, 1)));
-        hipLaunchKernelGGL(ptext_write_kernel, dim3(flat_grid(c, n_items)), dim3(256), 0, c->stream, g, (const u64 *)place, c->d_ptext.p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->ptext_bytes = total;
-        return DISCO_OK;
-    };
-    const int rc = body();
-    release(c, d_edges);
-    release(c, d_pieces);
-    release(c, d_edge_item);
-    release(c, d_piece_link);
-    release(c, d_first_item);
-    release(c, d_findex);
-    release(c, place);
-    release(c, d_off);
-    release(c, bytes);
-    if (rc != DISCO_OK) {
-        c->ptext_off.assign((size_t)n_files + 1, 0);
-        return rc;
+    LocalBuf<disco_ps_edge> d_edges(c);
+    LocalBuf<disco_ps_piece> d_pieces(c);
+    LocalBuf<u64> d_edge_item(c), d_piece_link(c), d_first_item(c), d_findex(c), place(c), d_off(c);
+    LocalBuf<u8> bytes(c);
+    std::vector<u64> off((size_t)n_files + 1, 0); /* (the context's offsets — all 0 — change only once the text is there) */
+    CHK(ensure(c, d_edges, n_edges));
+    CHK(ensure(c, d_pieces, std::max<u64>(n_pieces, 1)));
+    CHK(ensure(c, d_edge_item, n_edges + 1));
+    CHK(ensure(c, d_piece_link, n_pieces + 1));
+    CHK(ensure(c, d_first_item, (u64)n_files + 1));
+    CHK(ensure(c, d_off, (u64)n_files + 1));
+    CHK(ensure(c, bytes, n_items));
+    CHK(ensure(c, place, n_items + 1));
+    HIPCHK(c, hipMemcpyAsync(d_edges, edges, n_edges * sizeof(disco_ps_edge), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_pieces, pieces, n_pieces * sizeof(disco_ps_piece), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_edge_item, edge_item.data(), (n_edges + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_piece_link, piece_link.data(), (n_pieces + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_first_item, first_item.data(), ((size_t)n_files + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (file_index) {
+        CHK(ensure(c, d_findex, c->n));
+        HIPCHK(c, hipMemcpyAsync(d_findex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
     }
-    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = c->ptext_off[f];
+    PsView g;
+    g.edges = d_edges;
+    g.pieces = d_pieces;
+    g.edge_item = (const uint64_t *)d_edge_item.p;
+    g.piece_link = (const uint64_t *)d_piece_link.p;
+    g.comp = (const disco_chain_edge *)c->d_ch_comp.p;
+    g.links = (const disco_chain_link *)c->d_ch_links.p;
+    g.len = c->d_len;
+    g.file_index = (const uint64_t *)d_findex.p;
+    g.n_edges = n_edges;
+    g.n_pieces = n_pieces;
+    g.n_items = n_items;
+    hipLaunchKernelGGL(ptext_measure_kernel, dim3(flat_grid(c, n_items)), dim3(256), 0, c->stream, g, bytes.p);
+    u64 total = 0;
+    CHK((scan_exclusive<u8, u64>(c, bytes, n_items, place, true, &total)));
+    hipLaunchKernelGGL(ptext_offsets_kernel, dim3(1), dim3(256), 0, c->stream, (const uint64_t *)d_first_item.p, (const u64 *)place, n_files, (uint64_t *)d_off.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(off.data(), d_off, ((size_t)n_files + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    CHK(ensure(c, c->ptext.d, std::max<u64>(total, 1)));
+    hipLaunchKernelGGL(ptext_write_kernel, dim3(flat_grid(c, n_items)), dim3(256), 0, c->stream, g, (const u64 *)place, c->ptext.d.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ptext.off.swap(off);
+    c->ptext.bytes = total;
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = c->ptext.off[f];
     if (getenv("DISCO_VERBOSE"))
         fprintf(stderr, "[disco] par-simple lines: %llu edges, %llu pieces, %llu items, %llu bytes\n", (unsigned long long)n_edges, (unsigned long long)n_pieces,
-                (unsigned long long)n_items, (unsigned long long)c->ptext_bytes);
-    return (int64_t)c->ptext_bytes;
+                (unsigned long long)n_items, (unsigned long long)c->ptext.bytes);
+    return (int64_t)c->ptext.bytes;
 }
 
-int disco_fetch_par_simple_text(disco_ctx *c, char *out, uint64_t cap)
-{
-    if (!c || (!out && c->ptext_bytes)) return DISCO_E_ARG;
-    if (cap < c->ptext_bytes) return fail(c, DISCO_E_ARG, "disco_fetch_par_simple_text: need room for %llu bytes", (unsigned long long)c->ptext_bytes);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->ptext_bytes) {
-        HIPCHK(c, hipMemcpyAsync(out, c->d_ptext, c->ptext_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return DISCO_OK;
-}
+int disco_fetch_par_simple_text(disco_ctx *c, char *out, uint64_t cap) { return c ? fetch_text(c, "disco_fetch_par_simple_text", c->ptext, out, cap) : DISCO_E_ARG; }
 
-int disco_write_par_simple_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t host_threads)
+int disco_write_par_simple_text(disco_ctx *c, const int *fds, uint32_t n_files, uint32_t)
 {
     DISCO_TRACE("disco_write_par_simple_text");
-    if (!c || !fds) return DISCO_E_ARG;
-    if (c->ptext_off.size() != (size_t)n_files + 1) return fail(c, DISCO_E_STATE, "disco_write_par_simple_text: run disco_format_par_simple for %u files first", n_files);
-    HIPCHK(c, hipSetDevice(c->device));
-    (void)host_threads;
-    if (c->ptext_bytes == 0) return DISCO_OK;
-    return write_text_through_ring(c, "disco_write_par_simple_text", c->d_ptext, c->ptext_off, fds, n_files);
+    return c ? write_text(c, "disco_write_par_simple_text", "disco_format_par_simple", c->ptext, fds, n_files) : DISCO_E_ARG;
 }
 
 int disco_set_query_order(disco_ctx *c, const void *d_order_u64)
@@ -6192,36 +5965,29 @@ static int dist_partitioned_probe(disco_ctx *c)
     } else
         n_slow = nloc;
     /* the long way: queries per read, scan, fill behind the fast ones */
-    DevBuf<u32> slow_cnt;
-    DevBuf<u64> slow_start;
-    u64 nq_slow = 0;
-    int rc = DISCO_OK;
-    auto slow_count = [&]() -> int {
-        if (!n_slow) return DISCO_OK;
+    u64 nq_slow = 0, nqs = 0;
+    { /* (the two buffers of the long way are gone before the exchange below) */
+    LocalBuf<u32> slow_cnt(c);
+    LocalBuf<u64> slow_start(c);
+    if (n_slow) {
         CHK(ensure(c, slow_cnt, n_slow));
         CHK(ensure(c, slow_start, n_slow + 1));
         if (seeded) hipLaunchKernelGGL((pq_slow_kernel<true, true>), dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)nullptr, (ulonglong2 *)nullptr);
         else if (c->ks > 64) hipLaunchKernelGGL(pq_slow_kernel<true>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)nullptr, (ulonglong2 *)nullptr);
         else hipLaunchKernelGGL(pq_slow_kernel<false>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)nullptr, (ulonglong2 *)nullptr);
         CHK((scan_exclusive<u32, u64>(c, slow_cnt, n_slow, slow_start, false, &nq_slow)));
-        return DISCO_OK;
-    };
-    rc = slow_count();
-    const u64 nqs = nq_fast + nq_slow;
-    if (rc == DISCO_OK) rc = ensure(c, c->d_x16a, std::max<u64>(2 * nqs, 1)); /* flat list | partitioned by owner */
-    if (rc == DISCO_OK) {
-        HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
-        if (have_runs && nloc) make(c->d_x16a, false);
-        if (n_slow) {
-            if (seeded) hipLaunchKernelGGL((pq_slow_kernel<true, true>), dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
-            else if (c->ks > 64) hipLaunchKernelGGL(pq_slow_kernel<true>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
-            else hipLaunchKernelGGL(pq_slow_kernel<false>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
-        }
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, DISCO_E_HIP, "dist_partitioned_probe: query kernels failed");
     }
-    release(c, slow_cnt);
-    release(c, slow_start);
-    CHK(rc);
+    nqs = nq_fast + nq_slow;
+    CHK(ensure(c, c->d_x16a, std::max<u64>(2 * nqs, 1))); /* flat list | partitioned by owner */
+    HIPCHK(c, hipMemsetAsync(c->d_list_n, 0, sizeof(u64), c->stream));
+    if (have_runs && nloc) make(c->d_x16a, false);
+    if (n_slow) {
+        if (seeded) hipLaunchKernelGGL((pq_slow_kernel<true, true>), dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
+        else if (c->ks > 64) hipLaunchKernelGGL(pq_slow_kernel<true>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
+        else hipLaunchKernelGGL(pq_slow_kernel<false>, dim3(flat_grid(c, n_slow, 64)), dim3(64), 0, c->stream, v, slow, n_slow, lo, r, slow_cnt, (const u64 *)slow_start, c->d_x16a + nq_fast);
+    }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, DISCO_E_HIP, "dist_partitioned_probe: query kernels failed");
+    }
     c->slow_rows = have_runs ? n_slow : 0;
     /* 2. queries -> owners of their buckets */
     std::vector<u64> scnt, rcnt;
@@ -6664,49 +6430,48 @@ static int dist_complete_twins(disco_ctx *c, bool *done, u64 *asym_total)
     return DISCO_OK;
 }
 
-/* ---- order-dependent regime: everybody gets the whole adjacency and finishes the pass on its own --------------------- */
-static int dist_irregular(disco_ctx *c, const std::vector<u64> &adj_totals)
+/* every rank's degrees and rows on every rank, imported as the context's adjacency; with them the bitmaps of the reads that dropped a hit */
+static int dist_gather_adjacency(disco_ctx *c, const std::vector<u64> &adj_totals, u64 total)
 {
-    DISCO_TRACE("dist_irregular");
     const u32 G = (u32)c->comm->world, r = (u32)c->comm->rank;
-    const u64 lo = c->q_lo, hi = c->q_hi, nloc = hi - lo, per = c->per;
-    DevBuf<u32> deg_all;
-    DevBuf<u64> rows_all;
-    const u64 total = vsum(adj_totals);
+    const u64 per = c->per;
+    LocalBuf<u32> deg_all(c);
+    LocalBuf<u64> rows_all(c);
     CHK(ensure(c, deg_all, (u64)G * per));
     CHK(ensure(c, rows_all, std::max<u64>(total, 1)));
     u64 base = 0;
     for (u32 p = 0; p < r; p++) base += adj_totals[p];
-    int rc = DISCO_OK;
     const auto t0 = HClock::now();
-    do {
-        if ((rc = hipMemsetAsync(deg_all + (u64)r * per, 0, per * sizeof(u32), c->stream) == hipSuccess ? DISCO_OK : DISCO_E_HIP) != DISCO_OK) break;
-        if ((rc = disco_export_adjacency(c, deg_all + (u64)r * per, rows_all + base)) != DISCO_OK) break;
-        if ((rc = c->comm->all_gather(deg_all + (u64)r * per, deg_all, per * sizeof(u32), c->stream)) != DISCO_OK) break;
-        std::vector<size_t> off((size_t)G), cnt((size_t)G);
-        size_t a = 0;
-        for (u32 p = 0; p < G; p++) {
-            off[p] = a;
-            cnt[p] = adj_totals[p] * sizeof(u64);
-            a += cnt[p];
-            if (p != r) c->dinfo.bytes_sent[DISCO_X_ADJACENCY] += cnt[r] + per * sizeof(u32);
-        }
-        if ((rc = c->comm->all_gather_v(rows_all + base, rows_all, off.data(), cnt.data(), c->stream)) != DISCO_OK) break;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) {
-            rc = DISCO_E_HIP;
-            break;
-        }
-        c->dinfo.ms[DISCO_X_ADJACENCY] += ms_since(t0);
-        (void)nloc;
-        if ((rc = disco_import_adjacency(c, deg_all, rows_all, total)) != DISCO_OK) break;
-        /* which reads dropped a hit (ranges are multiples of 64 reads: whole bitmap words): the twin search below is limited to them */
-        if ((rc = c->comm->all_gather(c->d_dropbits + (u64)r * per / 64, c->d_dropbits, per / 8, c->stream)) != DISCO_OK) break;
-        c->dinfo.bytes_sent[DISCO_X_ADJACENCY] += (u64)(G - 1) * (per / 8);
-        c->drop_lo = 0;
-        c->drop_hi = c->n;
-    } while (0);
-    release(c, deg_all);
-    release(c, rows_all);
+    if (hipMemsetAsync(deg_all + (u64)r * per, 0, per * sizeof(u32), c->stream) != hipSuccess) return DISCO_E_HIP;
+    CHK(disco_export_adjacency(c, deg_all + (u64)r * per, rows_all + base));
+    CHK(c->comm->all_gather(deg_all + (u64)r * per, deg_all, per * sizeof(u32), c->stream));
+    std::vector<size_t> off((size_t)G), cnt((size_t)G);
+    size_t a = 0;
+    for (u32 p = 0; p < G; p++) {
+        off[p] = a;
+        cnt[p] = adj_totals[p] * sizeof(u64);
+        a += cnt[p];
+        if (p != r) c->dinfo.bytes_sent[DISCO_X_ADJACENCY] += cnt[r] + per * sizeof(u32);
+    }
+    CHK(c->comm->all_gather_v(rows_all + base, rows_all, off.data(), cnt.data(), c->stream));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return DISCO_E_HIP;
+    c->dinfo.ms[DISCO_X_ADJACENCY] += ms_since(t0);
+    CHK(disco_import_adjacency(c, deg_all, rows_all, total));
+    /* which reads dropped a hit (ranges are multiples of 64 reads: whole bitmap words): the twin search below is limited to them */
+    CHK(c->comm->all_gather(c->d_dropbits + (u64)r * per / 64, c->d_dropbits, per / 8, c->stream));
+    c->dinfo.bytes_sent[DISCO_X_ADJACENCY] += (u64)(G - 1) * (per / 8);
+    c->drop_lo = 0;
+    c->drop_hi = c->n;
+    return DISCO_OK;
+}
+
+/* ---- order-dependent regime: everybody gets the whole adjacency and finishes the pass on its own --------------------- */
+static int dist_irregular(disco_ctx *c, const std::vector<u64> &adj_totals)
+{
+    DISCO_TRACE("dist_irregular");
+    const u64 lo = c->q_lo, hi = c->q_hi;
+    const u64 total = vsum(adj_totals);
+    int rc = dist_gather_adjacency(c, adj_totals, total); /* (its buffers are gone before the rows are merged and marked) */
     if (rc != DISCO_OK) return c->err.empty() ? fail(c, rc, "adjacency exchange: %s", c->comm->err.c_str()) : rc;
     CHK(disco_symmetrize(c, 1, nullptr));
     CHK(merge_extras(c));
@@ -6927,14 +6692,14 @@ static int dist_validate(disco_ctx *c)
     c->job_n_long = 0;
     c->job_short_max = c->max_len;
     if (c->max_len > (u32)DISCO_SHORT_MAX) {
-        DevBuf<u64> d_ls;
+        LocalBuf<u64> d_ls(c);
         u64 hls[2] = {0, 0};
         CHK(ensure(c, d_ls, 2));
         HIPCHK(c, hipMemsetAsync(d_ls, 0, 2 * sizeof(u64), c->stream));
         if (nloc) hipLaunchKernelGGL(long_stats_kernel, dim3(flat_grid(c, nloc)), dim3(256), 0, c->stream, (const u16 *)c->d_len, c->q_lo, c->q_hi, d_ls);
         HIPCHK(c, hipMemcpyAsync(hls, d_ls, sizeof hls, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        release(c, d_ls);
+        release(c, d_ls); /* (before the ranks meet) */
         CHK(host_reduce(c, &hls[0], 1));
         CHK(host_reduce(c, &hls[1], 1, true));
         c->job_n_long = hls[0];
@@ -7655,8 +7420,8 @@ int64_t disco_dist_format_contained(disco_ctx *c, uint32_t n_files, const uint64
     if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_format_contained: more than 2^31 reads");
     HIPCHK(c, hipSetDevice(c->device));
     for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
-    c->ctext_bytes = 0;
-    c->ctext_off.assign((size_t)n_files + 1, 0);
+    c->ctext.bytes = 0;
+    c->ctext.off.assign((size_t)n_files + 1, 0);
     const u64 G = (u64)c->comm->world, r = (u64)c->comm->rank, n = c->n, F = n_files;
     if (c->d_best.cap < c->per * G) return fail(c, DISCO_E_STATE, "disco_dist_format_contained: the containment keys of the last pass are gone");
     CHK(settle_keys(c));
@@ -7671,11 +7436,96 @@ int64_t disco_dist_format_contained(disco_ctx *c, uint32_t n_files, const uint64
     const int rc = dist_agree(c, "disco_dist_format_contained", nb < 0 ? (int)nb : DISCO_OK);
     if (rc != DISCO_OK) {
         for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
-        c->ctext_bytes = 0;
-        c->ctext_off.assign((size_t)n_files + 1, 0);
+        c->ctext.bytes = 0;
+        c->ctext.off.assign((size_t)n_files + 1, 0);
         return rc;
     }
     return nb;
+}
+
+/* the buffers of disco_dist_format_edges and the figures its steps share */
+struct DistEdgeText {
+    LocalBuf<u32> src32;
+    LocalBuf<u64> src, ent, d_findex, within, place;
+    LocalBuf<u8> bytes, sel;
+    LocalBuf<u16> efile;
+    uint32_t n_files = 0, f_lo = 0, f_hi = 0; /* the rank's files: [f_lo, f_hi) */
+    u64 ne = 0;                              /* edges of the job */
+    explicit DistEdgeText(disco_ctx *c) : src32(c), src(c), ent(c), d_findex(c), within(c), place(c), bytes(c), sel(c), efile(c) {}
+};
+
+/* 2. everything the rank will need, and its own edges compacted to where they lie in the job's list (from first_own on) */
+static int dist_edge_text_prepare(disco_ctx *c, DistEdgeText &T, const uint64_t *file_index, u64 first_own)
+{
+    const u64 ne = T.ne, ne_own = c->n_out;
+    CHK(ensure(c, T.src32, ne));
+    CHK(ensure(c, T.ent, ne));
+    CHK(ensure(c, T.src, ne));
+    CHK(ensure(c, T.efile, ne));
+    CHK(ensure(c, T.bytes, ne));
+    if (T.f_hi > T.f_lo) {
+        CHK(ensure(c, T.sel, ne));
+        CHK(ensure(c, T.within, ne + 1));
+        CHK(ensure(c, T.place, ne));
+    }
+    if (file_index) {
+        CHK(ensure(c, T.d_findex, c->n));
+        HIPCHK(c, hipMemcpyAsync(T.d_findex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    if (ne_own) {
+        if (c->out_dense) {
+            hipLaunchKernelGGL(emit_src32_kernel, dim3(flat_grid(c, ne_own)), dim3(256), 0, c->stream, c->d_out_src, ne_own, T.src32.p + first_own);
+            HIPCHK(c, hipMemcpyAsync(T.ent.p + first_own, c->d_out_ent, ne_own * 8, hipMemcpyDeviceToDevice, c->stream));
+        } else
+            hipLaunchKernelGGL(emit_compact32_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos, c->out_used,
+                               T.src32.p + first_own, T.ent.p + first_own);
+        HIPCHK(c, hipGetLastError());
+    }
+    return DISCO_OK;
+}
+
+/* steps 2 to 5 of disco_dist_format_edges. *gathered: every rank is past the first verdict, so all of them meet again at the end */
+static int dist_edge_text(disco_ctx *c, DistEdgeText &T, const uint64_t *file_index, const std::vector<u64> &cnt, const std::vector<u64> &first, bool *gathered)
+{
+    const size_t G = (size_t)c->comm->world, r = (size_t)c->comm->rank;
+    const u64 ne = T.ne;
+    CHK(dist_agree(c, "disco_dist_format_edges", dist_edge_text_prepare(c, T, file_index, first[r])));
+    *gathered = true;
+    /* 3. the job's edges on every rank, in the order of the ranks */
+    std::vector<size_t> off(G), len(G);
+    for (size_t p = 0; p < G; p++) {
+        off[p] = (size_t)first[p] * 4;
+        len[p] = (size_t)cnt[p] * 4;
+    }
+    COMM_CHK(c, c->comm->all_gather_v(T.src32.p + first[r], T.src32.p, off.data(), len.data(), c->stream));
+    for (size_t p = 0; p < G; p++) {
+        off[p] *= 2;
+        len[p] *= 2;
+    }
+    COMM_CHK(c, c->comm->all_gather_v(T.ent.p + first[r], T.ent.p, off.data(), len.data(), c->stream));
+    hipLaunchKernelGGL(text_widen_src_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, (const u32 *)T.src32, ne, T.src.p);
+    HIPCHK(c, hipGetLastError());
+    /* 4. the files of the edges: on the device they stay */
+    const int64_t part = partition_edges(c, T.src, T.ent, nullptr, nullptr, ne, ne, c->n, T.n_files, nullptr, T.efile.p);
+    if (part < 0) return (int)part;
+    /* 5. all lines measured; those of the rank's files placed and written */
+    TextView g;
+    g.src = T.src;
+    g.ent = T.ent;
+    g.valid = nullptr;
+    g.pos = nullptr;
+    g.len = c->d_len;
+    g.file_index = T.d_findex;
+    g.n_slots = ne;
+    CHK(place_edge_lines(c, g, ne, T.efile, T.n_files, T.f_lo, T.f_hi, T.bytes, T.sel, T.within, T.place, (uint64_t *)c->text.off.data()));
+    const u64 base = c->text.off[T.n_files];
+    CHK(ensure(c, c->text.d, std::max<u64>(base, 1)));
+    if (base)
+        hipLaunchKernelGGL(text_write_owned_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, g, (const u64 *)T.place, (const u16 *)T.efile, T.f_lo, T.f_hi, c->text.d.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->text.bytes = base;
+    return DISCO_OK;
 }
 
 /* the edge lines: the ranks' edges — compacted, 12 bytes each — are all-gathered, every rank cuts the same files out of the same list
@@ -7693,8 +7543,8 @@ int64_t disco_dist_format_edges(disco_ctx *c, uint32_t n_files, const uint64_t *
     if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "disco_dist_format_edges: more than 2^31 reads");
     HIPCHK(c, hipSetDevice(c->device));
     for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = 0;
-    c->text_bytes = 0;
-    c->text_off.assign((size_t)n_files + 1, 0);
+    c->text.bytes = 0;
+    c->text.off.assign((size_t)n_files + 1, 0);
     const size_t G = (size_t)c->comm->world, r = (size_t)c->comm->rank;
     const u64 ne_own = c->n_out;
     /* 1. who has how many edges */
@@ -7709,107 +7559,24 @@ int64_t disco_dist_format_edges(disco_ctx *c, uint32_t n_files, const uint64_t *
     if (ne == 0) return 0;
     uint32_t f_lo, f_hi;
     dist_own_files(c, n_files, &f_lo, &f_hi);
-    DevBuf<u32> src32;
-    DevBuf<u64> src, ent, d_findex, within, place;
-    DevBuf<u8> bytes, sel;
-    DevBuf<u16> efile;
-    /* 2. everything the rank will need, and its own edges compacted to where they lie in the job's list */
-    auto prepare = [&]() -> int {
-        CHK(ensure(c, src32, ne));
-        CHK(ensure(c, ent, ne));
-        CHK(ensure(c, src, ne));
-        CHK(ensure(c, efile, ne));
-        CHK(ensure(c, bytes, ne));
-        if (f_hi > f_lo) {
-            CHK(ensure(c, sel, ne));
-            CHK(ensure(c, within, ne + 1));
-            CHK(ensure(c, place, ne));
-        }
-        if (file_index) {
-            CHK(ensure(c, d_findex, c->n));
-            HIPCHK(c, hipMemcpyAsync(d_findex, file_index, c->n * 8, hipMemcpyHostToDevice, c->stream));
-        }
-        if (ne_own) {
-            if (c->out_dense) {
-                hipLaunchKernelGGL(emit_src32_kernel, dim3(flat_grid(c, ne_own)), dim3(256), 0, c->stream, c->d_out_src, ne_own, src32.p + first[r]);
-                HIPCHK(c, hipMemcpyAsync(ent.p + first[r], c->d_out_ent, ne_own * 8, hipMemcpyDeviceToDevice, c->stream));
-            } else
-                hipLaunchKernelGGL(emit_compact32_kernel, dim3(flat_grid(c, c->out_used)), dim3(256), 0, c->stream, c->d_out_src, c->d_out_ent, c->d_out_valid, c->d_out_pos, c->out_used,
-                                   src32.p + first[r], ent.p + first[r]);
-            HIPCHK(c, hipGetLastError());
-        }
-        return DISCO_OK;
-    };
-    auto body = [&](bool *gathered) -> int {
-        CHK(dist_agree(c, "disco_dist_format_edges", prepare()));
-        *gathered = true; /* (every rank is past the verdict: all of them meet again at the end) */
-        /* 3. the job's edges on every rank, in the order of the ranks */
-        std::vector<size_t> off(G), len(G);
-        for (size_t p = 0; p < G; p++) {
-            off[p] = (size_t)first[p] * 4;
-            len[p] = (size_t)cnt[p] * 4;
-        }
-        COMM_CHK(c, c->comm->all_gather_v(src32.p + first[r], src32.p, off.data(), len.data(), c->stream));
-        for (size_t p = 0; p < G; p++) {
-            off[p] *= 2;
-            len[p] *= 2;
-        }
-        COMM_CHK(c, c->comm->all_gather_v(ent.p + first[r], ent.p, off.data(), len.data(), c->stream));
-        hipLaunchKernelGGL(text_widen_src_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, (const u32 *)src32, ne, src.p);
-        HIPCHK(c, hipGetLastError());
-        /* 4. the files of the edges: on the device they stay */
-        const int64_t part = partition_edges(c, src, ent, nullptr, nullptr, ne, ne, c->n, n_files, nullptr, efile.p);
-        if (part < 0) return (int)part;
-        /* 5. all lines measured; those of the rank's files placed and written */
-        TextView g;
-        g.src = src;
-        g.ent = ent;
-        g.valid = nullptr;
-        g.pos = nullptr;
-        g.len = c->d_len;
-        g.file_index = d_findex;
-        g.n_slots = ne;
-        hipLaunchKernelGGL(text_measure_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, g, bytes.p);
-        u64 base = 0;
-        for (uint32_t f = 0; f < n_files; f++) {
-            c->text_off[f] = base;
-            if (f < f_lo || f >= f_hi) continue;
-            u64 total = 0;
-            hipLaunchKernelGGL(text_select_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, (const u8 *)bytes, (const u16 *)efile, ne, f, sel.p);
-            CHK((scan_exclusive<u8, u64>(c, sel, ne, within, false, &total)));
-            hipLaunchKernelGGL(text_place_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, (const u64 *)within, (const u16 *)efile, ne, f, base, place.p);
-            base += total;
-        }
-        c->text_off[n_files] = base;
-        CHK(ensure(c, c->d_text, std::max<u64>(base, 1)));
-        if (base) hipLaunchKernelGGL(text_write_owned_kernel, dim3(flat_grid(c, ne)), dim3(256), 0, c->stream, g, (const u64 *)place, (const u16 *)efile, f_lo, f_hi, c->d_text.p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->text_bytes = base;
-        return DISCO_OK;
-    };
+    DistEdgeText T(c);
+    T.n_files = n_files;
+    T.f_lo = f_lo;
+    T.f_hi = f_hi;
+    T.ne = ne;
     bool gathered = false;
-    int rc = body(&gathered);
+    int rc = dist_edge_text(c, T, file_index, cnt, first, &gathered);
     if (gathered) rc = dist_agree(c, "disco_dist_format_edges", rc);
-    release(c, src32);
-    release(c, src);
-    release(c, ent);
-    release(c, d_findex);
-    release(c, within);
-    release(c, place);
-    release(c, bytes);
-    release(c, sel);
-    release(c, efile);
     if (rc != DISCO_OK) {
-        c->text_bytes = 0;
-        c->text_off.assign((size_t)n_files + 1, 0);
+        c->text.bytes = 0;
+        c->text.off.assign((size_t)n_files + 1, 0);
         return rc;
     }
-    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = c->text_off[f];
+    for (uint32_t f = 0; f <= n_files; f++) file_offsets[f] = c->text.off[f];
     if (getenv("DISCO_VERBOSE"))
         fprintf(stderr, "[disco] rank %zu of %zu: edge files [%u, %u) of %u, %llu bytes of %llu edges' lines; edges gathered, %llu bytes to the other ranks\n", r, G, f_lo, f_hi, n_files,
-                (unsigned long long)c->text_bytes, (unsigned long long)ne, (unsigned long long)((G - 1) * ne_own * 12));
-    return (int64_t)c->text_bytes;
+                (unsigned long long)c->text.bytes, (unsigned long long)ne, (unsigned long long)((G - 1) * ne_own * 12));
+    return (int64_t)c->text.bytes;
 }
 
 } /* extern "C" */

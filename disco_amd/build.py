@@ -47,6 +47,8 @@ STANDALONE = [
     # the line and item functions behind <prefix>.gfa, and the item functions behind <prefix>.unitigs.gfa
     ("gfa_check", _host("gfa_check.cpp"), _csrc("disco_gfa.h") + [_PRODUCT_H], _W, []),
     ("gfa_chains_check", _host("gfa_chains_check.cpp"), _csrc("disco_gfa_chains.h", "disco_gfa.h") + [_PRODUCT_H], _W, []),
+    # the states, rounds and lines behind <prefix>.unitigs.reads
+    ("unitig_reads_check", _host("unitig_reads_check.cpp"), _csrc("disco_unitig_reads.h", "disco_gfa_chains.h", "disco_gfa.h") + [_PRODUCT_H], _W, []),
     # buildG's output plan: every combination of options, knobs and demotions
     ("plan_check", _host("plan_check.cpp"), _host("output_plan.h"), _W, []),
     # the host's end of the output ring: split writers, pieces of several segments, files that take no bytes

@@ -133,9 +133,11 @@ ABI = [
     ("disco_write_contained_records", C.c_int, [_P, C.c_int, C.c_uint64, C.c_uint32]),
     ("disco_write_gfa", C.c_int64, [_P, C.c_int, _P, C.c_uint32, C.c_uint64, C.c_uint32]),
     ("disco_write_gfa_chains", C.c_int64, [_P, C.c_int, _P, C.c_uint32, C.c_uint64, C.c_uint32]),
+    ("disco_write_unitig_reads", C.c_int64, [_P, C.c_int, _P, C.c_uint32, C.c_uint64, C.c_uint32]),
 ]
 
 GFA_NO_SEQ = 1  # DISCO_GFA_NO_SEQ: S lines carry * instead of the bases
+UNITIG_READS_DEPTH_ONLY = 1  # DISCO_UNITIG_READS_DEPTH_ONLY: the H and U lines only
 
 ABI_VERSION = 2  # DISCO_ABI_VERSION of include/disco_hip.h (tests/test_abi.py keeps the two equal)
 FLAG_TWO_PASS_VERIFY = 1  # DISCO_FLAG_TWO_PASS_VERIFY
@@ -604,6 +606,15 @@ class BuildGraph:
         bytes written"""
         fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
         return self._chk(self.L.disco_write_gfa_chains(self._h, fd, None if fi is None else fi.ctypes.data, GFA_NO_SEQ if no_seq else 0, piece_bytes, threads))
+
+    def write_unitig_reads(self, fd: int, file_index=None, depth_only: bool = False, piece_bytes: int = 0, threads: int = 8) -> int:
+        """after contract_chains (without `edges`): the layout behind write_gfa_chains' file into the open file fd, from its byte 0 on
+        (disco_write_unitig_reads) — a U line per segment of that file with its LN, reads and bases, then an R line per read, contained
+        ones included: segment, strand, 0-based start, length, the root of its containment walk and the hops to it (depth_only: the U
+        lines alone). Returns the bytes written"""
+        fi = None if file_index is None else np.ascontiguousarray(file_index, dtype=np.uint64)
+        return self._chk(self.L.disco_write_unitig_reads(self._h, fd, None if fi is None else fi.ctypes.data, UNITIG_READS_DEPTH_ONLY if depth_only else 0, piece_bytes,
+                                                         threads))
 
     def fetch_edge_substitutions(self) -> np.ndarray:
         """substitutions of every edge's overlap, in the order of fetch_edges (all 0 unless max_substitutions > 0)"""

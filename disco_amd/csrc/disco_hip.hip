@@ -48,6 +48,7 @@
 #include "disco_binrec.h"
 #include "disco_gfa.h"
 #include "disco_gfa_chains.h"
+#include "disco_unitig_reads.h"
 #include "disco_partext.h"
 #include "disco_ringio.h"
 #include "disco_ingest.h"
@@ -5018,22 +5019,63 @@ int64_t disco_write_gfa(disco_ctx *c, int fd, const uint64_t *file_index, uint32
 }
 
 /* ---- the compacted graph as GFA 1.0: the composite edges of the contraction as segments with their merged bases (disco_gfa_chains.h) ---- */
-int64_t disco_write_gfa_chains(disco_ctx *c, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads)
+/* what disco_write_gfa_chains and disco_write_unitig_reads ask before they touch anything */
+static int gfu_preconditions(disco_ctx *c, const char *who)
 {
-    DISCO_TRACE("disco_write_gfa_chains");
-    static const char who[] = "disco_write_gfa_chains";
-    if (!c || fd < 0) return DISCO_E_ARG;
-    if (flags & ~(uint32_t)DISCO_GFA_NO_SEQ) return fail(c, DISCO_E_ARG, "%s: unknown flags %#x", who, flags);
     if (c->comm) return fail(c, DISCO_E_UNSUPPORTED, "%s: a rank holds its share of the graph only", who);
     if (c->prm.max_substitutions) return fail(c, DISCO_E_UNSUPPORTED, "%s: with max_substitutions > 0 the reads of a chain disagree about its bases", who);
     if (c->phase < 8) return fail(c, DISCO_E_STATE, "%s: run disco_transitive_reduce first", who);
     if (!c->ch_ready || !c->ch_resident || c->ch_edges_n != c->n_out)
         return fail(c, DISCO_E_STATE, "%s: run disco_contract_chains on the resident edges first (after disco_contract_chains_of the host holds them)", who);
     if (c->n >= (1ull << 31)) return fail(c, DISCO_E_UNSUPPORTED, "%s: more than 2^31 reads", who);
+    return DISCO_OK;
+}
+/* the resident contraction as disco_gfa_chains.h looks at it (lsum: gfu_link_sums) */
+static GfuChains gfu_chains(const disco_ctx *c, bool no_seq)
+{
+    GfuChains H;
+    H.comp = (const disco_chain_edge *)c->d_ch_comp.p;
+    H.links = (const disco_chain_link *)c->d_ch_links.p;
+    H.lsum = H.cplace = nullptr;
+    H.n_comp = c->ch_comp_n;
+    H.no_seq = no_seq;
+    return H;
+}
+/* skip[i] = 1 for the reads without a segment of their own: the contained ones and the interior reads of the chains */
+static int gfu_skip_flags(disco_ctx *c, const GfuChains &H, LocalBuf<u8> &skip)
+{
+    const u64 n = c->n, nl = c->ch_links_n;
+    CHK(ensure(c, skip, n));
+    HIPCHK(c, hipMemcpyAsync(skip, c->d_contained, n, hipMemcpyDeviceToDevice, c->stream));
+    if (H.n_comp) {
+        hipLaunchKernelGGL(gfu_mark_links_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, skip.p);
+        hipLaunchKernelGGL(gfu_unmark_ends_kernel, dim3(flat_grid(c, H.n_comp)), dim3(256), 0, c->stream, H.comp, H.n_comp, (const u8 *)c->d_contained, skip.p);
+    }
+    return DISCO_OK;
+}
+/* H.lsum: the exclusive scan of the links' offsets, total included (loff: room for the offsets themselves) */
+static int gfu_link_sums(disco_ctx *c, GfuChains &H, LocalBuf<u32> &loff, LocalBuf<u64> &lsum)
+{
+    const u64 nl = c->ch_links_n;
+    CHK(ensure(c, loff, nl));
+    CHK(ensure(c, lsum, nl + 1));
+    hipLaunchKernelGGL(gfu_link_offsets_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, loff.p);
+    CHK((scan_exclusive<u32, u64>(c, loff, nl, lsum, true, nullptr)));
+    H.lsum = (const uint64_t *)lsum.p;
+    return DISCO_OK;
+}
+
+int64_t disco_write_gfa_chains(disco_ctx *c, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads)
+{
+    DISCO_TRACE("disco_write_gfa_chains");
+    static const char who[] = "disco_write_gfa_chains";
+    if (!c || fd < 0) return DISCO_E_ARG;
+    if (flags & ~(uint32_t)DISCO_GFA_NO_SEQ) return fail(c, DISCO_E_ARG, "%s: unknown flags %#x", who, flags);
+    CHK(gfu_preconditions(c, who));
     HIPCHK(c, hipSetDevice(c->device));
     CHK(pinned_ring(c, who));
     const bool no_seq = (flags & DISCO_GFA_NO_SEQ) != 0;
-    const u64 n = c->n, ne = c->n_out, nk = c->ch_comp_n, nl = c->ch_links_n;
+    const u64 n = c->n, ne = c->n_out, nk = c->ch_comp_n;
     GfaSink o(c, who, fd, piece_bytes, host_threads);
     LocalBuf<u64> d_findex(c), place(c), lsum(c), cbytes(c), cplace(c);
     LocalBuf<u32> loff(c);
@@ -5048,21 +5090,11 @@ int64_t disco_write_gfa_chains(disco_ctx *c, int fd, const uint64_t *file_index,
     if (pwrite(fd, header, sizeof header - 1, 0) != (ssize_t)(sizeof header - 1)) return fail(c, DISCO_E_ARG, "%s: write error", who);
     o.file_off = sizeof header - 1;
     const GfaReads R = gfa_reads(c, d_findex);
-    GfuChains H;
-    H.comp = (const disco_chain_edge *)c->d_ch_comp.p;
-    H.links = (const disco_chain_link *)c->d_ch_links.p;
-    H.lsum = H.cplace = nullptr;
-    H.n_comp = nk;
-    H.no_seq = no_seq;
+    GfuChains H = gfu_chains(c, no_seq);
     u64 total = 0;
     /* S lines of the reads that are neither contained nor inside a chain: disco_write_gfa's writers behind the skip flags */
     if (n) {
-        CHK(ensure(c, skip, n));
-        HIPCHK(c, hipMemcpyAsync(skip, c->d_contained, n, hipMemcpyDeviceToDevice, c->stream));
-        if (nk) {
-            hipLaunchKernelGGL(gfu_mark_links_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, skip.p);
-            hipLaunchKernelGGL(gfu_unmark_ends_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, H.comp, nk, (const u8 *)c->d_contained, skip.p);
-        }
+        CHK(gfu_skip_flags(c, H, skip));
         CHK(ensure(c, sbytes, n));
         CHK(ensure(c, place, n + 1));
         hipLaunchKernelGGL(gfa_s_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, (const u8 *)skip, no_seq ? 1u : 0u, sbytes.p);
@@ -5079,13 +5111,9 @@ int64_t disco_write_gfa_chains(disco_ctx *c, int fd, const uint64_t *file_index,
     }
     /* S lines of the composite edges: one stream of bytes, a lane per 16 of them */
     if (nk) {
-        CHK(ensure(c, loff, nl));
-        CHK(ensure(c, lsum, nl + 1));
         CHK(ensure(c, cbytes, nk));
         CHK(ensure(c, cplace, nk + 1));
-        hipLaunchKernelGGL(gfu_link_offsets_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H.links, nl, loff.p);
-        CHK((scan_exclusive<u32, u64>(c, loff, nl, lsum, true, nullptr)));
-        H.lsum = (const uint64_t *)lsum.p;
+        CHK(gfu_link_sums(c, H, loff, lsum));
         hipLaunchKernelGGL(gfu_s_measure_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, H, (const u16 *)c->d_len, cbytes.p);
         CHK((scan_exclusive<u64, u64>(c, cbytes, nk, cplace, true, &total)));
         H.cplace = (const uint64_t *)cplace.p;
@@ -5127,6 +5155,139 @@ int64_t disco_write_gfa_chains(disco_ctx *c, int fd, const uint64_t *file_index,
     }
     CHK(o.ring.flush());
     settled.done = true;
+    return (int64_t)o.file_off;
+}
+
+/* ---- every read placed on its segment of the compacted graph, and every segment's reads and bases (disco_unitig_reads.h) -------------- */
+int64_t disco_write_unitig_reads(disco_ctx *c, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads)
+{
+    DISCO_TRACE("disco_write_unitig_reads");
+    static const char who[] = "disco_write_unitig_reads";
+    if (!c || fd < 0) return DISCO_E_ARG;
+    if (flags & ~(uint32_t)DISCO_UNITIG_READS_DEPTH_ONLY) return fail(c, DISCO_E_ARG, "%s: unknown flags %#x", who, flags);
+    CHK(gfu_preconditions(c, who));
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(pinned_ring(c, who));
+    const bool depth_only = (flags & DISCO_UNITIG_READS_DEPTH_ONLY) != 0, verbose = getenv("DISCO_VERBOSE") != nullptr;
+    const u64 n = c->n, nk = c->ch_comp_n, nl = c->ch_links_n;
+    const auto t0 = std::chrono::steady_clock::now();
+    GfaSink o(c, who, fd, piece_bytes, host_threads);
+    LocalBuf<u64> d_findex(c), place(c), lsum(c), st_a(c), st_b(c), cpos(c), rbases(c), lbases(c), kcnt(c), kbases(c);
+    LocalBuf<u32> loff(c), cseg(c), rcnt(c), lcnt(c), flag(c);
+    LocalBuf<u8> bytes(c), skip(c);
+    WaitUnlessDone settled{c};
+    if (file_index) {
+        CHK(ensure(c, d_findex, n));
+        HIPCHK(c, hipMemcpyAsync(d_findex, file_index, n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    const GfaReads R = gfa_reads(c, d_findex);
+    GfuChains H = gfu_chains(c, false);
+    UtrView V;
+    V.state = V.cpos = V.rbases = V.kcnt = V.kbases = nullptr;
+    V.cseg = V.rcnt = nullptr;
+    u32 rounds = 0;
+    if (n) {
+        /* roots: the initial states, then rounds of doubling until one moves nobody. flag[0]: keys that name no read; flag[1 + r]: round r moved somebody */
+        CHK(settle_keys(c));
+        CHK(ensure(c, st_a, n));
+        CHK(ensure(c, st_b, n));
+        CHK(ensure(c, flag, 1 + UTR_MAX_ROUNDS));
+        HIPCHK(c, hipMemsetAsync(flag, 0, (1 + UTR_MAX_ROUNDS) * sizeof(u32), c->stream));
+        hipLaunchKernelGGL(utr_init_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const u64 *)c->d_best, (const u8 *)c->d_contained, (const u16 *)c->d_len, n, (u32)c->k, (uint64_t *)st_a.p, flag.p);
+        HIPCHK(c, hipGetLastError());
+        u32 h_flag = 0;
+        HIPCHK(c, hipMemcpyAsync(&h_flag, flag, sizeof h_flag, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h_flag) return fail(c, DISCO_E_STATE, "%s: %u contained reads have a key that names no containing read", who, h_flag);
+        uint64_t *cur = (uint64_t *)st_a.p, *next = (uint64_t *)st_b.p;
+        bool moving = c->n_contained != 0;
+        while (moving && rounds < UTR_MAX_ROUNDS) {
+            hipLaunchKernelGGL(utr_round_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, (const uint64_t *)cur, next, (const u16 *)c->d_len, n, flag.p + 1 + rounds);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(&h_flag, flag.p + 1 + rounds, sizeof h_flag, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            std::swap(cur, next);
+            moving = h_flag != 0;
+            rounds++;
+        }
+        if (moving) return fail(c, DISCO_E_STATE, "%s: the containment keys do not settle in %u rounds of doubling: they hold a cycle", who, UTR_MAX_ROUNDS);
+        V.state = (const uint64_t *)cur;
+        /* segments: the interior reads of the chains at their s_j; everybody else is a segment of their own */
+        CHK(ensure(c, cseg, n));
+        CHK(ensure(c, cpos, n));
+        HIPCHK(c, hipMemsetAsync(cseg, 0xFF, n * sizeof(u32), c->stream));
+        if (nk) {
+            CHK(gfu_link_sums(c, H, loff, lsum));
+            hipLaunchKernelGGL(utr_place_links_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H, nl, cseg.p, (uint64_t *)cpos.p);
+        }
+        V.cseg = cseg.p;
+        V.cpos = (const uint64_t *)cpos.p;
+        /* counts: every read to its root, then the chains' totals as differences of one scan in link order */
+        CHK(ensure(c, rcnt, n));
+        CHK(ensure(c, rbases, n));
+        HIPCHK(c, hipMemsetAsync(rcnt, 0, n * sizeof(u32), c->stream));
+        HIPCHK(c, hipMemsetAsync(rbases, 0, n * sizeof(u64), c->stream));
+        hipLaunchKernelGGL(utr_count_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, V.state, (const u16 *)c->d_len, n, rcnt.p, rbases.p);
+        V.rcnt = rcnt.p;
+        V.rbases = (const uint64_t *)rbases.p;
+        if (nk) {
+            CHK(ensure(c, lcnt, nl));
+            CHK(ensure(c, lbases, nl));
+            CHK(ensure(c, kcnt, nl + 1));
+            CHK(ensure(c, kbases, nl + 1));
+            hipLaunchKernelGGL(utr_gather_kernel, dim3(flat_grid(c, nl)), dim3(256), 0, c->stream, H, nl, (const u32 *)rcnt, (const u64 *)rbases, lcnt.p, lbases.p);
+            CHK((scan_exclusive<u32, u64>(c, lcnt, nl, kcnt, true, nullptr)));
+            CHK((scan_exclusive<u64, u64>(c, lbases, nl, kbases, true, nullptr)));
+            V.kcnt = (const uint64_t *)kcnt.p;
+            V.kbases = (const uint64_t *)kbases.p;
+        }
+        HIPCHK(c, hipGetLastError());
+    }
+    double ms_resolve = 0;
+    if (verbose) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        ms_resolve = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    static const char header[] = UTR_HEADER;
+    if (pwrite(fd, header, sizeof header - 1, 0) != (ssize_t)(sizeof header - 1)) return fail(c, DISCO_E_ARG, "%s: write error", who);
+    o.file_off = sizeof header - 1;
+    u64 total = 0;
+    /* U lines of the read segments: a lane per read behind the skip flags of the S lines */
+    if (n) {
+        CHK(gfu_skip_flags(c, H, skip));
+        CHK(ensure(c, bytes, n));
+        CHK(ensure(c, place, n + 1));
+        hipLaunchKernelGGL(utr_u_read_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, V, (const u8 *)skip, bytes.p);
+        CHK((scan_exclusive<u8, u64>(c, bytes, n, place, true, &total)));
+        CHK(gfa_section(c, who, o, place, n, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+            hipLaunchKernelGGL(utr_u_read_write_kernel, dim3(flat_grid(c, b[0] - a[0])), dim3(256), 0, c->stream, R, V, (const u8 *)skip, (const u64 *)place, a[0], b[0], a[1], piece);
+        }));
+    }
+    /* U lines of the composite edges: a lane per composite edge */
+    if (nk) {
+        CHK(ensure(c, bytes, nk));
+        CHK(ensure(c, place, nk + 1));
+        hipLaunchKernelGGL(utr_u_chain_measure_kernel, dim3(flat_grid(c, nk)), dim3(256), 0, c->stream, R, H, V, bytes.p);
+        CHK((scan_exclusive<u8, u64>(c, bytes, nk, place, true, &total)));
+        CHK(gfa_section(c, who, o, place, nk, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+            hipLaunchKernelGGL(utr_u_chain_write_kernel, dim3(flat_grid(c, b[0] - a[0])), dim3(256), 0, c->stream, R, H, V, (const u64 *)place, a[0], b[0], a[1], piece);
+        }));
+    }
+    /* R lines: a lane per read */
+    if (n && !depth_only) {
+        CHK(ensure(c, bytes, n));
+        CHK(ensure(c, place, n + 1));
+        hipLaunchKernelGGL(utr_r_measure_kernel, dim3(flat_grid(c, n)), dim3(256), 0, c->stream, R, V, bytes.p);
+        CHK((scan_exclusive<u8, u64>(c, bytes, n, place, true, &total)));
+        CHK(gfa_section(c, who, o, place, n, total, nullptr, 0, [&](const u64 *a, const u64 *b, char *piece) {
+            hipLaunchKernelGGL(utr_r_write_kernel, dim3(flat_grid(c, b[0] - a[0])), dim3(256), 0, c->stream, R, V, (const u64 *)place, a[0], b[0], a[1], piece);
+        }));
+    }
+    CHK(o.ring.flush());
+    settled.done = true;
+    if (verbose)
+        fprintf(stderr, "[disco] unitig reads: %u rounds of doubling moved a read; roots, places and counts in %.3f ms; %llu bytes in %.3f ms\n", rounds ? rounds - 1 : 0u, ms_resolve, (unsigned long long)o.file_off,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return (int64_t)o.file_off;
 }
 

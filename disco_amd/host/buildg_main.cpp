@@ -70,7 +70,11 @@ static void usage()
               << "  --gfa-no-seq\t--gfa with * in place of the bases\n"
               << "  --gfa-unitigs\talso write <prefix>.unitigs.gfa: the compacted graph as GFA 1.0 — every unbranched chain of reads one segment c<k>\n"
               << "\t\twith its merged bases, spelled on the GPU; no contained reads (--gfa has them); exact overlaps, single GPU;\n"
-              << "\t\twith --gfa-no-seq beside it: * in place of the bases, and no <prefix>.gfa unless --gfa asks for it\n";
+              << "\t\twith --gfa-no-seq beside it: * in place of the bases, and no <prefix>.gfa unless --gfa asks for it\n"
+              << "  --unitig-reads\talso write <prefix>.unitigs.reads, the layout behind <prefix>.unitigs.gfa: a U line per segment (LN, reads, bases) and\n"
+              << "\t\tan R line per read, contained ones included (segment, strand, 0-based start, length, the root of its containment\n"
+              << "\t\twalk and the hops to it), resolved and formatted on the GPU; exact overlaps, single GPU\n"
+              << "  --unitig-depth\t--unitig-reads with the U lines only: reads and bases per segment (depth = bases / LN)\n";
 }
 
 static std::vector<std::string> split(const std::string &s, char d)
@@ -157,6 +161,7 @@ struct Args {
     bool same_device = false, mpi_names = false, binary_out = false, no_text = false, partitioned_index = false;
     bool gfa = false, gfa_no_seq = false; /* <prefix>.gfa, with or without the bases */
     bool gfa_unitigs = false;             /* <prefix>.unitigs.gfa */
+    bool unitig_reads = false, unitig_depth = false; /* <prefix>.unitigs.reads, whole or its U lines only (given both: whole) */
     std::string par_simple; /* prefix of the <prefix>_<i>_ParSimpleEdges.txt files, or empty */
     uint32_t min_overlap = 30, min_overlap_simplify = 0, max_subs = 0;
     std::vector<const char *> paths() const
@@ -216,6 +221,8 @@ static int parse_args(int argc, char **argv, Args &a)
         else if (o == "--gfa") gfa_cli = true;
         else if (o == "--gfa-no-seq") a.gfa_no_seq = true;
         else if (o == "--gfa-unitigs") a.gfa_unitigs = true;
+        else if (o == "--unitig-reads") a.unitig_reads = true;
+        else if (o == "--unitig-depth") a.unitig_depth = true;
         else {
             usage();
             if (o == "-h" || o == "--help") return 0;
@@ -230,6 +237,11 @@ static int parse_args(int argc, char **argv, Args &a)
     a.gfa = gfa_cli || (a.gfa_no_seq && !a.gfa_unitigs); /* alone, --gfa-no-seq means --gfa; beside --gfa-unitigs it is that file's */
     if (a.gfa_unitigs && a.gpus > 1) {
         std::cerr << "--gfa-unitigs writes the graph of one GPU: with --gpus " << a.gpus << " every rank holds its share only, run it without --gpus." << std::endl;
+        return 1;
+    }
+    const char *layout = a.unitig_reads ? "--unitig-reads" : a.unitig_depth ? "--unitig-depth" : nullptr;
+    if (layout && a.gpus > 1) {
+        std::cerr << layout << " writes the graph of one GPU: with --gpus " << a.gpus << " every rank holds its share only, run it without --gpus." << std::endl;
         return 1;
     }
     if (a.gfa && a.gpus > 1) {
@@ -250,6 +262,11 @@ static int parse_args(int argc, char **argv, Args &a)
     if (max_subs_cli >= 0) a.max_subs = (uint32_t)max_subs_cli;
     if (a.gfa_unitigs && a.max_subs) {
         std::cerr << "--gfa-unitigs spells every chain from reads that overlap exactly: with " << a.max_subs << " substitutions allowed (--max-substitutions, "
+                  << "MaxSubstitutions4BuildGraph) the reads of a chain disagree about its bases. Use --gfa." << std::endl;
+        return 1;
+    }
+    if (layout && a.max_subs) {
+        std::cerr << layout << " places every read on chains spelled from reads that overlap exactly: with " << a.max_subs << " substitutions allowed (--max-substitutions, "
                   << "MaxSubstitutions4BuildGraph) the reads of a chain disagree about its bases. Use --gfa." << std::endl;
         return 1;
     }
@@ -775,10 +792,9 @@ static int write_gfa_file(Job &J, disco_ctx *ctx)
 /* <prefix>.unitigs.gfa (--gfa-unitigs): the compacted graph — every chain one segment with its merged bases (disco_write_gfa_chains). A
  * stage of its own behind every planned product and --gfa: it contracts for itself, every overlap counted (filter 0), whatever
  * --par-simple contracted before (its files are written, and what the host needs of that contraction it holds). No product of the plan */
-static int write_gfa_unitigs_file(Job &J, disco_ctx *ctx)
+static int write_gfa_unitigs_file(Job &J, disco_ctx *ctx, uint64_t &nc, uint64_t &nl)
 {
     const std::string path = J.a.prefix + ".unitigs.gfa";
-    uint64_t nc = 0, nl = 0;
     auto t = Clock::now();
     DISCO_CALL(ctx, disco_contract_chains(ctx, 0, &nc, &nl));
     const double s_contract = secs(t);
@@ -793,6 +809,29 @@ static int write_gfa_unitigs_file(Job &J, disco_ctx *ctx)
         fprintf(stderr, "[disco host] GFA of unitigs: %llu chains of %llu links contracted in %.3f s; %lld bytes in %.3f s (%.2f GB/s)\n", (unsigned long long)nc, (unsigned long long)nl,
                 s_contract, (long long)nb, s, s > 0 ? (double)nb / s * 1e-9 : 0.0);
     J.lap("GFA of unitigs from the GPU into the file");
+    return GO_ON;
+}
+
+/* <prefix>.unitigs.reads (--unitig-reads; --unitig-depth: its U lines only): every read placed on its segment of the compacted graph
+ * (disco_write_unitig_reads). A stage of its own directly behind --gfa-unitigs', whose contraction it shares (contracted: nc, nl are
+ * that one's); alone it contracts for itself, every overlap counted. No product of the plan: every failure is an error of the run */
+static int write_unitig_reads_file(Job &J, disco_ctx *ctx, bool contracted, uint64_t nc, uint64_t nl)
+{
+    const std::string path = J.a.prefix + ".unitigs.reads";
+    auto t = Clock::now();
+    if (!contracted) DISCO_CALL(ctx, disco_contract_chains(ctx, 0, &nc, &nl));
+    const double s_contract = secs(t);
+    Fds fds;
+    fds.fd.assign(1, open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666));
+    if (fds.fd[0] < 0) return die("Unable to open file: " + path);
+    t = Clock::now();
+    const int64_t nb = disco_write_unitig_reads(ctx, fds.fd[0], J.ids(), J.a.unitig_reads ? 0u : DISCO_UNITIG_READS_DEPTH_ONLY, 0, (uint32_t)J.a.threads);
+    if (nb < 0) return die(std::string("disco_write_unitig_reads : ") + disco_last_error(ctx));
+    const double s = secs(t);
+    if (J.verbose) /* (the rounds of doubling and the time of the kernels that resolve and count stand in the library's own line) */
+        fprintf(stderr, "[disco host] reads on unitigs%s: %llu chains of %llu links %s in %.3f s; %lld bytes in %.3f s (%.2f GB/s)\n", J.a.unitig_reads ? "" : " (depth only)",
+                (unsigned long long)nc, (unsigned long long)nl, contracted ? "shared with the GFA of unitigs" : "contracted", s_contract, (long long)nb, s, s > 0 ? (double)nb / s * 1e-9 : 0.0);
+    J.lap("reads on unitigs from the GPU into the file");
     return GO_ON;
 }
 
@@ -938,7 +977,9 @@ static int graph_single_gpu(Job &J)
     }
     if (rc != GO_ON) return rc;
     if (a.gfa && (rc = write_gfa_file(J, ctx)) != GO_ON) return rc;
-    if (a.gfa_unitigs && (rc = write_gfa_unitigs_file(J, ctx)) != GO_ON) return rc;
+    uint64_t u_nc = 0, u_nl = 0;
+    if (a.gfa_unitigs && (rc = write_gfa_unitigs_file(J, ctx, u_nc, u_nl)) != GO_ON) return rc;
+    if ((a.unitig_reads || a.unitig_depth) && (rc = write_unitig_reads_file(J, ctx, a.gfa_unitigs, u_nc, u_nl)) != GO_ON) return rc;
     /* the context is released by a thread of its own while the files are written (0.07 s of hipFree at config 3) */
     J.ctx_releaser.t = std::thread([ctx]() { disco_destroy(ctx); });
     J.lap("release GPU context (in the background)");

@@ -618,6 +618,28 @@ int64_t disco_write_gfa(disco_ctx *ctx, int fd, const uint64_t *file_index, uint
  * and with max_substitutions > 0 (the reads of a chain would disagree about its bases). */
 int64_t disco_write_gfa_chains(disco_ctx *ctx, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads);
 
+/* <prefix>.unitigs.reads, the LAYOUT behind <prefix>.unitigs.gfa (disco_amd/csrc/disco_unitig_reads.h): where every read lies — contained
+ * reads and the interior reads of the chains included — and how many reads and bases every segment carries. LF line ends, tab separated:
+ *     H \t unitig-reads \t 1
+ *     U \t segment \t LN \t reads \t bases                              one per S line of <prefix>.unitigs.gfa, in that file's order
+ *     R \t read \t segment \t strand \t start \t len \t root \t hops    one per read, contained ones included, in read-id order
+ * read and root are names as disco_write_gfa writes them (file_index, or read id + 1), segment is a read's name or c<k>. Bases [start,
+ * start + len) of the segment's S line (start 0-based, 64 bits) are the read, or its reverse complement where strand is '-'. LN is the S
+ * line's LN, reads the number of R lines that name the segment, bases the sum of their len: depth = bases / LN.
+ * The place of read x: a read that is not contained is its own root (position 0, same strand, hops 0). A contained read has the row
+ * (container y, orient, start) its key decodes to (disco_contained_row), and oriented x is y[p, p + len[x]) with x on y's strand for
+ * orient 0 or 3, p = start for orient 3 or 2 and len[y] - start - len[x] for 0 or 1 — the C line of disco_write_gfa; where y is
+ * contained itself the walk goes on from y, root is the first read reached that is not contained and hops the number of steps. Two
+ * steps compose: x at (pos, s) of y, s = "on y's strand", and y at (q, t) of z put x at q + pos, s of z when t is plus and at
+ * q + len[y] - pos - len[x], !s when t is minus. A root that is interior read r_j of composite edge k (disco_write_gfa_chains) lies on
+ * c<k> at s_j, forward iff l_j.orient & 1, and the read's place is the same composition with (s_j, forward); every other root — the
+ * ends a and b of a chain, the reads of a ring, of a branch, of no edge — is the segment itself, at 0, forward.
+ * DISCO_UNITIG_READS_DEPTH_ONLY writes the H and U lines only. Arguments, pieces (all cut at line ends) and the return value as for
+ * disco_write_gfa_chains, and its preconditions and errors unchanged. DISCO_E_STATE also where a contained read's key names no read,
+ * and where the keys hold a cycle (the roots are found by pointer doubling, which a nest of less than 2^16 reads settles in 17 rounds). */
+#define DISCO_UNITIG_READS_DEPTH_ONLY 1u
+int64_t disco_write_unitig_reads(disco_ctx *ctx, int fd, const uint64_t *file_index, uint32_t flags, uint64_t piece_bytes, uint32_t host_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -259,11 +259,11 @@ struct disco_ctx {
     int bshift = 0;
     DevBuf<u32> d_bkt;
     DevBuf<u64> d_ent;
-    DevBuf<ulonglong2> d_rec; /* {key, record}[2n] scratch of the index build */
-    /* binned build (binned_build_index): decided once per index by index_begin — the count pass then leaves out its bucket atomics, and
-     * the bucket table is neither cleared nor scanned */
+    DevBuf<ulonglong2> d_rec; /* {key, record}[2n] scratch of the index build; binned build: 2n payloads, then 2n 4-byte keys (index_planes) */
+    /* binned build (binned_build_index): decided once per index by index_begin — the count pass then leaves out its bucket atomics and
+     * writes the records as planes, and the bucket table is neither cleared nor scanned */
     bool binned_index = false;
-    DevBuf<ulonglong2> d_rec2; /* the other side of the partition levels' ping-pong */
+    DevBuf<ulonglong2> d_rec2; /* the other side of the partition levels' ping-pong: 2n x 12 bytes in planes (first the grouping's items and theirs) */
     DevBuf<u32> d_binx;        /* segment starts and tile bases of two levels, the tile x bin counts of one */
 
     /* scan temporaries */
@@ -1118,76 +1118,124 @@ static int index_count_plan(disco_ctx *c, const DiscoView &v, u64 lo, u64 hi, In
 /* which instantiation counts this shape — the ONLY place that names the template arguments of index_runs_kernel / index_count_kernel.
  * lpr != 0: with the minimizer runs (16 / 32 words per read: NL 1 / 2), a window of nf m-mers; long_class: the long reads of two row
  * classes, from their full rows (never with runs) */
-typedef void (*IndexRunsFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u32 *, u64 *, u32, u32, u32, const u64 *);
-typedef void (*IndexCountFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64, u64, u32 *, u32 *, u64 *, u32, u32, const u64 *);
+typedef void (*IndexRunsFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64 *, u32 *, u64, u64, u32 *, u32 *, u32 *, u64 *, u32, u32, u32, const u64 *);
+typedef void (*IndexCountFn)(DiscoView, u32 *, ulonglong2 *, u32 *, u64 *, u32 *, u64, u64, u32 *, u32 *, u64 *, u32, u32, const u64 *);
 struct IndexCountKernel {
     IndexRunsFn runs = nullptr; /* one of the two */
     IndexCountFn plain = nullptr;
 };
-template <bool COUNT, int NF, int NFMAX, bool LONGK>
+template <int OUT, int NF, int NFMAX, bool LONGK>
 static IndexCountKernel index_runs_pick(int lpr)
 {
     IndexCountKernel k;
-    k.runs = lpr == 16 ? index_runs_kernel<COUNT, NF, 1, NFMAX, LONGK> : index_runs_kernel<COUNT, NF, 2, NFMAX, LONGK>;
+    k.runs = lpr == 16 ? index_runs_kernel<OUT, NF, 1, NFMAX, LONGK> : index_runs_kernel<OUT, NF, 2, NFMAX, LONGK>;
     return k;
 }
-template <bool COUNT>
+template <int OUT>
 static IndexCountKernel index_count_pick(int nf, int m, int lpr, bool longk, bool long_class)
 {
     if (long_class || !lpr) {
         IndexCountKernel k;
-        if (long_class) k.plain = longk ? index_count_kernel<COUNT, true, true> : index_count_kernel<COUNT, false, true>;
-        else k.plain = longk ? index_count_kernel<COUNT, true> : index_count_kernel<COUNT>;
+        if (long_class) k.plain = longk ? index_count_kernel<OUT, true, true> : index_count_kernel<OUT, false, true>;
+        else k.plain = longk ? index_count_kernel<OUT, true> : index_count_kernel<OUT>;
         return k;
     }
     if (runs_nf_built(nf, m)) switch (nf) {
-        case 7: return index_runs_pick<COUNT, 7, 7, false>(lpr);
-        case 12: return index_runs_pick<COUNT, 12, 12, false>(lpr);
-        case 17: return index_runs_pick<COUNT, 17, 17, false>(lpr);
-        case 22: return index_runs_pick<COUNT, 22, 22, false>(lpr);
-        default: return index_runs_pick<COUNT, 27, 27, false>(lpr);
+        case 7: return index_runs_pick<OUT, 7, 7, false>(lpr);
+        case 12: return index_runs_pick<OUT, 12, 12, false>(lpr);
+        case 17: return index_runs_pick<OUT, 17, 17, false>(lpr);
+        case 22: return index_runs_pick<OUT, 22, 22, false>(lpr);
+        default: return index_runs_pick<OUT, 27, 27, false>(lpr);
         }
     /* the window length as a run-time value: arrays for 32 or 64 m-mers */
     /* (the arrays are registers: an instantiation per size class keeps the waves per SIMD near the specialised kernels' — windows of 10
      * in arrays for 32 ran 9.8 ms at 20 M reads, in arrays for 12: 6.7) */
-    if (longk) return nf <= 48 ? index_runs_pick<COUNT, 0, 48, true>(lpr) : index_runs_pick<COUNT, 0, 64, true>(lpr);
-    if (nf <= 8) return index_runs_pick<COUNT, 0, 8, false>(lpr);
-    if (nf <= 12) return index_runs_pick<COUNT, 0, 12, false>(lpr);
-    if (nf <= 16) return index_runs_pick<COUNT, 0, 16, false>(lpr);
-    if (nf <= 24) return index_runs_pick<COUNT, 0, 24, false>(lpr);
-    if (nf <= 32) return index_runs_pick<COUNT, 0, 32, false>(lpr);
-    if (nf <= 48) return index_runs_pick<COUNT, 0, 48, false>(lpr);
-    return index_runs_pick<COUNT, 0, 64, false>(lpr);
+    if (longk) return nf <= 48 ? index_runs_pick<OUT, 0, 48, true>(lpr) : index_runs_pick<OUT, 0, 64, true>(lpr);
+    if (nf <= 8) return index_runs_pick<OUT, 0, 8, false>(lpr);
+    if (nf <= 12) return index_runs_pick<OUT, 0, 12, false>(lpr);
+    if (nf <= 16) return index_runs_pick<OUT, 0, 16, false>(lpr);
+    if (nf <= 24) return index_runs_pick<OUT, 0, 24, false>(lpr);
+    if (nf <= 32) return index_runs_pick<OUT, 0, 32, false>(lpr);
+    if (nf <= 48) return index_runs_pick<OUT, 0, 48, false>(lpr);
+    return index_runs_pick<OUT, 0, 64, false>(lpr);
 }
-/* count: the counting atomics on the bucket table ride along (the binned build counts for itself) */
-static IndexCountKernel index_count_pick(bool count, int nf, int m, int lpr, bool longk, bool long_class)
+/* out: what the pass leaves of a read's two records (IndexOut, disco_kernels.h) — with the counting atomics on the bucket table, as plain
+ * records, or as the two planes of the binned build, which counts for itself */
+static IndexCountKernel index_count_pick(int out, int nf, int m, int lpr, bool longk, bool long_class)
 {
-    return count ? index_count_pick<true>(nf, m, lpr, longk, long_class) : index_count_pick<false>(nf, m, lpr, longk, long_class);
+    switch (out) {
+    case INDEX_COUNTED: return index_count_pick<INDEX_COUNTED>(nf, m, lpr, longk, long_class);
+    case INDEX_RECORDS: return index_count_pick<INDEX_RECORDS>(nf, m, lpr, longk, long_class);
+    default: return index_count_pick<INDEX_PLANES>(nf, m, lpr, longk, long_class);
+    }
 }
 
-/* reads [a, b) of the planned range; rec_base = the records of read pl.lo */
-static int index_count_chunk(disco_ctx *c, const DiscoView &v, const IndexCountPlan &pl, bool count, ulonglong2 *rec_base, u64 a, u64 b)
+/* where the count pass writes: the records of read 0 of its range as one array, or as a key plane and a payload plane */
+struct IndexRecOut {
+    int form = INDEX_COUNTED;
+    ulonglong2 *rec = nullptr;
+    u32 *key = nullptr;
+    u64 *pay = nullptr;
+    IndexRecOut from_read(ptrdiff_t i) const /* ... of read i */
+    {
+        IndexRecOut o = *this;
+        if (o.rec) o.rec += 2 * i;
+        if (o.key) o.key += 2 * i, o.pay += 2 * i;
+        return o;
+    }
+};
+/* a side of the partition levels' ping-pong, as the kernels' view takes it (BinxForm<R>): one array a of records, or the key plane a and
+ * the payload plane b */
+template <typename R>
+struct BinxSide {
+    typename BinxForm<R>::A *a = nullptr;
+    typename BinxForm<R>::B *b = nullptr;
+};
+/* a side of the binned index build's ping-pong over 2n records, cut into planes: 2n payloads, then 2n keys (both 16-byte aligned) */
+static BinxSide<BinxKV> index_planes(ulonglong2 *side, u64 n)
+{
+    BinxSide<BinxKV> s;
+    s.b = (u64 *)side;
+    s.a = (u32 *)(s.b + 2 * n);
+    return s;
+}
+/* the single-GPU count pass: planes in d_rec for the binned build, counted records for the old path */
+static IndexRecOut index_rec_out(disco_ctx *c)
+{
+    IndexRecOut o;
+    if (c->binned_index) {
+        const BinxSide<BinxKV> s = index_planes(c->d_rec.p, c->n);
+        o.form = INDEX_PLANES;
+        o.key = s.a;
+        o.pay = s.b;
+    } else
+        o.rec = c->d_rec.p;
+    return o;
+}
+
+/* reads [a, b) of the planned range; out = the records of read pl.lo */
+static int index_count_chunk(disco_ctx *c, const DiscoView &v, const IndexCountPlan &pl, const IndexRecOut &out, u64 a, u64 b)
 {
     if (b <= a) return DISCO_OK;
     const dim3 grid((unsigned)((b - a + 255) / 256));
-    ulonglong2 *rec = rec_base + 2 * (a - pl.lo);
+    const IndexRecOut o = out.from_read((ptrdiff_t)(a - pl.lo));
     u32 *oslot = pl.oslot ? pl.oslot + (a - pl.lo) : nullptr;
     u64 *oitem = pl.oitem ? pl.oitem + (a - pl.lo) : nullptr; /* (at the read's global position, whichever chunk brings it) */
     u32 *okey = pl.list ? nullptr : c->d_okey.p; /* (a list: the keys were made when the reads were dealt, by read id) */
-    const IndexCountKernel k = index_count_pick(count, pl.nf, v.m, pl.lpr, c->ks > 64, false);
-    if (k.runs) hipLaunchKernelGGL(k.runs, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, c->d_runs + (a - pl.lo) * (u64)pl.lpr, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.osub, pl.list);
-    else hipLaunchKernelGGL(k.plain, grid, dim3(256), 0, c->stream, v, c->d_bkt, rec, okey, a, b, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.list);
+    const IndexCountKernel k = index_count_pick(o.form, pl.nf, v.m, pl.lpr, c->ks > 64, false);
+    if (k.runs) hipLaunchKernelGGL(k.runs, grid, dim3(256), 0, c->stream, v, c->d_bkt, o.rec, o.key, o.pay, okey, a, b, c->d_runs + (a - pl.lo) * (u64)pl.lpr, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.osub, pl.list);
+    else hipLaunchKernelGGL(k.plain, grid, dim3(256), 0, c->stream, v, c->d_bkt, o.rec, o.key, o.pay, okey, a, b, pl.ocnt, oslot, oitem, pl.oidbits, pl.oshift, pl.list);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
 }
 
-/* the long reads [x_lo, x_hi) of two row classes (positions in long_ids): their records, keys and slots, from their full rows; rec and
- * oslot by read id */
-static int index_count_long(disco_ctx *c, const DiscoView &v, const IndexCountPlan &pl, bool count, ulonglong2 *rec, u32 *oslot, u64 x_lo, u64 x_hi)
+/* the long reads [x_lo, x_hi) of two row classes (positions in long_ids): their records, keys and slots, from their full rows; out (the
+ * records of read 0) and oslot by read id */
+static int index_count_long(disco_ctx *c, const DiscoView &v, const IndexCountPlan &pl, const IndexRecOut &out, u32 *oslot, u64 x_lo, u64 x_hi)
 {
     const dim3 g((unsigned)((x_hi - x_lo + 255) / 256));
-    hipLaunchKernelGGL(index_count_pick(count, 0, v.m, 0, c->ks > 64, true).plain, g, dim3(256), 0, c->stream, v, c->d_bkt, rec, c->d_okey, x_lo, x_hi, pl.ocnt, oslot, (u64 *)nullptr, 0u, pl.oshift,
-                       (const u64 *)nullptr);
+    hipLaunchKernelGGL(index_count_pick(out.form, 0, v.m, 0, c->ks > 64, true).plain, g, dim3(256), 0, c->stream, v, c->d_bkt, out.rec, out.key, out.pay, c->d_okey, x_lo, x_hi, pl.ocnt, oslot,
+                       (u64 *)nullptr, 0u, pl.oshift, (const u64 *)nullptr);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
 }
@@ -1200,7 +1248,8 @@ static int index_count_long(disco_ctx *c, const DiscoView &v, const IndexCountPl
 static bool binned_index_wanted(disco_ctx *c, int logT)
 {
     if (getenv("DISCO_NO_BINNED_INDEX") || 2 * c->n >= 0xFFFF0000ull) return false;
-    if (logT > BINX_SPAN_BITS && ensure(c, c->d_rec2, 2 * c->n) != DISCO_OK) {
+    /* (2n records in planes: 2n x 12 bytes = 3n / 2 of d_rec2's 16-byte words — and never less than the n words of the grouping's items) */
+    if (logT > BINX_SPAN_BITS && ensure(c, c->d_rec2, (3 * c->n + 1) / 2) != DISCO_OK) {
         (void)hipGetLastError();
         c->err.clear();
         return false;
@@ -1259,12 +1308,15 @@ static BinxPlan binx_plan(int logT)
     return b;
 }
 
-/* the partition levels over rec[0 .. total), records {bucket << 32, payload} or one-word items, whose key word holds a bucket of `bits` bits
- * from bit kshift up (see "binned index build" in disco_kernels.h): src and dst are the two sides of the ping-pong; *out = the side the
- * partitions end up in, *part = their starts (n_part + 1 words in d_binx) */
+/* the partition levels over `total` records — the index's, as a key plane and a payload plane (R = BinxKV), or the grouping's
+ * one-word items (u64) — whose key word holds a bucket of `bits` bits from bit kshift up (see "binned
+ * index build" in disco_kernels.h): src and dst are the two sides of the ping-pong; *out = the side the partitions end up in, *part =
+ * their starts (n_part + 1 words in d_binx) */
 template <typename R>
-static int binx_partition(disco_ctx *c, const char *what, int bits, u32 kshift, u32 total, R *src, R *dst, const R **out, const u32 **part)
+static int binx_partition(disco_ctx *c, const char *what, int bits, u32 kshift, u32 total, BinxSide<R> src, BinxSide<R> dst, BinxSide<R> *out, const u32 **part)
 {
+    typedef typename BinxForm<R>::A A;
+    typedef typename BinxForm<R>::B B;
     const BinxPlan bp = binx_plan(bits);
     const u32 n_part = 1u << (bits - bp.span);
     const u32 tiles = (total + BINX_TILE - 1u) / BINX_TILE;
@@ -1284,9 +1336,10 @@ static int binx_partition(disco_ctx *c, const char *what, int bits, u32 kshift, 
         const u64 hlen = (u64)grid * nb + 1;
         hipLaunchKernelGGL(binx_segs_kernel, dim3(1), dim3(1024), 0, c->stream, l ? (const u32 *)hist : (const u32 *)nullptr, (const u32 *)tb[cur ^ 1], pseg, pnb, total, seg[cur], tb[cur]);
         HIPCHK(c, hipMemsetAsync(hist, 0, hlen * sizeof(u32), c->stream));
-        hipLaunchKernelGGL(binx_hist_kernel<R>, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const R *)src, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb, hist);
+        hipLaunchKernelGGL(binx_hist_kernel<R>, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const A *)src.a, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb, hist);
         CHK((scan_exclusive<u32, u32>(c, hist, hlen, hist, false, nullptr)));
-        hipLaunchKernelGGL(binx_scatter_kernel<R>, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const R *)src, dst, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb, (const u32 *)hist);
+        hipLaunchKernelGGL(binx_scatter_kernel<R>, dim3(grid), dim3(BINX_BLOCK), 0, c->stream, (const A *)src.a, (const B *)src.b, dst.a, dst.b, (const u32 *)seg[cur], (const u32 *)tb[cur], nseg, shift, nb,
+                           (const u32 *)hist);
         HIPCHK(c, hipGetLastError());
         std::swap(src, dst);
         pseg = nseg;
@@ -1303,16 +1356,18 @@ static int binx_partition(disco_ctx *c, const char *what, int bits, u32 kshift, 
     return DISCO_OK;
 }
 
-/* records rec[0 .. 2n) = {bucket << 32, payload} of the count pass (COUNT = false) -> bkt[0 .. T], ent[0 .. 2n) */
+/* the 2n records of the count pass (INDEX_PLANES: key[i] = bucket, pay[i] = payload, in d_rec) -> bkt[0 .. T], ent[0 .. 2n); the other
+ * side of the ping-pong is d_rec2, cut the same way */
 static int binned_build_index(disco_ctx *c)
 {
     const int logT = 64 - c->bshift;
     const u32 total = (u32)(2 * c->n);
-    const ulonglong2 *rec;
+    BinxSide<BinxKV> rec;
     const u32 *part;
-    CHK(binx_partition(c, "index build", logT, 32u, total, c->d_rec.p, c->d_rec2.p, &rec, &part));
+    CHK(binx_partition<BinxKV>(c, "index build", logT, 0u, total, index_planes(c->d_rec.p, c->n), index_planes(c->d_rec2.p, c->n), &rec, &part));
     const int span = std::min(logT, BINX_SPAN_BITS);
-    hipLaunchKernelGGL(binx_build_kernel<ulonglong2>, dim3(1u << (logT - span)), dim3(BINX_BUILD_BLOCK), 0, c->stream, rec, part, (u32)span, 32u, 0u, total, c->T, c->d_bkt.p, c->d_ent.p);
+    hipLaunchKernelGGL(binx_build_kernel<BinxKV>, dim3(1u << (logT - span)), dim3(BINX_BUILD_BLOCK), 0, c->stream, (const u32 *)rec.a, (const u64 *)rec.b, part, (u32)span, 0u, 0u, total, c->T,
+                       c->d_bkt.p, c->d_ent.p);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
 }
@@ -1324,12 +1379,13 @@ static int binned_build_order(disco_ctx *c)
 {
     const int bits = c->order_counted_bits + c->order_sub_bits; /* (bucket and sub-key: one key) */
     const u32 total = (u32)c->n, kshift = 64u - (u32)bits;
-    u64 *items = (u64 *)c->d_rec2.p;
-    const u64 *rec;
+    BinxSide<u64> items, other, rec;
+    items.a = (u64 *)c->d_rec2.p;
+    other.a = items.a + c->n;
     const u32 *part;
-    CHK(binx_partition(c, "grouping", bits, kshift, total, items, items + c->n, &rec, &part));
+    CHK(binx_partition<u64>(c, "grouping", bits, kshift, total, items, other, &rec, &part));
     const int span = std::min(bits, BINX_SPAN_BITS);
-    hipLaunchKernelGGL(binx_build_kernel<u64>, dim3(1u << (bits - span)), dim3(BINX_BUILD_BLOCK), 0, c->stream, rec, part, (u32)span, kshift, (u32)c->order_id_bits, total, (u64)0,
+    hipLaunchKernelGGL(binx_build_kernel<u64>, dim3(1u << (bits - span)), dim3(BINX_BUILD_BLOCK), 0, c->stream, (const u64 *)rec.a, (const u64 *)nullptr, part, (u32)span, kshift, (u32)c->order_id_bits, total, (u64)0,
                        (u32 *)nullptr, c->d_order_own.p);
     HIPCHK(c, hipGetLastError());
     return DISCO_OK;
@@ -2063,7 +2119,7 @@ static int upload_reads_impl(disco_ctx *c, const char *who, const uint64_t *pack
                 HIPCHK(c, hipEventRecord(c->ev_copied[b], c->copy_stream));
                 HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copied[b], 0));
             }
-            if (eager) CHK(index_count_chunk(c, v, pl, !c->binned_index, c->d_rec, lo, hi));
+            if (eager) CHK(index_count_chunk(c, v, pl, index_rec_out(c), lo, hi));
         }
         HIPCHK(c, hipGetLastError());
         t_issued = lapms();
@@ -3071,8 +3127,8 @@ int disco_build_index(disco_ctx *c)
         const DiscoView v = view(c);
         IndexCountPlan pl;
         CHK(index_count_plan(c, v, 0, c->n, &pl));
-        CHK(index_count_chunk(c, v, pl, !c->binned_index, c->d_rec, 0, c->n));
-        if (c->two_class) CHK(index_count_long(c, v, pl, !c->binned_index, c->d_rec, pl.oslot, 0, c->n_long));
+        CHK(index_count_chunk(c, v, pl, index_rec_out(c), 0, c->n));
+        if (c->two_class) CHK(index_count_long(c, v, pl, index_rec_out(c), pl.oslot, 0, c->n_long));
     }
     const bool binned = c->binned_index; /* (index_begin's decision, whoever counted) */
     if (!binned) CHK((scan_exclusive<u32, u32>(c, c->d_bkt, c->T + 1, c->d_bkt, false, nullptr)));
@@ -5987,12 +6043,15 @@ static int dist_build_index(disco_ctx *c)
     ph_begin(c, DISCO_PH_INDEX);
     DiscoView v = view(c);
     IndexCountPlan pl;
+    IndexRecOut rec_out; /* 16-byte records without a slot: they travel to the rank that owns their bucket and are counted there */
+    rec_out.form = INDEX_RECORDS;
+    rec_out.rec = c->d_rec.p;
     if (c->loci) { /* the own list: records and minimizer runs by POSITION in the processing order */
         CHK(index_count_plan(c, v, 0, c->n_own, &pl, c->d_order_own));
-        CHK(index_count_chunk(c, v, pl, false, c->d_rec, 0, c->n_own));
+        CHK(index_count_chunk(c, v, pl, rec_out, 0, c->n_own));
     } else {
         CHK(index_count_plan(c, v, c->q_lo, c->q_hi, &pl));
-        CHK(index_count_chunk(c, v, pl, false, c->d_rec, c->q_lo, c->q_hi));
+        CHK(index_count_chunk(c, v, pl, rec_out, c->q_lo, c->q_hi));
         if (c->two_class && nloc) {
             /* the long reads of the rank's range — long_ids is ascending, ovf[i] counts the long reads in front of read i: they are the
              * x in [ovf[q_lo], ovf[q_hi]) — from their full rows; records by read id from q_lo (the kernel indexes rec by read id) */
@@ -6001,9 +6060,9 @@ static int dist_build_index(disco_ctx *c)
             if (c->q_hi < c->n) HIPCHK(c, hipMemcpyAsync(&xb[1], c->d_ovf + c->q_hi, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (xb[1] > xb[0]) {
-                ulonglong2 *rec_by_id = c->d_rec - 2 * (ptrdiff_t)c->q_lo; /* rec_by_id[2 i] = the record of read i (never touched outside [q_lo, q_hi)) */
+                const IndexRecOut rec_by_id = rec_out.from_read(-(ptrdiff_t)c->q_lo); /* rec_by_id.rec[2 i] = the record of read i (never touched outside [q_lo, q_hi)) */
                 u32 *oslot_by_id = pl.oslot ? pl.oslot - (ptrdiff_t)c->q_lo : nullptr; /* (the grouping's slots: by read id too) */
-                CHK(index_count_long(c, v, pl, false, rec_by_id, oslot_by_id, xb[0], xb[1]));
+                CHK(index_count_long(c, v, pl, rec_by_id, oslot_by_id, xb[0], xb[1]));
             }
         }
     }

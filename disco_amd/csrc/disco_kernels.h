@@ -333,15 +333,37 @@ __global__ void validate_len_kernel(const u16 *__restrict__ len, u64 n, int S, i
  * okey[i] = smallest 32-bit order hash among ALL m-mers of the read (see "processing order" below).
  * (The previous version called the random-access mmer_order 34 times per read: 33 L2 requests per read, 10.2 ms at 50 M reads,
  * plus a separate 4.2 ms pass for the keys.) */
-/* Reads [lo, hi) (the whole table on one GPU, the rank's own range in the multi-GPU flow); rec is indexed from lo. COUNT = false
+/* Reads [lo, hi) (the whole table on one GPU, the rank's own range in the multi-GPU flow); rec is indexed from lo. OUT = INDEX_RECORDS
  * (multi-GPU): no counting atomics — the records are routed to the rank that owns their bucket range first and counted there
  * (shard_count_kernel), which is what replaces the range-partitioned hashData of RMA/HashTable.cpp:95-116. */
 /* LONGCLASS (two row classes, single GPU): [lo, hi) counts the long reads; read x is long_ids[x], its row full[x][SL]; its records, key
  * and slot go where the read's would (rec is indexed by read id); the suffix record carries the id of the read's tail row, n + x */
 /* list (multi-GPU flow, ranks own loci: the own reads are no id range): position x of [lo, hi) stands for read ORDER_ID(list[x]);
  * records, slots and keys are indexed by position */
-template <bool COUNT, bool LONGK = false, bool LONGCLASS = false>
-__global__ void __launch_bounds__(256) index_count_kernel(DiscoView v, u32 *__restrict__ bkt, ulonglong2 *__restrict__ rec, u32 *__restrict__ okey, u64 lo, u64 hi,
+/* What the pass leaves of the two records of a read (OUT, a constant: the stores are the end of a kernel bound by vector issue):
+ *   INDEX_COUNTED  rec[] = {bucket << 32 | slot, payload}, the slot from the counting atomic on bkt[]  (the path without the builder)
+ *   INDEX_RECORDS  rec[] = {bucket << 32, payload}, no atomic                    (multi-GPU: the records travel to their bucket's owner)
+ *   INDEX_PLANES   pkey[] = (u32) bucket, ppay[] = payload, no atomic            (the binned build, single GPU: twelve live bytes a record)
+ * j = the read's place in the output: records 2 j (prefix k-mer) and 2 j + 1 (suffix k-mer); both planes are 16-byte aligned at j = 0 */
+enum IndexOut { INDEX_COUNTED = 0, INDEX_RECORDS = 1, INDEX_PLANES = 2 };
+template <int OUT>
+__device__ __forceinline__ void index_put_pair(u32 *__restrict__ bkt, ulonglong2 *__restrict__ rec, u32 *__restrict__ pkey, u64 *__restrict__ ppay, u64 j, u64 bp, u64 pp, u64 bs,
+                                               u64 ps)
+{
+    if constexpr (OUT == INDEX_PLANES) {
+        ((uint2 *)pkey)[j] = make_uint2((u32)bp, (u32)bs);
+        ((ulonglong2 *)ppay)[j] = make_ulonglong2(pp, ps);
+    } else {
+        const u32 sp = OUT == INDEX_COUNTED ? atomicAdd(&bkt[bp], 1u) : 0u;
+        const u32 ss = OUT == INDEX_COUNTED ? atomicAdd(&bkt[bs], 1u) : 0u;
+        rec[2 * j] = make_ulonglong2((bp << 32) | sp, pp);
+        rec[2 * j + 1] = make_ulonglong2((bs << 32) | ss, ps);
+    }
+}
+
+template <int OUT, bool LONGK = false, bool LONGCLASS = false>
+__global__ void __launch_bounds__(256) index_count_kernel(DiscoView v, u32 *__restrict__ bkt, ulonglong2 *__restrict__ rec, u32 *__restrict__ pkey, u64 *__restrict__ ppay,
+                                                          u32 *__restrict__ okey, u64 lo, u64 hi,
                                                           u32 *__restrict__ ocnt, u32 *__restrict__ oslot, u64 *__restrict__ oitem, u32 oidbits, u32 oshift,
                                                           const u64 *__restrict__ list = nullptr)
 {
@@ -417,10 +439,7 @@ __global__ void __launch_bounds__(256) index_count_kernel(DiscoView v, u32 *__re
     const u64 kp = resolve(k1p, k2p, 0, tp, rp);
     const u64 ks = resolve(k1s, k2s, sfx0, ts, rs);
     const u64 bp = kp >> v.bshift, bs = ks >> v.bshift;
-    const u32 sp = COUNT ? atomicAdd(&bkt[bp], 1u) : 0u;
-    const u32 ss = COUNT ? atomicAdd(&bkt[bs], 1u) : 0u;
-    rec[2 * (i - lo)] = make_ulonglong2((bp << 32) | sp, PAY_MAKE(kp, rid, tp, rp, 0, L));
-    rec[2 * (i - lo) + 1] = make_ulonglong2((bs << 32) | ss, PAY_MAKE(ks, LONGCLASS ? v.n + x : rid, ts, rs, 1, L));
+    index_put_pair<OUT>(bkt, rec, pkey, ppay, i - lo, bp, PAY_MAKE(kp, rid, tp, rp, 0, L), bs, PAY_MAKE(ks, LONGCLASS ? v.n + x : rid, ts, rs, 1, L));
 }
 
 /* the rolling canonical m-mer of a 2-bit packed row on 32-bit halves, M a constant (odd, 2 M bits = one dword + 2 M - 32 bits): the
@@ -509,8 +528,9 @@ struct MmerRoll {
  * 22, 27: min-overlap 30 .. 50) do not cover, k above 64 (LONGK: the three-word k-mer comparison of the rare tied end k-mer) and
  * minimizers of up to 31 bases included. The block's arrays hold NFMAX words, the loops over a block are unrolled NFMAX times with a
  * SCALAR test per position (every thread of the wavefront is at the same position of the same block), so the work follows nf, not NFMAX. */
-template <bool COUNT, int NF, int NL, int NFMAX = NF, bool LONGK = false>
-__global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__restrict__ bkt, ulonglong2 *__restrict__ rec, u32 *__restrict__ okey, u64 lo, u64 hi,
+template <int OUT, int NF, int NL, int NFMAX = NF, bool LONGK = false>
+__global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__restrict__ bkt, ulonglong2 *__restrict__ rec, u32 *__restrict__ pkey, u64 *__restrict__ ppay,
+                                                         u32 *__restrict__ okey, u64 lo, u64 hi,
                                                          u32 *__restrict__ runs, u32 *__restrict__ ocnt, u32 *__restrict__ oslot, u64 *__restrict__ oitem, u32 oidbits,
                                                          u32 oshift, u32 osub,
                                                          const u64 *__restrict__ list = nullptr)
@@ -660,10 +680,7 @@ __global__ void __launch_bounds__(256) index_runs_kernel(DiscoView v, u32 *__res
         const u64 kp = resolve(P1, P2, 0, 0, tp, rp);
         const u64 ks = resolve(sx[0], sx[256], (int)sx[512], npos, ts, rs);
         const u64 bp = kp >> v.bshift, bs = ks >> v.bshift;
-        const u32 sp = COUNT ? atomicAdd(&bkt[bp], 1u) : 0u;
-        const u32 ss = COUNT ? atomicAdd(&bkt[bs], 1u) : 0u;
-        rec[2 * (i - lo)] = make_ulonglong2((bp << 32) | sp, PAY_MAKE(kp, rid, tp, rp, 0, L));
-        rec[2 * (i - lo) + 1] = make_ulonglong2((bs << 32) | ss, PAY_MAKE(ks, rid, ts, rs, 1, L));
+        index_put_pair<OUT>(bkt, rec, pkey, ppay, i - lo, bp, PAY_MAKE(kp, rid, tp, rp, 0, L), bs, PAY_MAKE(ks, rid, ts, rs, 1, L));
     }
     __syncthreads();
 #if defined(INDEX_EXP_NORUNS) /* timing experiment (results are wrong): the run lists stay in LDS */
@@ -703,8 +720,12 @@ __global__ void index_fill_ordered_kernel(u64 nq, const u64 *__restrict__ order,
 }
 
 /* ================================================================================================================
- * binned index build (single GPU) — the index as what it is: a counting sort of the 2n records {bucket << 32, payload} by bucket.
- * The count pass runs without its two bucket atomics per read (COUNT = false) and everything behind it streams: the records are
+ * binned index build (single GPU) — the index as what it is: a counting sort of the 2n records (bucket, payload) by bucket.
+ * The count pass runs without its two bucket atomics per read and leaves the records as TWO PLANES (OUT = INDEX_PLANES): key[i] = the
+ * bucket, 4 bytes (a bucket is below 2^32, and without the atomic there is no slot), pay[i] = the payload, 8 bytes — twelve live bytes
+ * where a record {bucket << 32 | slot, payload} takes sixteen, and whoever only needs the key (a level's histogram, the build kernel's
+ * count sweep) streams 4 bytes a record. A side of the ping-pong is the payload plane, then the key plane (BinxForm<BinxKV>; the
+ * same kernels take the grouping's 8-byte items as one array, BinxForm<u64>). Everything behind the count pass streams: the records are
  * partitioned by the HIGH bits of the bucket, most significant digit first, in levels of at most BINX_MAX_BITS bits (per level:
  * histogram per tile in LDS -> exclusive scan of the tile x bin counts -> scatter with the tile staged in LDS, so that a bin leaves as
  * one contiguous run), down to partitions of at most 2^BINX_SPAN_BITS buckets; then one workgroup per partition counts its buckets in
@@ -720,9 +741,10 @@ __global__ void index_fill_ordered_kernel(u64 nq, const u64 *__restrict__ order,
  * ============================================================================================================== */
 #define BINX_SPAN_BITS 14 /* buckets per partition of the build kernel: 2^14 32-bit counters = 64 KB of LDS, two workgroups per CU */
 #define BINX_MAX_BITS 8   /* bits per partition level */
-#define BINX_TILE 2048u   /* records per tile of a partition level: 32 KB staged; 128 bins leave in runs of 16 records = 256 bytes on average */
+#define BINX_TILE 2048u   /* records per tile of a partition level: 24 KB staged as planes; 128 bins leave in runs of 16 records on average */
 #define BINX_BLOCK 256u
 #define BINX_BUILD_BLOCK 1024u /* the build kernel's tile: records per step of its two sweeps */
+#define BINX_BUILD_UNROLL 4u   /* steps of a sweep whose loads are in flight together */
 
 /* exclusive scan over the 1024 threads of a block (s_w: 16 words), returns the exclusive value; *total = the block's sum */
 __device__ __forceinline__ u32 binx_block_scan1024(u32 x, u32 *s_w, u32 *total)
@@ -798,35 +820,99 @@ __device__ __forceinline__ bool binx_tile(const u32 *__restrict__ seg, const u32
     return true;
 }
 
-/* what the kernels partition: the index's records {bucket << 32, payload}, or the grouping's one-word items (ORDER_ITEM); the key word
- * holds the bucket from bit `kshift` up (records: 32) */
-__device__ __forceinline__ u64 binx_key(const ulonglong2 &r) { return r.x; }
-__device__ __forceinline__ u64 binx_key(u64 r) { return r; }
+/* what the kernels partition: the index's records (key = the bucket, payload), or the grouping's one-word items (ORDER_ITEM); the key word
+ * holds the bucket from bit `kshift` up (the index's keys: 0) */
 /* the digit of a level: bits [shift, shift + log2 nb) of the key word (the host adds kshift) */
 #define BINX_DIGIT(key, shift, nb) ((u32)((key) >> (shift)) & ((nb)-1u))
 
+/* The two forms a side of the ping-pong takes, behind one view: R is a record as a thread holds it, BinxForm<R> says where it lies.
+ *   u64      ONE array a[] of the grouping's items, b unused; the build kernel writes no bucket table (TABLE)
+ *   BinxKV   TWO PLANES: a[] = the 4-byte keys (the bucket itself: kshift 0), b[] = the 8-byte payloads — the index's records.
+ *            Whoever only looks at the key (the histogram of a level, the build kernel's count sweep) streams the key plane alone:
+ *            4 bytes a record.
+ * (16-byte records {bucket << 32 | slot, payload} no longer come here: they are the old path's and the multi-GPU flow's.)
+ * key_at: the key word of record i; load / store: record i; Stage: a tile in LDS (planes there too: 24 KB) */
 template <typename R>
-__global__ void __launch_bounds__(BINX_BLOCK) binx_hist_kernel(const R *__restrict__ rec, const u32 *__restrict__ seg, const u32 *__restrict__ tb, u32 nseg, u32 shift, u32 nb,
-                                                               u32 *__restrict__ hist)
+struct BinxForm;
+template <>
+struct BinxForm<u64> {
+    typedef u64 A;
+    typedef u64 B;
+    static constexpr bool TABLE = false;
+    struct Stage {
+        u64 r[BINX_TILE];
+    };
+    static __device__ __forceinline__ u64 key_at(const A *__restrict__ a, u32 i) { return a[i]; }
+    static __device__ __forceinline__ u64 key(const u64 &r) { return r; }
+    static __device__ __forceinline__ u64 load(const A *__restrict__ a, const B *__restrict__, u32 i) { return a[i]; }
+    static __device__ __forceinline__ void store(A *__restrict__ a, B *__restrict__, u32 j, const u64 &r) { a[j] = r; }
+    static __device__ __forceinline__ void stage(Stage &s, u32 j, const u64 &r) { s.r[j] = r; }
+    static __device__ __forceinline__ u64 staged(const Stage &s, u32 j) { return s.r[j]; }
+};
+struct BinxKV {
+    u64 pay;
+    u32 key;
+};
+template <>
+struct BinxForm<BinxKV> {
+    typedef u32 A;
+    typedef u64 B;
+    static constexpr bool TABLE = true;
+    struct Stage {
+        u64 pay[BINX_TILE];
+        u32 key[BINX_TILE];
+    };
+    static __device__ __forceinline__ u32 key_at(const A *__restrict__ a, u32 i) { return a[i]; }
+    static __device__ __forceinline__ u32 key(const BinxKV &r) { return r.key; }
+    static __device__ __forceinline__ BinxKV load(const A *__restrict__ a, const B *__restrict__ b, u32 i) { return BinxKV{b[i], a[i]}; }
+    static __device__ __forceinline__ void store(A *__restrict__ a, B *__restrict__ b, u32 j, const BinxKV &r)
+    {
+        a[j] = r.key;
+        b[j] = r.pay;
+    }
+    static __device__ __forceinline__ void stage(Stage &s, u32 j, const BinxKV &r)
+    {
+        s.key[j] = r.key;
+        s.pay[j] = r.pay;
+    }
+    static __device__ __forceinline__ BinxKV staged(const Stage &s, u32 j) { return BinxKV{s.pay[j], s.key[j]}; }
+};
+
+template <typename R>
+__global__ void __launch_bounds__(BINX_BLOCK) binx_hist_kernel(const typename BinxForm<R>::A *__restrict__ rec, const u32 *__restrict__ seg, const u32 *__restrict__ tb, u32 nseg,
+                                                               u32 shift, u32 nb, u32 *__restrict__ hist)
 {
+    typedef BinxForm<R> F;
     __shared__ u32 s_h[1u << BINX_MAX_BITS];
     u32 t0, nt, ti, lo, hi;
     if (!binx_tile(seg, tb, nseg, t0, nt, ti, lo, hi)) return;
     s_h[threadIdx.x] = 0;
     __syncthreads();
-    for (u32 i = lo + threadIdx.x; i < hi; i += BINX_BLOCK) atomicAdd(&s_h[BINX_DIGIT(binx_key(rec[i]), shift, nb)], 1u);
+    if (hi - lo == BINX_TILE) { /* a whole tile (all but a segment's last): the thread's loads leave together — a load and an atomic by turns
+                                   is one round trip to memory per record and thread, and the kernel then waits where it should stream */
+        constexpr u32 PER = BINX_TILE / BINX_BLOCK;
+        decltype(F::key_at(rec, 0u)) k[PER];
+#pragma unroll
+        for (u32 j = 0; j < PER; j++) k[j] = F::key_at(rec, lo + j * BINX_BLOCK + threadIdx.x);
+#pragma unroll
+        for (u32 j = 0; j < PER; j++) atomicAdd(&s_h[BINX_DIGIT(k[j], shift, nb)], 1u);
+    } else
+        for (u32 i = lo + threadIdx.x; i < hi; i += BINX_BLOCK) atomicAdd(&s_h[BINX_DIGIT(F::key_at(rec, i), shift, nb)], 1u);
     __syncthreads();
     if (threadIdx.x < nb) hist[(u64)nb * t0 + (u64)threadIdx.x * nt + ti] = s_h[threadIdx.x];
 }
 
-/* a tile's records to their bins' places in dst: staged in LDS in bin order, written out as one run per bin */
+/* a tile's records to their bins' places in dst: staged in LDS in bin order, written out as one run per bin (planes: one run per bin
+ * in either plane) */
 template <typename R>
-__global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const R *__restrict__ src, R *__restrict__ dst, const u32 *__restrict__ seg, const u32 *__restrict__ tb,
-                                                                  u32 nseg, u32 shift, u32 nb, const u32 *__restrict__ scan)
+__global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const typename BinxForm<R>::A *__restrict__ src, const typename BinxForm<R>::B *__restrict__ srcb,
+                                                                  typename BinxForm<R>::A *__restrict__ dst, typename BinxForm<R>::B *__restrict__ dstb, const u32 *__restrict__ seg,
+                                                                  const u32 *__restrict__ tb, u32 nseg, u32 shift, u32 nb, const u32 *__restrict__ scan)
 {
     static_assert(BINX_BLOCK == (1u << BINX_MAX_BITS) && BINX_TILE % BINX_BLOCK == 0, "a thread per bin; whole rounds per tile");
+    typedef BinxForm<R> F;
     constexpr u32 PER = BINX_TILE / BINX_BLOCK;
-    __shared__ R s_rec[BINX_TILE];
+    __shared__ typename F::Stage s_rec;
     __shared__ u32 s_cnt[BINX_BLOCK], s_base[BINX_BLOCK], s_w[BINX_BLOCK / 64u];
     const u32 tid = threadIdx.x;
     u32 t0, nt, ti, lo, hi;
@@ -835,12 +921,19 @@ __global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const R *__res
     __syncthreads();
     R r[PER];
     u32 rank[PER];
+    if (hi - lo == BINX_TILE) { /* a whole tile: every load of the thread in flight before the first atomic waits for one (see the histogram) */
 #pragma unroll
-    for (u32 j = 0; j < PER; j++) {
-        const u32 i = lo + j * BINX_BLOCK + tid;
-        if (i < hi) {
-            r[j] = src[i];
-            rank[j] = atomicAdd(&s_cnt[BINX_DIGIT(binx_key(r[j]), shift, nb)], 1u);
+        for (u32 j = 0; j < PER; j++) r[j] = F::load(src, srcb, lo + j * BINX_BLOCK + tid);
+#pragma unroll
+        for (u32 j = 0; j < PER; j++) rank[j] = atomicAdd(&s_cnt[BINX_DIGIT(F::key(r[j]), shift, nb)], 1u);
+    } else {
+#pragma unroll
+        for (u32 j = 0; j < PER; j++) {
+            const u32 i = lo + j * BINX_BLOCK + tid;
+            if (i < hi) {
+                r[j] = F::load(src, srcb, i);
+                rank[j] = atomicAdd(&s_cnt[BINX_DIGIT(F::key(r[j]), shift, nb)], 1u);
+            }
         }
     }
     __syncthreads();
@@ -862,12 +955,12 @@ __global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const R *__res
 #pragma unroll
     for (u32 j = 0; j < PER; j++) {
         const u32 i = lo + j * BINX_BLOCK + tid;
-        if (i < hi) s_rec[s_cnt[BINX_DIGIT(binx_key(r[j]), shift, nb)] + rank[j]] = r[j];
+        if (i < hi) F::stage(s_rec, s_cnt[BINX_DIGIT(F::key(r[j]), shift, nb)] + rank[j], r[j]);
     }
     __syncthreads();
     for (u32 j = tid; j < hi - lo; j += BINX_BLOCK) {
-        const R x = s_rec[j];
-        dst[s_base[BINX_DIGIT(binx_key(x), shift, nb)] + j] = x;
+        const R x = F::staged(s_rec, j);
+        F::store(dst, dstb, s_base[BINX_DIGIT(F::key(x), shift, nb)] + j, x);
     }
 }
 
@@ -878,13 +971,16 @@ __global__ void __launch_bounds__(BINX_BLOCK) binx_scatter_kernel(const R *__res
  * any number of records (copies of one read: all in one bucket); the sweeps step through it BINX_BUILD_BLOCK at a time. */
 /* the grouping's items (R = u64, ORDER_ITEM with the read id in `idbits` bits): the same two sweeps place the order words, reads of equal
  * bucket back to back in the partition's window of the processing order; the order has no bucket table (bkt, T: unused) */
-__device__ __forceinline__ u64 binx_payload(const ulonglong2 &r, u32, u32) { return r.y; }
 __device__ __forceinline__ u64 binx_payload(u64 r, u32 kshift, u32 idbits) { return ORDER_MAKE(r & ((1ull << idbits) - 1ull), (r << (64u - kshift)) >> (64u - kshift + idbits)); }
+__device__ __forceinline__ u64 binx_payload(const BinxKV &r, u32, u32) { return r.pay; }
+/* (planes: sweep 1 reads the key plane alone, sweep 2 both) */
 template <typename R>
-__global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const R *__restrict__ rec, const u32 *__restrict__ part, u32 span, u32 kshift, u32 idbits, u32 total, u64 T,
-                                                                      u32 *__restrict__ bkt, u64 *__restrict__ ent)
+__global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const typename BinxForm<R>::A *__restrict__ rec, const typename BinxForm<R>::B *__restrict__ recb,
+                                                                      const u32 *__restrict__ part, u32 span, u32 kshift, u32 idbits, u32 total, u64 T, u32 *__restrict__ bkt,
+                                                                      u64 *__restrict__ ent)
 {
-    constexpr bool TABLE = sizeof(R) == sizeof(ulonglong2);
+    typedef BinxForm<R> F;
+    constexpr bool TABLE = F::TABLE;
     __shared__ __attribute__((aligned(16))) u32 s_c[1u << BINX_SPAN_BITS];
     __shared__ u32 s_w[16];
     const u32 tid = threadIdx.x, p = blockIdx.x;
@@ -892,7 +988,17 @@ __global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const R *_
     const u32 beg = part[p], end = part[p + 1];
     for (u32 x = tid; x < nbk / 4u; x += BINX_BUILD_BLOCK) ((uint4 *)s_c)[x] = make_uint4(0u, 0u, 0u, 0u); /* (nbk is a multiple of the block) */
     __syncthreads();
-    for (u32 i = beg + tid; i < end; i += BINX_BUILD_BLOCK) atomicAdd(&s_c[(u32)(binx_key(rec[i]) >> kshift) & mask], 1u);
+    /* both sweeps take BINX_BUILD_UNROLL steps at a time with the loads of all of them in flight: with a load, an LDS atomic and a store by
+     * turns a thread makes one round trip to memory per record, 12 per sweep at 5 x 10^7 reads, and the kernel waits for those */
+    u32 i = beg + tid;
+    for (; i + (BINX_BUILD_UNROLL - 1u) * BINX_BUILD_BLOCK < end; i += BINX_BUILD_UNROLL * BINX_BUILD_BLOCK) { /* (2n < 2^32 - 2^16: no wrap) */
+        decltype(F::key_at(rec, 0u)) k[BINX_BUILD_UNROLL];
+#pragma unroll
+        for (u32 u = 0; u < BINX_BUILD_UNROLL; u++) k[u] = F::key_at(rec, i + u * BINX_BUILD_BLOCK);
+#pragma unroll
+        for (u32 u = 0; u < BINX_BUILD_UNROLL; u++) atomicAdd(&s_c[(u32)(k[u] >> kshift) & mask], 1u);
+    }
+    for (; i < end; i += BINX_BUILD_BLOCK) atomicAdd(&s_c[(u32)(F::key_at(rec, i) >> kshift) & mask], 1u);
     __syncthreads();
     u32 carry = beg;
     if constexpr (!TABLE) {
@@ -930,9 +1036,17 @@ __global__ void __launch_bounds__(BINX_BUILD_BLOCK) binx_build_kernel(const R *_
     }
     if (TABLE && (u64)(p + 1u) * nbk == T && tid == 0) bkt[T] = total;
     __syncthreads();
-    for (u32 i = beg + tid; i < end; i += BINX_BUILD_BLOCK) {
-        const R x = rec[i];
-        ent[atomicAdd(&s_c[(u32)(binx_key(x) >> kshift) & mask], 1u)] = binx_payload(x, kshift, idbits);
+    i = beg + tid;
+    for (; i + (BINX_BUILD_UNROLL - 1u) * BINX_BUILD_BLOCK < end; i += BINX_BUILD_UNROLL * BINX_BUILD_BLOCK) {
+        R x[BINX_BUILD_UNROLL];
+#pragma unroll
+        for (u32 u = 0; u < BINX_BUILD_UNROLL; u++) x[u] = F::load(rec, recb, i + u * BINX_BUILD_BLOCK);
+#pragma unroll
+        for (u32 u = 0; u < BINX_BUILD_UNROLL; u++) ent[atomicAdd(&s_c[(u32)(F::key(x[u]) >> kshift) & mask], 1u)] = binx_payload(x[u], kshift, idbits);
+    }
+    for (; i < end; i += BINX_BUILD_BLOCK) {
+        const R x = F::load(rec, recb, i);
+        ent[atomicAdd(&s_c[(u32)(F::key(x) >> kshift) & mask], 1u)] = binx_payload(x, kshift, idbits);
     }
 }
 
